@@ -20,8 +20,23 @@ workload).
   --config c5         the 64-keyframe / 100 000-landmark global BA, landmarks sharded over the N ranks (RCCL all-reduce of the
                       reduced camera system per trial round); a step = one full BA (two LM passes + chi2 re-check)
 PyTorch is used for device buffers and torch.distributed only.  Multi-GPU, c1-c3: replicas (no data-path collective, weak
-scaling); with N > 1 the line also carries the C5 sharded BA over the same ranks ("c5_sharded_ba"), the one collective of
-this path.
+scaling).
+
+A plain run measures the headline figure only: set-up, warm-up, the timed steps, the line.  --full adds everything else,
+after the timed steps: per-stage HIP-event timings (sampled inside the warm-up and timed steps), the roofline and path
+figures, the workload probe, the single-session latency line, --sweep, the CPU baselines (N = 1) and, with N > 1, the C5
+sharded BA over the same ranks ("c5_sharded_ba"), the one collective of this path.
+
+  --dump-outputs DIR  rank 0 writes what the timed steps computed as DIR/<name>.npy (float64, at most 64 MB in all):
+                      c1-c3: report.npy (the fleet report of the timed steps without its wall-clock fields, in the order of
+                      REPORT_FIELDS), and for up to 512 evenly spaced sessions (sessions.npy) the last 16 keyframes of each
+                      map (keyframe_frames.npy, keyframe_poses.npy: frame index and world <- camera pose, zero-padded;
+                      keyframe_counts.npy: keyframes in the map) and the matches of each session's last frame
+                      (last_frame_matches.npy: [left, right] keypoint per active map point, last_frame_outliers.npy,
+                      last_frame_counts.npy: rows per session); c5: the last BA's kf_pose.npy, lm.npy, pair_wrong.npy and
+                      final_error.npy.  The inputs depend on the arguments only, so two builds can be compared file by file.
+                      The device reductions are not bitwise reproducible: two c2 runs of one build agree exactly in the
+                      counts, frame indices and matches, and to about 1e-4 in the poses and report.npy's position errors.
 """
 import argparse
 import json
@@ -166,9 +181,57 @@ def cpu_baseline(cfg, frames, poses, vel, fwd, delay, threads, budget_s=16.0, wa
                                                    if threads else "single thread")}
 
 
-def run_c5(args, rank, world, local, dist, torch, backend):
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SESSIONS = 512       # sessions whose maps and last frames --dump-outputs writes (evenly spaced when there are more)
+DUMP_KEYFRAMES = 16       # most recent keyframes per session (the local BA's window is 10)
+# the fleet report's counters and errors; its wall-clock fields ("seconds", "max_session_seconds") differ from run to run
+REPORT_FIELDS = ("n_sessions", "frames", "keyframes", "mappings", "new_points", "ba_landmarks", "ba_pairs", "ba_residuals", "ba_free_kf",
+                 "ba_sum_k2", "ba_trials", "ba_iterations", "ba_rounds", "sum_inliers", "sum_rounds", "lost_frames", "sum_active",
+                 "min_inliers", "max_position_error", "sum_sq_position_error")
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as float64 DIR/<name>.npy; refuses to write more than DUMP_LIMIT_BYTES in all"""
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def dump_fleet_outputs(path, vc, fleet, rep):
+    """--dump-outputs of c1-c3 (the module docstring lists the files): what the timed steps handed back - the fleet report -
+    and the sessions' state after the last step, read through vslam_fleet_system and the vslam_system read-outs"""
+    import ctypes
+    L = vc.lib()
+    S = fleet.n_sessions
+    sel = np.unique(np.linspace(0, S - 1, min(S, DUMP_SESSIONS)).round().astype(np.int64))
+    kf_count = np.zeros(len(sel))
+    kf_frames = np.full((len(sel), DUMP_KEYFRAMES), -1.0)
+    kf_poses = np.zeros((len(sel), DUMP_KEYFRAMES, 4, 4))
+    matches, outliers, counts = [], [], np.zeros(len(sel))
+    for i, s in enumerate(sel):
+        h = ctypes.c_void_p()
+        vc._chk(L.vslam_fleet_system(fleet.h, int(s), ctypes.byref(h)))
+        sess = vc._BorrowedSystem(L, h.value)
+        fi, P = sess.keyframes()
+        kf_count[i] = len(fi)
+        n = min(len(fi), DUMP_KEYFRAMES)
+        if n:
+            kf_frames[i, :n], kf_poses[i, :n] = fi[-n:], P[-n:]
+        mt, ol = sess.last_frame()
+        matches.append(mt); outliers.append(ol); counts[i] = len(ol)
+    write_outputs(path, {"report": [rep[k] for k in REPORT_FIELDS], "sessions": sel, "keyframe_counts": kf_count,
+                         "keyframe_frames": kf_frames, "keyframe_poses": kf_poses,
+                         "last_frame_matches": np.concatenate(matches).reshape(-1, 2), "last_frame_outliers": np.concatenate(outliers),
+                         "last_frame_counts": counts})
+
+
+def run_c5(args, rank, world, local, dist, torch, backend, dump=""):
     """C5: 64-keyframe / 100 000-landmark BA, landmarks sharded lm % world over the ranks, RCCL all-reduce of the NB reduced
-    camera systems per trial round.  A step = one vslam_local_ba call."""
+    camera systems per trial round.  A step = one vslam_local_ba call.  dump: --dump-outputs of a --config c5 run."""
     import synth
     import vslam_capi as vc
     rig = synth.RIGS["synthetic"]
@@ -206,6 +269,8 @@ def run_c5(args, rank, world, local, dist, torch, backend):
         t = torch.tensor([el], device=torch.device("cuda", local) if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if dump and rank == 0:
+        write_outputs(dump, {"kf_pose": r["kf_pose"], "lm": r["lm"], "pair_wrong": r["pair_wrong"], "final_error": [r["reports"][1]["finalError"]]})
     tm = vc.local_ba_timings()
     trials = r["reports"][0]["inner"] + r["reports"][1]["inner"]
     iters = r["reports"][0]["iterations"] + r["reports"][1]["iterations"]
@@ -249,15 +314,19 @@ def main():
     ap.add_argument("--prime", type=int, default=-1, help="(default 160 corridor / 60 room) ""untimed frames every session tracks BEFORE the warm-up steps, so that the timed "
                     "steps see sessions in their steady state (a map with more than three keyframes, the local mapper running) "
                     "whatever --warmup / --steps are; part of the set-up like rendering the frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency-line", action="store_true", help="skip the extra single-session run")
-    ap.add_argument("--sweep", default="", help="comma-separated SESSIONSxLANES shapes (e.g. 1x0,1x1,8x8,32x32,64x32): throughput of each in the "
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need (see the module docstring)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the timed steps to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-latency-line", action="store_true", help="--full: skip the extra single-session run")
+    ap.add_argument("--sweep", default="", help="--full: comma-separated SESSIONSxLANES shapes (e.g. 1x0,1x1,8x8,32x32,64x32): throughput of each in the "
                                                 "\"sweep\" field (one process, same frames)")
     ap.add_argument("--c5-landmarks", type=int, default=100000)
     ap.add_argument("--c5-steps", type=int, default=5)
     ap.add_argument("--c5-warmup", type=int, default=1)
     ap.add_argument("--c5-timeout", type=int, default=180, help="N > 1: seconds the sharded-BA section may take before the line is printed without it")
     args = ap.parse_args()
+    if args.sweep and not args.full:
+        ap.error("--sweep is part of --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -310,7 +379,7 @@ def main():
     dev = torch.device("cuda", local)
 
     if args.config == "c5":
-        c5 = run_c5(args, rank, world, local, dist, torch, backend)
+        c5 = run_c5(args, rank, world, local, dist, torch, backend, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps({"metric": "LM trial rounds/s of the 64-KF / 100k-landmark global BA (landmark-sharded, RCCL all-reduce)",
                               "value": c5["lm_trials_per_s"], "unit": "trials/s", "n_gpus": world, "steps": args.c5_steps, "warmup": args.c5_warmup,
@@ -364,14 +433,16 @@ def main():
     fleet = make_fleet(args.sessions, lanes)
     if args.prime > 0:
         fleet.run(args.prime)        # set-up: the sessions' first frames (map initialisation, the first keyframes)
-    # per-stage HIP events on every 3rd step of group / session 0 (every step of a short timed region).  The warm-up steps are
-    # sampled too, so that the first timed sample does not carry the timers' one-time set-up; their readings are discarded.
-    sample_every = 1 if args.steps < 60 else 3
-    if os.environ.get("VSLAM_BENCH_NO_SAMPLING"):
-        sample_every = 0
-    fleet.set_sampling(sample_every)
+    # --full: per-stage HIP events on every 3rd step of group / session 0 (every step of a short timed region).  The warm-up
+    # steps are sampled too, so that the first timed sample does not carry the timers' one-time set-up; their readings are
+    # discarded.
+    sample_every = 0
+    if args.full and not os.environ.get("VSLAM_BENCH_NO_SAMPLING"):
+        sample_every = 1 if args.steps < 60 else 3
+        fleet.set_sampling(sample_every)
     fleet.run(args.warmup)
-    fleet.timings()
+    if sample_every:
+        fleet.timings()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -387,11 +458,14 @@ def main():
         t = torch.tensor([el], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    stage_ms, cnt = fleet.timings()
-    fleet.set_sampling(0)
+    if args.dump_outputs and rank == 0:
+        dump_fleet_outputs(args.dump_outputs, vc, fleet, rep)
+    if args.full:
+        stage_ms, cnt = fleet.timings()
+        fleet.set_sampling(0)
 
     latency = None
-    if rank == 0 and not args.no_latency_line and args.sessions > 1:
+    if args.full and rank == 0 and not args.no_latency_line and args.sessions > 1:
         fleet.close()
         f1 = make_fleet(1, 0)
         f1.run(max(args.prime, 1) + min(args.warmup, 20))
@@ -430,7 +504,7 @@ def main():
     # workload probe (after the timed region, its own extractor / matcher): the figures the byte formulas need and the fleet
     # report does not carry - keypoints per image, FAST candidates per image, the stereo kernel's own counters
     probe = None
-    if rank == 0:
+    if args.full and rank == 0:
         probe = workload_probe(vc, rig, cfg, bufs, w, h, args.host_images, local)
 
     # N > 1: the landmark-sharded 64-keyframe / 100 k-landmark BA over RCCL as an extra section of the line.  It is the
@@ -440,7 +514,7 @@ def main():
     emit_lock = __import__("threading").Lock()
     emitted = [False]
     emit_box = {}
-    if world > 1 and not os.environ.get("VSLAM_BENCH_SKIP_C5"):
+    if args.full and world > 1 and not os.environ.get("VSLAM_BENCH_SKIP_C5"):
         import threading
 
         def _watchdog():
@@ -453,11 +527,49 @@ def main():
 
     if rank == 0:
         S = args.sessions
-        px = level_pixels(w, h)
-        sumP, nimg, nfeat = sum(px), 2, cfg["nfeat"]
-        nBA = max(cnt["ba"], 1)
         nBAall = max(rep["mappings"], 1)
         R_, L_, k2, Fk = rep["ba_residuals"] / nBAall, rep["ba_landmarks"] / nBAall, rep["ba_sum_k2"] / nBAall, rep["ba_free_kf"] / nBAall
+        Mact = rep["sum_active"] / max(rep["frames"], 1)      # measured: active map points per tracked frame
+        frames_per_ba = rep["frames"] / nBAall
+        value = world * S * args.steps / el
+        out = {
+            "metric": "frames/sec (extract+match+localBA), %d feat stereo %dx%d" % (cfg["nfeat"], w, h),
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8/i32 (extract, match) + f64 (pose LM, local BA)", "data": "synthetic",
+            "config": {"workload": cfg["name"] + "; closed loop per session (keyframe rule, insertKeyFrame, new points + local BA on the tracker's "
+                                   "own covisibility window, write-back, changePosesLCA); %s; measured per run: one keyframe every %.1f frames, one local BA "
+                                   "every %.1f frames (%.0f landmarks, %.0f residual blocks, %.1f free keyframes on average), %s"
+                                   "%.0f active map points per frame"
+                                   % (("corridor scene: %d distinct stereo frames %s, %.2f m/s, every session walks forward from its own start frame%s"
+                                       % (args.frames, "in pinned host memory (H2D inside the step)" if args.host_images else "rendered into HBM",
+                                          args.speed, " and turns around at the end (the run is longer than the sequence)" if turns else
+                                          " and never revisits a place inside the run"))
+                                      if corridor else "room scene: %d rendered frames %s, replayed as a ping-pong"
+                                      % (args.frames, "in pinned host memory (H2D inside the step)" if args.host_images else "resident in HBM"),
+                                      rep["frames"] / max(rep["keyframes"], 1), frames_per_ba, L_, R_, Fk,
+                                      "%.0f keypoints per image, " % probe["keys_per_image"] if probe else "", Mact),
+                       "sessions_per_gpu": S, "lanes_per_group": lanes, "prime_frames": args.prime,
+                       "local_mapping": {0: "off", 1: "inside the frame (synchronous)", 2: "device work beside tracking, fixed schedule"}.get(args.mapping, "?") +
+                                        ("; new points %d frame(s) after the hand-over (mapping_np_delay), the BA's write-back + changePosesLCA %d frames "
+                                         "after it (mapping_delay): the schedule of tests/test_gpu_system.py::test_closed_loop_parity_async_*"
+                                         % (args.mapping_np_delay, args.mapping_delay) if args.mapping == 2 else ""),
+                       "step": "one stereo frame of each of the %d sessions" % S,
+                       "threads": ("%d lockstep groups of %d sessions (vslam_batch: one launch per stage for all lanes), one driver thread + a "
+                                   "host-phase pool + the mapping engine per group" % ((S + lanes - 1) // lanes, lanes)) if lanes > 0 else
+                                  "one host thread per session inside the library (vslam_fleet) + one mapping thread per session",
+                       "parallelism": "replicas x%d, %d sessions per GPU" % (world, S)},
+            "tracking": {"mean_inliers": rep["sum_inliers"] / max(rep["frames"] - 0, 1), "min_inliers": rep["min_inliers"],
+                         "lost_frames": rep["lost_frames"], "mean_rounds": rep["sum_rounds"] / max(rep["frames"], 1),
+                         "keyframes": rep["keyframes"], "local_bas": rep["mappings"], "new_points": rep["new_points"],
+                         "rms_position_error_m": float(np.sqrt(rep["sum_sq_position_error"] / max(rep["frames"], 1))),
+                         "max_position_error_m": rep["max_position_error"]},
+        }
+    if rank == 0 and args.full:
+        px = level_pixels(w, h)
+        sumP, nimg = sum(px), 2
+        nBA = max(cnt["ba"], 1)
         roundsPerBA = max(rep["ba_rounds"] / nBAall, 1.0)      # trial rounds per local BA (one round = up to 4 lambda candidates at once)
         launch_n = {k[:-2]: v for k, v in stage_ms.items() if k.endswith("#n")}      # measured launches behind the local-BA sums
         stage_ms = {k: v for k, v in stage_ms.items() if not k.endswith("#n")}
@@ -471,8 +583,6 @@ def main():
         nBA6 = 6 * Fk
         nk = probe["keys_per_image"]                 # measured: kept keypoints per image
         ncand = probe["fast_candidates_per_image"]   # measured: FAST corners per image before the suppression
-        Mact = rep["sum_active"] / max(rep["frames"], 1)      # measured: active map points per tracked frame
-        frames_per_ba = rep["frames"] / nBAall
         # One launch of a tracking / extraction stage serves `lb` sessions (the lanes of a lockstep group; 1 without batching).
         lb = max(lanes, 1)
         nStep = max(cnt["frames"] / lb, 1)         # sampled steps
@@ -519,39 +629,7 @@ def main():
             if k == "imu_preintegrate" and not cfg["imu"]:
                 continue
             path_bytes += ab * (n_l / (nBA * frames_per_ba) if k.startswith("ba_") else n_l / nS)
-        value = world * S * args.steps / el
-        out = {
-            "metric": "frames/sec (extract+match+localBA), %d feat stereo %dx%d" % (nfeat, w, h),
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8/i32 (extract, match) + f64 (pose LM, local BA)", "data": "synthetic",
-            "config": {"workload": cfg["name"] + "; closed loop per session (keyframe rule, insertKeyFrame, new points + local BA on the tracker's "
-                                   "own covisibility window, write-back, changePosesLCA); %s; measured per run: one keyframe every %.1f frames, one local BA "
-                                   "every %.1f frames (%.0f landmarks, %.0f residual blocks, %.1f free keyframes on average), %.0f keypoints per image, "
-                                   "%.0f active map points per frame"
-                                   % (("corridor scene: %d distinct stereo frames %s, %.2f m/s, every session walks forward from its own start frame%s"
-                                       % (args.frames, "in pinned host memory (H2D inside the step)" if args.host_images else "rendered into HBM",
-                                          args.speed, " and turns around at the end (the run is longer than the sequence)" if turns else
-                                          " and never revisits a place inside the run"))
-                                      if corridor else "room scene: %d rendered frames %s, replayed as a ping-pong"
-                                      % (args.frames, "in pinned host memory (H2D inside the step)" if args.host_images else "resident in HBM"),
-                                      rep["frames"] / max(rep["keyframes"], 1), frames_per_ba, L_, R_, Fk, nk, Mact),
-                       "sessions_per_gpu": S, "lanes_per_group": lanes, "prime_frames": args.prime,
-                       "local_mapping": {0: "off", 1: "inside the frame (synchronous)", 2: "device work beside tracking, fixed schedule"}.get(args.mapping, "?") +
-                                        ("; new points %d frame(s) after the hand-over (mapping_np_delay), the BA's write-back + changePosesLCA %d frames "
-                                         "after it (mapping_delay): the schedule of tests/test_gpu_system.py::test_closed_loop_parity_async_*"
-                                         % (args.mapping_np_delay, args.mapping_delay) if args.mapping == 2 else ""),
-                       "step": "one stereo frame of each of the %d sessions" % S,
-                       "threads": ("%d lockstep groups of %d sessions (vslam_batch: one launch per stage for all lanes), one driver thread + a "
-                                   "host-phase pool + the mapping engine per group" % ((S + lanes - 1) // lanes, lanes)) if lanes > 0 else
-                                  "one host thread per session inside the library (vslam_fleet) + one mapping thread per session",
-                       "parallelism": "replicas x%d, %d sessions per GPU" % (world, S)},
-            "tracking": {"mean_inliers": rep["sum_inliers"] / max(rep["frames"] - 0, 1), "min_inliers": rep["min_inliers"],
-                         "lost_frames": rep["lost_frames"], "mean_rounds": rep["sum_rounds"] / max(rep["frames"], 1),
-                         "keyframes": rep["keyframes"], "local_bas": rep["mappings"], "new_points": rep["new_points"],
-                         "rms_position_error_m": float(np.sqrt(rep["sum_sq_position_error"] / max(rep["frames"], 1))),
-                         "max_position_error_m": rep["max_position_error"]},
+        out.update({
             "workload_probe": probe,
             "stage_ms_per_frame": {k: v for k, v in sorted(per_frame.items())},
             "stage_sampling": "HIP events on every %s step of group 0 (all its lanes per launch) and on the local BAs of its first sessions that "
@@ -561,7 +639,7 @@ def main():
                      "frac": path_bytes * value / world / 1e9 / HBM_PEAK_GBS,
                      "note": "whole path: sum over the kernel groups of (algorithmic bytes per launch x launches per tracked frame, SURVEY 8(d) formulas "
                              "with the measured keypoint / candidate / active-point / stereo-test counts) x frames/s of one GPU / HBM peak"},
-        }
+        })
         if per_frame:
             # `roofline` prices the kernel group with the LARGEST ELAPSED DEVICE TIME per tracked frame in this run (HIP events on the
             # launching stream, summed over the sampled launches) - no weighting.  roofline_top5: the five largest by the same measure.
@@ -624,11 +702,12 @@ def main():
             else:
                 out["ba_solve_mfma"] = {"launch_ms": None, "unknowns": nBA6, "flops": groups["ba_solve"][2], "achieved_gflops": None, "fp64_frac": None,
                                         "note": "no sampled local BA in the timed region"}
+    if rank == 0:
         if latency:
             out["latency_single_session"] = latency
         if sweep:
             out["sweep"] = sweep
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the same frames on the host's cores (rank 0, N = 1 only): the first frames of the sequence
             nb = 224
             if corridor:
