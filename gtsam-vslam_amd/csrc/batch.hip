@@ -173,12 +173,12 @@ struct vslam_batch {
     vslam_status ensure_dn(size_t bytes);
     vslam_status serve_requests();
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
-    vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames,
+    vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
                       const uint8_t* const* nextL = nullptr, const uint8_t* const* nextR = nullptr, const uint8_t* nextMask = nullptr);
     // images of the NEXT step whose extraction was enqueued at the end of the previous one (prefetch)
-    std::vector<const uint8_t*> prefetched;
-    vslam_status enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, bool onDevice);
+    std::vector<const uint8_t*> prefetched; int prefetchedChannels = 1;
+    vslam_status enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, int channels, bool onDevice);
     static void submit_mapping(void* self, vslam_system* s) {
         vslam_batch* b = (vslam_batch*)self;
         bool now = false;
@@ -436,8 +436,13 @@ vslam_status vslam_batch::ensure_dn(size_t bytes) {
     } while (0)
 
 // level 0 of every active lane's pair + the whole extraction, on the extractor's stream
-vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, bool onDevice) {
-    if (onDevice) {
+vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, int channels,
+                                             bool onDevice) {
+    if (channels != 1) {        // colour frames: every active lane's pair converted by one launch (host: uploads, one wait, one launch)
+        imgPtrs.assign((size_t)2 * B, nullptr);
+        for (int b = 0; b < B; b++) if (!mask || mask[b]) { imgPtrs[2 * b] = L[b]; imgPtrs[2 * b + 1] = R[b]; }
+        VS_CHECK(fe->set_images_color(imgPtrs.data(), stride, channels, onDevice, true));
+    } else if (onDevice) {
         imgPtrs.assign((size_t)2 * B, nullptr);
         for (int b = 0; b < B; b++) if (!mask || mask[b]) { imgPtrs[2 * b] = L[b]; imgPtrs[2 * b + 1] = R[b]; }
         VS_CHECK(fe->set_images_device(imgPtrs.data(), stride));
@@ -452,7 +457,7 @@ vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint
     return fe->run();
 }
 
-vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames,
+vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                                const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
                                const uint8_t* const* nextL, const uint8_t* const* nextR, const uint8_t* nextMask) {
     if (!L || !R || !frames || !T_wc_out) return VSLAM_ERR_INVALID;
@@ -549,7 +554,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
 
     // ---- device: images, extraction (already in flight when the previous step prefetched exactly these images) -----------
     {
-        bool hit = onDevice && prefetched.size() == (size_t)2 * B;
+        bool hit = onDevice && prefetched.size() == (size_t)2 * B && prefetchedChannels == channels;
         for (int b = 0; b < B && hit; b++) {
             const bool on = ls[b].on;
             hit = prefetched[2 * b] == (on ? L[b] : nullptr) && prefetched[2 * b + 1] == (on ? R[b] : nullptr);
@@ -557,7 +562,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
         prefetched.clear();
         if (!hit) {
             if (fe->countsPending) VS_CHECK(fe->wait_counts());      // (a prefetch for other images: let it finish first)
-            VS_CHECK(enqueue_extraction(L, R, mask, stride, onDevice));
+            VS_CHECK(enqueue_extraction(L, R, mask, stride, channels, onDevice));
         }
     }
     lap(1);
@@ -746,8 +751,8 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
     // ---- prefetch: the next frames' extraction runs under this step's host phases and the next step's begin ----------------
     // (the extractor alternates between two output sets, so this frame's keys stay readable for keyframe insertion)
     if (nextL && nextR && onDevice) {
-        VS_CHECK(enqueue_extraction(nextL, nextR, nextMask, stride, true));
-        prefetched.assign((size_t)2 * B, nullptr);
+        VS_CHECK(enqueue_extraction(nextL, nextR, nextMask, stride, channels, true));
+        prefetched.assign((size_t)2 * B, nullptr); prefetchedChannels = channels;
         for (int b = 0; b < B; b++) if (!nextMask || nextMask[b]) { prefetched[2 * b] = nextL[b]; prefetched[2 * b + 1] = nextR[b]; }
     }
 
@@ -838,7 +843,7 @@ vslam_status vslam_batch_track_stereo(vslam_batch* b, const uint8_t* const* left
                                       int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
                                       const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports) {
     if (!b) return VSLAM_ERR_INVALID;
-    return b->step(left, right, stride, on_device != 0, frame_numbers, imu, lane_mask, T_wc_out, reports);
+    return b->step(left, right, stride, 1, on_device != 0, frame_numbers, imu, lane_mask, T_wc_out, reports);
 }
 
 vslam_status vslam_batch_track_stereo_prefetch(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
@@ -846,7 +851,33 @@ vslam_status vslam_batch_track_stereo_prefetch(vslam_batch* b, const uint8_t* co
                                                double* T_wc_out, vslam_frame_report* reports, const uint8_t* const* next_left,
                                                const uint8_t* const* next_right, const uint8_t* next_mask) {
     if (!b) return VSLAM_ERR_INVALID;
-    return b->step(left, right, stride, true, frame_numbers, imu, lane_mask, T_wc_out, reports, next_left, next_right, next_mask);
+    return b->step(left, right, stride, 1, true, frame_numbers, imu, lane_mask, T_wc_out, reports, next_left, next_right, next_mask);
+}
+
+static vslam_status batch_color_args(const vslam_batch* b, int32_t stride, int32_t channels, const char* fn) {
+    if ((channels != 1 && channels != 3 && channels != 4) || stride < b->fe->width * channels) {
+        set_error("%s: channels %d (1, 3 or 4), stride %d (at least width x channels)", fn, channels, stride);
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_batch_track_stereo_color(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                            int32_t channels, int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                            const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    VS_CHECK(batch_color_args(b, stride, channels, "vslam_batch_track_stereo_color"));
+    return b->step(left, right, stride, channels, on_device != 0, frame_numbers, imu, lane_mask, T_wc_out, reports);
+}
+
+vslam_status vslam_batch_track_stereo_prefetch_color(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                                     int32_t channels, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                                     const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports,
+                                                     const uint8_t* const* next_left, const uint8_t* const* next_right,
+                                                     const uint8_t* next_mask) {
+    if (!b) return VSLAM_ERR_INVALID;
+    VS_CHECK(batch_color_args(b, stride, channels, "vslam_batch_track_stereo_prefetch_color"));
+    return b->step(left, right, stride, channels, true, frame_numbers, imu, lane_mask, T_wc_out, reports, next_left, next_right, next_mask);
 }
 
 vslam_system* vslam_batch_system(vslam_batch* b, int32_t lane) {

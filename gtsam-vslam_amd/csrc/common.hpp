@@ -66,6 +66,14 @@ static inline int cv_ceil_d(double v) { int i = (int)v; return i + (i < v); }
 
 constexpr int MAX_LEVELS = 12;
 
+// cv::cvtColor(BGR2GRAY / BGRA2GRAY) on 8-bit images, the rule the reference's TrackImage applies to colour frames
+// (src/FeatureTracker.cpp:1130-1144): OpenCV 4.2 RGB2Gray<uchar> (imgproc color_rgb.simd.hpp), R2Y / G2Y / B2Y with
+// yuv_shift 14; the weights sum to 2^14, so equal channels v give v.  Alpha is ignored.  DESIGN §6 item 13 (parity unpinned).
+constexpr int GRAY_B = 1868, GRAY_G = 9617, GRAY_R = 4899, GRAY_SHIFT = 14;
+__host__ __device__ static inline int bgr_to_gray(int b, int g, int r) {
+    return (b * GRAY_B + g * GRAY_G + r * GRAY_R + (1 << (GRAY_SHIFT - 1))) >> GRAY_SHIFT;
+}
+
 // Per host thread: a helper stream and a cache of device blocks for the keyframe-rate entry points (new points,
 // descriptor selection, depth refresh, keyframe pose update).  Blocks go back to the cache instead of hipFree, so the
 // steady state of a session makes no hipMalloc / hipFree / hipStreamCreate call (each of which synchronises the device

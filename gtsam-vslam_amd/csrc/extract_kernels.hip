@@ -115,6 +115,52 @@ void launch_load_images(hipStream_t s, const uint8_t* const* dSrc, int stride, u
     hipLaunchKernelGGL(k_load_images, dim3((P.w[0] + 1023) / 1024, (P.h[0] + 3) / 4, nimg), dim3(64, 4), 0, s, dSrc, stride, pyr, P);
 }
 
+// The same from interleaved BGR (CN = 3) / BGRA (CN = 4) sources, converted to gray on the way (bgr_to_gray, common.hpp;
+// the reference's cvtColor at src/FeatureTracker.cpp:1130-1144).  A thread makes 16 output pixels (one uint4 store) from its
+// 16 CN source bytes: when the row and x0 CN are 16-byte aligned, as CN uint4 loads whose bytes are taken apart with shifts
+// at compile-time indices (no local byte array: it would live in scratch); otherwise byte loads.
+template <int CN>
+__global__ __launch_bounds__(256) void k_load_images_color(const uint8_t* const* __restrict__ src, int stride,
+                                                           uint8_t* __restrict__ pyr, PyrDesc P) {
+    const int img = blockIdx.z;
+    const uint8_t* __restrict__ S = src[img];
+    if (!S) return;
+    uint8_t* __restrict__ D = pyr + (size_t)img * P.imgStride + P.off[0];
+    const int w = P.w[0], h = P.h[0], dp = P.pitch[0];
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 16;
+    if (y >= h || x0 >= w) return;
+    const uint8_t* sp = S + (size_t)y * stride + (size_t)x0 * CN;
+    uint8_t* dq = D + (size_t)y * dp + x0;
+    if (x0 + 16 <= w && ((((uintptr_t)sp) | ((uintptr_t)dq)) & 15) == 0) {
+        unsigned wd[4 * CN];
+#pragma unroll
+        for (int k = 0; k < CN; k++) {
+            const uint4 v = ((const uint4*)sp)[k];
+            wd[4 * k] = v.x; wd[4 * k + 1] = v.y; wd[4 * k + 2] = v.z; wd[4 * k + 3] = v.w;
+        }
+        unsigned o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int p = 0; p < 16; p++) {
+            const int bi = p * CN;        // byte index of the pixel's B; G, R follow
+            const int b = (wd[bi >> 2] >> (8 * (bi & 3))) & 0xff;
+            const int g = (wd[(bi + 1) >> 2] >> (8 * ((bi + 1) & 3))) & 0xff;
+            const int r = (wd[(bi + 2) >> 2] >> (8 * ((bi + 2) & 3))) & 0xff;
+            o[p >> 2] |= (unsigned)bgr_to_gray(b, g, r) << (8 * (p & 3));
+        }
+        *(uint4*)dq = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        for (int i = 0; i < 16 && x0 + i < w; i++)
+            dq[i] = (uint8_t)bgr_to_gray(sp[i * CN], sp[i * CN + 1], sp[i * CN + 2]);
+    }
+}
+void launch_load_images_color(hipStream_t s, const uint8_t* const* dSrc, int stride, int channels, uint8_t* pyr, const PyrDesc& P,
+                              int nimg) {
+    const dim3 grid((P.w[0] + 1023) / 1024, (P.h[0] + 3) / 4, nimg), block(64, 4);
+    if (channels == 3) hipLaunchKernelGGL(k_load_images_color<3>, grid, block, 0, s, dSrc, stride, pyr, P);
+    else hipLaunchKernelGGL(k_load_images_color<4>, grid, block, 0, s, dSrc, stride, pyr, P);
+}
+
 void launch_resize(hipStream_t s, uint8_t* pyr, const PyrDesc& P, int level, const int2* xtab,
                    const int2* ytab, int nimg) {
     dim3 block(64, 4);

@@ -51,6 +51,9 @@ constexpr int BLUR_RPT = 16;              // rows per thread of k_blur
 constexpr int BLUR_TW = 256, BLUR_TH = 4 * BLUR_RPT;   // output tile of one 256-thread workgroup
 
 void launch_load_images(hipStream_t s, const uint8_t* const* dSrc, int stride, uint8_t* pyr, const PyrDesc& P, int nimg);
+// level 0 from BGR (channels 3) / BGRA (4) sources, converted to gray; same grid and nullptr = keep rule
+void launch_load_images_color(hipStream_t s, const uint8_t* const* dSrc, int stride, int channels, uint8_t* pyr, const PyrDesc& P,
+                              int nimg);
 void launch_resize(hipStream_t s, uint8_t* pyr, const PyrDesc& P, int level, const int2* xtab,
                    const int2* ytab, int nimg);
 void launch_fast(hipStream_t s, const uint8_t* pyr, const PyrDesc& P, const FastDesc& F,

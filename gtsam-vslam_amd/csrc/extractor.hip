@@ -278,6 +278,10 @@ void vslam_extractor::release() {
     if (h_counts) hipHostFree(h_counts);
     if (h_imgPtrs) hipHostFree(h_imgPtrs);
     hipFree(d_imgPtrs); h_imgPtrs = nullptr; d_imgPtrs = nullptr;
+    if (h_colPtrs) hipHostFree(h_colPtrs);
+    hipFree(d_colPtrs); hipFree(d_colStage); h_colPtrs = nullptr; d_colPtrs = nullptr; d_colStage = nullptr; colStageBytes = 0;
+    if (evColPtrs) hipEventDestroy(evColPtrs);
+    evColPtrs = nullptr;
     d_sscTmp = nullptr; d_taskCount = nullptr; d_sscFlags = nullptr; h_counts = nullptr;
     if (evGather) hipEventDestroy(evGather);
     if (evDone) hipEventDestroy(evDone);
@@ -341,6 +345,50 @@ vslam_status vslam_extractor::set_images_device(const uint8_t* const* ptrs, int 
     VS_HIP(hipMemcpyAsync(d_imgPtrs, h_imgPtrs, (size_t)nimg * sizeof(void*), hipMemcpyHostToDevice, stream));
     launch_load_images(stream, d_imgPtrs, stride, d_pyr, P, nimg);
     VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
+vslam_status vslam_extractor::set_images_color(const uint8_t* const* ptrs, int stride, int channels, bool srcOnDevice, bool sync) {
+    if (!ptrs || (channels != 3 && channels != 4) || stride < width * channels) {
+        set_error("set_images_color: channels %d (3 or 4), stride %d (at least width x channels = %d)", channels, stride, width * channels);
+        return VSLAM_ERR_INVALID;
+    }
+    VS_HIP(hipSetDevice(device));
+    if (!h_colPtrs) {
+        VS_HIP(hipHostMalloc((void**)&h_colPtrs, (size_t)nimg * sizeof(void*), hipHostMallocDefault));
+        VS_HIP(hipMalloc((void**)&d_colPtrs, (size_t)nimg * sizeof(void*)));
+        VS_HIP(hipEventCreateWithFlags(&evColPtrs, hipEventDisableTiming));
+    } else {
+        VS_HIP(hipEventSynchronize(evColPtrs));        // the previous table upload has been read before it is overwritten
+    }
+    wait_consumers();
+    int srcStride = stride;
+    if (srcOnDevice) {
+        for (int i = 0; i < nimg; i++) h_colPtrs[i] = ptrs[i];
+    } else {
+        // host sources: one 2D upload per image into the staging buffer (rows padded to 16 bytes: the kernel's vector path)
+        const int pitch = align_up(width * channels, 16);
+        const size_t need = (size_t)nimg * height * pitch;
+        if (need > colStageBytes) {                     // first colour host image, or more channels than before
+            VS_HIP(hipStreamSynchronize(stream));
+            hipFree(d_colStage); d_colStage = nullptr; colStageBytes = 0;
+            VS_HIP(hipMalloc((void**)&d_colStage, need));
+            colStageBytes = need;
+        }
+        for (int i = 0; i < nimg; i++) {
+            h_colPtrs[i] = nullptr;
+            if (!ptrs[i]) continue;
+            uint8_t* dst = d_colStage + (size_t)i * height * pitch;
+            VS_HIP(hipMemcpy2DAsync(dst, pitch, ptrs[i], stride, (size_t)width * channels, height, hipMemcpyHostToDevice, stream));
+            h_colPtrs[i] = dst;
+        }
+        srcStride = pitch;
+    }
+    VS_HIP(hipMemcpyAsync(d_colPtrs, h_colPtrs, (size_t)nimg * sizeof(void*), hipMemcpyHostToDevice, stream));
+    VS_HIP(hipEventRecord(evColPtrs, stream));
+    launch_load_images_color(stream, d_colPtrs, srcStride, channels, d_pyr, P, nimg);
+    VS_HIP(hipGetLastError());
+    if (sync && !srcOnDevice) VS_HIP(hipStreamSynchronize(stream));  // caller may reuse its buffers
     return VSLAM_OK;
 }
 
@@ -521,6 +569,18 @@ vslam_status vslam_extractor_set_image_device(vslam_extractor* ex, int32_t i, co
 vslam_status vslam_extractor_set_image_host(vslam_extractor* ex, int32_t i, const uint8_t* g, int32_t stride) {
     if (!ex) return VSLAM_ERR_INVALID;
     return ex->set_image(i, g, stride, false);
+}
+vslam_status vslam_extractor_set_image_color(vslam_extractor* ex, int32_t i, const void* src, int32_t stride, int32_t channels,
+                                             int32_t on_device) {
+    if (!ex) return VSLAM_ERR_INVALID;
+    if ((channels != 1 && channels != 3 && channels != 4) || i < 0 || i >= ex->nimg || !src || stride < ex->width * channels) {
+        set_error("vslam_extractor_set_image_color: image %d, channels %d (1, 3 or 4), stride %d (at least width x channels)", i, channels, stride);
+        return VSLAM_ERR_INVALID;
+    }
+    if (channels == 1) return ex->set_image(i, src, stride, on_device != 0);
+    std::vector<const uint8_t*> ptrs(ex->nimg, nullptr);
+    ptrs[i] = (const uint8_t*)src;
+    return ex->set_images_color(ptrs.data(), stride, channels, on_device != 0, true);
 }
 vslam_status vslam_extractor_run(vslam_extractor* ex) {
     if (!ex) return VSLAM_ERR_INVALID;

@@ -77,5 +77,12 @@ struct vslam_extractor {
     // all images at once from device buffers (ptrs[i] == nullptr: unchanged): one pointer-table upload + one launch
     vslam_status set_images_device(const uint8_t* const* ptrs, int stride);
     const uint8_t** h_imgPtrs = nullptr; const uint8_t** d_imgPtrs = nullptr;
+    // colour sources (channels 3 / 4): ptrs[i] != nullptr -> level 0 of image i, converted to gray by ONE launch of
+    // k_load_images_color.  Host sources are uploaded into d_colStage first (allocated on the first colour host image,
+    // nimg x h rows of colPitch bytes); sync: return only once the host sources may be reused
+    vslam_status set_images_color(const uint8_t* const* ptrs, int stride, int channels, bool srcOnDevice, bool sync);
+    uint8_t* d_colStage = nullptr; size_t colStageBytes = 0;
+    const uint8_t** h_colPtrs = nullptr; const uint8_t** d_colPtrs = nullptr;
+    hipEvent_t evColPtrs = nullptr;   // the last upload of the colour pointer table has been read
     vslam_status run();
 };

@@ -9,9 +9,10 @@
 //   remap  sx = cvRound(map * 32) (round-half-even), integer part / 5-bit fraction, weights (32-fx)(32-fy) ... x 32 of
 //          scale 2^15 (they sum to 2^15 exactly, so the table normalisation of initInterTab2D never fires), result
 //          (sum + 2^14) >> 15, BORDER_CONSTANT 0 per tap.
-// The reference remaps the 3-channel image imread gives it and converts to gray afterwards; for the gray datasets it
-// supports (EuRoC, KITTI gray) the three channels are equal and BGR2GRAY's weights sum to 2^14, so that equals remapping
-// the gray image (what this entry point takes).
+// The reference remaps the 3-channel image imread gives it and converts to gray afterwards (TrackImage's cvtColor,
+// src/FeatureTracker.cpp:1130-1144).  k_remap_linear_gray does exactly that in one pass: the tap rule above per channel,
+// each channel rounded before BGR(A)2GRAY (bgr_to_gray, common.hpp) - remap-then-convert, which differs from
+// convert-then-remap whenever the channels differ.  k_remap_linear remaps a gray image (channels = 1).
 #include "common.hpp"
 
 namespace vslam {
@@ -57,6 +58,41 @@ __global__ __launch_bounds__(256) void k_remap_linear(const uint8_t* const* __re
         const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
         const int v = px(ix, iy) * w00 + px(ix + 1, iy) * w01 + px(ix, iy + 1) * w10 + px(ix + 1, iy + 1) * w11;
         o |= (unsigned)((v + (1 << 14)) >> 15) << (8 * i);
+    }
+    uint8_t* q = D + (size_t)y * dstStride + x0;
+    if (x0 + 4 <= w && (((uintptr_t)q) & 3) == 0) *(unsigned*)q = o;
+    else for (int i = 0; i < 4 && x0 + i < w; i++) q[i] = (uint8_t)(o >> (8 * i));
+}
+
+// cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) of a BGR (CN = 3) / BGRA (CN = 4) image, then cvtColor(BGR(A)2GRAY); thread = 4
+// horizontally adjacent output pixels, as k_remap_linear.  Out-of-image taps are 0 in every channel.
+template <int CN>
+__global__ __launch_bounds__(256) void k_remap_linear_gray(const uint8_t* const* __restrict__ src, int srcStride, int sw, int sh,
+                                                           const float* __restrict__ mapX, const float* __restrict__ mapY, int w, int h,
+                                                           uint8_t* const* __restrict__ dst, int dstStride) {
+    const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x0 >= w || y >= h) return;
+    const uint8_t* __restrict__ S = src[blockIdx.z];
+    uint8_t* __restrict__ D = dst[blockIdx.z];
+    unsigned o = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int x = x0 + i;
+        if (x >= w) break;
+        const int sx = __float2int_rn(mapX[(size_t)y * w + x] * 32.0f), sy = __float2int_rn(mapY[(size_t)y * w + x] * 32.0f);
+        const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
+        const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+        const bool in0 = (unsigned)ix < (unsigned)sw, in1 = (unsigned)(ix + 1) < (unsigned)sw;
+        const bool r0 = (unsigned)iy < (unsigned)sh, r1 = (unsigned)(iy + 1) < (unsigned)sh;
+        const long long o00 = (long long)iy * srcStride + (long long)ix * CN;     // (read only at taps inside the image)
+        int v[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int a = (r0 && in0) ? (int)S[o00 + c] : 0, b = (r0 && in1) ? (int)S[o00 + CN + c] : 0;
+            const int d = (r1 && in0) ? (int)S[o00 + srcStride + c] : 0, e = (r1 && in1) ? (int)S[o00 + srcStride + CN + c] : 0;
+            v[c] = (a * w00 + b * w01 + d * w10 + e * w11 + (1 << 14)) >> 15;
+        }
+        o |= (unsigned)bgr_to_gray(v[0], v[1], v[2]) << (8 * i);
     }
     uint8_t* q = D + (size_t)y * dstStride + x0;
     if (x0 + 4 <= w && (((uintptr_t)q) & 3) == 0) *(unsigned*)q = o;
@@ -156,6 +192,44 @@ vslam_status vslam_rectifier_remap(vslam_rectifier* r, const uint8_t* const* src
     return VSLAM_OK;
 }
 
+static vslam_status remap_gray_args(const vslam_rectifier* r, const void* src, int32_t src_stride, int32_t channels, const void* dst,
+                                     int32_t dst_stride, int32_t n, const char* fn) {
+    if (!r || !src || !dst || n < 1 || (channels != 1 && channels != 3 && channels != 4) || src_stride < r->sw * channels || dst_stride < r->w) {
+        set_error("%s: channels %d (1, 3 or 4), src_stride %d (at least src_width x channels), dst_stride %d, n %d", fn, channels,
+                  src_stride, dst_stride, n);
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
+// colour (or gray) device images in, gray device images out: remap per channel, then BGR(A)2GRAY, one launch for n images
+vslam_status vslam_rectifier_remap_gray(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, int32_t channels,
+                                        uint8_t* const* dst, int32_t dst_stride, int32_t n) {
+    VS_CHECK(remap_gray_args(r, src, src_stride, channels, dst, dst_stride, n, "vslam_rectifier_remap_gray"));
+    if (channels == 1) return vslam_rectifier_remap(r, src, src_stride, dst, dst_stride, n);
+    VS_HIP(hipSetDevice(r->device));
+    if (2 * n > r->ptrCap) {
+        VS_HIP(hipStreamSynchronize(r->stream));
+        if (r->h_ptrs) hipHostFree(r->h_ptrs);
+        hipFree(r->d_ptrs);
+        r->ptrCap = 2 * n + 16;
+        VS_HIP(hipHostMalloc((void**)&r->h_ptrs, (size_t)r->ptrCap * sizeof(void*), hipHostMallocDefault));
+        VS_HIP(hipMalloc((void**)&r->d_ptrs, (size_t)r->ptrCap * sizeof(void*)));
+    }
+    for (int i = 0; i < n; i++) { r->h_ptrs[i] = src[i]; r->h_ptrs[n + i] = dst[i]; }
+    VS_HIP(hipMemcpyAsync(r->d_ptrs, r->h_ptrs, (size_t)2 * n * sizeof(void*), hipMemcpyHostToDevice, r->stream));
+    const dim3 grid((r->w + 255) / 256, (r->h + 3) / 4, n);
+    if (channels == 3)
+        hipLaunchKernelGGL(k_remap_linear_gray<3>, grid, dim3(256), 0, r->stream, r->d_ptrs, src_stride, r->sw, r->sh, r->d_mapX, r->d_mapY,
+                           r->w, r->h, (uint8_t* const*)(r->d_ptrs + n), dst_stride);
+    else
+        hipLaunchKernelGGL(k_remap_linear_gray<4>, grid, dim3(256), 0, r->stream, r->d_ptrs, src_stride, r->sw, r->sh, r->d_mapX, r->d_mapY,
+                           r->w, r->h, (uint8_t* const*)(r->d_ptrs + n), dst_stride);
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipStreamSynchronize(r->stream));
+    return VSLAM_OK;
+}
+
 // host images in, host images out (what the reference's loop has after cv::imread): one upload, one launch, one download
 vslam_status vslam_rectifier_remap_host(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, uint8_t* const* dst,
                                         int32_t dst_stride, int32_t n) {
@@ -176,6 +250,34 @@ vslam_status vslam_rectifier_remap_host(vslam_rectifier* r, const uint8_t* const
         if (hipMemcpy2D(dst[i], dst_stride, dp[i], r->w, r->w, r->h, hipMemcpyDeviceToHost) != hipSuccess) st = VSLAM_ERR_HIP;
     hipFree(buf);
     if (st == VSLAM_ERR_HIP) set_error("vslam_rectifier_remap_host: copy failed");
+    return st;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+// the same with host images: upload (rows of src_width x channels bytes), one launch, download of the gray results
+vslam_status vslam_rectifier_remap_gray_host(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, int32_t channels,
+                                             uint8_t* const* dst, int32_t dst_stride, int32_t n) {
+    VS_CHECK(remap_gray_args(r, src, src_stride, channels, dst, dst_stride, n, "vslam_rectifier_remap_gray_host"));
+    if (channels == 1) return vslam_rectifier_remap_host(r, src, src_stride, dst, dst_stride, n);
+    VS_HIP(hipSetDevice(r->device));
+    const size_t sRow = (size_t)r->sw * channels, sB = sRow * r->sh, dB = (size_t)r->w * r->h;
+    uint8_t* buf = nullptr;
+    VS_HIP(hipMalloc((void**)&buf, (size_t)n * (sB + dB)));
+    std::vector<const uint8_t*> sp(n);
+    std::vector<uint8_t*> dp(n);
+    vslam_status st = VSLAM_OK;
+    for (int i = 0; i < n && st == VSLAM_OK; i++) {
+        sp[i] = buf + (size_t)i * sB; dp[i] = buf + (size_t)n * sB + (size_t)i * dB;
+        if (hipMemcpy2D((void*)sp[i], sRow, src[i], src_stride, sRow, r->sh, hipMemcpyHostToDevice) != hipSuccess) st = VSLAM_ERR_HIP;
+    }
+    if (st == VSLAM_OK) st = vslam_rectifier_remap_gray(r, sp.data(), (int32_t)sRow, channels, dp.data(), r->w, n);
+    for (int i = 0; i < n && st == VSLAM_OK; i++)
+        if (hipMemcpy2D(dst[i], dst_stride, dp[i], r->w, r->w, r->h, hipMemcpyDeviceToHost) != hipSuccess) st = VSLAM_ERR_HIP;
+    hipFree(buf);
+    if (st == VSLAM_ERR_HIP) set_error("vslam_rectifier_remap_gray_host: copy failed");
     return st;
 }
 

@@ -641,14 +641,18 @@ vslam_status vslam_system::frame_post_b(SysFrameCtx& c, double* T_wc_out, vslam_
     return VSLAM_OK;
 }
 
-vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame,
+vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame,
                                  const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* rep) {
     if (!L || !R || !T_wc_out) return VSLAM_ERR_INVALID;
     SysFrameCtx& c = ctx;
     VS_CHECK(frame_begin(c, frame, imu));
     VS_CHECK(frame_mid());
     // images -> pyramid level 0, extraction, stereo match (extractORBAndStereoMatch :56-70); nothing here depends on the map
-    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
+    if (channels != 1) {        // colour frames (cvtColor :1130-1144): both images converted by one launch
+        std::vector<const uint8_t*> ptrs(fe->nimg, nullptr);
+        ptrs[img0] = L; ptrs[img0 + 1] = R;
+        VS_CHECK(fe->set_images_color(ptrs.data(), stride, channels, onDevice, true));
+    } else if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
     else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
     VS_CHECK(vslam_extractor_run(fe));
     VS_CHECK(fm->stereo_match());
@@ -1173,7 +1177,18 @@ void vslam_system_destroy(vslam_system* s) {
 vslam_status vslam_system_track_stereo(vslam_system* s, const uint8_t* left, const uint8_t* right, int32_t stride, int32_t on_device,
                                        int32_t frame_number, const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* report) {
     if (!s) return VSLAM_ERR_INVALID;
-    return s->track(left, right, stride, on_device != 0, frame_number, imu, T_wc_out, report);
+    return s->track(left, right, stride, 1, on_device != 0, frame_number, imu, T_wc_out, report);
+}
+
+vslam_status vslam_system_track_stereo_color(vslam_system* s, const uint8_t* left, const uint8_t* right, int32_t stride, int32_t channels,
+                                             int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu, double* T_wc_out,
+                                             vslam_frame_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    if ((channels != 1 && channels != 3 && channels != 4) || stride < s->cfg.rig.width * channels) {
+        set_error("vslam_system_track_stereo_color: channels %d (1, 3 or 4), stride %d (at least width x channels)", channels, stride);
+        return VSLAM_ERR_INVALID;
+    }
+    return s->track(left, right, stride, channels, on_device != 0, frame_number, imu, T_wc_out, report);
 }
 
 vslam_status vslam_system_wait_mapping(vslam_system* s) {

@@ -255,7 +255,7 @@ struct vslam_system {
     vslam_status frame_post_b(SysFrameCtx& c, double* T_wc_out, vslam_frame_report* rep);
     void run_mapping();
     void finish_job(vslam_status s, const char* err);
-    vslam_status track(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
+    vslam_status track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame, const vslam_imu_bucket* imu,
                        double* T_wc_out, vslam_frame_report* rep);
     vslam_status fetch_keys(SysKeys& k);
     void mp_update(SysMP& mp, int kfNumb, std::vector<int>& needDesc, int mpIndex);

@@ -56,6 +56,16 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _image(a, h, w):
+    """a host image (h, w) gray, (h, w, 3) BGR or (h, w, 4) BGRA -> (contiguous u8 array, channels, row stride in bytes)"""
+    a = np.ascontiguousarray(a, np.uint8)
+    if a.ndim == 2:         # (gray: what the callers passed before colour input existed, unchecked here)
+        return a, 1, a.shape[1]
+    if a.ndim == 3 and a.shape[2] in (3, 4) and a.shape[:2] == (h, w):
+        return a, a.shape[2], a.strides[0]
+    raise ValueError("image of shape %s: expected (%d, %d), (%d, %d, 3) BGR or (%d, %d, 4) BGRA" % (a.shape, h, w, h, w, h, w))
+
+
 def device_count():
     return int(lib().vslam_device_count())
 
@@ -89,13 +99,20 @@ class Extractor:
         except Exception:
             pass
 
-    def set_image(self, idx, gray):
-        gray = np.ascontiguousarray(gray, np.uint8)
-        assert gray.shape == (self.height, self.width)
-        _chk(self.L.vslam_extractor_set_image_host(self.h, idx, _p(gray), gray.shape[1]))
+    def set_image(self, idx, image):
+        """image: (H, W) gray, (H, W, 3) BGR or (H, W, 4) BGRA u8 (colour: converted to gray on the device)"""
+        img, ch, st = _image(image, self.height, self.width)
+        assert img.shape[:2] == (self.height, self.width)
+        if ch == 1:
+            _chk(self.L.vslam_extractor_set_image_host(self.h, idx, _p(img), st))
+        else:
+            _chk(self.L.vslam_extractor_set_image_color(self.h, idx, _p(img), st, ch, 0))
 
-    def set_image_device(self, idx, dptr, stride):
-        _chk(self.L.vslam_extractor_set_image_device(self.h, idx, C.c_void_p(dptr), stride))
+    def set_image_device(self, idx, dptr, stride, channels=1):
+        if channels == 1:
+            _chk(self.L.vslam_extractor_set_image_device(self.h, idx, C.c_void_p(dptr), stride))
+        else:
+            _chk(self.L.vslam_extractor_set_image_color(self.h, idx, C.c_void_p(dptr), int(stride), int(channels), 1))
 
     def run(self):
         _chk(self.L.vslam_extractor_run(self.h))
@@ -820,8 +837,9 @@ class System:
         except Exception:
             pass
 
-    def track(self, left, right, frame_number, imu_bucket=None, on_device=False, stride=None):
-        """left / right: u8 arrays (host) or device pointers (on_device).  imu_bucket: (acc (n,3), gyro (n,3), timestamps_ns (n))."""
+    def track(self, left, right, frame_number, imu_bucket=None, on_device=False, stride=None, channels=1):
+        """left / right: u8 arrays (host: (H, W) gray, (H, W, 3) BGR or (H, W, 4) BGRA) or device pointers (on_device, with
+        `channels`).  imu_bucket: (acc (n,3), gyro (n,3), timestamps_ns (n))."""
         T = np.zeros((4, 4))
         rep = FrameReport()
         b = None
@@ -831,13 +849,20 @@ class System:
             keep = [acc, gyr, ts]
             b = ImuBucket(len(ts), _p(acc), _p(gyr), _p(ts))
         if on_device:
-            lp, rp, st = C.c_void_p(left), C.c_void_p(right), stride or self.w
+            lp, rp, st, ch = C.c_void_p(left), C.c_void_p(right), stride or self.w * channels, channels
         else:
-            left = np.ascontiguousarray(left, np.uint8); right = np.ascontiguousarray(right, np.uint8)
+            left, ch, st = _image(left, self.h, self.w)
+            right, chr_, _ = _image(right, self.h, self.w)
+            if chr_ != ch or right.strides[0] != st:
+                raise ValueError("left and right images differ in channels")
             keep += [left, right]
-            lp, rp, st = _p(left), _p(right), left.shape[1]
-        _chk(self.L.vslam_system_track_stereo(self.h_sys, lp, rp, st, int(on_device), int(frame_number),
-                                              C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
+            lp, rp = _p(left), _p(right)
+        if ch == 1:
+            _chk(self.L.vslam_system_track_stereo(self.h_sys, lp, rp, st, int(on_device), int(frame_number),
+                                                  C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
+        else:
+            _chk(self.L.vslam_system_track_stereo_color(self.h_sys, lp, rp, int(st), int(ch), int(on_device), int(frame_number),
+                                                        C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
         d = {f[0]: getattr(rep, f[0]) for f in FrameReport._fields_ if f[0] != "ba_report"}
         d["ba_report"] = [dict(iterations=r.iterations, inner=r.inner_iterations, initialError=r.initial_error,
                                finalError=r.final_error, lam=r.lam) for r in rep.ba_report]
@@ -914,18 +939,28 @@ class Rectifier:
         return mx, my
 
     def remap(self, images):
-        """host u8 images (sh x sw each) -> list of rectified host images (h x w)"""
+        """host u8 images (sh x sw gray, or sh x sw x 3 BGR / x 4 BGRA, all alike) -> list of rectified gray host images (h x w)"""
         n = len(images)
-        src = [np.ascontiguousarray(i, np.uint8) for i in images]
+        src = [_image(i, self.sh, self.sw) for i in images]
+        ch, st = src[0][1], src[0][2]
+        if any(c != ch for _, c, _ in src):
+            raise ValueError("remap: images differ in channels")
         dst = [np.zeros((self.h, self.w), np.uint8) for _ in range(n)]
-        sp = (C.c_void_p * n)(*[a.ctypes.data for a in src]); dp = (C.c_void_p * n)(*[a.ctypes.data for a in dst])
-        _chk(self.L.vslam_rectifier_remap_host(self.h_r, sp, self.sw, dp, self.w, n))
+        sp = (C.c_void_p * n)(*[a.ctypes.data for a, _, _ in src]); dp = (C.c_void_p * n)(*[a.ctypes.data for a in dst])
+        if ch == 1:
+            _chk(self.L.vslam_rectifier_remap_host(self.h_r, sp, self.sw, dp, self.w, n))
+        else:
+            _chk(self.L.vslam_rectifier_remap_gray_host(self.h_r, sp, int(st), int(ch), dp, self.w, n))
         return dst
 
-    def remap_device(self, src_ptrs, src_stride, dst_ptrs, dst_stride):
+    def remap_device(self, src_ptrs, src_stride, dst_ptrs, dst_stride, channels=1):
+        """device images: sources gray (channels = 1) or BGR / BGRA, destinations gray"""
         n = len(src_ptrs)
         sp = (C.c_void_p * n)(*src_ptrs); dp = (C.c_void_p * n)(*dst_ptrs)
-        _chk(self.L.vslam_rectifier_remap(self.h_r, sp, int(src_stride), dp, int(dst_stride), n))
+        if channels == 1:
+            _chk(self.L.vslam_rectifier_remap(self.h_r, sp, int(src_stride), dp, int(dst_stride), n))
+        else:
+            _chk(self.L.vslam_rectifier_remap_gray(self.h_r, sp, int(src_stride), int(channels), dp, int(dst_stride), n))
 
     def close(self):
         if self.h_r:
@@ -1037,24 +1072,71 @@ class Batch:
         except Exception:
             pass
 
-    def track(self, lefts, rights, frame_numbers, imu_buckets=None, mask=None, on_device=False, stride=None):
-        """lefts / rights: per-lane u8 arrays (host) or device pointers; imu_buckets: per-lane (acc, gyro, ts) or None entries."""
+    def _images(self, lefts, rights, mask, on_device, stride, channels, keep):
+        """per-lane pointer tables, row stride and channels (host arrays: (H, W), (H, W, 3) BGR or (H, W, 4) BGRA, all alike)"""
         B = self.lanes
-        T = np.zeros((B, 4, 4))
-        reps = (FrameReport * B)()
-        keep = []
         lp = (C.c_void_p * B)(); rp = (C.c_void_p * B)()
-        st = stride or self.w
+        st, ch = stride or self.w * channels, channels
+        seen = set()
         for b in range(B):
             if mask is not None and not mask[b]:
                 continue
             if on_device:
                 lp[b], rp[b] = lefts[b], rights[b]
             else:
-                l = np.ascontiguousarray(lefts[b], np.uint8); r = np.ascontiguousarray(rights[b], np.uint8)
+                l, cl, sl = _image(lefts[b], self.h, self.w); r, cr, sr = _image(rights[b], self.h, self.w)
+                seen |= {(cl, sl), (cr, sr)}
                 keep += [l, r]
                 lp[b], rp[b] = l.ctypes.data, r.ctypes.data
-                st = l.shape[1]
+                ch, st = cl, sl
+        if len(seen) > 1:
+            raise ValueError("Batch.track: the lanes' images differ in channels")
+        return lp, rp, st, ch
+
+    def track(self, lefts, rights, frame_numbers, imu_buckets=None, mask=None, on_device=False, stride=None, channels=1):
+        """lefts / rights: per-lane u8 arrays (host: gray, BGR or BGRA) or device pointers (with `channels`); imu_buckets:
+        per-lane (acc, gyro, ts) or None entries."""
+        B = self.lanes
+        T = np.zeros((B, 4, 4))
+        reps = (FrameReport * B)()
+        keep = []
+        lp, rp, st, ch = self._images(lefts, rights, mask, on_device, stride, channels, keep)
+        bk = self._buckets(imu_buckets, keep)
+        fr = np.ascontiguousarray(frame_numbers, np.int32)
+        mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
+        if ch == 1:
+            _chk(self.L.vslam_batch_track_stereo(self.h_b, lp, rp, int(st), int(on_device), _p(fr), bk, _p(mk) if mk is not None else None,
+                                                 _p(T), reps))
+        else:
+            _chk(self.L.vslam_batch_track_stereo_color(self.h_b, lp, rp, int(st), int(ch), int(on_device), _p(fr), bk,
+                                                       _p(mk) if mk is not None else None, _p(T), reps))
+        return T, [_report_dict(reps[b]) for b in range(B)]
+
+    def track_prefetch(self, lefts, rights, frame_numbers, next_lefts=None, next_rights=None, imu_buckets=None, mask=None,
+                       next_mask=None, stride=None, channels=1):
+        """device images of this step and (optionally) of the next one, whose extraction then starts under this step's host
+        phases; the next call must pass exactly those pointers and channels to use it"""
+        B = self.lanes
+        T = np.zeros((B, 4, 4))
+        reps = (FrameReport * B)()
+        keep = []
+        lp, rp, st, ch = self._images(lefts, rights, mask, True, stride, channels, keep)
+        nl = nr = None
+        if next_lefts is not None:
+            nl, nr, _, _ = self._images(next_lefts, next_rights, next_mask, True, stride, channels, keep)
+        bk = self._buckets(imu_buckets, keep)
+        fr = np.ascontiguousarray(frame_numbers, np.int32)
+        mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
+        nmk = np.ascontiguousarray(next_mask, np.uint8) if next_mask is not None else None
+        args = (_p(fr), bk, _p(mk) if mk is not None else None, _p(T), reps, nl, nr, _p(nmk) if nmk is not None else None)
+        if ch == 1:
+            _chk(self.L.vslam_batch_track_stereo_prefetch(self.h_b, lp, rp, int(st), *args))
+        else:
+            _chk(self.L.vslam_batch_track_stereo_prefetch_color(self.h_b, lp, rp, int(st), int(ch), *args))
+        return T, [_report_dict(reps[b]) for b in range(B)]
+
+    def _buckets(self, imu_buckets, keep):
+        B = self.lanes
         bk = None
         if imu_buckets is not None:
             bk = (ImuBucket * B)()
@@ -1064,11 +1146,7 @@ class Batch:
                 acc, gyr, ts = (np.ascontiguousarray(a, np.float64) for a in imu_buckets[b])
                 keep += [acc, gyr, ts]
                 bk[b] = ImuBucket(len(ts), acc.ctypes.data, gyr.ctypes.data, ts.ctypes.data)
-        fr = np.ascontiguousarray(frame_numbers, np.int32)
-        mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
-        _chk(self.L.vslam_batch_track_stereo(self.h_b, lp, rp, int(st), int(on_device), _p(fr), bk, _p(mk) if mk is not None else None,
-                                             _p(T), reps))
-        return T, [_report_dict(reps[b]) for b in range(B)]
+        return bk
 
     def system(self, lane):
         return _BorrowedSystem(self.L, self.L.vslam_batch_system(self.h_b, lane))

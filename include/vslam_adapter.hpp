@@ -8,7 +8,10 @@
 //   * default              : POD containers (std::vector<vslam_keypoint>, std::vector<uint8_t>) — compiles
 //                            anywhere (this is what the repository's CPU build check compiles);
 //   * -DVSLAM_WITH_OPENCV  : adds the cv::Mat / cv::KeyPoint overloads with the reference's exact
-//                            signatures (needs OpenCV + Eigen, which this image does not have; untested here).
+//                            signatures (needs OpenCV + Eigen; tests/native/adapter_color.cpp compiles this branch
+//                            against a minimal stand-in of the two headers and runs it on the GPU).
+// Colour frames (cv::imread IMREAD_COLOR in the reference's loop) are converted to gray on the device: the cv::Mat
+// overloads dispatch on channels() as TrackImage does (src/FeatureTracker.cpp:1130-1144), the POD forms take `channels`.
 #pragma once
 #include <chrono>
 #include <cstring>
@@ -142,6 +145,15 @@ class FeatureExtractor {
         else return;   // the last image of the batch triggers the launches for all of them
         fetch(index, keypoints, descriptors);
     }
+    // the same for a gray (channels = 1), BGR (3) or BGRA (4) image; colour is converted to gray on the device first
+    void extractKeysNewChannels(const uint8_t* image, int stride, int channels, std::vector<vslam_keypoint>& keypoints,
+                                std::vector<uint8_t>& descriptors, int index = 0) {
+        if (!h_) throw std::runtime_error("FeatureExtractor: not bound to an image size yet (FeatureMatcher / FeatureTracker bind it)");
+        vs_check(vslam_extractor_set_image_color(h_, index, image, stride, channels, 0), "set_image_color");
+        if (index == batch_ - 1) vs_check(vslam_extractor_run(h_), "extractor_run");
+        else return;
+        fetch(index, keypoints, descriptors);
+    }
     void fetch(int index, std::vector<vslam_keypoint>& keypoints, std::vector<uint8_t>& descriptors) {
         int32_t n = 0;
         vs_check(vslam_extractor_count(h_, index, &n), "extractor_count");
@@ -151,11 +163,13 @@ class FeatureExtractor {
         vs_check(vslam_extractor_fetch(h_, index, keypoints.data(), descriptors.data(), n, &n), "extractor_fetch");
     }
 #ifdef VSLAM_WITH_OPENCV
-    // the reference signature: void extractKeysNew(cv::Mat& image, std::vector<cv::KeyPoint>&, cv::Mat& desc)
+    // the reference signature: void extractKeysNew(cv::Mat& image, std::vector<cv::KeyPoint>&, cv::Mat& desc); 8-bit images
+    // of 1, 3 (BGR) or 4 (BGRA) channels
     void extractKeysNew(cv::Mat& image, std::vector<cv::KeyPoint>& keypoints, cv::Mat& descriptors, int index = 0) {
+        if (image.depth() != CV_8U) throw std::runtime_error("extractKeysNew: the image is not 8-bit");
         std::vector<vslam_keypoint> k;
         std::vector<uint8_t> d;
-        extractKeysNew(image.ptr<uint8_t>(), (int)image.step, k, d, index);
+        extractKeysNewChannels(image.ptr<uint8_t>(), (int)image.step, image.channels(), k, d, index);
         if (k.empty()) return;
         keypoints.resize(k.size());
         for (size_t i = 0; i < k.size(); i++)
@@ -310,9 +324,29 @@ class FeatureTracker {
                                            IMUDataptr ? &b : nullptr, lastPose, &lastReport), "vslam_system_track_stereo");
         if (zedPtr) std::memcpy(zedPtr->mCameraPose.pose, lastPose, sizeof(lastPose));      // zedPtr->mCameraPose (updatePoses :1699-1708)
     }
+    // the same for gray (channels = 1), BGR (3) or BGRA (4) images: colour is converted to gray on the device, as TrackImage's
+    // cvtColor does (src/FeatureTracker.cpp:1130-1144).  (Its own name: an int overload of TrackImage would make a literal 0
+    // frame number ambiguous against the shared_ptr argument.)
+    void TrackImageChannels(const uint8_t* leftRect, const uint8_t* rightRect, int stride, int channels, const int frameNumb,
+                            std::shared_ptr<IMUData> IMUDataptr = nullptr, bool onDevice = false) {
+        vslam_imu_bucket b{};
+        if (IMUDataptr) b = IMUDataptr->bucket();
+        vs_check(vslam_system_track_stereo_color(map->handle(), leftRect, rightRect, stride, channels, onDevice ? 1 : 0, frameNumb,
+                                                 IMUDataptr ? &b : nullptr, lastPose, &lastReport), "vslam_system_track_stereo_color");
+        if (zedPtr) std::memcpy(zedPtr->mCameraPose.pose, lastPose, sizeof(lastPose));
+    }
 #ifdef VSLAM_WITH_OPENCV
+    // the reference signature (include/FeatureTracker.h:90): 8-bit images of 1, 3 (BGR) or 4 (BGRA) channels, dispatched on
+    // channels() as src/FeatureTracker.cpp:1130-1144 does; left and right must agree in size, channels and row stride
     void TrackImage(const cv::Mat& leftRect, const cv::Mat& rightRect, const int frameNumb, std::shared_ptr<IMUData> IMUDataptr = nullptr) {
-        TrackImage(leftRect.ptr<uint8_t>(), rightRect.ptr<uint8_t>(), (int)leftRect.step, frameNumb, IMUDataptr);
+        if (leftRect.depth() != CV_8U || rightRect.depth() != CV_8U) throw std::runtime_error("TrackImage: images are not 8-bit");
+        if (leftRect.rows != rightRect.rows || leftRect.cols != rightRect.cols || leftRect.channels() != rightRect.channels() ||
+            (size_t)leftRect.step != (size_t)rightRect.step)
+            throw std::runtime_error("TrackImage: left and right images differ in size, channels or row stride");
+        const int cn = leftRect.channels();
+        if (cn != 1 && cn != 3 && cn != 4) throw std::runtime_error("TrackImage: images of 1, 3 (BGR) or 4 (BGRA) channels only");
+        if (cn == 1) TrackImage(leftRect.ptr<uint8_t>(), rightRect.ptr<uint8_t>(), (int)leftRect.step, frameNumb, IMUDataptr);
+        else TrackImageChannels(leftRect.ptr<uint8_t>(), rightRect.ptr<uint8_t>(), (int)leftRect.step, cn, frameNumb, IMUDataptr);
     }
 #endif
     // matchesIdxs / MPsOutliers of the last tracked frame (FeatureTracker's locals that System.cpp draws)

@@ -91,6 +91,15 @@ vslam_status vslam_extractor_set_image_device(vslam_extractor* ex, int32_t image
                                               const void* d_gray, int32_t stride);
 vslam_status vslam_extractor_set_image_host(vslam_extractor* ex, int32_t image_index,
                                             const uint8_t* gray, int32_t stride);
+/* Colour frames, as the reference's TrackImage receives them from cv::imread(IMREAD_COLOR) (src/VIOSlam.cpp:289-311) and
+ * converts first (cvtColor BGR2GRAY / BGRA2GRAY, src/FeatureTracker.cpp:1130-1144): image `image_index` from interleaved
+ * BGR (channels = 3) or BGRA (4, alpha ignored) bytes, `stride` bytes per row (at least width x channels), converted to
+ * gray on the device while pyramid level 0 is written (gray = (1868 B + 9617 G + 4899 R + 8192) >> 14).  channels = 1 is
+ * set_image_device / set_image_host.  Host sources are staged in a device buffer the extractor allocates on its first
+ * colour host image; returns once the caller may reuse `src`.  Anything but channels 1 / 3 / 4 or a short stride:
+ * VSLAM_ERR_INVALID before any work is queued. */
+vslam_status vslam_extractor_set_image_color(vslam_extractor* ex, int32_t image_index, const void* src, int32_t stride,
+                                             int32_t channels, int32_t on_device);
 vslam_status vslam_extractor_run(vslam_extractor* ex);
 vslam_status vslam_extractor_count(const vslam_extractor* ex, int32_t image_index, int32_t* n_out);
 vslam_status vslam_extractor_fetch(vslam_extractor* ex, int32_t image_index, vslam_keypoint* kps,
@@ -644,6 +653,13 @@ void vslam_system_destroy(vslam_system* sys);
 vslam_status vslam_system_track_stereo(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
                                        int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
                                        double* T_wc_out, vslam_frame_report* report);
+/* the same for colour frames: what VSlamSystem::TrackStereo / TrackStereoIMU receive from the reference's frame loop
+ * (src/VIOSlam.cpp:289-311: imread IMREAD_COLOR, remap, Track*) and TrackImage converts (src/FeatureTracker.cpp:1130-1144).
+ * channels = 3 (BGR) or 4 (BGRA): both images converted to gray on the device by one launch before extraction; channels = 1
+ * is vslam_system_track_stereo.  stride >= width x channels, else VSLAM_ERR_INVALID with nothing tracked. */
+vslam_status vslam_system_track_stereo_color(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
+                                             int32_t channels, int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
+                                             double* T_wc_out, vslam_frame_report* report);
 /* blocks until the device work of the pass in flight (local_mapping = 2) has finished; reports its failure, if any.
  * (Its results are still applied at the frames the schedule names.) */
 vslam_status vslam_system_wait_mapping(vslam_system* sys);
@@ -695,6 +711,17 @@ vslam_status vslam_batch_track_stereo_prefetch(vslam_batch* batch, const uint8_t
                                                const int32_t* frame_numbers, const vslam_imu_bucket* imu, const uint8_t* lane_mask,
                                                double* T_wc_out, vslam_frame_report* reports, const uint8_t* const* next_left,
                                                const uint8_t* const* next_right, const uint8_t* next_mask);
+/* the two entry points above for colour frames (channels = 3 BGR / 4 BGRA, after stride; 1 = the gray entry points):
+ * every active lane's pair converted to gray by one launch (host images: all lanes' uploads, one wait, one launch).  A
+ * prefetch is used by the next call only if it passes exactly those pointers with the same channels. */
+vslam_status vslam_batch_track_stereo_color(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                            int32_t channels, int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                            const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports);
+vslam_status vslam_batch_track_stereo_prefetch_color(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right,
+                                                     int32_t stride, int32_t channels, const int32_t* frame_numbers,
+                                                     const vslam_imu_bucket* imu, const uint8_t* lane_mask, double* T_wc_out,
+                                                     vslam_frame_report* reports, const uint8_t* const* next_left,
+                                                     const uint8_t* const* next_right, const uint8_t* next_mask);
 /* a lane's session (borrowed: valid until vslam_batch_destroy) for the vslam_system_* read-outs */
 vslam_system* vslam_batch_system(vslam_batch* batch, int32_t lane);
 int32_t vslam_batch_lanes(const vslam_batch* batch);
@@ -777,6 +804,14 @@ vslam_status vslam_rectifier_remap(vslam_rectifier* r, const uint8_t* const* src
 /* the same with HOST images (upload, one launch, download) */
 vslam_status vslam_rectifier_remap_host(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, uint8_t* const* dst,
                                         int32_t dst_stride, int32_t n);
+/* colour images, as the reference remaps them (src/VIOSlam.cpp:296-297: cv::remap of the 3-channel imread image, cvtColor
+ * afterwards in TrackImage, src/FeatureTracker.cpp:1130-1144): remap each channel of BGR (channels = 3) / BGRA (4) sources
+ * (src_stride >= src_width x channels), round it, then convert to gray, in one pass; dst: gray (dst_stride >= width).
+ * channels = 1 is vslam_rectifier_remap / _remap_host.  Device and host forms; synchronous. */
+vslam_status vslam_rectifier_remap_gray(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, int32_t channels,
+                                        uint8_t* const* dst, int32_t dst_stride, int32_t n);
+vslam_status vslam_rectifier_remap_gray_host(vslam_rectifier* r, const uint8_t* const* src, int32_t src_stride, int32_t channels,
+                                             uint8_t* const* dst, int32_t dst_stride, int32_t n);
 
 /* vslam_dataset: EuRoC (kind 0: <images_path>cam0/data.csv + cam0/data/, cam1/data/) or KITTI (kind 1: image_0/, image_1/,
  * names by .png count); imu_path: directory with data.csv (timestamp, w_xyz, a_xyz) or NULL.  Host only. */
