@@ -122,6 +122,9 @@ __device__ __forceinline__ bool ba_enter(BaDev& D, int state, int c = 0) {
 constexpr int BA_SCHUR_WAVES = 16;         // max landmarks in flight per workgroup (one per wave): the LDS copy of S is
                                            // zeroed / written out once per group; the host picks 16, 8 or 4 to fit the LDS
 constexpr int BA_LDS_MAX_F = 20;          // (6F)^2 doubles must fit next to the W staging in 160 KB
+// A workgroup gets 160 KB of LDS, static and dynamic together.  The batch's kernels with dynamic LDS have (almost) no static LDS:
+// its plan keeps BA_STATIC_LDS_RESERVE bytes for it, and ba_kernel_attributes checks the code objects against the reserve.
+constexpr int BA_LDS_BYTES = 160 * 1024, BA_STATIC_LDS_RESERVE = 1024, BA_DYN_LDS_MAX = BA_LDS_BYTES - BA_STATIC_LDS_RESERVE;
 
 // whitened residual / Jacobians of one projection factor (cheirality: constant 2*fx residual)
 __device__ __forceinline__ void ba_eval_fac(const BaDev& D, const DPose& T, const double* p, bool right,
@@ -2655,19 +2658,23 @@ struct BaPassHost {
 static vslam_status ba_kernel_attributes() {
     static std::once_flag once;
     static hipError_t err = hipSuccess;
+    static bool reserveOk = true;
     std::call_once(once, [] {
-        const int cap = 160 * 1024;
+        const int cap = BA_LDS_BYTES;
         const void* fns[] = {(const void*)k_ba_schur, (const void*)k_ba_schur_win, (const void*)k_ba_solve, (const void*)k_ba_back,
                              (const void*)k_ba_solve_mfma, (const void*)k_ba_chol_col, (const void*)k_ba_chol_back, (const void*)k_ba_lm_prep,
                              (const void*)k_ba_schur2, (const void*)k_ba_back2};
+        const void* batchFns[] = {(const void*)k_ba_schur, (const void*)k_ba_schur2, (const void*)k_ba_back, (const void*)k_ba_back2, (const void*)k_ba_solve_mfma};
         for (const void* f : fns) {
             hipFuncAttributes fa{};      // (the limit is on static + dynamic LDS together)
             hipError_t e = hipFuncGetAttributes(&fa, f);
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cap - (int)fa.sharedSizeBytes);
             if (e != hipSuccess && err == hipSuccess) err = e;
+            for (const void* b : batchFns) if (b == f && e == hipSuccess && fa.sharedSizeBytes > (size_t)BA_STATIC_LDS_RESERVE) reserveOk = false;
         }
     });
     if (err != hipSuccess) { set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(err)); return VSLAM_ERR_HIP; }
+    if (!reserveOk) { set_error("local BA: a batch kernel's static LDS exceeds BA_STATIC_LDS_RESERVE"); return VSLAM_ERR_CAPACITY; }
     return VSLAM_OK;
 }
 
@@ -3435,9 +3442,97 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
 // one-problem path.
 static std::atomic<long long> g_bbsNs[12], g_bbsCalls{0}, g_bbsPolls{0};
 static const char* g_bbsName[12] = {"check+count", "arena fill", "tables+upload", "lm pass 1", "chi2 1", "second-pass prep", "lm pass 2", "chi2 2 + fetch", "results", nullptr, nullptr, nullptr};
+
+// ---- launch plan of the batch: a pure function of the cohort's shape (no device calls; exported as vslam_local_ba_batch_plan) -----
+struct BaPlanKnobs { bool schur2, back2, sharedW; int s2Waves, b2Waves, schurWaves, lmBlocks; };
+static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the environment (none set: the production plan)
+    static const bool s2Env = !(getenv("VSLAM_BA_SCHUR2") && atoi(getenv("VSLAM_BA_SCHUR2")) == 0);
+    static const bool b2Env = !(getenv("VSLAM_BA_BACK2") && atoi(getenv("VSLAM_BA_BACK2")) == 0);
+    BaPlanKnobs k;
+    k.schur2 = s2Env; k.back2 = b2Env;
+    k.sharedW = getenv("VSLAM_BA_SCHUR_SHARED") ? atoi(getenv("VSLAM_BA_SCHUR_SHARED")) != 0 : true;
+    k.schurWaves = getenv("VSLAM_BA_SCHUR_WAVES_B") ? atoi(getenv("VSLAM_BA_SCHUR_WAVES_B")) : 0;
+    k.lmBlocks = getenv("VSLAM_BA_LMBLOCKS") ? atoi(getenv("VSLAM_BA_LMBLOCKS")) : 0;
+    // (alone on the GPU 8 / 12 / 16 waves per workgroup take the same time; between the lockstep groups' wide kernels the smaller LDS footprint
+    //  finds a CU sooner: 8 waves here, 4 for the back-substitution - ba_back 15.7 -> 10.6 us per tracked frame)
+    k.s2Waves = getenv("VSLAM_BA_SCHUR2_WAVES") ? atoi(getenv("VSLAM_BA_SCHUR2_WAVES")) : 8;
+    k.b2Waves = getenv("VSLAM_BA_BACK2_WAVES") ? atoi(getenv("VSLAM_BA_BACK2_WAVES")) : 4;
+    return k;
+}
+static inline int ba_batch_solve_kind(int n, bool useMfma) { return (n <= 64 && useMfma) ? BA_SOLVE_MFMA64 : n <= BA_WAVE_N ? BA_SOLVE_WAVE : BA_SOLVE_MFMA; }
+// problems outside the batched class (the LDS solve lives in the one-problem path; empty graphs; another rig)
+static inline bool ba_batch_single(const vslam_ba_lane_shape& s, bool useMfma) {
+    return s.own_rig || s.n_free_kf > BA_LDS_MAX_F || s.n_free_kf <= 0 || s.n_factors <= 0 || s.n_pairs <= 0 || (!useMfma && 6 * s.n_free_kf > BA_WAVE_N);
+}
+static void ba_batch_plan(const vslam_ba_batch_shape& S, const BaPlanKnobs& kn, vslam_ba_batch_plan& p) {
+    p = vslam_ba_batch_plan{};
+    const int NB = std::max(1, std::min((int)BA_MAX_NB, (int)S.lookahead));
+    const bool useMfma = S.solver == 0;
+    p.status = VSLAM_OK; p.lookahead = NB;
+    int maxSlots = 1, maxFac = 1, fMax = 0, lpMax = 0, NL = 0;
+    for (int i = 0; i < S.n_lanes; i++) {
+        const vslam_ba_lane_shape& s = S.lanes[i];
+        if (ba_batch_single(s, useMfma)) { p.n_single++; continue; }
+        NL++;
+        maxSlots = std::max(maxSlots, (int)s.max_slots); maxFac = std::max(maxFac, (int)s.max_factors);
+        fMax = std::max(fMax, (int)s.n_free_kf); lpMax = std::max(lpMax, (int)s.n_points);
+        p.solve_kinds |= 1 << ba_batch_solve_kind(6 * s.n_free_kf, useMfma);
+    }
+    p.n_batch = NL; p.f_max = fMax; p.max_slots = maxSlots; p.max_factors = maxFac; p.lp_max = lpMax;
+    if (NL == 0) { p.solve_kinds = 0; return; }
+    const int nCU = 256, nMax = 6 * fMax;
+    const size_t sysMax = (size_t)nMax * nMax + nMax;
+    // k_ba_schur: a wave per landmark, W staging by slots; one workgroup for all lambda candidates (sharedW) when NB copies of the
+    // system fit next to the staging
+    constexpr int SCHUR_LPW = 64 / BA_LPL_SCHUR, BACK_LPW = 64 / BA_LPL_BACK;
+    auto stage_lds = [&](int nw) { return (size_t)nw * SCHUR_LPW * 2 * maxSlots * 18 * sizeof(double) + (size_t)nw * SCHUR_LPW * maxSlots * sizeof(int) + 16; };
+    auto schur_lds = [&](int nw, int copies) { return copies * sysMax * sizeof(double) + stage_lds(nw); };
+    int sharedW = 0, schurWaves = BA_SCHUR_WAVES;
+    if (NB > 1 && kn.sharedW) for (int nw : {16, 12, 8, 6, 4, 2}) if (schur_lds(nw, NB) <= 150 * 1024) { sharedW = 1; schurWaves = nw; break; }
+    if (!sharedW) { if (kn.schurWaves) schurWaves = kn.schurWaves; while (schurWaves > 2 && schur_lds(schurWaves, 1) > 150 * 1024) schurWaves /= 2; }
+    const size_t schurLds = schur_lds(schurWaves, sharedW ? NB : 1);
+    const int schurUnits = schurWaves * SCHUR_LPW;
+    int lmBlocks = std::max(1, std::min((lpMax + schurUnits - 1) / schurUnits, kn.lmBlocks ? kn.lmBlocks : std::max(16, 2 * nCU / NL)));
+    // k_ba_schur2 (tracker windows): one LDS copy of the system + a staging region per landmark-wave
+    const size_t s2StageB = (size_t)ba2_stage_doubles(maxFac, maxSlots) * sizeof(double);
+    int s2Waves = std::max(2, std::min(16, kn.s2Waves));
+    while (s2Waves > 2 && sysMax * sizeof(double) + s2Waves * s2StageB > 156 * 1024) s2Waves /= 2;
+    const size_t s2Lds = sysMax * sizeof(double) + (size_t)s2Waves * s2StageB;
+    const bool useSchur2 = kn.schur2 && fMax <= BA2_MAX_F && maxSlots <= BA2_MAX_F && s2Lds <= 156 * 1024;
+    // (the kernel is a latency chain per landmark-wave: every workgroup of the cohort resident at once - one per CU at this LDS size -,
+    //  each wave walks a few landmarks)
+    if (useSchur2) lmBlocks = std::max(1, std::min((lpMax + 2 * s2Waves - 1) / (2 * s2Waves), kn.lmBlocks ? kn.lmBlocks : std::max(4, (16 / s2Waves) * nCU / NL)));
+    // k_ba_back2 holds b2Waves staging regions and no system: that k_ba_schur2 fits does not make it fit (4 regions of a landmark with
+    // ~120-200 stereo views exceed 160 KB where 2 regions + the system do not), so it halves its own waves until the launch fits
+    int b2Waves = std::max(1, std::min(8, kn.b2Waves));
+    while (b2Waves > 1 && (size_t)b2Waves * s2StageB > BA_DYN_LDS_MAX) b2Waves /= 2;
+    const size_t b2Lds = (size_t)b2Waves * s2StageB;
+    const bool useBack2 = useSchur2 && kn.back2 && b2Lds <= BA_DYN_LDS_MAX;
+    int backWaves = BA_SCHUR_WAVES / BACK_LPW;
+    auto back_lds = [&](int nw) { return (size_t)nw * BACK_LPW * maxSlots * 18 * sizeof(double) + (size_t)nw * BACK_LPW * maxSlots * sizeof(int) + 16; };
+    while (backWaves > 1 && back_lds(backWaves) > 150 * 1024) backWaves /= 2;
+    p.schur_kernel = useSchur2 ? VSLAM_BA_KERNEL_SCHUR2 : VSLAM_BA_KERNEL_SCHUR;
+    p.schur_waves = useSchur2 ? s2Waves : schurWaves;
+    p.schur_shared_w = useSchur2 ? 0 : sharedW;
+    p.schur_blocks = lmBlocks;
+    p.schur_lds = (int)(useSchur2 ? s2Lds : schurLds);
+    p.back_kernel = useBack2 ? VSLAM_BA_KERNEL_BACK2 : VSLAM_BA_KERNEL_BACK;
+    if (useBack2) {
+        p.back_waves = b2Waves; p.back_shared = 1; p.back_lds = (int)b2Lds;
+        p.back_blocks = std::max(1, std::min((lpMax + 2 * b2Waves - 1) / (2 * b2Waves), std::max(8, (16 / b2Waves) * nCU / NL)));
+    } else {
+        p.back_waves = backWaves; p.back_shared = NB > 1 ? 1 : 0; p.back_lds = (int)back_lds(backWaves);
+        p.back_blocks = std::max(1, std::min((lpMax + backWaves * BACK_LPW - 1) / (backWaves * BACK_LPW), std::max(16, 2 * nCU / NL)));
+    }
+    p.solve_lds = (p.solve_kinds & (1 << BA_SOLVE_MFMA)) ? (int)(((size_t)BA_MFMA_N * BA_MFMA_LD + 16 + BA_MFMA_N) * sizeof(double)) : 0;
+    if (p.schur_lds > BA_DYN_LDS_MAX || p.back_lds > BA_DYN_LDS_MAX || p.solve_lds > BA_DYN_LDS_MAX) p.status = VSLAM_ERR_CAPACITY;
+}
+thread_local vslam_ba_batch_plan g_baLastPlan{};
+
 static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_result* const* Rs, int N, int device) {
+    g_baLastPlan = vslam_ba_batch_plan{};
     if (N <= 0 || !Ps || !Rs) return VSLAM_ERR_INVALID;
-    if (N == 1) return ba_run(Ps[0], Rs[0], device, nullptr);
+    if (N == 1) { g_baLastPlan.n_single = 1; return ba_run(Ps[0], Rs[0], device, nullptr); }
     auto bbs_t = std::chrono::steady_clock::now();
     g_bbsCalls++;
     auto BBS = [&](int k) { const auto t_ = std::chrono::steady_clock::now(); g_bbsNs[k] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - bbs_t).count(); bbs_t = t_; };
@@ -3485,7 +3580,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
 
     struct Lane {
         const vslam_ba_problem* P; vslam_ba_result* R; int K, L, NP;
-        std::vector<DPose> pose0; BaHostTmp T; BaPassHost H; bool single = false;
+        std::vector<DPose> pose0; BaHostTmp T; BaPassHost H; bool single = false, ownRig = false;
         std::vector<uint8_t> wrong;
         // constants of the call in the arena
         DPose* h_pose0; double* h_lm0; int *h_pairKf, *h_pairLm, *h_pairOct; uint8_t *h_pairFlags, *h_kfLocal; float* h_pairUv;
@@ -3497,6 +3592,12 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         bool pass2 = false;
     };
     std::vector<Lane> lanes(N);
+    auto lane_shape = [](const Lane& q) {      // (max_slots / max_factors are known after the fill)
+        vslam_ba_lane_shape s{};
+        s.n_free_kf = q.H.F; s.n_points = q.H.Lp; s.n_factors = q.H.NF; s.n_edges = q.H.NE; s.n_pairs = q.NP;
+        s.max_slots = q.H.maxSlots; s.max_factors = q.H.maxFac; s.own_rig = q.ownRig ? 1 : 0;
+        return s;
+    };
     std::vector<int> singles;
     for (int i = 0; i < N; i++) {
         Lane& q = lanes[i];
@@ -3513,7 +3614,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
             if (P->pair_kf[p] < 0 || P->pair_kf[p] >= q.K || P->pair_lm[p] < 0 || P->pair_lm[p] >= q.L ||
                 P->pair_octave[2 * p] < 0 || P->pair_octave[2 * p] >= P->n_levels || P->pair_octave[2 * p + 1] < 0 ||
                 P->pair_octave[2 * p + 1] >= P->n_levels) { set_error("vslam_local_ba_batch: pair index out of range (problem %d)", i); return VSLAM_ERR_INVALID; }
-        if (memcmp(&P->rig, &Ps[0]->rig, sizeof(P->rig)) || P->n_levels != Ps[0]->n_levels) q.single = true;      // (per-lane rigs would work; not needed)
+        q.ownRig = memcmp(&P->rig, &Ps[0]->rig, sizeof(P->rig)) || P->n_levels != Ps[0]->n_levels;      // (per-lane rigs would work; not needed)
         q.wrong.assign(std::max(q.NP, 1), 0);
         q.pose0.resize(q.K);
         for (int k = 0; k < q.K; k++) pose_from_rm16(P->kf_pose_wc + 16 * (size_t)k, q.pose0[k]);
@@ -3522,14 +3623,19 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     W.pool.run(N, [&](int i) {
         Lane& q = lanes[i];
         q.H.count(q.P, q.wrong.data(), 0, 1, q.T);
-        if (q.H.F > BA_LDS_MAX_F || q.H.n <= 0 || q.H.NF <= 0 || q.NP <= 0 || (!useMfma && q.H.n > BA_WAVE_N)) q.single = true;      // (the LDS solve lives in the one-problem path)
+        q.single = ba_batch_single(lane_shape(q), useMfma);
     });
     std::vector<int> act;
     for (int i = 0; i < N; i++) (lanes[i].single ? singles : act).push_back(i);
     const int NL = (int)act.size();
     BBS(0);
     auto run_singles = [&]() -> vslam_status { for (int i : singles) VS_CHECK(ba_run(Ps[i], Rs[i], device, nullptr)); return VSLAM_OK; };
-    if (NL == 0) return run_singles();
+    auto plan_cohort = [&]() {
+        std::vector<vslam_ba_lane_shape> shapes(N);
+        for (int i = 0; i < N; i++) shapes[i] = lane_shape(lanes[i]);
+        ba_batch_plan(vslam_ba_batch_shape{N, shapes.data(), NB, useMfma ? 0 : 1}, ba_plan_knobs(), g_baLastPlan);
+    };
+    if (NL == 0) { plan_cohort(); return run_singles(); }
     auto& A = W.arena;
     size_t arenaBytes = 8192 + (size_t)NL * (CTL_DOUBLES * 8 + sizeof(BaDev) + sizeof(BaLaneAux) + 768);
     for (int i : act) arenaBytes += (size_t)lanes[i].K + std::max(lanes[i].L, 1) + 64;      // (the shared membership block)
@@ -3573,57 +3679,25 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         ba_init_ctl(q.H.h_ctl, 0, adaptive ? 1 : NB);
     });
     BBS(1);
-    // ---- launch geometry shared by the lanes ---------------------------------------------------------------------------
-    int maxSlots = 1, maxFac = 1, fMax = 0, nMax = 0, neMax = 0, nfMax = 0, lpMax = 0, npMax = 0, valMax = 0;
-    bool anyMfma64 = false, anyWave = false, anyMfma = false;
+    // ---- launch geometry shared by the lanes: the plan of the cohort's shape -----------------------------------------------
+    int nMax = 0, neMax = 0, nfMax = 0, npMax = 0, valMax = 0;
     for (int i : act) {
         const Lane& q = lanes[i];
-        maxFac = std::max(maxFac, q.H.maxFac); fMax = std::max(fMax, q.H.F);
-        maxSlots = std::max(maxSlots, q.H.maxSlots); nMax = std::max(nMax, q.H.n); neMax = std::max(neMax, q.H.NE);
-        nfMax = std::max(nfMax, q.H.NF); lpMax = std::max(lpMax, q.H.Lp); npMax = std::max(npMax, q.NP);
+        nMax = std::max(nMax, q.H.n); neMax = std::max(neMax, q.H.NE);
+        nfMax = std::max(nfMax, q.H.NF); npMax = std::max(npMax, q.NP);
         valMax = std::max(valMax, std::max(q.K * (int)(sizeof(DPose) / sizeof(double)), 3 * q.L));
     }
+    plan_cohort();
+    const vslam_ba_batch_plan& plan = g_baLastPlan;
+    if (plan.status != VSLAM_OK) { set_error("local BA batch: landmark with too many views for the LDS staging"); return VSLAM_ERR_CAPACITY; }
     const int nCU = 256;
     const int obsBlocks = std::max(1, std::min((nfMax + 255) / 256, std::max(16, 2 * nCU / NL)));
     const int facBlocks = obsBlocks + std::max(neMax, 1);
     const size_t sysMax = (size_t)nMax * nMax + nMax;
-    constexpr int SCHUR_LPW = 64 / BA_LPL_SCHUR, BACK_LPW = 64 / BA_LPL_BACK;
-    auto stage_lds = [&](int nw) { return (size_t)nw * SCHUR_LPW * 2 * maxSlots * 18 * sizeof(double) + (size_t)nw * SCHUR_LPW * maxSlots * sizeof(int) + 16; };
-    auto schur_lds = [&](int nw, int copies) { return copies * sysMax * sizeof(double) + stage_lds(nw); };
-    int sharedW = 0, schurWaves = BA_SCHUR_WAVES;
-    const int shEnv = getenv("VSLAM_BA_SCHUR_SHARED") ? atoi(getenv("VSLAM_BA_SCHUR_SHARED")) : 1;
-    const int swEnv = getenv("VSLAM_BA_SCHUR_WAVES_B") ? atoi(getenv("VSLAM_BA_SCHUR_WAVES_B")) : 0;
-    if (NB > 1 && shEnv) for (int nw : {16, 12, 8, 6, 4, 2}) if (schur_lds(nw, NB) <= 150 * 1024) { sharedW = 1; schurWaves = nw; break; }
-    if (!sharedW) { if (swEnv) schurWaves = swEnv; while (schurWaves > 2 && schur_lds(schurWaves, 1) > 150 * 1024) schurWaves /= 2; }
-    const size_t schurLds = schur_lds(schurWaves, sharedW ? NB : 1);
-    if (schurLds > 160 * 1024) { set_error("local BA batch: landmark with too many views for the LDS staging"); return VSLAM_ERR_CAPACITY; }
-    const int schurUnits = schurWaves * SCHUR_LPW;
-    const int lbEnv = getenv("VSLAM_BA_LMBLOCKS") ? atoi(getenv("VSLAM_BA_LMBLOCKS")) : 0;
-    int lmBlocks = std::max(1, std::min((lpMax + schurUnits - 1) / schurUnits, lbEnv ? lbEnv : std::max(16, 2 * nCU / NL)));
-    // k_ba_schur2 (tracker windows): one LDS copy of the system + a staging region per landmark-wave
-    static const bool s2Env = !(getenv("VSLAM_BA_SCHUR2") && atoi(getenv("VSLAM_BA_SCHUR2")) == 0);
-    // (alone on the GPU 8 / 12 / 16 waves per workgroup take the same time; between the lockstep groups' wide kernels the smaller LDS footprint
-    //  finds a CU sooner: 8 waves here, 4 for the back-substitution - ba_back 15.7 -> 10.6 us per tracked frame)
-    const int s2WavesEnv = getenv("VSLAM_BA_SCHUR2_WAVES") ? atoi(getenv("VSLAM_BA_SCHUR2_WAVES")) : 8;
-    const size_t s2StageB = (size_t)ba2_stage_doubles(maxFac, maxSlots) * sizeof(double);
-    int s2Waves = std::max(2, std::min(16, s2WavesEnv));
-    while (s2Waves > 2 && sysMax * sizeof(double) + s2Waves * s2StageB > 156 * 1024) s2Waves /= 2;
-    const size_t s2Lds = sysMax * sizeof(double) + (size_t)s2Waves * s2StageB;
-    const bool useSchur2 = s2Env && fMax <= BA2_MAX_F && maxSlots <= BA2_MAX_F && s2Lds <= 156 * 1024;
-    // (the kernel is a latency chain per landmark-wave: every workgroup of the cohort resident at once - one per CU at this LDS size -,
-    //  each wave walks a few landmarks)
-    if (useSchur2) lmBlocks = std::max(1, std::min((lpMax + 2 * s2Waves - 1) / (2 * s2Waves), lbEnv ? lbEnv : std::max(4, (16 / s2Waves) * nCU / NL)));
-    static const bool b2Env = !(getenv("VSLAM_BA_BACK2") && atoi(getenv("VSLAM_BA_BACK2")) == 0);
-    const int b2Waves = std::max(1, std::min(8, getenv("VSLAM_BA_BACK2_WAVES") ? atoi(getenv("VSLAM_BA_BACK2_WAVES")) : 4));
-    const size_t b2Lds = b2Waves * s2StageB;
-    const int b2Blocks = std::max(1, std::min((lpMax + 2 * b2Waves - 1) / (2 * b2Waves), std::max(8, (16 / b2Waves) * nCU / NL)));
-    int backWaves = BA_SCHUR_WAVES / BACK_LPW;
-    auto back_lds = [&](int nw) { return (size_t)nw * BACK_LPW * maxSlots * 18 * sizeof(double) + (size_t)nw * BACK_LPW * maxSlots * sizeof(int) + 16; };
-    while (backWaves > 1 && back_lds(backWaves) > 150 * 1024) backWaves /= 2;
-    const int backBlocks = std::max(1, std::min((lpMax + backWaves * BACK_LPW - 1) / (backWaves * BACK_LPW), std::max(16, 2 * nCU / NL)));
-    const size_t backLds = back_lds(backWaves);
-    const int sharedBack = NB > 1 ? 1 : 0;
-    const size_t mfmaLds = ((size_t)BA_MFMA_N * BA_MFMA_LD + 16 + BA_MFMA_N) * sizeof(double);
+    const int maxSlots = plan.max_slots, maxFac = plan.max_factors, lmBlocks = plan.schur_blocks;
+    const bool useSchur2 = plan.schur_kernel == VSLAM_BA_KERNEL_SCHUR2, useBack2 = plan.back_kernel == VSLAM_BA_KERNEL_BACK2;
+    const bool anyMfma64 = plan.solve_kinds & (1 << BA_SOLVE_MFMA64), anyWave = plan.solve_kinds & (1 << BA_SOLVE_WAVE),
+               anyMfma = plan.solve_kinds & (1 << BA_SOLVE_MFMA);
     VS_CHECK(ba_kernel_attributes());
     // ---- device memory: one buffer, bump-allocated; a zeroed head region (arrival counters, slot-0 edge accumulators) ----
     size_t dBytes = 0;
@@ -3691,10 +3765,9 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         D.sysStride = (size_t)n * n + 2 * n + 8; D.dLStride = (size_t)3 * H.Lp;
         D.partialStride = (size_t)2 * obsBlocks + 2 * (size_t)std::max(H.NE, 1); D.partial = q.d_partial;
         D.spartStride = ((size_t)n * n + n) * lmBlocks; D.Spart = q.d_Spart;
-        D.solveKind = (n <= 64 && useMfma) ? BA_SOLVE_MFMA64 : n <= BA_WAVE_N ? BA_SOLVE_WAVE : BA_SOLVE_MFMA;
+        D.solveKind = ba_batch_solve_kind(n, useMfma);
         D.Lg = q.d_Lg;
         D.ctlHost = (double*)(W.h_back + oBackCtl) + (size_t)CTL_DOUBLES * a;
-        anyMfma64 |= D.solveKind == BA_SOLVE_MFMA64; anyWave |= D.solveKind == BA_SOLVE_WAVE; anyMfma |= D.solveKind == BA_SOLVE_MFMA;
         *H.h_D = D;
         BaLaneAux X{};
         X.C.NP = q.NP; X.C.pairKf = A.dev(q.h_pairKf); X.C.pairLm = A.dev(q.h_pairLm); X.C.pairFlags = A.dev(q.h_pairFlags); X.C.pairUv = A.dev(q.h_pairUv);
@@ -3723,18 +3796,18 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
             g_baTimer.end(t);
         }
         t = g_baTimer.begin("ba_schur");
-        if (useSchur2) hipLaunchKernelGGL(k_ba_schur2, dim3(lmBlocks, NB, NL), dim3(64 * s2Waves), s2Lds, stream, dTab, maxSlots, maxFac);
-        else hipLaunchKernelGGL(k_ba_schur, dim3(lmBlocks, sharedW ? 1 : NB, NL), dim3(64 * schurWaves), schurLds, stream, dTab, maxSlots, sharedW);
+        if (useSchur2) hipLaunchKernelGGL(k_ba_schur2, dim3(lmBlocks, NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, maxFac);
+        else hipLaunchKernelGGL(k_ba_schur, dim3(lmBlocks, plan.schur_shared_w ? 1 : NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, plan.schur_shared_w);
         g_baTimer.end(t);
         t = g_baTimer.begin("ba_solve");
         hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysMax + 31) / 32, NB, NL), dim3(256), 0, stream, dTab, lmBlocks);
         if (anyMfma64) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB, 1, NL), dim3(64), 0, stream, dTab);
         if (anyWave) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB, 1, NL), dim3(64), 0, stream, dTab);
-        if (anyMfma) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB, 1, NL), dim3(64 * BA_MFMA_NW), mfmaLds, stream, dTab, (double*)nullptr);
+        if (anyMfma) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB, 1, NL), dim3(64 * BA_MFMA_NW), plan.solve_lds, stream, dTab, (double*)nullptr);
         g_baTimer.end(t);
         t = g_baTimer.begin("ba_back");
-        if (useSchur2 && b2Env) hipLaunchKernelGGL(k_ba_back2, dim3(b2Blocks, 1, NL), dim3(64 * b2Waves), b2Lds, stream, dTab, maxSlots, maxFac);
-        else hipLaunchKernelGGL(k_ba_back, dim3(backBlocks, sharedBack ? 1 : NB, NL), dim3(64 * backWaves), backLds, stream, dTab, maxSlots, sharedBack);
+        if (useBack2) hipLaunchKernelGGL(k_ba_back2, dim3(plan.back_blocks, 1, NL), dim3(64 * plan.back_waves), plan.back_lds, stream, dTab, maxSlots, maxFac);
+        else hipLaunchKernelGGL(k_ba_back, dim3(plan.back_blocks, plan.back_shared ? 1 : NB, NL), dim3(64 * plan.back_waves), plan.back_lds, stream, dTab, maxSlots, plan.back_shared);
         g_baTimer.end(t);
         t = g_baTimer.begin("ba_eval");
         hipLaunchKernelGGL(k_ba_factors<1>, dim3(facBlocks, NB, NL), dim3(256), 0, stream, dTab, obsBlocks, 1, relTol, absTol);
@@ -3910,6 +3983,19 @@ vslam_status vslam_local_ba(const vslam_ba_problem* problem, vslam_ba_result* re
 /* n tracker-window problems optimised together (one launch per stage for all of them); results equal n vslam_local_ba calls */
 vslam_status vslam_local_ba_batch(const vslam_ba_problem* const* problems, vslam_ba_result* const* results, int32_t n, int32_t device) {
     return ba_run_batch(problems, results, n, device);
+}
+
+vslam_status vslam_local_ba_batch_plan(const vslam_ba_batch_shape* shape, vslam_ba_batch_plan* plan) {
+    if (!shape || !plan || shape->n_lanes < 0 || (shape->n_lanes > 0 && !shape->lanes) || shape->lookahead < 1 || shape->lookahead > BA_MAX_NB ||
+        shape->solver < 0 || shape->solver > 1) return VSLAM_ERR_INVALID;
+    ba_batch_plan(*shape, ba_plan_knobs(), *plan);
+    return VSLAM_OK;
+}
+
+vslam_status vslam_local_ba_last_batch_plan(vslam_ba_batch_plan* plan) {
+    if (!plan) return VSLAM_ERR_INVALID;
+    *plan = g_baLastPlan;
+    return VSLAM_OK;
 }
 
 vslam_status vslam_local_ba_timings(const char** names, float* ms, int32_t cap, int32_t* n_out) {

@@ -200,10 +200,15 @@ def _small_pose(rng, rot_sigma, trans_sigma):
 
 
 def make_ba_problem(rig_name="euroc", n_local=10, n_fixed=4, n_lm=3000, seed=0xBA5E, max_views=12,
-                    pix_noise=0.5, pose_noise=(0.009, 0.02), point_noise=0.03, outlier_frac=0.02, circle=False):
+                    pix_noise=0.5, pose_noise=(0.009, 0.02), point_noise=0.03, outlier_frac=0.02, circle=False,
+                    kf_step=4, n_persist=0):
     """Flattened local-BA problem: keyframes on a trajectory (or on a circle looking
     inward for the 64-KF global case), landmarks seen by every keyframe whose frustum holds them
-    (cap max_views), left + `close` right observations, pixel noise scaled by the octave."""
+    (cap max_views), left + `close` right observations, pixel noise scaled by the octave.
+    kf_step: trajectory frames between keyframes (small values: a slow or hovering camera).
+    n_persist: landmarks appended after the n_lm others that every keyframe sees within stereo `close` range (a left
+    and a right factor per keyframe, no view cap), drawn from a random stream of their own, so that the other
+    outputs of a seed do not depend on it."""
     rig = RIGS[rig_name]
     rng = np.random.Generator(np.random.PCG64(seed))
     K = n_local + n_fixed
@@ -217,7 +222,7 @@ def make_ba_problem(rig_name="euroc", n_local=10, n_fixed=4, n_lm=3000, seed=0xB
             y = np.cross(z, x)
             T = np.eye(4); T[:3, 0], T[:3, 1], T[:3, 2], T[:3, 3] = x, y, z, c
         else:
-            T = pose_at(4 * k, rig["fps"])
+            T = pose_at(kf_step * k, rig["fps"])
         poses.append(T)
     poses = np.array(poses)
     if circle:
@@ -262,11 +267,53 @@ def make_ba_problem(rig_name="euroc", n_local=10, n_fixed=4, n_lm=3000, seed=0xB
     for k in range(n_local):
         init_poses[k] = poses[k] @ _small_pose(rng, pose_noise[0], pose_noise[1])
     init_lm = lm + rng.normal(0, point_noise, lm.shape)
+    if n_persist:
+        lm_p, obs = _persistent_landmarks(rig, poses, n_persist, seed, pix_noise, outlier_frac, scale, n_lm)
+        prng = np.random.Generator(np.random.PCG64([seed, 2]))
+        lm = np.concatenate([lm, lm_p])
+        init_lm = np.concatenate([init_lm, lm_p + prng.normal(0, point_noise, lm_p.shape)])
+        for o, d in zip((pk, pl, pf, puv, poct), obs):
+            o.extend(d)
     # keyframe ids: local ones are the newest
     kf_id = np.concatenate([np.arange(n_fixed, K), np.arange(0, n_fixed)]).astype(np.int64)
     return dict(rig=rig, kf_pose=init_poses, kf_pose_true=poses, kf_id=kf_id, kf_fixed=kf_fixed, kf_local=kf_local,
                 lm=init_lm, lm_true=lm, pair_kf=np.array(pk, np.int32), pair_lm=np.array(pl, np.int32),
                 pair_flags=np.array(pf, np.uint8), pair_uv=np.array(puv, np.float32), pair_oct=np.array(poct, np.int32))
+
+
+def _persistent_landmarks(rig, poses, n, seed, pix_noise, outlier_frac, scale, l0):
+    """n landmarks inside every keyframe's frustum at 1.5-3.5 m depth (stereo `close`), each observed left and right by every
+    keyframe: (positions, (pair_kf, pair_lm, pair_flags, pair_uv, pair_oct) lists)"""
+    rng = np.random.Generator(np.random.PCG64([seed, 1]))
+    Tcw = np.linalg.inv(poses)
+    T0 = poses[len(poses) // 2]
+    pts = []
+    for _ in range(10000 * n):
+        if len(pts) == n:
+            break
+        pc = np.array([rng.uniform(-1.0, 1.0), rng.uniform(-0.6, 0.6), rng.uniform(1.5, 3.5)])
+        p = T0[:3, :3] @ pc + T0[:3, 3]
+        q = np.einsum("kij,j->ki", Tcw[:, :3, :3], p) + Tcw[:, :3, 3]
+        u = rig["fx"] * q[:, 0] / q[:, 2] + rig["cx"]; v = rig["fy"] * q[:, 1] / q[:, 2] + rig["cy"]
+        uR = rig["fx"] * (q[:, 0] - rig["bl"]) / q[:, 2] + rig["cx"]
+        if ((q[:, 2] > 0.3) & (q[:, 2] < 40 * rig["bl"]) & (u >= 20) & (u < rig["w"] - 20) & (v >= 20) & (v < rig["h"] - 20) & (uR >= 20)).all():
+            pts.append(p)
+    if len(pts) < n:
+        raise ValueError("no point is seen by every keyframe: keyframes too far apart for persistent landmarks")
+    pts = np.array(pts).reshape(-1, 3)
+    pk, pl, pf, puv, poct = [], [], [], [], []
+    for j, p in enumerate(pts):
+        for k in range(len(poses)):
+            q = Tcw[k, :3, :3] @ p + Tcw[k, :3, 3]
+            u = rig["fx"] * q[0] / q[2] + rig["cx"]; v = rig["fy"] * q[1] / q[2] + rig["cy"]
+            uR = rig["fx"] * (q[0] - rig["bl"]) / q[2] + rig["cx"]
+            oct_ = int(np.clip(np.round(np.log(max(q[2], 1e-3) / 2.0) / np.log(1.2)), 0, 7))
+            nz = rng.normal(0, pix_noise * scale[oct_], 4)
+            if rng.random() < outlier_frac:
+                nz += rng.normal(0, 25, 4)
+            pk.append(k); pl.append(l0 + j); pf.append(3)
+            puv.append([u + nz[0], v + nz[1], uR + nz[2], v + nz[3]]); poct.append([oct_, oct_])
+    return pts, (pk, pl, pf, puv, poct)
 
 
 def make_ba_problem_c5(n_lm=100000, n_local=62, n_fixed=2, seed=0xBA5E, max_views=12, rig_name="synthetic",

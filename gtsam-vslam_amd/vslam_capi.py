@@ -375,6 +375,52 @@ def local_ba_batch(rig, sigma_factor, inv_sigma_factor, probs, device=0):
     return [b[2]["read"]() for b in built]
 
 
+class BaLaneShape(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("n_free_kf", "n_points", "n_factors", "n_edges", "n_pairs", "max_slots", "max_factors", "own_rig")]
+
+
+class BaBatchShape(C.Structure):
+    _fields_ = [("n_lanes", C.c_int32), ("lanes", C.POINTER(BaLaneShape)), ("lookahead", C.c_int32), ("solver", C.c_int32)]
+
+
+class BaBatchPlan(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("status", "n_batch", "n_single", "lookahead", "f_max", "max_slots", "max_factors", "lp_max",
+                                         "schur_kernel", "schur_waves", "schur_shared_w", "schur_blocks", "schur_lds",
+                                         "back_kernel", "back_waves", "back_shared", "back_blocks", "back_lds", "solve_kinds", "solve_lds")]
+
+
+BA_KERNELS = {0: None, 1: "schur", 2: "schur2", 3: "back", 4: "back2"}
+BA_SOLVES = {1: "mfma64", 2: "wave", 4: "mfma"}
+
+
+def _plan_dict(p):
+    d = {f: int(getattr(p, f)) for f, _ in BaBatchPlan._fields_}
+    d["schur_kernel"] = BA_KERNELS[d["schur_kernel"]]
+    d["back_kernel"] = BA_KERNELS[d["back_kernel"]]
+    d["solves"] = {name for bit, name in BA_SOLVES.items() if d["solve_kinds"] & bit}
+    return d
+
+
+def local_ba_batch_plan(lanes, lookahead=4, solver=0):
+    """vslam_local_ba_batch_plan (pure host function, no GPU): lanes = list of dicts with the vslam_ba_lane_shape fields
+    (missing ones 0); returns the plan as a dict (kernels by name, `solves` the set of solve kinds)."""
+    arr = (BaLaneShape * max(len(lanes), 1))()
+    for i, ln in enumerate(lanes):
+        for k, v in ln.items():
+            setattr(arr[i], k, int(v))
+    S = BaBatchShape(len(lanes), arr, int(lookahead), int(solver))
+    P = BaBatchPlan()
+    _chk(lib().vslam_local_ba_batch_plan(C.byref(S), C.byref(P)))
+    return _plan_dict(P)
+
+
+def local_ba_last_batch_plan():
+    """the plan of this thread's last local_ba_batch call"""
+    P = BaBatchPlan()
+    _chk(lib().vslam_local_ba_last_batch_plan(C.byref(P)))
+    return _plan_dict(P)
+
+
 def local_ba_timings():
     names = (C.c_char_p * 32)()
     ms = (C.c_float * 32)()

@@ -407,6 +407,53 @@ void vslam_comm_destroy(vslam_comm* comm);
  * outside that class (more than 20 free keyframes, empty graphs) are served by the one-problem path inside the call. */
 vslam_status vslam_local_ba_batch(const vslam_ba_problem* const* problems, vslam_ba_result* const* results, int32_t n, int32_t device);
 
+/* Launch plan of vslam_local_ba_batch.  The call measures each problem's first-pass graph (vslam_ba_lane_shape), sends the
+ * problems outside the batched class to the one-problem path and picks the kernels and launch geometry of the others from
+ * the cohort's maxima.  vslam_local_ba_batch_plan is that choice as a pure host function (no device needed); the batch
+ * call uses the same function, and vslam_local_ba_last_batch_plan returns what it chose on the calling thread. */
+typedef struct vslam_ba_lane_shape {
+    int32_t n_free_kf;      /* free keyframes of the graph (6 unknowns each) */
+    int32_t n_points;       /* landmarks of the graph */
+    int32_t n_factors;      /* projection factors (left and right) */
+    int32_t n_edges;        /* odometry edges */
+    int32_t n_pairs;        /* the problem's (keyframe, landmark) pairs */
+    int32_t max_slots;      /* most free keyframes observing one landmark */
+    int32_t max_factors;    /* most factors of one landmark (fixed keyframes included) */
+    int32_t own_rig;        /* 1: rig or pyramid differs from the first problem's */
+} vslam_ba_lane_shape;
+
+typedef struct vslam_ba_batch_shape {
+    int32_t n_lanes;
+    const vslam_ba_lane_shape* lanes;
+    int32_t lookahead;      /* lambda candidates per trial round, 1..4 (vslam_local_ba_set_lookahead) */
+    int32_t solver;         /* 0 MFMA forms, 1 wave / LDS forms (vslam_local_ba_set_solver) */
+} vslam_ba_batch_shape;
+
+enum {
+    VSLAM_BA_KERNEL_NONE = 0,
+    VSLAM_BA_KERNEL_SCHUR = 1,      /* k_ba_schur: Schur accumulation staged by slots */
+    VSLAM_BA_KERNEL_SCHUR2 = 2,     /* k_ba_schur2: tracker windows, staged by factors */
+    VSLAM_BA_KERNEL_BACK = 3,       /* k_ba_back */
+    VSLAM_BA_KERNEL_BACK2 = 4       /* k_ba_back2 */
+};
+enum { VSLAM_BA_SOLVE_MFMA64 = 1, VSLAM_BA_SOLVE_WAVE = 2, VSLAM_BA_SOLVE_MFMA = 4 };      /* bits of solve_kinds */
+
+typedef struct vslam_ba_batch_plan {
+    int32_t status;         /* VSLAM_OK, or VSLAM_ERR_CAPACITY when a launch cannot fit the LDS */
+    int32_t n_batch;        /* problems run by the batched kernels */
+    int32_t n_single;       /* problems sent to the one-problem path */
+    int32_t lookahead;
+    int32_t f_max, max_slots, max_factors, lp_max;      /* maxima over the batched problems */
+    int32_t schur_kernel, schur_waves, schur_shared_w, schur_blocks, schur_lds;   /* waves per workgroup, dynamic LDS bytes */
+    int32_t back_kernel, back_waves, back_shared, back_blocks, back_lds;
+    int32_t solve_kinds;    /* VSLAM_BA_SOLVE_* bits of the solves launched */
+    int32_t solve_lds;      /* dynamic LDS bytes of the MFMA solve (0 if it is not launched) */
+} vslam_ba_batch_plan;
+
+vslam_status vslam_local_ba_batch_plan(const vslam_ba_batch_shape* shape, vslam_ba_batch_plan* plan);
+/* the plan of the calling thread's last vslam_local_ba_batch call (zeroed if that call returned before planning) */
+vslam_status vslam_local_ba_last_batch_plan(vslam_ba_batch_plan* plan);
+
 vslam_status vslam_local_ba(const vslam_ba_problem* problem, vslam_ba_result* result, int32_t device,
                             const vslam_comm* comm);
 /* device time per kernel group of the last vslam_local_ba call on this thread */

@@ -13,6 +13,12 @@ def _compare(oracle, capi, prob, tol=1e-7):
     ex = oracle.Extractor(1500)
     ref = oracle.local_ba(prob["rig"], ex.sigmaFactor, ex.InvSigmaFactor, prob)
     got = capi.local_ba(prob["rig"], ex.sigmaFactor, ex.InvSigmaFactor, prob)
+    _check_vs_oracle(ref, got, prob, tol)
+    return ref, got
+
+
+def _check_vs_oracle(ref, got, prob, tol=1e-7):
+    """the oracle comparison's bar: LM trajectory, errors, poses, observable landmarks, chi2 flags of both passes, work figures"""
     for s in range(2):
         assert (got["reports"][s]["iterations"], got["reports"][s]["inner"]) == \
                (ref["reports"][s]["iterations"], ref["reports"][s]["inner"]), (s, got["reports"], ref["reports"])
@@ -38,7 +44,6 @@ def _compare(oracle, capi, prob, tol=1e-7):
     assert np.array_equal(got["pair_wrong"], ref["pair_wrong"])
     assert (got["residuals"], got["landmarks"], got["free_kf"], got["sum_k2"]) == \
            (ref["residuals"], ref["landmarks"], ref["free_kf"], ref["sum_k2"])
-    return ref, got
 
 
 def test_ba_parity_c1_class(oracle, capi):
@@ -220,6 +225,19 @@ def test_write_back_depth_refresh_parity(oracle, capi):
     assert np.array_equal(d0, d1) and np.array_equal(c0, c1) and 0 < c0.sum() < u0.sum()
 
 
+def _check_batch_lane(a, b, i):
+    """lane i of a batch (b) against its own vslam_local_ba call (a): identical LM trajectory, chi2 flags of both passes and work
+    figures, poses to the round-off of the LDS atomics"""
+    assert [(r["iterations"], r["inner"]) for r in a["reports"]] == [(r["iterations"], r["inner"]) for r in b["reports"]], i
+    for s in range(2):
+        assert abs(a["reports"][s]["finalError"] - b["reports"][s]["finalError"]) <= 1e-9 * max(1.0, a["reports"][s]["finalError"]), i
+    assert np.array_equal(a["pair_wrong1"], b["pair_wrong1"]) and np.array_equal(a["pair_wrong"], b["pair_wrong"]), i
+    assert np.abs(a["kf_pose"] - b["kf_pose"]).max() < 1e-9, (i, np.abs(a["kf_pose"] - b["kf_pose"]).max())
+    d = np.linalg.norm(a["lm"] - b["lm"], axis=1)      # (weakly observed points amplify the atomics' round-off along their ray)
+    assert np.median(d) < 1e-8 and d.max() < 1e-3, (i, np.median(d), d.max())
+    assert (a["residuals"], a["landmarks"], a["free_kf"], a["sum_k2"]) == (b["residuals"], b["landmarks"], b["free_kf"], b["sum_k2"]), i
+
+
 def test_ba_batch_equals_single_calls(oracle, capi):
     """vslam_local_ba_batch (one launch per stage for all problems; the local mapping of a lockstep group) against
     vslam_local_ba on each problem: identical LM trajectories (iteration / trial counts, chi2 flags of both passes, work
@@ -245,14 +263,7 @@ def test_ba_batch_equals_single_calls(oracle, capi):
     batch = capi.local_ba_batch(rig, ex.sigmaFactor, ex.InvSigmaFactor, probs)
     assert set(capi.local_ba_timings()) >= {"ba_linearize", "ba_schur", "ba_solve", "ba_back", "ba_eval", "ba_chi2"}
     for i, (a, b) in enumerate(zip(singles, batch)):
-        assert [(r["iterations"], r["inner"]) for r in a["reports"]] == [(r["iterations"], r["inner"]) for r in b["reports"]], i
-        for s in range(2):
-            assert abs(a["reports"][s]["finalError"] - b["reports"][s]["finalError"]) <= 1e-9 * max(1.0, a["reports"][s]["finalError"]), i
-        assert np.array_equal(a["pair_wrong1"], b["pair_wrong1"]) and np.array_equal(a["pair_wrong"], b["pair_wrong"]), i
-        assert np.abs(a["kf_pose"] - b["kf_pose"]).max() < 1e-9, (i, np.abs(a["kf_pose"] - b["kf_pose"]).max())
-        d = np.linalg.norm(a["lm"] - b["lm"], axis=1)      # (weakly observed points amplify the atomics' round-off along their ray)
-        assert np.median(d) < 1e-8 and d.max() < 1e-3, (i, np.median(d), d.max())
-        assert (a["residuals"], a["landmarks"], a["free_kf"], a["sum_k2"]) == (b["residuals"], b["landmarks"], b["free_kf"], b["sum_k2"]), i
+        _check_batch_lane(a, b, i)
     # and against the oracle for one of them
     ref = oracle.local_ba(rig, ex.sigmaFactor, ex.InvSigmaFactor, probs[0])
     assert [(r["iterations"], r["inner"]) for r in ref["reports"]] == [(r["iterations"], r["inner"]) for r in batch[0]["reports"]]

@@ -74,6 +74,25 @@ def test_local_ba_noise_free_recovers_points(oracle):
     assert np.array_equal(r["kf_pose"][10:], prob["kf_pose"][10:])          # fixed keyframes never move
 
 
+def test_local_ba_noise_free_many_view_landmarks_recover_truth(oracle):
+    """Landmarks seen by every keyframe of a hovering camera (160 keyframes 2.5 ms apart, 10 free): 320 stereo factors per
+    landmark, the shape that drives the batched BA's many-view plans.  Noise-free, exact poses: the points return to the
+    truth, the free poses stay, nothing is flagged."""
+    ex = oracle.Extractor(1500)
+    n_lm, n_persist = 300, 60
+    prob = synth.make_ba_problem(n_local=10, n_fixed=150, n_lm=n_lm, seed=5, kf_step=0.05, n_persist=n_persist, pix_noise=0.0,
+                                 outlier_frac=0.0, pose_noise=(0, 0), point_noise=0.05)
+    views = np.bincount(prob["pair_lm"], minlength=len(prob["lm"]))
+    assert (views[n_lm:] == 160).all() and (prob["pair_flags"][prob["pair_lm"] >= n_lm] == 3).all()
+    r = oracle.local_ba(prob["rig"], ex.sigmaFactor, ex.InvSigmaFactor, prob)
+    err = np.linalg.norm(r["lm"] - prob["lm_true"], axis=1)
+    assert err[n_lm:].max() < 1e-5 and err[:n_lm][views[:n_lm] >= 2].max() < 1e-3
+    assert np.abs(r["kf_pose"] - prob["kf_pose_true"]).max() < 1e-6
+    assert np.array_equal(r["kf_pose"][10:], prob["kf_pose"][10:])
+    assert r["reports"][0]["finalError"] < 1e-5 and r["pair_wrong"].sum() == 0
+    assert r["free_kf"] == 10 and r["residuals"] >= 2 * 160 * n_persist
+
+
 def test_local_ba_flags_gross_outliers_and_caps_iterations(oracle):
     ex = oracle.Extractor(1500)
     prob = synth.make_ba_problem(n_lm=600, outlier_frac=0.03)
