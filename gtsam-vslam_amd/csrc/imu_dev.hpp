@@ -301,6 +301,7 @@ struct ImuLane {
     const double* samples; const double* dts; int n;
     double* bias; DPim* pim; double* Lam; DNav si; DNav* pred;
     const double* takeFrom;
+    double* status;          // out: 0, or 1 when the covariance had no Cholesky factor (Lam is then all zero)
 };
 
 }  // namespace vslam

@@ -79,7 +79,8 @@ struct vslam_matcher {
     int* d_poseOut = nullptr;        // nIn, nStereo, iterations, inner
     vslam_status ensure_pose_cap(int M);
     vslam_status pose_enqueue(int M, const int* Mdev = nullptr, const int* gate = nullptr, int gateMin = 0, int outSlot = 0);
-    // small device results in ONE block (one D2H copy per frame): poseIO [0,32) | imu io [32,48) | poseOut 2x4 ints
+    // small device results in ONE block (one D2H copy per frame): poseIO [0,32) | imu io [32,48) (velocity, bias, then the
+    // pre-integration's status word at IMU_IO_STATUS) | poseOut 2x4 ints
     // at [48,52) | trCount 2 ints at [52,53); h_res is its pinned host mirror
     double* d_res = nullptr; double* h_res = nullptr;
     vslam_status ensure_res();
@@ -92,6 +93,11 @@ struct vslam_matcher {
     vslam_status imu_setup(const vslam_imu_input* imu, double lastDt = 0.0);
     vslam_status imu_stage(const vslam_imu_input* imu, double lastDt, double* h, double* dSamples, vslam::ImuLane& L);
     void imu_lane(vslam::ImuLane& L, bool rechain);
+    static constexpr int IMU_IO_STATUS = 15;   // imuIo slot: 1 when the last pre-integration had no information matrix
+    vslam_status imu_status(const double* io);
+    vslam_status imu_preintegrate_tap(const vslam_imu_input* imu, double* pimOut, double* lamOut, double* predOut);
+    vslam_status imu_preintegrate_batch_tap(int B, const vslam_imu_input* imus, const double* const* solveIo, double* pimOut,
+                                            double* lamOut, double* predOut);
     double* d_imuStage = nullptr; double* imuSamplesDev = nullptr;   // device mirror of the staged bucket (own or the batch's)
     void pose_lane(vslam::PoseArgs& A, int M, const int* Mdev, const int* gate, int gateMin, int outSlot, int monoOnly);
     void pose_imu_lane(vslam::PoseLane& L, int M, const int* Mdev, const int* gate, int gateMin, int outSlot, int monoOnly);

@@ -17,7 +17,8 @@ constexpr int PIM_CHUNK = 12;        // samples whose step matrices are held in 
 __device__ __forceinline__ void imu_preintegrate_body(const DImuParams& P, const double* __restrict__ samples,
                                                       const double* __restrict__ dts, int n,
                                                       const double* __restrict__ biasHat, DPim* __restrict__ pimOut,
-                                                      double* __restrict__ Lam, const DNav& si, DNav* __restrict__ predOut) {
+                                                      double* __restrict__ Lam, const DNav& si, DNav* __restrict__ predOut,
+                                                      double* __restrict__ status) {
     __shared__ DPim pim;
     __shared__ double sA[PIM_CHUNK][81], sB[PIM_CHUNK][27], sC[PIM_CHUNK][27], sF[PIM_CHUNK][225], sG[PIM_CHUNK][225];
     __shared__ double sState[PIM_CHUNK + 1][9];
@@ -81,16 +82,20 @@ __device__ __forceinline__ void imu_preintegrate_body(const DImuParams& P, const
         __syncthreads();
     }
     // information matrix Lambda = cov^-1 (Cholesky + 15 column solves), one wave; next to it a second wave predicts
-    // the state at j from (x_i, v_i, biasHat) - the initial value, prior mean and factor prediction of the pose solve
-    if (tid < 64) wave_spd_inverse<15>(pim.cov, FP, Lam);
-    else if (tid == 64) { DNav pr; pim_predict(pim, P, si, pr); *predOut = pr; }
+    // the state at j from (x_i, v_i, biasHat) - the initial value, prior mean and factor prediction of the pose solve.
+    // A covariance without a Cholesky factor leaves Lam all zero, i.e. no IMU factor: *status tells the host (imu_status).
+    if (tid < 64) {
+        const bool ok = wave_spd_inverse<15>(pim.cov, FP, Lam);
+        if (tid == 0) *status = ok ? 0.0 : 1.0;
+    } else if (tid == 64) { DNav pr; pim_predict(pim, P, si, pr); *predOut = pr; }
     for (int i = tid; i < (int)(sizeof(DPim) / sizeof(double)); i += 256) ((double*)pimOut)[i] = ((double*)&pim)[i];
 }
 
 __global__ __launch_bounds__(256) void k_imu_preintegrate(DImuParams P, const double* __restrict__ samples, const double* __restrict__ dts,
                                                           int n, const double* __restrict__ biasHat, DPim* __restrict__ pimOut,
-                                                          double* __restrict__ Lam, DNav si, DNav* __restrict__ predOut) {
-    imu_preintegrate_body(P, samples, dts, n, biasHat, pimOut, Lam, si, predOut);
+                                                          double* __restrict__ Lam, DNav si, DNav* __restrict__ predOut,
+                                                          double* __restrict__ status) {
+    imu_preintegrate_body(P, samples, dts, n, biasHat, pimOut, Lam, si, predOut, status);
 }
 // batched form: blockIdx.x = lane
 __global__ __launch_bounds__(256) void k_imu_preintegrate_b(const ImuLane* __restrict__ lanes) {
@@ -100,7 +105,7 @@ __global__ __launch_bounds__(256) void k_imu_preintegrate_b(const ImuLane* __res
         if (threadIdx.x < 6) L.bias[threadIdx.x] = L.takeFrom[3 + threadIdx.x];
         __syncthreads();
     }
-    imu_preintegrate_body(L.P, L.samples, L.dts, L.n, L.bias, L.pim, L.Lam, L.si, L.pred);
+    imu_preintegrate_body(L.P, L.samples, L.dts, L.n, L.bias, L.pim, L.Lam, L.si, L.pred, L.status);
 }
 void launch_imu_batch(hipStream_t s, const ImuLane* dLanes, int B) {
     hipLaunchKernelGGL(k_imu_preintegrate_b, dim3(B), dim3(256), 0, s, dLanes);
@@ -447,6 +452,14 @@ void vslam_matcher::imu_lane(vslam::ImuLane& L, bool rechain) {
     L.samples = imuSamplesDev; L.dts = imuSamplesDev + (size_t)6 * imuN; L.n = imuN;
     L.bias = imuBiasDev; L.pim = (DPim*)imuPim; L.Lam = imuLam; L.pred = (DNav*)imuPred;
     L.takeFrom = rechain ? imuIo : nullptr;
+    L.status = imuIo + IMU_IO_STATUS;
+}
+
+// the host side of the pre-integration's status word (io: the host mirror of imuIo)
+vslam_status vslam_matcher::imu_status(const double* io) {
+    if (io[IMU_IO_STATUS] == 0.0) return VSLAM_OK;
+    set_error("IMU pre-integration: the 15x15 covariance has no Cholesky factor (no information matrix, no IMU factor)");
+    return VSLAM_ERR_INVALID;
 }
 
 vslam_status vslam_matcher::imu_setup(const vslam_imu_input* imu, double lastDt) {
@@ -474,7 +487,8 @@ vslam_status vslam_matcher::imu_setup(const vslam_imu_input* imu, double lastDt)
     VS_CHECK(imu_stage(imu, lastDt, h_imuStage, d_imuStage, L));
     VS_HIP(hipMemcpyAsync(d_imuStage, h_imuStage, (size_t)hn * sizeof(double), hipMemcpyHostToDevice, is));
     int t = timer.begin("imu_preintegrate");
-    hipLaunchKernelGGL(k_imu_preintegrate, dim3(1), dim3(256), 0, is, L.P, L.samples, L.dts, L.n, (const double*)L.bias, L.pim, L.Lam, L.si, L.pred);
+    hipLaunchKernelGGL(k_imu_preintegrate, dim3(1), dim3(256), 0, is, L.P, L.samples, L.dts, L.n, (const double*)L.bias, L.pim, L.Lam, L.si, L.pred,
+                       L.status);
     timer.end(t);
     VS_HIP(hipGetLastError());
     imuPending = is != stream;
@@ -505,7 +519,8 @@ vslam_status vslam_matcher::imu_rechain() {
     imu_lane(L, true);
     hipLaunchKernelGGL(k_imu_take_bias, dim3(1), dim3(64), 0, is, (const double*)imuIo, imuBiasDev);
     int t = timer.begin("imu_preintegrate");
-    hipLaunchKernelGGL(k_imu_preintegrate, dim3(1), dim3(256), 0, is, L.P, L.samples, L.dts, L.n, (const double*)L.bias, L.pim, L.Lam, L.si, L.pred);
+    hipLaunchKernelGGL(k_imu_preintegrate, dim3(1), dim3(256), 0, is, L.P, L.samples, L.dts, L.n, (const double*)L.bias, L.pim, L.Lam, L.si, L.pred,
+                       L.status);
     timer.end(t);
     VS_HIP(hipGetLastError());
     imuPending = is != stream;
@@ -577,7 +592,7 @@ vslam_status vslam_matcher::estimate_pose_imu(vslam_pose_problem* prob, const vs
         VS_HIP(hipMemcpyAsync(d_matches, prob->matches, (size_t)M * 8, hipMemcpyHostToDevice, stream));
     }
     VS_CHECK(pose_imu_enqueue(M, nullptr, nullptr, 0, 0, monoOnly));
-    double io[19], vb[9];
+    double io[19], vb[IMU_IO_STATUS + 1];
     int out[4];
     VS_HIP(hipMemcpyAsync(io, d_poseIO, sizeof(io), hipMemcpyDeviceToHost, stream));
     VS_HIP(hipMemcpyAsync(vb, imuIo, sizeof(vb), hipMemcpyDeviceToHost, stream));
@@ -587,6 +602,7 @@ vslam_status vslam_matcher::estimate_pose_imu(vslam_pose_problem* prob, const vs
         VS_HIP(hipMemcpyAsync(prob->mps_outliers, fl + 3 * pc, M, hipMemcpyDeviceToHost, stream));
     }
     VS_HIP(hipStreamSynchronize(stream));
+    VS_CHECK(imu_status(vb));
     memcpy(prob->T_cw, io, 16 * sizeof(double));
     if (outp) { for (int k = 0; k < 3; k++) outp->velocity[k] = vb[k]; for (int k = 0; k < 6; k++) outp->bias[k] = vb[3 + k]; }
     if (nIn) *nIn = out[0];
@@ -634,9 +650,10 @@ vslam_status vslam_matcher::imu_predict(const vslam_imu_input* imu, const double
     VS_CHECK(imu_join());
     hipLaunchKernelGGL(k_imu_predict_out, dim3(1), dim3(64), 0, stream, (const DPim*)imuPim, P, si, imuIo);
     VS_HIP(hipGetLastError());
-    VS_HIP(hipMemcpyAsync(h_res + 32, imuIo, 15 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(h_res + 32, imuIo, (IMU_IO_STATUS + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
     const double* o = h_res + 32;
+    VS_CHECK(imu_status(o));
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) T_wc_out[4 * r + c] = o[3 * r + c]; T_wc_out[4 * r + 3] = o[9 + r]; }
     T_wc_out[12] = T_wc_out[13] = T_wc_out[14] = 0; T_wc_out[15] = 1;
     if (vel_out) for (int k = 0; k < 3; k++) vel_out[k] = o[12 + k];
@@ -647,4 +664,105 @@ extern "C" vslam_status vslam_imu_predict(vslam_matcher* m, const vslam_imu_inpu
                                           double* T_wc_out, double* velocity_out) {
     if (!m) return VSLAM_ERR_INVALID;
     return m->imu_predict(imu, pred_velocity, last_dt, T_wc_out, velocity_out);
+}
+
+// ---- test taps: the pre-integration's outputs (the same staging, dt rule and launches as a frame) ----------------------
+static_assert(sizeof(DPim) == 295 * sizeof(double) && sizeof(DNav) == 15 * sizeof(double), "tap layout: DPim 295, DNav 15 doubles");
+
+vslam_status vslam_matcher::imu_preintegrate_tap(const vslam_imu_input* imu, double* pimOut, double* lamOut, double* predOut) {
+    if (!imu || !pimOut || !lamOut || !predOut) return VSLAM_ERR_INVALID;
+    VS_HIP(hipSetDevice(device));
+    UseMark mark{this};
+    VS_CHECK(imu_setup(imu));
+    VS_CHECK(imu_join());
+    double io[IMU_IO_STATUS + 1];
+    VS_HIP(hipMemcpyAsync(pimOut, imuPim, sizeof(DPim), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(lamOut, imuLam, 225 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(predOut, imuPred, sizeof(DNav), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(io, imuIo, sizeof(io), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipStreamSynchronize(stream));
+    return imu_status(io);
+}
+
+// B lanes in one k_imu_preintegrate_b launch.  Active lanes are staged by imu_stage (as vslam_batch stages them) into a
+// block of their own; an empty bucket (n_samples = 0) becomes an idle lane (n = 0) that reaches the kernel.  The output
+// blocks are uploaded from the caller's arrays first, so whatever the kernel does not write comes back unchanged.
+vslam_status vslam_matcher::imu_preintegrate_batch_tap(int B, const vslam_imu_input* imus, const double* const* solveIo, double* pimOut,
+                                                       double* lamOut, double* predOut) {
+    if (B <= 0 || !imus || !pimOut || !lamOut || !predOut) return VSLAM_ERR_INVALID;
+    for (int b = 0; b < B; b++) if (imus[b].n_samples < 0) { set_error("IMU batch tap: negative bucket length"); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(device));
+    UseMark mark{this};
+    VS_CHECK(ensure_res());
+    constexpr size_t PD = sizeof(DPim) / sizeof(double), ND = sizeof(DNav) / sizeof(double), OUT = PD + 225 + ND + 1;
+    std::vector<size_t> off(B + 1, 0);      // per lane: samples, dts, bias (7 n + 6), then the 9-double solve io
+    for (int b = 0; b < B; b++) off[b + 1] = off[b] + 7 * (size_t)imus[b].n_samples + 6 + 9;
+    std::vector<double> hIn(off[B], 0.0), hOut(B * OUT, 0.0);
+    for (int b = 0; b < B; b++) {
+        double* o = hOut.data() + b * OUT;
+        memcpy(o, pimOut + b * PD, PD * sizeof(double));
+        memcpy(o + PD, lamOut + b * 225, 225 * sizeof(double));
+        memcpy(o + PD + 225, predOut + b * ND, ND * sizeof(double));
+    }
+    double *dIn = nullptr, *dOut = nullptr;
+    ImuLane* dLanes = nullptr;
+    std::vector<ImuLane> lanes(B);
+    vslam_status st = VSLAM_OK;
+    auto run = [&]() -> vslam_status {
+        VS_HIP(hipMalloc(&dIn, off[B] * sizeof(double)));
+        VS_HIP(hipMalloc(&dOut, hOut.size() * sizeof(double)));
+        VS_HIP(hipMalloc(&dLanes, B * sizeof(ImuLane)));
+        for (int b = 0; b < B; b++) {
+            const int n = imus[b].n_samples;
+            ImuLane& L = lanes[b];
+            if (n > 0) VS_CHECK(imu_stage(&imus[b], 0.0, hIn.data() + off[b], dIn + off[b], L));
+            else { L = ImuLane{}; L.n = 0; }
+            double* o = dOut + b * OUT;
+            L.pim = (DPim*)o; L.Lam = o + PD; L.pred = (DNav*)(o + PD + 225); L.status = o + PD + 225 + ND;
+            L.takeFrom = nullptr;
+            if (solveIo && solveIo[b]) {
+                memcpy(hIn.data() + off[b + 1] - 9, solveIo[b], 9 * sizeof(double));
+                L.takeFrom = dIn + off[b + 1] - 9;
+            }
+        }
+        VS_HIP(hipMemcpyAsync(dIn, hIn.data(), off[B] * sizeof(double), hipMemcpyHostToDevice, stream));
+        VS_HIP(hipMemcpyAsync(dOut, hOut.data(), hOut.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        VS_HIP(hipMemcpyAsync(dLanes, lanes.data(), B * sizeof(ImuLane), hipMemcpyHostToDevice, stream));
+        launch_imu_batch(stream, dLanes, B);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(hOut.data(), dOut, hOut.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        VS_HIP(hipStreamSynchronize(stream));
+        return VSLAM_OK;
+    };
+    st = run();
+    hipFree(dIn); hipFree(dOut); hipFree(dLanes);
+    // the matcher's staged-bucket views pointed into dIn: nothing may run on them until the next imu_setup
+    imuSamplesDev = nullptr; imuBiasDev = nullptr; imuN = 0;
+    if (st != VSLAM_OK) return st;
+    int bad = -1;
+    for (int b = 0; b < B; b++) {
+        const double* o = hOut.data() + b * OUT;
+        memcpy(pimOut + b * PD, o, PD * sizeof(double));
+        memcpy(lamOut + b * 225, o + PD, 225 * sizeof(double));
+        memcpy(predOut + b * ND, o + PD + 225, ND * sizeof(double));
+        if (imus[b].n_samples > 0 && o[OUT - 1] != 0.0 && bad < 0) bad = b;
+    }
+    if (bad >= 0) {
+        set_error("IMU batch tap lane %d: the 15x15 covariance has no Cholesky factor (no information matrix)", bad);
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
+extern "C" vslam_status vslam_imu_preintegrate(vslam_matcher* m, const vslam_imu_input* imu, double* pim_out, double* lam_out,
+                                               double* pred_out) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->imu_preintegrate_tap(imu, pim_out, lam_out, pred_out);
+}
+
+extern "C" vslam_status vslam_imu_preintegrate_batch(vslam_matcher* m, int32_t n_lanes, const vslam_imu_input* imus,
+                                                     const double* const* solve_io, double* pim_out, double* lam_out,
+                                                     double* pred_out) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->imu_preintegrate_batch_tap(n_lanes, imus, solve_io, pim_out, lam_out, pred_out);
 }

@@ -426,6 +426,7 @@ vslam_status vslam_matcher::track_finish(double* T_cw_out, vslam_track_report* r
     }
     const float lastRad = rad;
     if (T_cw_out) memcpy(T_cw_out, h_res, 16 * sizeof(double));
+    if (trImu) VS_CHECK(imu_status(h_res + 32));
     if (trImu && imuOut) { for (int k = 0; k < 3; k++) imuOut->velocity[k] = h_res[32 + k]; for (int k = 0; k < 6; k++) imuOut->bias[k] = h_res[35 + k]; }
     if (rep) {
         rep->n_map_points = trN; rep->n_active = M; rep->rounds = rounds; rep->n_inliers = h_out[4]; rep->n_stereo = h_out[5];
@@ -510,6 +511,7 @@ vslam_status vslam_matcher::track_frame_mono(const vslam_imu_input* imu, const d
     trN = h_cnt[0];
     actN = M;
     memcpy(T_cw_out, h_res, 16 * sizeof(double));
+    VS_CHECK(imu_status(h_res + 32));
     if (imuOut) { for (int k = 0; k < 3; k++) imuOut->velocity[k] = h_res[32 + k]; for (int k = 0; k < 6; k++) imuOut->bias[k] = h_res[35 + k]; }
     if (rep) {
         rep->n_map_points = trN; rep->n_active = M; rep->rounds = rounds; rep->n_inliers = h_out[0]; rep->n_stereo = h_out[1];

@@ -673,6 +673,35 @@ def imu_predict(matcher, gravity, noise, T_body_sensor, T_wc_prev, pred_velocity
     return T, v
 
 
+def imu_preintegrate(matcher, gravity, noise, T_body_sensor, T_wc_prev, vel_prev, bias_prev, acc, gyro, timestamps_ns, hz):
+    """Test tap: the pose solve's pre-integration of one bucket; returns (pim[295], Lam (15, 15), pred[15])."""
+    imu = _imu_input(gravity, noise, T_body_sensor, T_wc_prev, vel_prev, bias_prev, acc, gyro, timestamps_ns, hz)
+    pim, lam, pred = np.zeros(295), np.zeros(225), np.zeros(15)
+    _chk(matcher.L.vslam_imu_preintegrate(matcher.h, C.byref(imu), _p(pim), _p(lam), _p(pred)))
+    return pim, lam.reshape(15, 15), pred
+
+
+def imu_preintegrate_batch(matcher, buckets, solve_io=None, fill=np.nan):
+    """Test tap: one batched pre-integration launch.  buckets: per lane the argument tuple of imu_preintegrate after
+    `matcher` (an empty bucket = idle lane); solve_io: None or per lane None / 9 doubles (velocity, bias of a solve).
+    The outputs start at `fill`; returns (pim (B, 295), Lam (B, 15, 15), pred (B, 15))."""
+    B = len(buckets)
+    imus = (ImuInput * B)()
+    keep = []
+    for b, args in enumerate(buckets):
+        one = _imu_input(*args)
+        keep.append(one)                        # (its arrays stay alive while the copy in imus[b] points at them)
+        imus[b] = one
+    io = None
+    if solve_io is not None:
+        arrs = [None if v is None else np.ascontiguousarray(v, np.float64) for v in solve_io]
+        keep.append(arrs)
+        io = (C.c_void_p * B)(*[None if a is None else a.ctypes.data for a in arrs])
+    pim, lam, pred = np.full((B, 295), fill), np.full((B, 225), fill), np.full((B, 15), fill)
+    _chk(matcher.L.vslam_imu_preintegrate_batch(matcher.h, B, imus, io, _p(pim), _p(lam), _p(pred)))
+    return pim, lam.reshape(B, 15, 15), pred
+
+
 def tracker_set_map(matcher, xyz, desc, max_scale_dist, is_outlier=None):
     xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
     desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)

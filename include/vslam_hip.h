@@ -276,6 +276,22 @@ vslam_status vslam_estimate_pose_mono(vslam_matcher* m, vslam_pose_problem* prob
  * single-sample bucket.  dt0 <= 0 selects 1 / hz. */
 vslam_status vslam_imu_predict(vslam_matcher* m, const vslam_imu_input* imu, const double* pred_velocity, double dt0,
                                double* T_wc_out, double* velocity_out);
+/* The IMU calls above and the tracking / system / batch calls in IMU mode return VSLAM_ERR_INVALID when the bucket's
+ * 15x15 pre-integration covariance has no Cholesky factor (there would be no information matrix, so no IMU factor). */
+
+/* test taps: the pre-integration of one bucket as a pose solve stages it (dt rule above, dt0 = 1 / hz) and runs it
+ * (k_imu_preintegrate).  pim_out: 295 doubles (deltaTij, preint[9] = theta, position, velocity, H_biasAcc[27],
+ * H_biasOmega[27] (9 x 3 row-major), cov[225], biasHat[6]); lam_out: the information matrix (225); pred_out: the state
+ * predicted from (T_wc_prev, velocity_prev, bias_prev): R[9], t[3], v[3].  Errors as above. */
+vslam_status vslam_imu_preintegrate(vslam_matcher* m, const vslam_imu_input* imu, double* pim_out, double* lam_out,
+                                    double* pred_out);
+/* the same for n_lanes buckets in ONE launch of the batched kernel (k_imu_preintegrate_b), outputs [n_lanes][295 | 225 |
+ * 15].  A bucket with n_samples = 0 is an idle lane: its outputs are left as the caller filled them.  solve_io: NULL,
+ * or [n_lanes] pointers, each NULL or the 9-double io block of a pose solve (velocity, bias): entries [3..8] become the
+ * lane's integration bias on the device (the rechained pre-integration after a solve).  Invalidates the matcher's
+ * staged IMU bucket. */
+vslam_status vslam_imu_preintegrate_batch(vslam_matcher* m, int32_t n_lanes, const vslam_imu_input* imus,
+                                          const double* const* solve_io, double* pim_out, double* lam_out, double* pred_out);
 
 /* worldToFrame for n points and both cameras with pose T_cw: fills pred_l/pred_r (n x 2 floats),
  * scale_level_l/r, in_frame/in_frame_r.  log_scale = KeyFrame::logScale (float log(imScale)). */

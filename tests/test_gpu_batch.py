@@ -106,6 +106,18 @@ def test_batch_lanes_equal_single_sessions(capi, use_imu, mapping, delay, np_del
     assert tot[0] >= 4 and tot[1] >= 2      # the comparison covered keyframe insertions and local BAs
 
 
+def test_batch_imu_mixed_bucket_lengths(capi):
+    """IMU lanes on different gap schedules (1-2-3, 3-1-2, 2-3-1): every step's batched pre-integration and IMU solve mix
+    buckets of 9, 19 and 29 samples across the lanes.  Every lane equals its single session."""
+    cycles = [(1, 2, 3), (3, 1, 2), (2, 3, 1)]
+    schedules = [[f0 + int(x) for x in np.cumsum([0] + list(c) * 6)] for f0, c in zip((0, 4, 8), cycles)]
+    for n in range(1, len(schedules[0])):
+        assert sorted(10 * (sc[n] - sc[n - 1]) - 1 for sc in schedules) == [9, 19, 29]
+    lanes = _batched(capi, "euroc", 1500, schedules, [0, 0, 0], True, 1)
+    for b, sc in enumerate(schedules):
+        _same(_single(capi, "euroc", 1500, sc, True, 1), lanes[b])
+
+
 def test_fleet_batched_with_prefetch_equals_one_thread_per_session(capi):
     """vslam_fleet on device-resident frames: the lockstep groups (whose driver prefetches the next frames' extraction into the
     extractor's second output set while a step's host phases run) must add up to the same run as one thread + one set of

@@ -98,6 +98,16 @@ def test_closed_loop_parity_stereo_imu(oracle, capi):
     assert np.abs(out[-1][3] - out[-1][1]).max() < 0.02
 
 
+def test_closed_loop_parity_stereo_imu_irregular_gaps(oracle, capi):
+    """C2 on an irregular frame schedule (gaps 1, 2 and 3): IMU buckets of 9, 19 and 29 samples, the longer ones
+    crossing the pre-integration's chunk boundary, in the initial and the rechained pre-integration of every frame."""
+    gaps = [1, 2, 1, 3, 2, 1, 3, 1, 2, 3] * 2
+    frames = [int(f) for f in np.cumsum([0] + gaps)]
+    assert {10 * (b - a) - 1 for a, b in zip(frames, frames[1:])} == {9, 19, 29}
+    ref, got, out = _run(oracle, capi, "euroc", 1500, frames, use_imu=True)
+    _check(ref, got, out, pose_tol=1e-6)
+
+
 def test_closed_loop_parity_async_stereo(oracle, capi):
     """The mode bench.py times: the optimizer's device work beside tracking on the fixed schedule mapping_delay = 4 (new points
     one frame after the hand-over, the BA's write-back + changePosesLCA four frames after it) - frame by frame against the
