@@ -193,11 +193,19 @@ __device__ __forceinline__ bool has9(unsigned m) {
 // compaction), so the expensive stage only ever sees pixels that need it:
 //   1  every detection pixel: two ADJACENT cardinal ring pixels (0/4/8/12) both darker or both brighter than the
 //      quick-reject threshold - a necessary condition for any 9-arc;
-//   2  survivors: the 16-pixel ring masks and the 9-contiguous test at the quick-reject threshold;
-//   3  survivors: the exact score M (max over arcs of the min difference) -> score plane in LDS.
+//   2  survivors: the 16-pixel ring masks and the 9-contiguous test at the quick-reject threshold (ring_test, below);
+//   3  survivors: the exact score M (max over arcs of the min difference, on the side of the arc that stage 2 found:
+//      fast_score_side, below) -> score plane in LDS.
 // Then, per threshold, 3x3 strict-maximum suppression and the ordered emission (row-major) by ballot prefix.
 constexpr int FQ_MASK = 255;          // queue capacity (entries) - 1: at most 64 + 63 entries are ever pending
 constexpr int FQ3_CAP = 512;          // corner list of a cell (pixels whose score passes the threshold), row-major order
+constexpr int FQ_BRIGHT = 1 << 14;    // q2 entries: this bit = the 9-arc is brighter than the centre
+// The queues carry a pixel as the byte offset of its centre in the LDS tile (no row * pitch product in stages 2 and 3).
+static_assert(FAST_TILE_MAX * FAST_TILE_PITCH < FQ_BRIGHT, "a tile offset must fit below the side bit of a queue entry");
+// lanes below this one whose bit is set in a ballot (+ base): two v_mbcnt
+__device__ __forceinline__ int lanes_below(unsigned long long bal, int base) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, (unsigned)base));
+}
 
 __device__ __forceinline__ int fast_score(const uint8_t* p, const int* ro) {
     const int v = p[0];
@@ -227,6 +235,89 @@ __device__ __forceinline__ int fast_score(const uint8_t* p, const int* ro) {
     const int M = max(A, -B);
     return M < 0 ? 0 : M;
 }
+
+#define FAST_HD __host__ __device__ __forceinline__
+// ---- packed forms of stages 2 and 3: ring pixels k and k + 8 share one register as two 16-bit halves (v_pk_*_i16) -----------
+typedef short fast_s2 __attribute__((ext_vector_type(2)));
+FAST_HD unsigned fs2_bits(fast_s2 x) { return __builtin_bit_cast(unsigned, x); }
+FAST_HD fast_s2 fs2_swap(fast_s2 x) { return __builtin_shufflevector(x, x, 1, 0); }
+// element j of the 16-long circular sequence whose elements j and j + 8 are the halves of a[j]
+FAST_HD fast_s2 fs2_at(const fast_s2* a, int j) { return j < 8 ? a[j] : fs2_swap(a[j - 8]); }
+
+FAST_HD void ring_pairs(const uint8_t* p, const int* ro, fast_s2* P) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) P[j] = fast_s2{(short)p[ro[j]], (short)p[ro[j + 8]]};
+}
+
+// Stage 2: 0 = no 9-arc at threshold t, 1 = nine contiguous ring pixels darker than v - t, 2 = nine brighter than v + t (never
+// both: 18 > 16).  The bounds are clamped to the pixel range first - q < v - t is false for every q when v - t <= 0 and equals
+// q < 0; the same at 255 - so every difference lies in [-255, 255] and bits 8..15 of a 16-bit half all carry its sign: pair j
+// leaves its two sign bits at bits 8 + j and 24 + j of the accumulator (one v_pk_sub_i16 and one AND per pair and side).
+FAST_HD int ring_test(const uint8_t* p, const int* ro, int t) {
+    const int v = p[0];
+    const short lo = (short)max(v - t, 0), hi = (short)min(v + t, 255);
+    const fast_s2 LO = {lo, lo}, HI = {hi, hi};
+    fast_s2 P[8];
+    ring_pairs(p, ro, P);
+    unsigned da = 0, ba = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        da |= fs2_bits(P[j] - LO) & (0x01000100u << j);     // ring < lo
+        ba |= fs2_bits(HI - P[j]) & (0x01000100u << j);     // ring > hi
+    }
+    // the 16-bit ring mask, doubled for the circular test: bytes 1 and 3 of the accumulator
+    auto nine = [](unsigned a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const unsigned m = __builtin_amdgcn_perm(a, a, 0x03010301u);
+#else
+        const unsigned m16 = ((a >> 8) & 0xffu) | ((a >> 16) & 0xff00u), m = m16 | (m16 << 16);
+#endif
+        unsigned w = m & (m >> 1);
+        w &= w >> 2;
+        w &= w >> 4;
+        w &= m >> 8;
+        return (w & 0xffffu) != 0;
+    };
+    return nine(da) ? 1 : nine(ba) ? 2 : 0;
+}
+
+// Stage 3 for a pixel that stage 2 found to be a corner: its arc lies on one side, every other 9-arc intersects it, so the
+// other side's term of M = max(A, -B) is below -t and M is the max over arcs of the min of e_k = s (v - ring_k), s = +1 for a
+// dark arc and -1 for a bright one.  Arcs j and j + 8 are computed in the two halves of one register.
+FAST_HD int fast_score_side(const uint8_t* p, const int* ro, bool bright) {
+    const short s = bright ? (short)-1 : (short)1, sv = (short)(s * (int)p[0]), ns = (short)-s;
+    const fast_s2 S = {ns, ns}, V = {sv, sv};
+    fast_s2 E[8], m2[8], m4[8], m8[8];
+    ring_pairs(p, ro, E);
+#pragma unroll
+    for (int j = 0; j < 8; j++) E[j] = E[j] * S + V;
+#pragma unroll
+    for (int j = 0; j < 8; j++) m2[j] = __builtin_elementwise_min(E[j], fs2_at(E, j + 1));
+#pragma unroll
+    for (int j = 0; j < 8; j++) m4[j] = __builtin_elementwise_min(m2[j], fs2_at(m2, j + 2));
+#pragma unroll
+    for (int j = 0; j < 8; j++) m8[j] = __builtin_elementwise_min(m4[j], fs2_at(m4, j + 4));
+    fast_s2 A = {-512, -512};
+#pragma unroll
+    for (int j = 0; j < 8; j++) A = __builtin_elementwise_max(A, __builtin_elementwise_min(m8[j], fs2_at(E, j + 8)));
+    const int M = max((int)A.x, (int)A.y);
+    return M < 0 ? 0 : M;
+}
+
+#ifdef VSLAM_FAST_CHECK
+// Debug build only: pixels on which a packed stage disagreed with its scalar form (read back by fast_check_failures()).
+__device__ int g_fastCheckFail;
+__device__ __forceinline__ int ring_test_scalar(const uint8_t* p, const int* ro, int t) {
+    const int v = p[0], lo = v - t, hi = v + t;
+    unsigned dm = 0, bm = 0;
+    for (int k = 0; k < 16; k++) {
+        const int q = p[ro[k]];
+        dm |= (unsigned)(q < lo) << k;
+        bm |= (unsigned)(q > hi) << k;
+    }
+    return has9(dm) ? 1 : has9(bm) ? 2 : 0;
+}
+#endif
 
 // XCD-aware (chunk, image) of a workgroup of a (chunks, images) grid.  Workgroups are dealt round-robin to the 8 XCDs in launch
 // order (linear id mod 8 labels the blocks that share an XCD - a speed assumption only, MI355X_MICROARCH.md "Workgroup dispatch"):
@@ -331,8 +422,8 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
     const int ro[16] = {3 * TP,      3 * TP + 1,  2 * TP + 2,  TP + 3,  3,       -TP + 3,
                         -2 * TP + 2, -3 * TP + 1, -3 * TP,     -3 * TP - 1, -2 * TP - 2, -TP - 3,
                         -3,          TP - 3,      2 * TP - 2,  3 * TP - 1};
-    const unsigned long long lt = (1ull << lane) - 1ull;
     const int npix = detW * detH;
+    const int scDelta = 2 * TP + 2 + xoff;                 // tile offset of a pixel's centre -> its offset in the score plane
     uint32_t* slots = cellSlots + ((size_t)img * nCellsTotal + cell) * F.cellCap;
     int total = 0;
     // The cell is processed at the high threshold first: only pixels that are corners at THAT threshold need a score (the
@@ -350,14 +441,17 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
         auto stage3 = [&](int rc, bool valid) {
             bool corner = false;
             if (valid) {
-                const int r = rc >> 7, c = rc & 127;
-                const int s = fast_score(&tile[(r + 3) * TP + (c + 3 + xoff)], ro);
-                sc[(r + 1) * TP + (c + 1)] = (uint8_t)s;
+                const uint8_t* p = &tile[rc & (FQ_BRIGHT - 1)];
+                const int s = fast_score_side(p, ro, (rc & FQ_BRIGHT) != 0);
+#ifdef VSLAM_FAST_CHECK
+                if (s != fast_score(p, ro)) atomicAdd(&g_fastCheckFail, 1);
+#endif
+                sc[(rc & (FQ_BRIGHT - 1)) - scDelta] = (uint8_t)s;
                 corner = s > tq;
             }
             const unsigned long long bal = __ballot(corner);
-            const int at = n3 + __popcll(bal & lt);
-            if (corner && at < listCap) q3[at] = (unsigned short)rc;
+            const int at = lanes_below(bal, n3);
+            if (corner && at < listCap) q3[at] = (unsigned short)(rc & ~FQ_BRIGHT);
             n3 += __popcll(bal);
         };
         auto drain2 = [&](bool all) {
@@ -369,22 +463,17 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
             }
         };
         auto stage2 = [&](int rc, bool valid) {
-            bool ok = false;
+            int side = 0;
             if (valid) {
-                const int r = rc >> 7, c = rc & 127;
-                const uint8_t* p = &tile[(r + 3) * TP + (c + 3 + xoff)];
-                const int v = p[0], lo = v - tq, hi = v + tq;
-                unsigned dm = 0, bm = 0;
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int q = p[ro[k]];
-                    dm |= (unsigned)(q < lo) << k;
-                    bm |= (unsigned)(q > hi) << k;
-                }
-                ok = has9(dm) || has9(bm);
+                const uint8_t* p = &tile[rc];
+                side = ring_test(p, ro, tq);
+#ifdef VSLAM_FAST_CHECK
+                if (side != ring_test_scalar(p, ro, tq)) atomicAdd(&g_fastCheckFail, 1);
+#endif
             }
+            const bool ok = side != 0;
             const unsigned long long bal = __ballot(ok);
-            if (ok) q2[(t2 + __popcll(bal & lt)) & FQ_MASK] = (unsigned short)rc;
+            if (ok) q2[lanes_below(bal, t2) & FQ_MASK] = (unsigned short)(side == 2 ? rc | FQ_BRIGHT : rc);
             t2 += __popcll(bal);
             drain2(false);
         };
@@ -399,12 +488,14 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
         {
             int r = 0, c = lane;
             while (c >= detW) { c -= detW; r++; }
+            int o = (r + 3) * TP + (c + 3 + xoff);                        // the lane's pixel: tile offset of its centre
             const int adv_r = 64 / detW, adv_c = 64 - adv_r * detW;      // 64 pixels further: wave-uniform quotient / remainder
+            const int adv_o = adv_r * TP + adv_c, wrap_o = TP - detW;
             for (int base = 0; base < npix; base += 64) {
                 const bool valid = base + lane < npix;
                 bool ok = false;
                 if (valid) {
-                    const uint8_t* p = &tile[(r + 3) * TP + (c + 3 + xoff)];
+                    const uint8_t* p = &tile[o];
                     const int v = p[0], lo = v - tq, hi = v + tq;
                     const int c0 = p[3 * TP], c4 = p[3], c8 = p[-3 * TP], c12 = p[-3];
                     const bool d0 = c0 < lo, d4 = c4 < lo, d8 = c8 < lo, d12 = c12 < lo;
@@ -412,11 +503,11 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
                     ok = (d0 && d4) || (d4 && d8) || (d8 && d12) || (d12 && d0) || (b0 && b4) || (b4 && b8) || (b8 && b12) || (b12 && b0);
                 }
                 const unsigned long long bal = __ballot(ok);
-                if (ok) q1[(t1 + __popcll(bal & lt)) & FQ_MASK] = (unsigned short)((r << 7) | c);
+                if (ok) q1[lanes_below(bal, t1) & FQ_MASK] = (unsigned short)o;
                 t1 += __popcll(bal);
                 drain1(false);
-                c += adv_c; r += adv_r;
-                if (c >= detW) { c -= detW; r++; }
+                c += adv_c; o += adv_o;
+                if (c >= detW) { c -= detW; o += wrap_o; }
             }
         }
         drain1(true);
@@ -428,13 +519,14 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
         const int t = tq;
         total = 0;
         if (n3 <= listCap) {
+            const unsigned invTP = 0xffffffffu / (unsigned)TP + 1u;
             for (int base = 0; base < n3; base += 64) {
                 bool flag = false;
                 int s = 0, r = 0, c = 0;
                 if (base + lane < n3) {
-                    const int rc = q3[base + lane];
-                    r = rc >> 7; c = rc & 127;
-                    const uint8_t* z = &sc[(r + 1) * TP + (c + 1)];
+                    const int o = q3[base + lane];
+                    r = (int)__umulhi((unsigned)o, invTP) - 3; c = o - (r + 3) * TP - 3 - xoff;     // (exact: o * TP < 2^32)
+                    const uint8_t* z = &sc[o - scDelta];
                     s = z[0];
                     flag = true;
 #pragma unroll
@@ -449,7 +541,7 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
                 }
                 const unsigned long long bal = __ballot(flag);
                 if (flag) {
-                    const int pos = total + __popcll(bal & lt);
+                    const int pos = lanes_below(bal, total);
                     if (pos < F.cellCap) slots[pos] = pack_cand(cStart + 3 + c, rStart + 3 + r, s - 1);
                 }
                 total += __popcll(bal);
@@ -478,7 +570,7 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* __restrict__ pyr, P
                 }
                 const unsigned long long bal = __ballot(flag);
                 if (flag) {
-                    const int pos = total + __popcll(bal & lt);
+                    const int pos = lanes_below(bal, total);
                     if (pos < F.cellCap) slots[pos] = pack_cand(cStart + 3 + c, rStart + 3 + r, s - 1);
                 }
                 total += __popcll(bal);
@@ -500,6 +592,16 @@ void launch_fast(hipStream_t s, const uint8_t* pyr, const PyrDesc& P, const Fast
     if (const char* e = getenv("VSLAM_FAST_LIST_CAP")) listCap = std::max(0, std::min(FQ3_CAP, atoi(e)));
     hipLaunchKernelGGL(k_fast, grid, dim3(256), lds, s, pyr, P, F, cellSlots, cellCount, maxThr, minThr, listCap, nimg);
 }
+
+#ifdef VSLAM_FAST_CHECK
+// waits for the stream; the number of pixels on which a packed stage of k_fast disagreed with its scalar form (-1: HIP error)
+int fast_check_failures(hipStream_t s) {
+    int n = 0;
+    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_fastCheckFail), sizeof(int)) != hipSuccess) return -1;
+    return n;
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // K2b: gather cell lists into one level-major, cell-row-major candidate list per image

@@ -58,6 +58,9 @@ void launch_resize(hipStream_t s, uint8_t* pyr, const PyrDesc& P, int level, con
                    const int2* ytab, int nimg);
 void launch_fast(hipStream_t s, const uint8_t* pyr, const PyrDesc& P, const FastDesc& F,
                  uint32_t* cellSlots, int* cellCount, int maxThr, int minThr, int nimg);
+#ifdef VSLAM_FAST_CHECK
+int fast_check_failures(hipStream_t s);      // debug build (-DVSLAM_FAST_CHECK): packed stages of k_fast against their scalar forms
+#endif
 void launch_gather(hipStream_t s, const uint32_t* cellSlots, const int* cellCount, const FastDesc& F,
                    int nLevels, int* cellOff, uint32_t* cand, int candCap, int* levelCount, int nimg);
 void launch_blur(hipStream_t s, const uint8_t* pyr, uint8_t* blur, const PyrDesc& P,

@@ -457,6 +457,12 @@ vslam_status vslam_extractor::run() {
     launch_fast(stream, d_pyr, P, F, d_cellSlots, d_cellCount, prm.max_fast_threshold,
                 prm.min_fast_threshold, nimg);
     timer.end(t);
+#ifdef VSLAM_FAST_CHECK
+    if (const int bad = fast_check_failures(stream)) {
+        set_error("k_fast: %d pixels on which a packed stage disagrees with its scalar form", bad);
+        return VSLAM_ERR_HIP;
+    }
+#endif
     t = timer.begin("gather");
     launch_gather(stream, d_cellSlots, d_cellCount, F, nLevels, d_cellOff, d_cand, candCap,
                   d_levelCount, nimg);
