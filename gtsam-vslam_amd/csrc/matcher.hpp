@@ -51,6 +51,7 @@ struct vslam_matcher {
     uint8_t* d_close = nullptr;
     unsigned long long* d_stats = nullptr;   // 4 counters
     bool stereoDone = false;
+    vslam_status stereo_finalize_arrays(const int32_t* best, const float* depth, const int32_t* sad, int nL, int nR);
 
     // matchByProjectionRPred buffers
     int projCap = 0;             // map-point capacity

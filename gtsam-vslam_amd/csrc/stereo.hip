@@ -642,7 +642,44 @@ vslam_status vslam_matcher::stereo_match() {
     return VSLAM_OK;
 }
 
+// test tap: the finalize kernel alone on host-supplied per-left (best right index or -1, depth, SAD) arrays
+vslam_status vslam_matcher::stereo_finalize_arrays(const int32_t* best, const float* depth, const int32_t* sad, int nL, int nR) {
+    if (mono) { set_error("stereo_finalize_arrays on a mono matcher"); return VSLAM_ERR_INVALID; }
+    if (nL < 0 || nR < 0 || (nL > 0 && (!best || !depth || !sad))) { set_error("stereo_finalize_arrays: invalid arguments"); return VSLAM_ERR_INVALID; }
+    if (nL > STEREO_MAX_L) {       // (the limit of stereo_lane: 20 B of dynamic LDS per left key)
+        set_error("stereo_finalize_arrays: %d left keypoints exceed the LDS staging (%d)", nL, STEREO_MAX_L);
+        return VSLAM_ERR_CAPACITY;
+    }
+    for (int i = 0; i < nL; i++)
+        if (best[i] >= nR) { set_error("stereo_finalize_arrays: best[%d] = %d with %d right keypoints", i, best[i], nR); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(device));
+    VS_HIP(hipStreamSynchronize(stream));          // an earlier finalize may still read the buffers the copies overwrite
+    VS_CHECK(ensure_cap(std::max(nL, nR)));
+    VS_CHECK(stereo_attrs());
+    if (nL > 0) {
+        VS_HIP(hipMemcpy(d_mBest, best, (size_t)nL * sizeof(int), hipMemcpyHostToDevice));
+        VS_HIP(hipMemcpy(d_mDepth, depth, (size_t)nL * sizeof(float), hipMemcpyHostToDevice));
+        VS_HIP(hipMemcpy(d_mSad, sad, (size_t)nL * sizeof(int), hipMemcpyHostToDevice));
+    }
+    VS_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), stream));
+    // the key views no longer describe these arrays: drop the overrides, the next match re-reads the extractors' keys
+    overridden[0] = overridden[1] = false;
+    nKeys[0] = nL; nKeys[1] = nR;
+    const int t = timer.begin("stereo_finalize");
+    launch_stereo_finalize(stream, nL, nR, d_mBest, d_mDepth, d_mSad, rig.baseline * 40, d_rightIdxs, d_leftIdxs, d_depth, d_close);
+    timer.end(t);
+    VS_HIP(hipGetLastError());
+    stereoDone = true;
+    return VSLAM_OK;
+}
+
 extern "C" {
+
+vslam_status vslam_stereo_finalize_arrays(vslam_matcher* m, const int32_t* best, const float* depth, const int32_t* sad,
+                                          int32_t n_left, int32_t n_right) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->stereo_finalize_arrays(best, depth, sad, n_left, n_right);
+}
 
 vslam_status vslam_matcher_create(const vslam_rig* rig, vslam_extractor* fe_left, int32_t left_image,
                                   vslam_extractor* fe_right, int32_t right_image, vslam_matcher** out) {

@@ -215,6 +215,14 @@ class Matcher:
     def stereo_match(self):
         _chk(self.L.vslam_stereo_match(self.h))
 
+    def stereo_finalize_arrays(self, best, depth, sad, nR, nL=None):
+        """The finalize kernel alone on per-left (accepted right index or -1, depth, SAD) arrays (test tap);
+        read the result with stereo_fetch(len(best), nR).  nL overrides the count passed down (error-path tests)."""
+        best = np.ascontiguousarray(best, np.int32); depth = np.ascontiguousarray(depth, np.float32)
+        sad = np.ascontiguousarray(sad, np.int32)
+        assert len(best) == len(depth) == len(sad)
+        _chk(self.L.vslam_stereo_finalize_arrays(self.h, _p(best), _p(depth), _p(sad), len(best) if nL is None else int(nL), int(nR)))
+
     def stereo_fetch(self, nL, nR):
         ri = np.full(max(nL, 1), -1, np.int32); li = np.full(max(nR, 1), -1, np.int32)
         dp = np.full(max(nL, 1), -1, np.float32); cl = np.zeros(max(nL, 1), np.uint8)

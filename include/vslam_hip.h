@@ -176,6 +176,15 @@ vslam_status vslam_stereo_fetch(vslam_matcher* m, int32_t* right_idxs, int32_t* 
                                 float* estimated_depth, uint8_t* close_flags, int32_t cap_left,
                                 int32_t cap_right, int64_t* stats3);
 
+/* test tap: the tail of findStereoMatchesORB2R (src/FeatureMatcher.cpp:655-705 - accepted pairs entered in left
+ * order, the nearest-1 % depth cut, the 2.1 x median-SAD cut) on caller-supplied per-left arrays: best[i] = accepted
+ * right index or < 0, depth[i] and sad[i] of that pair - the same kernel a frame runs, fed directly.  The result is
+ * read with vslam_stereo_fetch (stats all 0).  n_left above the matcher's left-key limit (7680) or more than 65535
+ * keys give VSLAM_ERR_CAPACITY; best[i] >= n_right or negative sizes give VSLAM_ERR_INVALID.  Drops any set_keys
+ * override: the next vslam_stereo_match reads the extractors' keys again unless set_keys is called anew. */
+vslam_status vslam_stereo_finalize_arrays(vslam_matcher* m, const int32_t* best, const float* depth, const int32_t* sad,
+                                          int32_t n_left, int32_t n_right);
+
 /* matchByProjectionRPred (include/FeatureMatcher.h:57, src/FeatureMatcher.cpp:254-389).
  * vslam_mappoint_view flattens the MapPoint fields that function reads (desc, predL/predR,
  * scaleLevelL/R, inFrame/inFrameR — include/Map.h).  Map points are processed in array order

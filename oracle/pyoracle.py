@@ -173,18 +173,38 @@ def descriptor_distance(a, b):
 
 
 def stereo_match(exL, exR, rig, kpsL, descL, kpsR, descR):
-    """findStereoMatchesORB2R on the pyramids exL/exR hold from their last extract()."""
+    """findStereoMatchesORB2R on the pyramids exL/exR hold from their last extract().  preBest / preDepth / preSad: per
+    left key what the matching loop accepted (right index or -1, depth, SAD) before the depth and SAD cuts."""
     kpsL = np.ascontiguousarray(kpsL, KP_DTYPE); kpsR = np.ascontiguousarray(kpsR, KP_DTYPE)
     descL = np.ascontiguousarray(descL, np.uint8); descR = np.ascontiguousarray(descR, np.uint8)
     nL, nR = len(kpsL), len(kpsR)
     rightIdxs = np.full(max(nL, 1), -1, np.int32); leftIdxs = np.full(max(nR, 1), -1, np.int32)
     depth = np.full(max(nL, 1), -1, np.float32); close = np.zeros(max(nL, 1), np.uint8)
+    preBest = np.full(max(nL, 1), -1, np.int32); preDepth = np.full(max(nL, 1), -1, np.float32)
+    preSad = np.zeros(max(nL, 1), np.int32)
     stats = np.zeros(3, np.int64)
     lib().vo_stereo_match(exL.h, exR.h, C.c_double(rig["fx"]), C.c_double(rig["fy"]), C.c_double(rig["cx"]),
                           C.c_double(rig["cy"]), C.c_float(rig["bl"]), rig["w"], rig["h"], _p(kpsL), _p(descL), nL,
-                          _p(kpsR), _p(descR), nR, _p(rightIdxs), _p(leftIdxs), _p(depth), _p(close), _p(stats))
+                          _p(kpsR), _p(descR), nR, _p(rightIdxs), _p(leftIdxs), _p(depth), _p(close), _p(stats),
+                          _p(preBest), _p(preDepth), _p(preSad))
     return dict(rightIdxs=rightIdxs[:nL], leftIdxs=leftIdxs[:nR], depth=depth[:nL], close=close[:nL],
-                candidates=int(stats[0]), sad=int(stats[1]), matches=int(stats[2]))
+                candidates=int(stats[0]), sad=int(stats[1]), matches=int(stats[2]),
+                preBest=preBest[:nL], preDepth=preDepth[:nL], preSad=preSad[:nL])
+
+
+def stereo_finalize(best, depth, sad, nR, rig):
+    """The tail of findStereoMatchesORB2R alone: per-left (accepted right index or -1, depth, SAD) -> rightIdxs,
+    leftIdxs, depth, close after the nearest-1 % depth cut and the 2.1 x median-SAD cut."""
+    best = np.ascontiguousarray(best, np.int32); depth = np.ascontiguousarray(depth, np.float32)
+    sad = np.ascontiguousarray(sad, np.int32)
+    nL = len(best)
+    assert len(depth) == nL and len(sad) == nL and (nL == 0 or int(best.max()) < nR)
+    rightIdxs = np.full(max(nL, 1), -1, np.int32); leftIdxs = np.full(max(nR, 1), -1, np.int32)
+    out = np.full(max(nL, 1), -1, np.float32); close = np.zeros(max(nL, 1), np.uint8)
+    close_depth = np.float32(rig["bl"]) * np.float32(40)          # closeNumber, include/FeatureMatcher.h:36
+    lib().vo_stereo_finalize(_p(best), _p(depth), _p(sad), nL, nR, C.c_float(close_depth), _p(rightIdxs), _p(leftIdxs),
+                             _p(out), _p(close))
+    return dict(rightIdxs=rightIdxs[:nL], leftIdxs=leftIdxs[:nR], depth=out[:nL], close=close[:nL])
 
 
 def match_projection(exL, rig, mps, kpsL, descL, kpsR, descR, rightIdxs, leftIdxs, matchedL, matchedR, matches, rad):

@@ -115,10 +115,11 @@ int vo_descriptor_distance(const uint8_t* a, const uint8_t* b) { return descript
 
 // findStereoMatchesORB2R on the pyramids the two extractors hold from their last extract().
 // stats[3] = {hamming candidates, SAD refinements, pre-filter matches}
+// preBest / preDepth / preSad (nL each, may be null): what the matching loop hands to the two cuts
 void vo_stereo_match(void* hL, void* hR, double fx, double fy, double cx, double cy, float baseline,
                      int width, int height, const KeyPoint* kpsL, const uint8_t* descL, int nL,
                      const KeyPoint* kpsR, const uint8_t* descR, int nR, int* rightIdxs, int* leftIdxs,
-                     float* depth, uint8_t* close, long long* stats) {
+                     float* depth, uint8_t* close, long long* stats, int* preBest, float* preDepth, int* preSad) {
     Extractor* eL = (Extractor*)hL;
     Extractor* eR = (Extractor*)hR;
     Rig rig{fx, fy, cx, cy, baseline, width, height};
@@ -128,10 +129,30 @@ void vo_stereo_match(void* hL, void* hR, double fx, double fy, double cx, double
     k.Desc.assign(descL, descL + (size_t)nL * 32);
     k.rightDesc.assign(descR, descR + (size_t)nR * 32);
     StereoStats st;
-    findStereoMatchesORB2R(*eL, *eR, rig, k, &st);
+    StereoPreCut pre;
+    findStereoMatchesORB2R(*eL, *eR, rig, k, &st, &pre);
     for (int i = 0; i < nL; i++) { rightIdxs[i] = k.rightIdxs[i]; depth[i] = k.estimatedDepth[i]; close[i] = k.close[i]; }
     for (int i = 0; i < nR; i++) leftIdxs[i] = k.leftIdxs[i];
     if (stats) { stats[0] = st.candidates; stats[1] = st.sadRefinements; stats[2] = st.matches; }
+    for (int i = 0; i < nL; i++) {
+        if (preBest) preBest[i] = pre.best[i];
+        if (preDepth) preDepth[i] = pre.depth[i];
+        if (preSad) preSad[i] = pre.sad[i];
+    }
+}
+
+// the tail of findStereoMatchesORB2R alone (stereoFinalize): per-left (best, depth, sad) -> the four output arrays
+void vo_stereo_finalize(const int* best, const float* bestDepth, const int* bestSad, int nL, int nR, float closeDepth,
+                        int* rightIdxs, int* leftIdxs, float* depth, uint8_t* close) {
+    TrackedKeys k;
+    k.estimatedDepth.assign(nL, -1.0f);
+    k.close.assign(nL, 0);
+    k.rightIdxs.assign(nL, -1);
+    k.leftIdxs.assign(nR, -1);
+    stereoFinalize(k, std::vector<int>(best, best + nL), std::vector<float>(bestDepth, bestDepth + nL),
+                   std::vector<int>(bestSad, bestSad + nL), closeDepth);
+    for (int i = 0; i < nL; i++) { rightIdxs[i] = k.rightIdxs[i]; depth[i] = k.estimatedDepth[i]; close[i] = k.close[i]; }
+    for (int i = 0; i < nR; i++) leftIdxs[i] = k.leftIdxs[i];
 }
 
 // matchByProjectionRPred.  mps: M MapPointView records; matchedIdxsL/R and matches (M x 2) are in/out.

@@ -42,7 +42,7 @@ static void distributeRightKeys(const Extractor& feRight, const std::vector<KeyP
 
 // findStereoMatchesORB2R: src/FeatureMatcher.cpp:528-708
 void findStereoMatchesORB2R(const Extractor& feLeft, const Extractor& feRight, const Rig& rig,
-                            TrackedKeys& keys, StereoStats* stats) {
+                            TrackedKeys& keys, StereoStats* stats, StereoPreCut* pre) {
     std::vector<std::vector<int>> indexes;
     distributeRightKeys(feRight, keys.rightKeyPoints, rig.height, indexes);
     const size_t leftEnd = keys.keyPoints.size();
@@ -54,8 +54,8 @@ void findStereoMatchesORB2R(const Extractor& feLeft, const Extractor& feRight, c
     const float minD = 0;
     const float maxD = (float)rig.fx;
     const int windowRadius = 5, windowMovementX = 5;
-    std::vector<std::pair<float, int>> allDepths;
-    std::vector<std::pair<int, int>> allDists2;
+    std::vector<int> best(leftEnd, -1), bestSad(leftEnd, 0);     // per left key, before the two cuts
+    std::vector<float> bestDepth(leftEnd, -1.0f);
     for (size_t leftRow = 0; leftRow < leftEnd; leftRow++) {
         const KeyPoint& kl = keys.keyPoints[leftRow];
         const int yKey = cvRoundF(kl.y);
@@ -116,13 +116,33 @@ void findStereoMatchesORB2R(const Extractor& feLeft, const Extractor& feRight, c
         const float disparity = kl.x - newuR;
         if (disparity > 0.0f && (double)disparity < rig.fx) {
             const float depth = ((float)rig.fx * rig.baseline) / disparity;
-            keys.rightIdxs[leftRow] = bestIdx;
-            keys.leftIdxs[bestIdx] = (int)leftRow;
-            keys.estimatedDepth[leftRow] = depth;
-            allDists2.emplace_back(bestDistW, (int)leftRow);
-            allDepths.emplace_back(depth, (int)leftRow);
-            if (depth < rig.baseline * closeNumber) keys.close[leftRow] = 1;
+            best[leftRow] = bestIdx;
+            bestDepth[leftRow] = depth;
+            bestSad[leftRow] = bestDistW;
         }
+    }
+    if (pre) { pre->best = best; pre->depth = bestDepth; pre->sad = bestSad; }
+    stereoFinalize(keys, best, bestDepth, bestSad, rig.baseline * closeNumber);
+}
+
+// The tail of findStereoMatchesORB2R (src/FeatureMatcher.cpp:655-705) on per-left (best right index or -1, depth,
+// SAD): the accepted pairs are entered in ascending left order (so the last left key accepted onto a right key owns
+// leftIdxs), then the nearest 1 % by (depth, index) and every pair whose SAD is not below 2.1 x the median SAD are
+// invalidated.  keys.rightIdxs / estimatedDepth / close (nL) and keys.leftIdxs (nR) must be sized and hold -1 / -1 / 0.
+void stereoFinalize(TrackedKeys& keys, const std::vector<int>& best, const std::vector<float>& bestDepth,
+                    const std::vector<int>& bestSad, float closeDepth) {
+    std::vector<std::pair<float, int>> allDepths;
+    std::vector<std::pair<int, int>> allDists2;
+    for (size_t leftRow = 0; leftRow < best.size(); leftRow++) {
+        const int bestIdx = best[leftRow];
+        if (bestIdx < 0) continue;
+        const float depth = bestDepth[leftRow];
+        keys.rightIdxs[leftRow] = bestIdx;
+        keys.leftIdxs[bestIdx] = (int)leftRow;
+        keys.estimatedDepth[leftRow] = depth;
+        allDists2.emplace_back(bestSad[leftRow], (int)leftRow);
+        allDepths.emplace_back(depth, (int)leftRow);
+        if (depth < closeDepth) keys.close[leftRow] = 1;
     }
     if (allDepths.empty()) return;
     std::sort(allDepths.begin(), allDepths.end());

@@ -28,8 +28,14 @@ struct TrackedKeys {
 struct StereoStats { long long candidates = 0; long long sadRefinements = 0; long long matches = 0; };
 
 int descriptorDistance(const uint8_t* a, const uint8_t* b);   // src/FeatureMatcher.cpp:710-726
+// what the matching loop hands to the two cuts: per left key the accepted right index (or -1), its depth and SAD
+struct StereoPreCut { std::vector<int> best; std::vector<float> depth; std::vector<int> sad; };
+
 void findStereoMatchesORB2R(const Extractor& feLeft, const Extractor& feRight, const Rig& rig,
-                            TrackedKeys& keys, StereoStats* stats = nullptr);  // :528-708
+                            TrackedKeys& keys, StereoStats* stats = nullptr, StereoPreCut* pre = nullptr);  // :528-708
+// its tail (:655-705): accepted pairs entered in left order, nearest-1 % depth cut, 2.1 x median-SAD cut
+void stereoFinalize(TrackedKeys& keys, const std::vector<int>& best, const std::vector<float>& bestDepth,
+                    const std::vector<int>& bestSad, float closeDepth);
 void assignKeysToGrids(TrackedKeys& keys, const std::vector<KeyPoint>& kps,
                        std::vector<std::vector<int>>& grid, int width, int height);  // FeatureTracker.cpp:28-54
 void getMatchIdxs(float px, float py, std::vector<int>& idxs, const TrackedKeys& keys,
