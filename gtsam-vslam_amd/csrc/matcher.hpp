@@ -208,6 +208,17 @@ struct ProjLane {            // one lane of the batched projection matching
 };
 void launch_proj_batch(hipStream_t s, const ProjLane* dLanes, int B, int maxM, int maxL, int maxR, StageTimer* tm = nullptr, bool buildCells = true);
 constexpr int PROJ_MAX_CELLS = 64 * 64;      // xGrids = 64, yGrids = ceil(64 / aspect) <= 64 for landscape images
+// candidate key of the window scans (proj_dev.hpp): dist | cell | idx | octave, most significant first.  A portrait rig has
+// more than 64 grid rows (480 x 752: 101), so the cell field is wider than PROJ_MAX_CELLS needs.
+constexpr int KEY_OCT_BITS = 8, KEY_IDX_BITS = 16, KEY_CELL_BITS = 16, KEY_DIST_BITS = 9;
+constexpr int KEY_IDX_SHIFT = KEY_OCT_BITS, KEY_CELL_SHIFT = KEY_IDX_SHIFT + KEY_IDX_BITS, KEY_DIST_SHIFT = KEY_CELL_SHIFT + KEY_CELL_BITS;
+static_assert(KEY_DIST_SHIFT + KEY_DIST_BITS <= 63, "a valid key stays below KEY_NONE");
+static_assert(PROJ_MAX_CELLS <= (1 << KEY_CELL_BITS), "bucketed grids fit the cell field");
+// matching grid of a w x h rig (assignKeysToGrids): does every cell index fit the key's cell field?
+inline bool key_grid_fits(int w, int h) {
+    if (w <= 0 || h <= 0) return false;
+    return 64 * (long long)cv_ceil_f(64.f / ((float)w / (float)h)) <= (1ll << KEY_CELL_BITS);
+}
 void launch_proj_cells(hipStream_t s, const ProjArgs& A);
 void launch_proj_candidates(hipStream_t s, const ProjArgs& A, const int* matches,
                             unsigned long long* topk, unsigned long long* stats);

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_np_match(const NpArgs* __restrict__ tab
     if (lane == 0) {
         const int matchDistLBA = 50;         // include/FeatureMatcher.h:29
         const float ratioLBA = 0.6f;         // :30
-        const unsigned long long POS = ((1ull << 36) - 1ull) & ~0xffull;      // (cell, idx) = visit position
+        const unsigned long long POS = KEY_POS_MASK;      // (cell, idx) = visit position
         int bestDist = 256, bestIdx = -1, bestLev = -1, bestLev2 = -1, secDist = 256;
         if (l2[0] != KEY_NONE && key_dist(l2[0]) < 256) { bestDist = key_dist(l2[0]); bestIdx = key_idx(l2[0]); bestLev = key_oct(l2[0]); }
         if (l2[1] != KEY_NONE && key_dist(l2[1]) < 256 && bestIdx >= 0) {
@@ -602,6 +602,7 @@ static vslam_status np_run(const vslam_new_points_problem* const* Ps, vslam_new_
             set_error("vslam_find_new_points: invalid problem");
             return VSLAM_ERR_INVALID;
         }
+        if (!key_grid_fits(P->rig.width, P->rig.height)) { set_error("vslam_find_new_points: the matching grid of a %d x %d rig does not fit the candidate keys", P->rig.width, P->rig.height); return VSLAM_ERR_INVALID; }
         const vslam_kf_view& K0 = P->kfs[0];
         if (K0.n_left > 0 && (!P->estimated_depth || !P->has_mp || !K0.right_idxs || !K0.unmatched_f)) { set_error("vslam_find_new_points: last keyframe arrays missing"); return VSLAM_ERR_INVALID; }
         for (int k = 0; k < P->n_kf; k++) {

@@ -9,14 +9,16 @@ __device__ __forceinline__ int p_cvFloor(float v) { int i = (int)v; return i - (
 __device__ __forceinline__ int p_cvCeil(float v) { int i = (int)v; return i + (i < v); }
 
 constexpr unsigned long long KEY_NONE = ~0ull;
-// key = dist << 36 | cell << 24 | idx << 8 | octave   (idx unique => octave never decides order)
+// key = dist | cell | idx | octave at the KEY_*_SHIFT positions of matcher.hpp   (idx unique => octave never decides order)
 __device__ __forceinline__ unsigned long long make_key(int dist, int cell, int idx, int oct) {
-    return ((unsigned long long)dist << 36) | ((unsigned long long)cell << 24) |
-           ((unsigned long long)idx << 8) | (unsigned long long)(oct & 0xff);
+    return ((unsigned long long)dist << KEY_DIST_SHIFT) | ((unsigned long long)cell << KEY_CELL_SHIFT) |
+           ((unsigned long long)idx << KEY_IDX_SHIFT) | (unsigned long long)(oct & ((1 << KEY_OCT_BITS) - 1));
 }
-__device__ __forceinline__ int key_dist(unsigned long long k) { return (int)(k >> 36); }
-__device__ __forceinline__ int key_idx(unsigned long long k) { return (int)((k >> 8) & 0xffff); }
-__device__ __forceinline__ int key_oct(unsigned long long k) { return (int)(k & 0xff); }
+__device__ __forceinline__ int key_dist(unsigned long long k) { return (int)(k >> KEY_DIST_SHIFT); }
+__device__ __forceinline__ int key_idx(unsigned long long k) { return (int)((k >> KEY_IDX_SHIFT) & ((1 << KEY_IDX_BITS) - 1)); }
+__device__ __forceinline__ int key_oct(unsigned long long k) { return (int)(k & ((1 << KEY_OCT_BITS) - 1)); }
+// (cell, idx) of a key = its position in the reference's visit order (rows, columns, then the order within a cell)
+constexpr unsigned long long KEY_POS_MASK = ((1ull << KEY_DIST_SHIFT) - 1ull) & ~((1ull << KEY_IDX_SHIFT) - 1ull);
 
 template <int K>
 __device__ __forceinline__ void insert_sorted(unsigned long long (&a)[K], unsigned long long key) {

@@ -502,6 +502,7 @@ hipEvent_t vslam_matcher::use_event(vslam_extractor* fe, bool create) {
 vslam_status vslam_matcher::init(const vslam_rig* r, vslam_extractor* l, int il, vslam_extractor* rr, int ir) {
     if (!r) { set_error("vslam_matcher_create: invalid arguments"); return VSLAM_ERR_INVALID; }
     rig = *r;
+    if (!key_grid_fits(rig.width, rig.height)) { set_error("vslam_matcher_create: the matching grid of a %d x %d rig does not fit the candidate keys", rig.width, rig.height); return VSLAM_ERR_INVALID; }
     VS_CHECK(bind(l, il, rr, ir));
     device = l->device;
     VS_HIP(hipSetDevice(device));

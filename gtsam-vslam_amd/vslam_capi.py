@@ -750,10 +750,83 @@ class NewPointsResult(C.Structure):
                 ("accepted", C.c_void_p), ("xyz", C.c_void_p), ("n_obs", C.c_void_p), ("obs", C.c_void_p)]
 
 
-def find_new_points(rig, scale_pyramid, sigma_factor, kfs, last, device=0):
-    """kfs: list of dicts (T_wc, id, kpsL, descL, kpsR, descR, rightIdxs, leftIdxs, unF, unFR), kfs[0] = lastKF;
-    last: dict(depth, hasMp, mpXyz, mpDesc)."""
+def _kf_view(v, kf, ptr):
+    v.T_wc = ptr(kf["T_wc"], np.float64); v.id = int(kf["id"]); v.n_left = len(kf["kpsL"]); v.n_right = len(kf["kpsR"])
+    v.kps_l, v.desc_l = ptr(kf["kpsL"], KP_DTYPE), ptr(kf["descL"], np.uint8)
+    v.kps_r, v.desc_r = ptr(kf["kpsR"], KP_DTYPE), ptr(kf["descR"], np.uint8)
+    v.right_idxs, v.left_idxs = ptr(kf["rightIdxs"], np.int32), ptr(kf["leftIdxs"], np.int32)
+    v.unmatched_f, v.unmatched_fr = ptr(kf["unF"], np.int32), ptr(kf["unFR"], np.int32)
+
+
+def _np_call(rig, scale_pyramid, sigma_factor, kfs, last, keep, n_kf=None, capacity=None, device_keys=None):
+    """problem and result structures of one window (their arrays stay alive in `keep`) -> (P, R, result arrays)"""
     n = len(kfs)
+
+    def ptr(a, dt):
+        a = np.ascontiguousarray(a, dt)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    views = (KfView * max(n, 1))()
+    for k, kf in enumerate(kfs):
+        _kf_view(views[k], kf, ptr)
+        if device_keys and k in device_keys:
+            views[k].device_keys = int(device_keys[k])
+    sp = np.ascontiguousarray(scale_pyramid, np.float32); sg = np.ascontiguousarray(sigma_factor, np.float32)
+    keep.extend([views, sp, sg])
+    P = NewPointsProblem()
+    P.rig = make_rig(rig); P.n_levels = len(sp); P.scale_pyramid, P.sigma_factor = _p(sp), _p(sg)
+    P.log_scale = float(np.float32(np.log(np.float64(sp[1])))); P.n_kf = n if n_kf is None else int(n_kf); P.kfs = C.cast(views, C.c_void_p)
+    P.estimated_depth, P.has_mp = ptr(last["depth"], np.float32), ptr(last["hasMp"], np.uint8)
+    P.mp_xyz, P.mp_desc = ptr(last["mpXyz"], np.float64), ptr(last["mpDesc"], np.uint8)
+    n0 = max(len(kfs[0]["kpsL"]), 1)
+    out = dict(cL=np.zeros(n0, np.int32), cR=np.zeros(n0, np.int32), acc=np.zeros(n0, np.uint8), xyz=np.zeros((n0, 3)),
+               nObs=np.zeros(n0, np.int32), obs=np.full((n0, max(n, 1), 3), -1, np.int32))
+    R = NewPointsResult()
+    R.capacity = n0 if capacity is None else int(capacity)
+    R.cand_left, R.cand_right, R.accepted, R.xyz, R.n_obs, R.obs = (_p(out[k]) for k in ("cL", "cR", "acc", "xyz", "nObs", "obs"))
+    return P, R, out
+
+
+def _np_out(R, o):
+    nc = R.n_candidates
+    return dict(n=nc, candL=o["cL"][:nc], candR=o["cR"][:nc], accepted=o["acc"][:nc], xyz=o["xyz"][:nc], nObs=o["nObs"][:nc], obs=o["obs"][:nc])
+
+
+def find_new_points(rig, scale_pyramid, sigma_factor, kfs, last, device=0, n_kf=None, capacity=None, device_keys=None):
+    """kfs: list of dicts (T_wc, id, kpsL, descL, kpsR, descR, rightIdxs, leftIdxs, unF, unFR), kfs[0] = lastKF;
+    last: dict(depth, hasMp, mpXyz, mpDesc).  Test taps: n_kf / capacity override what the structures say (argument
+    checks; a VslamError then carries n_candidates), device_keys = {k: device address of keyframe k's resident block}."""
+    keep = []
+    P, R, o = _np_call(rig, scale_pyramid, sigma_factor, kfs, last, keep, n_kf, capacity, device_keys)
+    st = lib().vslam_find_new_points(C.byref(P), C.byref(R), int(device))
+    if st != OK:
+        e = VslamError(st, lib().vslam_last_error().decode())
+        e.n_candidates = R.n_candidates
+        raise e
+    return _np_out(R, o)
+
+
+def find_new_points_batch(rig, scale_pyramid, sigma_factor, windows, device=0):
+    """vslam_find_new_points_batch: windows = list of (kfs, last); one result dict per window"""
+    keep, calls = [], []
+    for kfs, last in windows:
+        calls.append(_np_call(rig, scale_pyramid, sigma_factor, kfs, last, keep))
+    n = len(calls)
+    Ps = (C.POINTER(NewPointsProblem) * n)(*[C.pointer(c[0]) for c in calls])
+    Rs = (C.POINTER(NewPointsResult) * n)(*[C.pointer(c[1]) for c in calls])
+    _chk(lib().vslam_find_new_points_batch(Ps, Rs, n, int(device)))
+    return [_np_out(c[1], c[2]) for c in calls]
+
+
+def kf_keys_bytes(n_left, n_right):
+    lib().vslam_kf_keys_bytes.restype = C.c_size_t
+    return int(lib().vslam_kf_keys_bytes(int(n_left), int(n_right)))
+
+
+def kf_keys_upload(kf, device_block, device=0):
+    """fills the device block at address device_block (kf_keys_bytes(...) bytes of device memory owned by the caller) from
+    the keyframe dict's host arrays"""
     keep = []
 
     def ptr(a, dt):
@@ -761,29 +834,9 @@ def find_new_points(rig, scale_pyramid, sigma_factor, kfs, last, device=0):
         keep.append(a)
         return a.ctypes.data if a.size else None
 
-    views = (KfView * n)()
-    for k, kf in enumerate(kfs):
-        v = views[k]
-        v.T_wc = ptr(kf["T_wc"], np.float64); v.id = int(kf["id"]); v.n_left = len(kf["kpsL"]); v.n_right = len(kf["kpsR"])
-        v.kps_l, v.desc_l = ptr(kf["kpsL"], KP_DTYPE), ptr(kf["descL"], np.uint8)
-        v.kps_r, v.desc_r = ptr(kf["kpsR"], KP_DTYPE), ptr(kf["descR"], np.uint8)
-        v.right_idxs, v.left_idxs = ptr(kf["rightIdxs"], np.int32), ptr(kf["leftIdxs"], np.int32)
-        v.unmatched_f, v.unmatched_fr = ptr(kf["unF"], np.int32), ptr(kf["unFR"], np.int32)
-    sp = np.ascontiguousarray(scale_pyramid, np.float32); sg = np.ascontiguousarray(sigma_factor, np.float32)
-    P = NewPointsProblem()
-    P.rig = make_rig(rig); P.n_levels = len(sp); P.scale_pyramid, P.sigma_factor = _p(sp), _p(sg)
-    P.log_scale = float(np.float32(np.log(np.float64(sp[1])))); P.n_kf = n; P.kfs = C.cast(views, C.c_void_p)
-    P.estimated_depth, P.has_mp = ptr(last["depth"], np.float32), ptr(last["hasMp"], np.uint8)
-    P.mp_xyz, P.mp_desc = ptr(last["mpXyz"], np.float64), ptr(last["mpDesc"], np.uint8)
-    n0 = max(len(kfs[0]["kpsL"]), 1)
-    cL = np.zeros(n0, np.int32); cR = np.zeros(n0, np.int32); acc = np.zeros(n0, np.uint8); xyz = np.zeros((n0, 3))
-    nObs = np.zeros(n0, np.int32); obs = np.full((n0, n, 3), -1, np.int32)
-    R = NewPointsResult()
-    R.capacity = n0
-    R.cand_left, R.cand_right, R.accepted, R.xyz, R.n_obs, R.obs = _p(cL), _p(cR), _p(acc), _p(xyz), _p(nObs), _p(obs)
-    _chk(lib().vslam_find_new_points(C.byref(P), C.byref(R), int(device)))
-    nc = R.n_candidates
-    return dict(n=nc, candL=cL[:nc], candR=cR[:nc], accepted=acc[:nc], xyz=xyz[:nc], nObs=nObs[:nc], obs=obs[:nc])
+    v = KfView()
+    _kf_view(v, kf, ptr)
+    _chk(lib().vslam_kf_keys_upload(C.byref(v), int(device), C.c_void_p(int(device_block))))
 
 
 class MonoPointsProblem(C.Structure):

@@ -4,6 +4,7 @@ Candidate lists, match triples and accept flags bit-exact; triangulated position
 import numpy as np
 import pytest
 import synth
+import newpts_cases as nc
 
 pytestmark = pytest.mark.gpu
 
@@ -110,3 +111,109 @@ def test_keyframe_update_pose_parity(oracle, capi):
         got = capi.keyframe_update_pose(*_kf_update_args(capi, pr))
         assert np.array_equal(got["dropL"], ref["dropL"]) and np.array_equal(got["dropR"], ref["dropR"])
         assert np.array_equal(got["lm"], ref["lm"]) and np.array_equal(got["pose"], ref["pose"])
+
+
+# ---- crafted windows (tests/newpts_cases.py; tests/test_oracle_newpts.py proves on the CPU that each is in its regime) ----------
+def _assert_same(got, ref, what):
+    """the bar of test_find_new_points_parity: everything bit-exact, accepted positions within 1e-9 relative"""
+    assert got["n"] == ref["n"], what
+    for f in ("candL", "candR", "nObs", "obs", "accepted"):
+        assert np.array_equal(got[f], ref[f]), (what, f, np.nonzero(np.asarray(got[f] != ref[f]).reshape(len(ref[f]), -1).any(1))[0][:8])
+    a = ref["accepted"] > 0
+    if a.any():
+        scale = np.maximum(1.0, np.abs(ref["xyz"][a]).max(axis=1))
+        assert (np.abs(got["xyz"][a] - ref["xyz"][a]).max(axis=1) / scale).max() < 1e-9, what
+
+
+def _crafted_parity(oracle, capi, c):
+    ref = oracle.find_new_points(c.ex, c.g.rig, c.kfs, c.last)
+    got = capi.find_new_points(c.g.rig, c.ex.scalePyramid, c.ex.sigmaFactor, c.kfs, c.last)
+    _assert_same(got, ref, c.name)
+    assert got["n"] == len(c.cands)
+    # what the case guarantees: its accepted and rejected probes, each with the outcome it was built for
+    assert int(got["accepted"].sum()) >= c.min_accepted and int((got["accepted"] == 0).sum()) >= c.min_rejected
+    for name, f in c.finals.items():
+        ci = c.probes[name]["cand"]
+        assert got["accepted"][ci] == f["accepted"] and got["nObs"][ci] == f["nObs"], (c.name, name)
+    for name, p in c.probes.items():
+        if p["kf"] is not None and p["expect"].get("verdict", "").startswith("matched"):
+            assert got["nObs"][p["cand"]] == 2 and got["obs"][p["cand"]][1].tolist() == [p["kf"]] + list(c.pairs[p["cand"]][p["kf"]]["out"]), (c.name, name)
+        elif p["kf"] is not None:
+            assert got["nObs"][p["cand"]] == 1, (c.name, name)
+    return ref, got
+
+
+@pytest.mark.parametrize("rig_name", nc.RIG_NAMES)
+@pytest.mark.parametrize("name", list(nc.ALL_CASES))
+def test_crafted_window_parity(oracle, capi, name, rig_name):
+    _crafted_parity(oracle, capi, nc.get(oracle, name, rig_name))
+
+
+@pytest.mark.parametrize("name", list(nc.PORTRAIT_CASES))
+def test_portrait_window_parity(oracle, capi, name):
+    """480 x 752: 101 grid rows, so the keys of rows >= 64 have cell indices beyond 4095 (more than 12 bits)"""
+    _crafted_parity(oracle, capi, nc.get(oracle, name, "portrait"))
+
+
+@pytest.mark.parametrize("rig_name", nc.RIG_NAMES)
+def test_batch_of_unequal_lanes(oracle, capi, rig_name):
+    """one vslam_find_new_points_batch call, lanes of n_left 0 / 70 / 1025 and n_kf 1 / 5 / 16: the grids are sized by the
+    largest lane, the small lanes ignore the excess blocks; each lane equals its own single call and the oracle"""
+    lanes = [nc.get(oracle, n, rig_name) for n in ("empty_last", "skip_mid_70", "row_counts_1025")]
+    wins = [(c.kfs[:1] if c.name == "empty_last" else c.kfs, c.last) for c in lanes]
+    assert [len(k[0]["kpsL"]) for k, _ in wins] == [0, 70, 1025] and [len(k) for k, _ in wins] == [1, 5, 16]
+    ex, rig = lanes[0].ex, lanes[0].g.rig
+    got = capi.find_new_points_batch(rig, ex.scalePyramid, ex.sigmaFactor, wins)
+    for c, (kfs, last), g in zip(lanes, wins, got):
+        one = capi.find_new_points(rig, ex.scalePyramid, ex.sigmaFactor, kfs, last)
+        for f in ("n", "candL", "candR", "nObs", "obs", "accepted", "xyz"):
+            assert np.array_equal(g[f], one[f]), (c.name, f)
+        _assert_same(g, oracle.find_new_points(ex, rig, kfs, last), c.name)
+    assert got[0]["n"] == 0 and got[1]["accepted"].sum() == 10 and got[2]["accepted"].sum() == 36
+    # the lanes in another order: the largest first
+    rev = capi.find_new_points_batch(rig, ex.scalePyramid, ex.sigmaFactor, wins[::-1])[::-1]
+    for a, b in zip(got, rev):
+        for f in ("n", "candL", "candR", "nObs", "obs", "accepted", "xyz"):
+            assert np.array_equal(a[f], b[f])
+
+
+def test_resident_keyframes_equal_host_keyframes(oracle, capi):
+    """keyframes 1 and 3 of a five-keyframe window uploaded once (vslam_kf_keys_upload) and passed as device_keys, their
+    host arrays still given for unF / unFR: the result is the all-host call's"""
+    import torch
+    c = nc.get(oracle, "skip_mid_70", "euroc")
+    host = capi.find_new_points(c.g.rig, c.ex.scalePyramid, c.ex.sigmaFactor, c.kfs, c.last)
+    blocks = {}
+    for k in (1, 3):
+        nb = capi.kf_keys_bytes(len(c.kfs[k]["kpsL"]), len(c.kfs[k]["kpsR"]))
+        assert nb >= 28 * (len(c.kfs[k]["kpsL"]) + len(c.kfs[k]["kpsR"])) + 36 * (len(c.kfs[k]["kpsL"]) + len(c.kfs[k]["kpsR"]))
+        blocks[k] = torch.zeros(nb, dtype=torch.uint8, device="cuda")
+        capi.kf_keys_upload(c.kfs[k], blocks[k].data_ptr())
+    torch.cuda.synchronize()
+    # the host copies of the immutable arrays of a resident keyframe are not read: scramble them
+    kfs = [dict(k) for k in c.kfs]
+    for k in (1, 3):
+        kfs[k]["descL"] = np.zeros_like(kfs[k]["descL"]); kfs[k]["descR"] = np.zeros_like(kfs[k]["descR"])
+    res = capi.find_new_points(c.g.rig, c.ex.scalePyramid, c.ex.sigmaFactor, kfs, c.last, device_keys={k: b.data_ptr() for k, b in blocks.items()})
+    for f in ("n", "candL", "candR", "nObs", "obs", "accepted", "xyz"):
+        assert np.array_equal(res[f], host[f]), f
+    assert res["accepted"].sum() == 10
+    _assert_same(res, oracle.find_new_points(c.ex, c.g.rig, c.kfs, c.last), "resident")
+
+
+def test_new_points_argument_checks(oracle, capi):
+    """more than 16 keyframes and none are rejected before any launch; a result capacity below the candidate count is
+    reported after the search (whose own buffers are sized by the last keyframe's key count) with n_candidates set and
+    nothing written to the caller's arrays"""
+    c = nc.get(oracle, "chunk_1025_65", "euroc")
+    args = (c.g.rig, c.ex.scalePyramid, c.ex.sigmaFactor)
+    with pytest.raises(capi.VslamError) as e:
+        capi.find_new_points(*args, [c.kfs[0]] + [c.kfs[1]] * 16, c.last)
+    assert e.value.status == capi.ERR_INVALID
+    with pytest.raises(capi.VslamError) as e:
+        capi.find_new_points(*args, c.kfs, c.last, n_kf=0)
+    assert e.value.status == capi.ERR_INVALID
+    with pytest.raises(capi.VslamError) as e:
+        capi.find_new_points(*args, c.kfs, c.last, capacity=64)
+    assert e.value.status == capi.ERR_CAPACITY and e.value.n_candidates == 65
+    assert capi.find_new_points(*args, c.kfs, c.last, capacity=65)["n"] == 65

@@ -53,8 +53,8 @@ def test_projection_parity(oracle, capi, rad, jitter, dup):
     _projection_parity(oracle, capi, rad, jitter, dup)
 
 
-def _projection_parity(oracle, capi, rad, jitter, dup, rig_name="euroc", nfeat=1500, n_mps=900):
-    rig, oL, (kL, dL, kR, dR), st, ge, m = _frontend(oracle, capi, nfeat=nfeat, rig_name=rig_name)
+def _projection_parity(oracle, capi, rad, jitter, dup, rig_name="euroc", nfeat=1500, n_mps=900, frontend=None):
+    rig, oL, (kL, dL, kR, dR), st, ge, m = frontend or _frontend(oracle, capi, nfeat=nfeat, rig_name=rig_name)
     rng = np.random.default_rng(int(rad) + dup)
     mps = _make_mps(oracle, kL, dL, kR, dR, st, rng, n_mps, jitter, dup=dup)
     M = len(mps)
@@ -83,6 +83,27 @@ def _projection_parity(oracle, capi, rad, jitter, dup, rig_name="euroc", nfeat=1
     n2, mL2, mR2, mt2, _ = capi.match_projection(m, mps, 4.0, mL1, mR1, mt1)
     assert n2 == n_ref2
     assert np.array_equal(mt2, mt_ref2) and np.array_equal(mL2, mL_ref2) and np.array_equal(mR2, mR_ref2)
+
+
+def test_projection_parity_portrait_rig(oracle, capi):
+    """480 x 752: the matching grid has 101 rows of 64 cells, more than the bucket tables hold, so every lane of scan_side
+    strides over all keys (under claims), and the keys of grid rows >= 64 carry cell indices beyond 4095.  Same bar as
+    test_projection_parity."""
+    rig = dict(synth.RIGS["euroc"], w=480, h=752, cx=240.0, cy=376.0)
+    L = synth.random_image(rig["w"], rig["h"], 91)
+    speckle = np.random.default_rng(92).random(L.shape) < 0.25
+    R = np.minimum(np.roll(L, -12, axis=1).astype(np.int32) + speckle, 255).astype(np.uint8)
+    oL, oR = oracle.Extractor(1500), oracle.Extractor(1500)
+    kL, dL = oL.extract(L)
+    kR, dR = oR.extract(R)
+    st = oracle.stereo_match(oL, oR, rig, kL, dL, kR, dR)
+    ge = capi.Extractor(rig["w"], rig["h"], 1500, batch=2)
+    ge.extract([L, R])
+    m = capi.Matcher(rig, ge, 0, ge, 1)
+    m.stereo_match()
+    yMult = np.float32(101) / np.float32(rig["h"])
+    assert (np.rint(kL["y"] * yMult) >= 64).sum() > 200 and (st["rightIdxs"] >= 0).sum() > 100       # keys in the high rows, stereo pairs
+    _projection_parity(oracle, capi, 10.0, 6.0, 150, frontend=(rig, oL, (kL, dL, kR, dR), st, ge, m))
 
 
 def test_projection_claim_exhaustion_forces_rescan(oracle, capi):
