@@ -175,10 +175,14 @@ struct vslam_batch {
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
     vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
-                      const uint8_t* const* nextL = nullptr, const uint8_t* const* nextR = nullptr, const uint8_t* nextMask = nullptr);
+                      const uint8_t* const* nextL = nullptr, const uint8_t* const* nextR = nullptr, const uint8_t* nextMask = nullptr,
+                      bool raw = false);
     // images of the NEXT step whose extraction was enqueued at the end of the previous one (prefetch)
-    std::vector<const uint8_t*> prefetched; int prefetchedChannels = 1;
-    vslam_status enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, int channels, bool onDevice);
+    std::vector<const uint8_t*> prefetched; int prefetchedChannels = 1; bool prefetchedRaw = false;
+    // raw: unrectified frames through each lane's rectifiers (sys[b]->rectL / rectR)
+    vslam_status enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, int channels, bool onDevice,
+                                    bool raw);
+    std::vector<const vslam_rectifier*> rectPtrs;
     static void submit_mapping(void* self, vslam_system* s) {
         vslam_batch* b = (vslam_batch*)self;
         bool now = false;
@@ -437,8 +441,15 @@ vslam_status vslam_batch::ensure_dn(size_t bytes) {
 
 // level 0 of every active lane's pair + the whole extraction, on the extractor's stream
 vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint8_t* const* R, const uint8_t* mask, int stride, int channels,
-                                             bool onDevice) {
-    if (channels != 1) {        // colour frames: every active lane's pair converted by one launch (host: uploads, one wait, one launch)
+                                             bool onDevice, bool raw) {
+    if (raw) {                  // unrectified frames: every active lane's pair through its own cameras' maps, one launch
+        imgPtrs.assign((size_t)2 * B, nullptr); rectPtrs.assign((size_t)2 * B, nullptr);
+        for (int b = 0; b < B; b++) if (!mask || mask[b]) {
+            imgPtrs[2 * b] = L[b]; imgPtrs[2 * b + 1] = R[b];
+            rectPtrs[2 * b] = sys[b]->rectL; rectPtrs[2 * b + 1] = sys[b]->rectR;
+        }
+        VS_CHECK(fe->set_images_raw(imgPtrs.data(), rectPtrs.data(), stride, channels, onDevice, true));
+    } else if (channels != 1) {        // colour frames: every active lane's pair converted by one launch (host: uploads, one wait, one launch)
         imgPtrs.assign((size_t)2 * B, nullptr);
         for (int b = 0; b < B; b++) if (!mask || mask[b]) { imgPtrs[2 * b] = L[b]; imgPtrs[2 * b + 1] = R[b]; }
         VS_CHECK(fe->set_images_color(imgPtrs.data(), stride, channels, onDevice, true));
@@ -459,7 +470,7 @@ vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint
 
 vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                                const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
-                               const uint8_t* const* nextL, const uint8_t* const* nextR, const uint8_t* nextMask) {
+                               const uint8_t* const* nextL, const uint8_t* const* nextR, const uint8_t* nextMask, bool raw) {
     if (!L || !R || !frames || !T_wc_out) return VSLAM_ERR_INVALID;
     VS_HIP(hipSetDevice(device));
     vslam::thread_pool_wants_priority() = true;      // this thread's pool serves the group's requests (serve_requests)
@@ -554,7 +565,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
 
     // ---- device: images, extraction (already in flight when the previous step prefetched exactly these images) -----------
     {
-        bool hit = onDevice && prefetched.size() == (size_t)2 * B && prefetchedChannels == channels;
+        bool hit = onDevice && prefetched.size() == (size_t)2 * B && prefetchedChannels == channels && prefetchedRaw == raw;
         for (int b = 0; b < B && hit; b++) {
             const bool on = ls[b].on;
             hit = prefetched[2 * b] == (on ? L[b] : nullptr) && prefetched[2 * b + 1] == (on ? R[b] : nullptr);
@@ -562,7 +573,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
         prefetched.clear();
         if (!hit) {
             if (fe->countsPending) VS_CHECK(fe->wait_counts());      // (a prefetch for other images: let it finish first)
-            VS_CHECK(enqueue_extraction(L, R, mask, stride, channels, onDevice));
+            VS_CHECK(enqueue_extraction(L, R, mask, stride, channels, onDevice, raw));
         }
     }
     lap(1);
@@ -751,8 +762,8 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
     // ---- prefetch: the next frames' extraction runs under this step's host phases and the next step's begin ----------------
     // (the extractor alternates between two output sets, so this frame's keys stay readable for keyframe insertion)
     if (nextL && nextR && onDevice) {
-        VS_CHECK(enqueue_extraction(nextL, nextR, nextMask, stride, channels, true));
-        prefetched.assign((size_t)2 * B, nullptr); prefetchedChannels = channels;
+        VS_CHECK(enqueue_extraction(nextL, nextR, nextMask, stride, channels, true, raw));
+        prefetched.assign((size_t)2 * B, nullptr); prefetchedChannels = channels; prefetchedRaw = raw;
         for (int b = 0; b < B; b++) if (!nextMask || nextMask[b]) { prefetched[2 * b] = nextL[b]; prefetched[2 * b + 1] = nextR[b]; }
     }
 
@@ -878,6 +889,43 @@ vslam_status vslam_batch_track_stereo_prefetch_color(vslam_batch* b, const uint8
     if (!b) return VSLAM_ERR_INVALID;
     VS_CHECK(batch_color_args(b, stride, channels, "vslam_batch_track_stereo_prefetch_color"));
     return b->step(left, right, stride, channels, true, frame_numbers, imu, lane_mask, T_wc_out, reports, next_left, next_right, next_mask);
+}
+
+vslam_status vslam_batch_set_rectifiers(vslam_batch* b, int32_t lane, const vslam_rectifier* left, const vslam_rectifier* right) {
+    if (!b) return VSLAM_ERR_INVALID;
+    if (lane < -1 || lane >= b->B) { set_error("vslam_batch_set_rectifiers: lane %d of %d (-1 = every lane)", lane, b->B); return VSLAM_ERR_INVALID; }
+    // (all lanes share rig and device: what one lane accepts, every lane accepts)
+    for (int k = 0; k < b->B; k++) if (lane < 0 || k == lane) VS_CHECK(b->sys[k]->set_rectifiers(left, right, "vslam_batch_set_rectifiers"));
+    b->prefetched.clear();      // a prefetched extraction went through the rectifiers bound before
+    return VSLAM_OK;
+}
+
+// a raw call's arguments against the rectifiers of every lane that is active in this step (or the prefetched one)
+static vslam_status batch_raw_args(const vslam_batch* b, int32_t stride, int32_t channels, const uint8_t* mask, const uint8_t* nextMask,
+                                   bool next, const char* fn) {
+    for (int k = 0; k < b->B; k++) {
+        if (!((!mask || mask[k]) || (next && (!nextMask || nextMask[k])))) continue;
+        VS_CHECK(b->sys[k]->raw_args(stride, channels, fn));
+    }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_batch_track_stereo_raw(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                          int32_t channels, int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                          const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    VS_CHECK(batch_raw_args(b, stride, channels, lane_mask, nullptr, false, "vslam_batch_track_stereo_raw"));
+    return b->step(left, right, stride, channels, on_device != 0, frame_numbers, imu, lane_mask, T_wc_out, reports, nullptr, nullptr, nullptr, true);
+}
+
+vslam_status vslam_batch_track_stereo_prefetch_raw(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                                   int32_t channels, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                                   const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports,
+                                                   const uint8_t* const* next_left, const uint8_t* const* next_right,
+                                                   const uint8_t* next_mask) {
+    if (!b) return VSLAM_ERR_INVALID;
+    VS_CHECK(batch_raw_args(b, stride, channels, lane_mask, next_mask, next_left && next_right, "vslam_batch_track_stereo_prefetch_raw"));
+    return b->step(left, right, stride, channels, true, frame_numbers, imu, lane_mask, T_wc_out, reports, next_left, next_right, next_mask, true);
 }
 
 vslam_system* vslam_batch_system(vslam_batch* b, int32_t lane) {

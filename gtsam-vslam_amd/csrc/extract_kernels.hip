@@ -161,6 +161,98 @@ void launch_load_images_color(hipStream_t s, const uint8_t* const* dSrc, int str
     else hipLaunchKernelGGL(k_load_images_color<4>, grid, block, 0, s, dSrc, stride, pyr, P);
 }
 
+// One output pixel of cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) followed by BGR(A)2GRAY, with the arithmetic of
+// k_remap_linear / k_remap_linear_gray (rectify.hip) exactly: cvRound(map x 32), 5-bit fractions, weights x 32 of scale 2^15,
+// (sum + 2^14) >> 15 per channel, a tap outside the source 0 in every channel, each channel rounded BEFORE the conversion.
+// The kernel is bound by the number of gather instructions, not by bytes: the two taps of a source row are 2 CN contiguous
+// bytes, so when both lie inside the row they are fetched together (2, 4 + 2 or 8 bytes as packed structs: the compiler picks the
+// widest loads the target allows at byte alignment) instead of one byte load per tap and channel.  Sources and maps are device
+// buffers whose pointers come from a table in memory: typed as global pointers here, or every load would be a flat one.
+#define VS_GLOBAL __attribute__((address_space(1)))
+typedef const VS_GLOBAL uint8_t* gbytes_t;
+struct __attribute__((packed)) Packed2 { unsigned short v; };
+struct __attribute__((packed)) Packed4 { unsigned v; };
+struct __attribute__((packed)) Packed8 { unsigned x, y; };
+typedef float MapQuad __attribute__((ext_vector_type(4)));      // (a builtin vector: loadable through a global pointer)
+template <int CN>
+__device__ __forceinline__ void rect_row(gbytes_t q, bool row, bool in0, bool in1, unsigned& a, unsigned& b) {
+    // a / b: the row's left / right tap, B | G << 8 | R << 16 (CN = 1: the gray value); 0 outside the source
+    a = 0u; b = 0u;
+    if (!row) return;
+    if (in0 && in1) {
+        if constexpr (CN == 1) {
+            const unsigned v = ((const VS_GLOBAL Packed2*)q)->v;
+            a = v & 0xffu; b = v >> 8;
+        } else if constexpr (CN == 3) {
+            const unsigned u = ((const VS_GLOBAL Packed4*)q)->v, v = ((const VS_GLOBAL Packed2*)(q + 4))->v;
+            a = u & 0xffffffu; b = (u >> 24) | (v << 8);
+        } else {
+            const VS_GLOBAL Packed8* u = (const VS_GLOBAL Packed8*)q;
+            a = u->x; b = u->y;
+        }
+    } else if (in0 || in1) {
+        gbytes_t t = in0 ? q : q + CN;
+        const unsigned v = CN == 1 ? (unsigned)t[0] : ((unsigned)t[0] | ((unsigned)t[1] << 8) | ((unsigned)t[2] << 16));
+        if (in0) a = v; else b = v;
+    }
+}
+template <int CN>
+__device__ __forceinline__ unsigned rect_pixel(gbytes_t S, int stride, int sw, int sh, float mx, float my) {
+    const int sx = __float2int_rn(mx * 32.0f), sy = __float2int_rn(my * 32.0f);
+    const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
+    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+    const bool in0 = (unsigned)ix < (unsigned)sw, in1 = (unsigned)(ix + 1) < (unsigned)sw;
+    const bool r0 = (unsigned)iy < (unsigned)sh, r1 = (unsigned)(iy + 1) < (unsigned)sh;
+    gbytes_t p = S + ((long long)iy * stride + (long long)ix * CN);      // (read only at taps inside the image)
+    unsigned a, b, d, e;
+    rect_row<CN>(p, r0, in0, in1, a, b);
+    rect_row<CN>(p + stride, r1, in0, in1, d, e);
+    auto chan = [&](int sh8) -> int {
+        return (int)(((a >> sh8) & 0xff) * w00 + ((b >> sh8) & 0xff) * w01 + ((d >> sh8) & 0xff) * w10 + ((e >> sh8) & 0xff) * w11 + (1 << 14)) >> 15;
+    };
+    if constexpr (CN == 1) return (unsigned)chan(0);
+    else return (unsigned)bgr_to_gray(chan(0), chan(8), chan(16));
+}
+
+// Level 0 of every image of the step from RAW sources: rectification (and the gray conversion of BGR / BGRA sources) fused
+// into the load, one launch.  thread = 4 horizontally adjacent output pixels (two float4 map loads, one dword store; rows
+// whose maps are not 16-byte aligned and the last columns of a width that is no multiple of 4 take the scalar tail).
+// grid.x = image: the workgroups of one output tile are dispatched next to each other for all images, so a tile of the
+// (mostly shared) float maps is fetched from HBM once per L2 rather than once per image.
+template <int CN>
+__global__ __launch_bounds__(256) void k_load_images_rect(const RectSrc* __restrict__ tab, uint8_t* __restrict__ pyr, PyrDesc P) {
+    const int img = blockIdx.x;
+    const RectSrc T = tab[img];
+    if (!T.src) return;
+    const int w = P.w[0], h = P.h[0], dp = P.pitch[0];
+    const int y = blockIdx.z * 4 + threadIdx.y;
+    const int x0 = (blockIdx.y * 64 + threadIdx.x) * 4;
+    if (y >= h || x0 >= w) return;
+    gbytes_t S = (gbytes_t)T.src;
+    const VS_GLOBAL float* mxp = (const VS_GLOBAL float*)T.mapX + (size_t)y * w + x0;
+    const VS_GLOBAL float* myp = (const VS_GLOBAL float*)T.mapY + (size_t)y * w + x0;
+    uint8_t* q = pyr + (size_t)img * P.imgStride + P.off[0] + (size_t)y * dp + x0;      // (4-byte aligned: pitch and x0 are)
+    if (x0 + 4 <= w && ((((uintptr_t)mxp) | ((uintptr_t)myp)) & 15) == 0) {
+        const MapQuad mx = *(const VS_GLOBAL MapQuad*)mxp, my = *(const VS_GLOBAL MapQuad*)myp;
+        *(unsigned*)q = rect_pixel<CN>(S, T.stride, T.sw, T.sh, mx.x, my.x) |
+                        (rect_pixel<CN>(S, T.stride, T.sw, T.sh, mx.y, my.y) << 8) |
+                        (rect_pixel<CN>(S, T.stride, T.sw, T.sh, mx.z, my.z) << 16) |
+                        (rect_pixel<CN>(S, T.stride, T.sw, T.sh, mx.w, my.w) << 24);
+    } else {
+        const int n = min(4, w - x0);
+        unsigned o = 0;
+        for (int i = 0; i < n; i++) o |= rect_pixel<CN>(S, T.stride, T.sw, T.sh, mxp[i], myp[i]) << (8 * i);
+        if (n == 4) *(unsigned*)q = o;
+        else for (int i = 0; i < n; i++) q[i] = (uint8_t)(o >> (8 * i));
+    }
+}
+void launch_load_images_rect(hipStream_t s, const RectSrc* dTab, int channels, uint8_t* pyr, const PyrDesc& P, int nimg) {
+    const dim3 grid(nimg, (P.w[0] + 255) / 256, (P.h[0] + 3) / 4), block(64, 4);
+    if (channels == 1) hipLaunchKernelGGL(k_load_images_rect<1>, grid, block, 0, s, dTab, pyr, P);
+    else if (channels == 3) hipLaunchKernelGGL(k_load_images_rect<3>, grid, block, 0, s, dTab, pyr, P);
+    else hipLaunchKernelGGL(k_load_images_rect<4>, grid, block, 0, s, dTab, pyr, P);
+}
+
 void launch_resize(hipStream_t s, uint8_t* pyr, const PyrDesc& P, int level, const int2* xtab,
                    const int2* ytab, int nimg) {
     dim3 block(64, 4);

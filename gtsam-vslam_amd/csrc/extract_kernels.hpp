@@ -54,6 +54,15 @@ void launch_load_images(hipStream_t s, const uint8_t* const* dSrc, int stride, u
 // level 0 from BGR (channels 3) / BGRA (4) sources, converted to gray; same grid and nullptr = keep rule
 void launch_load_images_color(hipStream_t s, const uint8_t* const* dSrc, int stride, int channels, uint8_t* pyr, const PyrDesc& P,
                               int nimg);
+// level 0 from RAW (unrectified) sources: one table entry per image - the source (nullptr = keep), that camera's CV_32F
+// maps ([h0][w0], the pyramid's level-0 size) and the source geometry.  Left / right cameras and the lanes of a batch may
+// differ in all of it.
+struct RectSrc {
+    const uint8_t* src; const float* mapX; const float* mapY;
+    int sw, sh, stride, pad;
+};
+// cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) per channel, then BGR(A)2GRAY (channels 3 / 4), written straight into level 0
+void launch_load_images_rect(hipStream_t s, const RectSrc* dTab, int channels, uint8_t* pyr, const PyrDesc& P, int nimg);
 void launch_resize(hipStream_t s, uint8_t* pyr, const PyrDesc& P, int level, const int2* xtab,
                    const int2* ytab, int nimg);
 void launch_fast(hipStream_t s, const uint8_t* pyr, const PyrDesc& P, const FastDesc& F,

@@ -282,6 +282,10 @@ void vslam_extractor::release() {
     hipFree(d_colPtrs); hipFree(d_colStage); h_colPtrs = nullptr; d_colPtrs = nullptr; d_colStage = nullptr; colStageBytes = 0;
     if (evColPtrs) hipEventDestroy(evColPtrs);
     evColPtrs = nullptr;
+    if (h_rectTab) hipHostFree(h_rectTab);
+    hipFree(d_rectTab); h_rectTab = nullptr; d_rectTab = nullptr;
+    if (evRectTab) hipEventDestroy(evRectTab);
+    evRectTab = nullptr;
     d_sscTmp = nullptr; d_taskCount = nullptr; d_sscFlags = nullptr; h_counts = nullptr;
     if (evGather) hipEventDestroy(evGather);
     if (evDone) hipEventDestroy(evDone);
@@ -387,6 +391,66 @@ vslam_status vslam_extractor::set_images_color(const uint8_t* const* ptrs, int s
     VS_HIP(hipMemcpyAsync(d_colPtrs, h_colPtrs, (size_t)nimg * sizeof(void*), hipMemcpyHostToDevice, stream));
     VS_HIP(hipEventRecord(evColPtrs, stream));
     launch_load_images_color(stream, d_colPtrs, srcStride, channels, d_pyr, P, nimg);
+    VS_HIP(hipGetLastError());
+    if (sync && !srcOnDevice) VS_HIP(hipStreamSynchronize(stream));  // caller may reuse its buffers
+    return VSLAM_OK;
+}
+
+vslam_status vslam_extractor::set_images_raw(const uint8_t* const* ptrs, const vslam_rectifier* const* rects, int stride, int channels,
+                                             bool srcOnDevice, bool sync) {
+    if (!ptrs || !rects || (channels != 1 && channels != 3 && channels != 4)) {
+        set_error("set_images_raw: channels %d (1, 3 or 4)", channels);
+        return VSLAM_ERR_INVALID;
+    }
+    size_t need = 0;                                    // staging bytes of the host sources
+    for (int i = 0; i < nimg; i++) {
+        if (!ptrs[i]) continue;
+        const vslam_rectifier* r = rects[i];
+        if (!r) { set_error("set_images_raw: image %d has no rectifier", i); return VSLAM_ERR_INVALID; }
+        if (r->device != device) { set_error("set_images_raw: the rectifier of image %d is on device %d, the extractor on %d", i, r->device, device); return VSLAM_ERR_INVALID; }
+        if (r->w != width || r->h != height) {
+            set_error("set_images_raw: the rectifier of image %d makes %d x %d images, the extractor takes %d x %d", i, r->w, r->h, width, height);
+            return VSLAM_ERR_INVALID;
+        }
+        if ((long long)stride < (long long)r->sw * channels) {
+            set_error("set_images_raw: stride %d (at least src_width x channels = %d)", stride, r->sw * channels);
+            return VSLAM_ERR_INVALID;
+        }
+        need += (size_t)r->sh * align_up(r->sw * channels, 16);
+    }
+    VS_HIP(hipSetDevice(device));
+    if (!h_rectTab) {
+        VS_HIP(hipHostMalloc((void**)&h_rectTab, (size_t)nimg * sizeof(RectSrc), hipHostMallocDefault));
+        VS_HIP(hipMalloc((void**)&d_rectTab, (size_t)nimg * sizeof(RectSrc)));
+        VS_HIP(hipEventCreateWithFlags(&evRectTab, hipEventDisableTiming));
+    } else {
+        VS_HIP(hipEventSynchronize(evRectTab));        // the previous table upload has been read before it is overwritten
+    }
+    wait_consumers();
+    if (!srcOnDevice && need > colStageBytes) {         // (the staging buffer is shared with the colour path: same stream)
+        VS_HIP(hipStreamSynchronize(stream));
+        hipFree(d_colStage); d_colStage = nullptr; colStageBytes = 0;
+        VS_HIP(hipMalloc((void**)&d_colStage, need));
+        colStageBytes = need;
+    }
+    size_t at = 0;
+    for (int i = 0; i < nimg; i++) {
+        RectSrc& t = h_rectTab[i];
+        t = RectSrc{};
+        if (!ptrs[i]) continue;
+        const vslam_rectifier* r = rects[i];
+        t.mapX = r->d_mapX; t.mapY = r->d_mapY; t.sw = r->sw; t.sh = r->sh;
+        if (srcOnDevice) { t.src = ptrs[i]; t.stride = stride; continue; }
+        // host sources: one 2D upload per image, rows of the SOURCE padded to 16 bytes
+        const int pitch = align_up(r->sw * channels, 16);
+        uint8_t* dst = d_colStage + at;
+        at += (size_t)r->sh * pitch;
+        VS_HIP(hipMemcpy2DAsync(dst, pitch, ptrs[i], stride, (size_t)r->sw * channels, r->sh, hipMemcpyHostToDevice, stream));
+        t.src = dst; t.stride = pitch;
+    }
+    VS_HIP(hipMemcpyAsync(d_rectTab, h_rectTab, (size_t)nimg * sizeof(RectSrc), hipMemcpyHostToDevice, stream));
+    VS_HIP(hipEventRecord(evRectTab, stream));
+    launch_load_images_rect(stream, d_rectTab, channels, d_pyr, P, nimg);
     VS_HIP(hipGetLastError());
     if (sync && !srcOnDevice) VS_HIP(hipStreamSynchronize(stream));  // caller may reuse its buffers
     return VSLAM_OK;
@@ -587,6 +651,18 @@ vslam_status vslam_extractor_set_image_color(vslam_extractor* ex, int32_t i, con
     std::vector<const uint8_t*> ptrs(ex->nimg, nullptr);
     ptrs[i] = (const uint8_t*)src;
     return ex->set_images_color(ptrs.data(), stride, channels, on_device != 0, true);
+}
+vslam_status vslam_extractor_set_image_raw(vslam_extractor* ex, int32_t i, const vslam_rectifier* rect, const void* src, int32_t stride,
+                                           int32_t channels, int32_t on_device) {
+    if (!ex) return VSLAM_ERR_INVALID;
+    if (i < 0 || i >= ex->nimg || !src || !rect) {
+        set_error("vslam_extractor_set_image_raw: image %d of %d, %s", i, ex->nimg, !rect ? "no rectifier" : "no source");
+        return VSLAM_ERR_INVALID;
+    }
+    std::vector<const uint8_t*> ptrs(ex->nimg, nullptr);
+    std::vector<const vslam_rectifier*> rects(ex->nimg, nullptr);
+    ptrs[i] = (const uint8_t*)src; rects[i] = rect;
+    return ex->set_images_raw(ptrs.data(), rects.data(), stride, channels, on_device != 0, true);
 }
 vslam_status vslam_extractor_run(vslam_extractor* ex) {
     if (!ex) return VSLAM_ERR_INVALID;

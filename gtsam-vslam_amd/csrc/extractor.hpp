@@ -3,6 +3,7 @@
 // `nimg` same-sized images per run).
 #pragma once
 #include "extract_kernels.hpp"
+#include "rectifier.hpp"
 #include <mutex>
 
 struct vslam_extractor {
@@ -84,5 +85,13 @@ struct vslam_extractor {
     uint8_t* d_colStage = nullptr; size_t colStageBytes = 0;
     const uint8_t** h_colPtrs = nullptr; const uint8_t** d_colPtrs = nullptr;
     hipEvent_t evColPtrs = nullptr;   // the last upload of the colour pointer table has been read
+    // RAW (unrectified) sources, channels 1 / 3 / 4: ptrs[i] != nullptr -> level 0 of image i, remapped through rects[i]'s maps
+    // (and converted to gray) by ONE launch of k_load_images_rect.  stride / channels describe the sources (rows of at least
+    // src_width x channels bytes).  Host sources are uploaded into d_colStage first (rows of the source, padded to 16 bytes).
+    // The rectifiers are borrowed: they must stay alive until the launch has run.
+    vslam_status set_images_raw(const uint8_t* const* ptrs, const vslam_rectifier* const* rects, int stride, int channels, bool srcOnDevice,
+                                bool sync);
+    vslam::RectSrc* h_rectTab = nullptr; vslam::RectSrc* d_rectTab = nullptr;
+    hipEvent_t evRectTab = nullptr;   // the last upload of the raw-source table has been read
     vslam_status run();
 };

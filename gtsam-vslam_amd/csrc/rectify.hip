@@ -13,7 +13,9 @@
 // src/FeatureTracker.cpp:1130-1144).  k_remap_linear_gray does exactly that in one pass: the tap rule above per channel,
 // each channel rounded before BGR(A)2GRAY (bgr_to_gray, common.hpp) - remap-then-convert, which differs from
 // convert-then-remap whenever the channels differ.  k_remap_linear remaps a gray image (channels = 1).
-#include "common.hpp"
+// These kernels are the stand-alone stage (rectified images in the caller's buffers).  The closed-loop handles remap inside
+// their level-0 load instead: k_load_images_rect (extract_kernels.hip) restates the tap rule and is tested against these.
+#include "rectifier.hpp"
 
 namespace vslam {
 
@@ -102,13 +104,6 @@ __global__ __launch_bounds__(256) void k_remap_linear_gray(const uint8_t* const*
 }  // namespace vslam
 
 using namespace vslam;
-
-struct vslam_rectifier {
-    int device = 0, w = 0, h = 0, sw = 0, sh = 0;
-    hipStream_t stream = nullptr;
-    float* d_mapX = nullptr; float* d_mapY = nullptr;
-    const uint8_t** h_ptrs = nullptr; const uint8_t** d_ptrs = nullptr; int ptrCap = 0;      // [src..., dst...]
-};
 
 static bool inv3(const double* m, double* o) {
     const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];

@@ -641,14 +641,47 @@ vslam_status vslam_system::frame_post_b(SysFrameCtx& c, double* T_wc_out, vslam_
     return VSLAM_OK;
 }
 
+vslam_status vslam_system::set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn) {
+    if (!l && !r) { rectL = rectR = nullptr; return VSLAM_OK; }
+    if (!l || !r) { set_error("%s: left and right rectifier are bound together (or both NULL to unbind)", fn); return VSLAM_ERR_INVALID; }
+    for (const vslam_rectifier* q : {l, r}) {
+        if (q->w != cfg.rig.width || q->h != cfg.rig.height) {
+            set_error("%s: a rectifier makes %d x %d images, the rig is %d x %d", fn, q->w, q->h, cfg.rig.width, cfg.rig.height);
+            return VSLAM_ERR_INVALID;
+        }
+        if (q->device != fe->device) { set_error("%s: a rectifier is on device %d, the session on %d", fn, q->device, fe->device); return VSLAM_ERR_INVALID; }
+    }
+    if (l->sw != r->sw || l->sh != r->sh) {
+        set_error("%s: the rectifiers' source sizes differ (%d x %d, %d x %d)", fn, l->sw, l->sh, r->sw, r->sh);
+        return VSLAM_ERR_INVALID;
+    }
+    rectL = l; rectR = r;
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system::raw_args(int stride, int channels, const char* fn) const {
+    if (!rectL || !rectR) { set_error("%s: no rectifiers bound (vslam_system_set_rectifiers / vslam_batch_set_rectifiers)", fn); return VSLAM_ERR_INVALID; }
+    if ((channels != 1 && channels != 3 && channels != 4) || (long long)stride < (long long)rectL->sw * channels) {
+        set_error("%s: channels %d (1, 3 or 4), stride %d (at least src_width x channels)", fn, channels, stride);
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
 vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame,
-                                 const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* rep) {
+                                 const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* rep, bool raw) {
     if (!L || !R || !T_wc_out) return VSLAM_ERR_INVALID;
+    if (raw) VS_CHECK(raw_args(stride, channels, "vslam_system_track_stereo_raw"));
     SysFrameCtx& c = ctx;
     VS_CHECK(frame_begin(c, frame, imu));
     VS_CHECK(frame_mid());
     // images -> pyramid level 0, extraction, stereo match (extractORBAndStereoMatch :56-70); nothing here depends on the map
-    if (channels != 1) {        // colour frames (cvtColor :1130-1144): both images converted by one launch
+    if (raw) {                  // unrectified frames (cv::remap, src/VIOSlam.cpp:296-297): both images rectified (and converted) by one launch
+        std::vector<const uint8_t*> ptrs(fe->nimg, nullptr);
+        std::vector<const vslam_rectifier*> rects(fe->nimg, nullptr);
+        ptrs[img0] = L; ptrs[img0 + 1] = R; rects[img0] = rectL; rects[img0 + 1] = rectR;
+        VS_CHECK(fe->set_images_raw(ptrs.data(), rects.data(), stride, channels, onDevice, true));
+    } else if (channels != 1) { // colour frames (cvtColor :1130-1144): both images converted by one launch
         std::vector<const uint8_t*> ptrs(fe->nimg, nullptr);
         ptrs[img0] = L; ptrs[img0 + 1] = R;
         VS_CHECK(fe->set_images_color(ptrs.data(), stride, channels, onDevice, true));
@@ -1189,6 +1222,18 @@ vslam_status vslam_system_track_stereo_color(vslam_system* s, const uint8_t* lef
         return VSLAM_ERR_INVALID;
     }
     return s->track(left, right, stride, channels, on_device != 0, frame_number, imu, T_wc_out, report);
+}
+
+vslam_status vslam_system_set_rectifiers(vslam_system* s, const vslam_rectifier* left, const vslam_rectifier* right) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->set_rectifiers(left, right, "vslam_system_set_rectifiers");
+}
+
+vslam_status vslam_system_track_stereo_raw(vslam_system* s, const uint8_t* left, const uint8_t* right, int32_t stride, int32_t channels,
+                                           int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu, double* T_wc_out,
+                                           vslam_frame_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->track(left, right, stride, channels, on_device != 0, frame_number, imu, T_wc_out, report, true);
 }
 
 vslam_status vslam_system_wait_mapping(vslam_system* s) {

@@ -255,8 +255,13 @@ struct vslam_system {
     vslam_status frame_post_b(SysFrameCtx& c, double* T_wc_out, vslam_frame_report* rep);
     void run_mapping();
     void finish_job(vslam_status s, const char* err);
+    // raw: L / R are unrectified frames (stride / channels describe them), rectified through rectL / rectR on the way into level 0
     vslam_status track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame, const vslam_imu_bucket* imu,
-                       double* T_wc_out, vslam_frame_report* rep);
+                       double* T_wc_out, vslam_frame_report* rep, bool raw = false);
+    // the cameras' rectifiers for raw frames (borrowed; both set or both null)
+    const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
+    vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);
+    vslam_status raw_args(int stride, int channels, const char* fn) const;      // a raw call's arguments against the bound rectifiers
     vslam_status fetch_keys(SysKeys& k);
     void mp_update(SysMP& mp, int kfNumb, std::vector<int>& needDesc, int mpIndex);
     vslam_status calc_descriptors(const std::vector<int>& mps);

@@ -114,6 +114,17 @@ class Extractor:
         else:
             _chk(self.L.vslam_extractor_set_image_color(self.h, idx, C.c_void_p(dptr), int(stride), int(channels), 1))
 
+    def set_image_raw(self, idx, rectifier, image, stride=None, channels=1, on_device=False):
+        """an UNRECTIFIED image through `rectifier` (a Rectifier whose output size is this extractor's) into level 0: host u8
+        array (sh, sw) gray, (sh, sw, 3) BGR or (sh, sw, 4) BGRA, or a device pointer with `channels` (stride default sw x cn)"""
+        if on_device:
+            sp, ch, st = C.c_void_p(image), channels, stride or rectifier.sw * channels
+        else:
+            img, ch, st = _image(image, rectifier.sh, rectifier.sw)
+            assert img.shape[:2] == (rectifier.sh, rectifier.sw)
+            sp = _p(img)
+        _chk(self.L.vslam_extractor_set_image_raw(self.h, idx, rectifier.h_r, sp, int(st), int(ch), int(on_device)))
+
     def run(self):
         _chk(self.L.vslam_extractor_run(self.h))
 
@@ -973,9 +984,15 @@ class System:
         except Exception:
             pass
 
-    def track(self, left, right, frame_number, imu_bucket=None, on_device=False, stride=None, channels=1):
+    def set_rectifiers(self, left, right):
+        """bind the cameras' Rectifier objects for track(raw=True) (None, None unbinds); they must outlive the session"""
+        _chk(self.L.vslam_system_set_rectifiers(self.h_sys, left.h_r if left is not None else None, right.h_r if right is not None else None))
+        self.src_size = (left.sw, left.sh) if left is not None else None
+
+    def track(self, left, right, frame_number, imu_bucket=None, on_device=False, stride=None, channels=1, raw=False):
         """left / right: u8 arrays (host: (H, W) gray, (H, W, 3) BGR or (H, W, 4) BGRA) or device pointers (on_device, with
-        `channels`).  imu_bucket: (acc (n,3), gyro (n,3), timestamps_ns (n))."""
+        `channels`).  imu_bucket: (acc (n,3), gyro (n,3), timestamps_ns (n)).  raw: unrectified frames of the bound
+        rectifiers' source size (sh, sw[, cn]; stride default sw x cn), rectified on the way into the pyramid."""
         T = np.zeros((4, 4))
         rep = FrameReport()
         b = None
@@ -984,16 +1001,20 @@ class System:
             acc, gyr, ts = (np.ascontiguousarray(a, np.float64) for a in imu_bucket)
             keep = [acc, gyr, ts]
             b = ImuBucket(len(ts), _p(acc), _p(gyr), _p(ts))
+        sw, sh = (getattr(self, "src_size", None) or (self.w, self.h)) if raw else (self.w, self.h)
         if on_device:
-            lp, rp, st, ch = C.c_void_p(left), C.c_void_p(right), stride or self.w * channels, channels
+            lp, rp, st, ch = C.c_void_p(left), C.c_void_p(right), stride or sw * channels, channels
         else:
-            left, ch, st = _image(left, self.h, self.w)
-            right, chr_, _ = _image(right, self.h, self.w)
+            left, ch, st = _image(left, sh, sw)
+            right, chr_, _ = _image(right, sh, sw)
             if chr_ != ch or right.strides[0] != st:
                 raise ValueError("left and right images differ in channels")
             keep += [left, right]
             lp, rp = _p(left), _p(right)
-        if ch == 1:
+        if raw:
+            _chk(self.L.vslam_system_track_stereo_raw(self.h_sys, lp, rp, int(st), int(ch), int(on_device), int(frame_number),
+                                                      C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
+        elif ch == 1:
             _chk(self.L.vslam_system_track_stereo(self.h_sys, lp, rp, st, int(on_device), int(frame_number),
                                                   C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
         else:
@@ -1208,11 +1229,20 @@ class Batch:
         except Exception:
             pass
 
-    def _images(self, lefts, rights, mask, on_device, stride, channels, keep):
-        """per-lane pointer tables, row stride and channels (host arrays: (H, W), (H, W, 3) BGR or (H, W, 4) BGRA, all alike)"""
+    def set_rectifiers(self, lane, left, right):
+        """bind lane `lane`'s (-1: every lane's) Rectifier objects for the raw=True calls (None, None unbinds); they must
+        outlive the batch.  All lanes' sources share one size, stride and channel count per call."""
+        _chk(self.L.vslam_batch_set_rectifiers(self.h_b, int(lane), left.h_r if left is not None else None,
+                                               right.h_r if right is not None else None))
+        self.src_size = (left.sw, left.sh) if left is not None else None
+
+    def _images(self, lefts, rights, mask, on_device, stride, channels, keep, raw=False):
+        """per-lane pointer tables, row stride and channels (host arrays: (H, W), (H, W, 3) BGR or (H, W, 4) BGRA, all alike;
+        raw: of the rectifiers' source size)"""
         B = self.lanes
         lp = (C.c_void_p * B)(); rp = (C.c_void_p * B)()
-        st, ch = stride or self.w * channels, channels
+        w, h = (getattr(self, "src_size", None) or (self.w, self.h)) if raw else (self.w, self.h)
+        st, ch = stride or w * channels, channels
         seen = set()
         for b in range(B):
             if mask is not None and not mask[b]:
@@ -1220,7 +1250,7 @@ class Batch:
             if on_device:
                 lp[b], rp[b] = lefts[b], rights[b]
             else:
-                l, cl, sl = _image(lefts[b], self.h, self.w); r, cr, sr = _image(rights[b], self.h, self.w)
+                l, cl, sl = _image(lefts[b], h, w); r, cr, sr = _image(rights[b], h, w)
                 seen |= {(cl, sl), (cr, sr)}
                 keep += [l, r]
                 lp[b], rp[b] = l.ctypes.data, r.ctypes.data
@@ -1229,18 +1259,21 @@ class Batch:
             raise ValueError("Batch.track: the lanes' images differ in channels")
         return lp, rp, st, ch
 
-    def track(self, lefts, rights, frame_numbers, imu_buckets=None, mask=None, on_device=False, stride=None, channels=1):
+    def track(self, lefts, rights, frame_numbers, imu_buckets=None, mask=None, on_device=False, stride=None, channels=1, raw=False):
         """lefts / rights: per-lane u8 arrays (host: gray, BGR or BGRA) or device pointers (with `channels`); imu_buckets:
-        per-lane (acc, gyro, ts) or None entries."""
+        per-lane (acc, gyro, ts) or None entries.  raw: unrectified frames through the lanes' bound rectifiers."""
         B = self.lanes
         T = np.zeros((B, 4, 4))
         reps = (FrameReport * B)()
         keep = []
-        lp, rp, st, ch = self._images(lefts, rights, mask, on_device, stride, channels, keep)
+        lp, rp, st, ch = self._images(lefts, rights, mask, on_device, stride, channels, keep, raw)
         bk = self._buckets(imu_buckets, keep)
         fr = np.ascontiguousarray(frame_numbers, np.int32)
         mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
-        if ch == 1:
+        if raw:
+            _chk(self.L.vslam_batch_track_stereo_raw(self.h_b, lp, rp, int(st), int(ch), int(on_device), _p(fr), bk,
+                                                     _p(mk) if mk is not None else None, _p(T), reps))
+        elif ch == 1:
             _chk(self.L.vslam_batch_track_stereo(self.h_b, lp, rp, int(st), int(on_device), _p(fr), bk, _p(mk) if mk is not None else None,
                                                  _p(T), reps))
         else:
@@ -1249,23 +1282,25 @@ class Batch:
         return T, [_report_dict(reps[b]) for b in range(B)]
 
     def track_prefetch(self, lefts, rights, frame_numbers, next_lefts=None, next_rights=None, imu_buckets=None, mask=None,
-                       next_mask=None, stride=None, channels=1):
+                       next_mask=None, stride=None, channels=1, raw=False):
         """device images of this step and (optionally) of the next one, whose extraction then starts under this step's host
-        phases; the next call must pass exactly those pointers and channels to use it"""
+        phases; the next call must pass exactly those pointers and channels (and raw) to use it"""
         B = self.lanes
         T = np.zeros((B, 4, 4))
         reps = (FrameReport * B)()
         keep = []
-        lp, rp, st, ch = self._images(lefts, rights, mask, True, stride, channels, keep)
+        lp, rp, st, ch = self._images(lefts, rights, mask, True, stride, channels, keep, raw)
         nl = nr = None
         if next_lefts is not None:
-            nl, nr, _, _ = self._images(next_lefts, next_rights, next_mask, True, stride, channels, keep)
+            nl, nr, _, _ = self._images(next_lefts, next_rights, next_mask, True, stride, channels, keep, raw)
         bk = self._buckets(imu_buckets, keep)
         fr = np.ascontiguousarray(frame_numbers, np.int32)
         mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
         nmk = np.ascontiguousarray(next_mask, np.uint8) if next_mask is not None else None
         args = (_p(fr), bk, _p(mk) if mk is not None else None, _p(T), reps, nl, nr, _p(nmk) if nmk is not None else None)
-        if ch == 1:
+        if raw:
+            _chk(self.L.vslam_batch_track_stereo_prefetch_raw(self.h_b, lp, rp, int(st), int(ch), *args))
+        elif ch == 1:
             _chk(self.L.vslam_batch_track_stereo_prefetch(self.h_b, lp, rp, int(st), *args))
         else:
             _chk(self.L.vslam_batch_track_stereo_prefetch_color(self.h_b, lp, rp, int(st), int(ch), *args))

@@ -100,6 +100,17 @@ vslam_status vslam_extractor_set_image_host(vslam_extractor* ex, int32_t image_i
  * VSLAM_ERR_INVALID before any work is queued. */
 vslam_status vslam_extractor_set_image_color(vslam_extractor* ex, int32_t image_index, const void* src, int32_t stride,
                                              int32_t channels, int32_t on_device);
+/* RAW (unrectified) frames, as the reference's frame loop has them before cv::remap (src/VIOSlam.cpp:278-311): image
+ * `image_index` from a gray (channels = 1), BGR (3) or BGRA (4) source of the rectifier's SOURCE size, `stride` bytes per row
+ * (at least src_width x channels), remapped through `rectifier`'s maps - and converted to gray, each channel rounded first,
+ * as vslam_rectifier_remap_gray does - while pyramid level 0 is written: one launch, no rectified image in between, the
+ * bytes of vslam_rectifier_remap(_gray) followed by set_image.  Ordering and synchronisation as set_image_color: the host
+ * form returns once `src` may be reused, the other images keep their level 0.  The rectifier is borrowed for the call; its
+ * output size must be the extractor's width x height and its device the extractor's.  VSLAM_ERR_INVALID (nothing queued)
+ * for anything else, channels other than 1 / 3 / 4 or a short stride. */
+typedef struct vslam_rectifier vslam_rectifier;
+vslam_status vslam_extractor_set_image_raw(vslam_extractor* ex, int32_t image_index, const vslam_rectifier* rectifier, const void* src,
+                                           int32_t stride, int32_t channels, int32_t on_device);
 vslam_status vslam_extractor_run(vslam_extractor* ex);
 vslam_status vslam_extractor_count(const vslam_extractor* ex, int32_t image_index, int32_t* n_out);
 vslam_status vslam_extractor_fetch(vslam_extractor* ex, int32_t image_index, vslam_keypoint* kps,
@@ -732,6 +743,18 @@ vslam_status vslam_system_track_stereo(vslam_system* sys, const uint8_t* left, c
 vslam_status vslam_system_track_stereo_color(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
                                              int32_t channels, int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
                                              double* T_wc_out, vslam_frame_report* report);
+/* RAW (unrectified) frames: the whole per-frame part of the reference's loop (src/VIOSlam.cpp:278-311: remap through the
+ * per-camera maps, cvtColor, Track*) in one call.  vslam_system_set_rectifiers binds the left and right camera's rectifier
+ * (both non-NULL, or both NULL to unbind): output size = the rig's width x height, the session's device, equal source sizes,
+ * else VSLAM_ERR_INVALID.  The session borrows them: a bound rectifier must outlive the session or be unbound first (no
+ * reference counting).  vslam_system_track_stereo_raw then takes source-sized frames (channels 1 / 3 / 4, stride >=
+ * src_width x channels): both images are rectified (and converted) on the way into pyramid level 0 by one launch; everything
+ * after level 0, and every result, is that of vslam_rectifier_remap(_gray) followed by vslam_system_track_stereo.  Without
+ * bound rectifiers, with other channels or a short stride: VSLAM_ERR_INVALID with nothing tracked. */
+vslam_status vslam_system_set_rectifiers(vslam_system* sys, const vslam_rectifier* left, const vslam_rectifier* right);
+vslam_status vslam_system_track_stereo_raw(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
+                                           int32_t channels, int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
+                                           double* T_wc_out, vslam_frame_report* report);
 /* blocks until the device work of the pass in flight (local_mapping = 2) has finished; reports its failure, if any.
  * (Its results are still applied at the frames the schedule names.) */
 vslam_status vslam_system_wait_mapping(vslam_system* sys);
@@ -794,6 +817,21 @@ vslam_status vslam_batch_track_stereo_prefetch_color(vslam_batch* batch, const u
                                                      const vslam_imu_bucket* imu, const uint8_t* lane_mask, double* T_wc_out,
                                                      vslam_frame_report* reports, const uint8_t* const* next_left,
                                                      const uint8_t* const* next_right, const uint8_t* next_mask);
+/* the same for RAW (unrectified) frames.  vslam_batch_set_rectifiers binds lane `lane`'s cameras (-1 = every lane; the
+ * rules and the lifetime of vslam_system_set_rectifiers; lanes may have different cameras), the _raw calls take the
+ * parameter lists of the _color forms with source-sized frames: every active lane's pair is rectified (and converted)
+ * through its own maps by ONE launch into level 0 - with device sources no host wait, no rectified image in HBM.  The
+ * prefetch form loads the next step's raw frames the same way.  Every lane that is active in the step (or the prefetched
+ * one) must have rectifiers bound; binding discards a pending prefetch. */
+vslam_status vslam_batch_set_rectifiers(vslam_batch* batch, int32_t lane, const vslam_rectifier* left, const vslam_rectifier* right);
+vslam_status vslam_batch_track_stereo_raw(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                          int32_t channels, int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu,
+                                          const uint8_t* lane_mask, double* T_wc_out, vslam_frame_report* reports);
+vslam_status vslam_batch_track_stereo_prefetch_raw(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right,
+                                                   int32_t stride, int32_t channels, const int32_t* frame_numbers,
+                                                   const vslam_imu_bucket* imu, const uint8_t* lane_mask, double* T_wc_out,
+                                                   vslam_frame_report* reports, const uint8_t* const* next_left,
+                                                   const uint8_t* const* next_right, const uint8_t* next_mask);
 /* a lane's session (borrowed: valid until vslam_batch_destroy) for the vslam_system_* read-outs */
 vslam_system* vslam_batch_system(vslam_batch* batch, int32_t lane);
 int32_t vslam_batch_lanes(const vslam_batch* batch);
@@ -863,8 +901,9 @@ vslam_status vslam_fleet_timings(vslam_fleet* fleet, const char** names, float* 
  * vslam_rectifier: cv::initUndistortRectifyMap(K, D, R, P[0:3,0:3], size, CV_32F) once, then cv::remap(INTER_LINEAR,
  * BORDER_CONSTANT 0) of n gray images per launch.  K, R, P_new: 3x3 row-major (R NULL = identity); D: n_dist of
  * (k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4).  OpenCV's published fixed-point semantics; parity against OpenCV itself unpinned.
+ * The calls below are a stage of their own (own stream, synchronous, rectified images in the caller's buffers); the
+ * closed-loop handles rectify inside their level-0 load instead (vslam_*_set_rectifiers, the *_raw entry points).
  * ------------------------------------------------------------------------- */
-typedef struct vslam_rectifier vslam_rectifier;
 vslam_status vslam_rectifier_create(const double* K, const double* D, int32_t n_dist, const double* R, const double* P_new,
                                     int32_t src_width, int32_t src_height, int32_t width, int32_t height, int32_t device,
                                     vslam_rectifier** out);
