@@ -2001,23 +2001,28 @@ __global__ __launch_bounds__(256) void k_ba_chi2(BaChi C) {
     C.wrong[p] = w;
 }
 
-// MapPoint::updatePos (src/Map.cpp:212-234) for every kFMatches entry: depth / close refresh from the optimised values
+// MapPoint::updatePos (src/Map.cpp:212-234) for every kFMatches entry: depth / close refresh from the optimised values.
+// The close threshold (40 x baseline) is the camera's: kfCloseTh != null holds one per staged keyframe pose (the merged requests of a
+// lockstep group's lanes, whose rigs may differ); null: closeTh for every pair (one request, one rig).
 __global__ __launch_bounds__(256) void k_ba_refresh_depth(int NP, const int* __restrict__ pairKf, const int* __restrict__ pairLm,
                                                           const uint8_t* __restrict__ pairWrong, const uint8_t* __restrict__ lmOutlier,
                                                           const float* __restrict__ curDepth, const DPose* __restrict__ Tcw,
-                                                          const double* __restrict__ lm, float closeTh, float* __restrict__ depthOut,
-                                                          uint8_t* __restrict__ closeOut, uint8_t* __restrict__ updated) {
+                                                          const double* __restrict__ lm, const float* __restrict__ kfCloseTh, float closeTh,
+                                                          float* __restrict__ depthOut, uint8_t* __restrict__ closeOut,
+                                                          uint8_t* __restrict__ updated) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= NP) return;
     uint8_t up = 0, cl = 0;
     float d = 0.f;
     const int l = pairLm[p];
     if (!pairWrong[p] && !lmOutlier[l] && !(curDepth[p] <= 0)) {
-        const DPose& T = Tcw[pairKf[p]];
+        const int k = pairKf[p];
+        const DPose& T = Tcw[k];
         const double* w = lm + 3 * (size_t)l;
         const double z = T.R[6] * w[0] + T.R[7] * w[1] + T.R[8] * w[2] + T.t[2] * 1.0;     // row 2 of getInvPose() * wp
         d = (float)z;
-        cl = z <= (double)closeTh ? 1 : 0;
+        const float th = kfCloseTh ? kfCloseTh[k] : closeTh;
+        cl = z <= (double)th ? 1 : 0;
         up = 1;
     }
     depthOut[p] = d; closeOut[p] = cl; updated[p] = up;
@@ -3614,7 +3619,9 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
             if (P->pair_kf[p] < 0 || P->pair_kf[p] >= q.K || P->pair_lm[p] < 0 || P->pair_lm[p] >= q.L ||
                 P->pair_octave[2 * p] < 0 || P->pair_octave[2 * p] >= P->n_levels || P->pair_octave[2 * p + 1] < 0 ||
                 P->pair_octave[2 * p + 1] >= P->n_levels) { set_error("vslam_local_ba_batch: pair index out of range (problem %d)", i); return VSLAM_ERR_INVALID; }
-        q.ownRig = memcmp(&P->rig, &Ps[0]->rig, sizeof(P->rig)) || P->n_levels != Ps[0]->n_levels;      // (per-lane rigs would work; not needed)
+        // (the rig is the lane's own - BaDev / BaChi2 carry fx, fy, cx, cy, b per lane, the host fill reads its own problem: the lanes of a
+        //  fleet's cohort have different cameras and stay on the batched path; only another pyramid depth runs on its own)
+        q.ownRig = P->n_levels != Ps[0]->n_levels;
         q.wrong.assign(std::max(q.NP, 1), 0);
         q.pose0.resize(q.K);
         for (int k = 0; k < q.K; k++) pose_from_rm16(P->kf_pose_wc + 16 * (size_t)k, q.pose0[k]);
@@ -4049,32 +4056,97 @@ namespace vslam {
 // group's serve_requests): inputs are staged in the calling thread's pinned arena, which the kernel addresses directly, the outputs land
 // there too; `out` points into the arena and is valid once the pool's stream has been synchronised (DevPool::sync recycles the arena,
 // so the caller copies the results out first).  Returns VSLAM_ERR_CAPACITY when the arena has no room yet (it grows at the next sync):
-// the caller then takes the synchronous entry point.  Arguments as vslam_ba_refresh_depth (validated by the caller).
-vslam_status refresh_depth_enqueue(const vslam_rig* rig, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
+// the caller then takes the synchronous form.  The requests may come from different cameras: kf_close_th holds the close threshold
+// (refresh_close_th) of every staged keyframe pose, written into the same arena block as the poses.  Other arguments as
+// vslam_ba_refresh_depth (validated by the caller).
+vslam_status refresh_depth_enqueue(const float* kf_close_th, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
                                    const uint8_t* lm_outlier, int n_pairs, const int* pair_kf, const int* pair_lm, const uint8_t* pair_wrong,
                                    const float* cur_depth, int device, RefreshTicket* out) {
-    if (n_pairs <= 0 || n_kf < 1 || !out) return VSLAM_ERR_INVALID;
+    if (n_pairs <= 0 || n_kf < 1 || !out || !kf_close_th) return VSLAM_ERR_INVALID;
+    // test switch: behave as if the arena had no room, so that the callers' synchronous per-keyframe form is reached at will
+    if (const char* e = getenv("VSLAM_REFRESH_FORCE_CAPACITY")) if (atoi(e) != 0) return VSLAM_ERR_CAPACITY;
     VS_HIP(hipSetDevice(device));
     DevPool* pool = thread_pool(device);
     if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t oT = take(n_kf * sizeof(DPose)), oLm = take((size_t)3 * std::max(n_lm, 1) * sizeof(double)), oO = take(std::max(n_lm, 1)),
-                 oKf = take(n_pairs * sizeof(int)), oL = take(n_pairs * sizeof(int)), oW = take(n_pairs), oCur = take(n_pairs * sizeof(float)),
-                 oD = take(n_pairs * sizeof(float)), oC = take(n_pairs), oU = take(n_pairs);
+    const size_t oT = take(n_kf * sizeof(DPose)), oTh = take(n_kf * sizeof(float)), oLm = take((size_t)3 * std::max(n_lm, 1) * sizeof(double)),
+                 oO = take(std::max(n_lm, 1)), oKf = take(n_pairs * sizeof(int)), oL = take(n_pairs * sizeof(int)), oW = take(n_pairs),
+                 oCur = take(n_pairs * sizeof(float)), oD = take(n_pairs * sizeof(float)), oC = take(n_pairs), oU = take(n_pairs);
     uint8_t* st = pool->stage(off);
     if (!st) return VSLAM_ERR_CAPACITY;
     DPose* Tcw = (DPose*)(st + oT);
     for (int k = 0; k < n_kf; k++) { DPose T; pose_from_rm16(kf_pose_wc + 16 * (size_t)k, T); pose_inverse(T, Tcw[k]); }
+    memcpy(st + oTh, kf_close_th, n_kf * sizeof(float));
     if (n_lm) { memcpy(st + oLm, lm_xyz, (size_t)3 * n_lm * sizeof(double)); memcpy(st + oO, lm_outlier, n_lm); }
     memcpy(st + oKf, pair_kf, n_pairs * sizeof(int)); memcpy(st + oL, pair_lm, n_pairs * sizeof(int));
     memcpy(st + oW, pair_wrong, n_pairs); memcpy(st + oCur, cur_depth, n_pairs * sizeof(float));
-    const float closeTh = rig->baseline * 40;
     hipLaunchKernelGGL(k_ba_refresh_depth, dim3((n_pairs + 255) / 256), dim3(256), 0, pool->stream, n_pairs, (const int*)(st + oKf),
                        (const int*)(st + oL), (const uint8_t*)(st + oW), (const uint8_t*)(st + oO), (const float*)(st + oCur),
-                       (const DPose*)(st + oT), (const double*)(st + oLm), closeTh, (float*)(st + oD), st + oC, st + oU);
+                       (const DPose*)(st + oT), (const double*)(st + oLm), (const float*)(st + oTh), 0.f, (float*)(st + oD), st + oC, st + oU);
     VS_HIP(hipGetLastError());
     out->dep = (const float*)(st + oD); out->clo = st + oC; out->up = st + oU;
+    return VSLAM_OK;
+}
+
+// The synchronous form behind vslam_ba_refresh_depth: one threshold for all pairs (kf_close_th == null: the public call, as it always
+// was) or one per keyframe pose (the group's fallback while the arena has no room).  Arguments validated by the caller.
+vslam_status refresh_depth_sync(const float* kf_close_th, float closeTh, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
+                                const uint8_t* lm_outlier, int n_pairs, const int* pair_kf, const int* pair_lm, const uint8_t* pair_wrong,
+                                const float* cur_depth, int device, float* depth_out, uint8_t* close_out, uint8_t* updated_out) {
+    VS_HIP(hipSetDevice(device));
+    std::vector<DPose> Tcw(n_kf);
+    for (int k = 0; k < n_kf; k++) { DPose T; pose_from_rm16(kf_pose_wc + 16 * (size_t)k, T); pose_inverse(T, Tcw[k]); }
+    // one device block for all operands, from the calling thread's block cache (no hipMalloc / hipFree in the steady state)
+    DevPool* pool = thread_pool(device);
+    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+    hipStream_t ps = pool->stream;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    const size_t oT = take(n_kf * sizeof(DPose)), oLm = take((size_t)3 * std::max(n_lm, 1) * sizeof(double)), oO = take(std::max(n_lm, 1)),
+                 oKf = take(n_pairs * sizeof(int)), oL = take(n_pairs * sizeof(int)), oW = take(n_pairs), oCur = take(n_pairs * sizeof(float)),
+                 oTh = take(kf_close_th ? n_kf * sizeof(float) : 0),
+                 oD = take(n_pairs * sizeof(float)), oC = take(n_pairs), oU = take(n_pairs);
+    PoolBuf<uint8_t> mem(pool);
+    VS_HIP(mem.alloc(off));
+    // ONE upload for the inputs (they are laid out back to back, oT .. oTh: staged in the pool's pinned arena in the
+    // device layout) and ONE download for the three outputs (oD .. oU): every copy is a blit launch that queues behind the
+    // lockstep groups' wide kernels, and a mapping pass had ~37 of them
+    {
+        const size_t inBytes = oD;
+        uint8_t* st = pool->stage(inBytes);
+        auto put = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
+            if (!bytes) return hipSuccess;
+            if (st) { memcpy(st + at, src, bytes); return hipSuccess; }
+            return pool->h2d(mem.p + at, src, bytes);      // (no staging room yet: one copy per array)
+        };
+        VS_HIP(put(oT, Tcw.data(), n_kf * sizeof(DPose)));
+        if (n_lm) { VS_HIP(put(oLm, lm_xyz, (size_t)3 * n_lm * sizeof(double))); VS_HIP(put(oO, lm_outlier, n_lm)); }
+        VS_HIP(put(oKf, pair_kf, n_pairs * sizeof(int))); VS_HIP(put(oL, pair_lm, n_pairs * sizeof(int)));
+        VS_HIP(put(oW, pair_wrong, n_pairs)); VS_HIP(put(oCur, cur_depth, n_pairs * sizeof(float)));
+        if (kf_close_th) VS_HIP(put(oTh, kf_close_th, n_kf * sizeof(float)));
+        if (st) VS_HIP(hipMemcpyAsync(mem.p, st, inBytes, hipMemcpyHostToDevice, ps));
+    }
+    hipLaunchKernelGGL(k_ba_refresh_depth, dim3((n_pairs + 255) / 256), dim3(256), 0, ps, n_pairs, (const int*)(mem.p + oKf),
+                       (const int*)(mem.p + oL), (const uint8_t*)(mem.p + oW), (const uint8_t*)(mem.p + oO), (const float*)(mem.p + oCur),
+                       (const DPose*)(mem.p + oT), (const double*)(mem.p + oLm), kf_close_th ? (const float*)(mem.p + oTh) : nullptr, closeTh,
+                       (float*)(mem.p + oD), mem.p + oC, mem.p + oU);
+    VS_HIP(hipGetLastError());
+    {
+        const size_t outBytes = off - oD;
+        uint8_t* st = pool->stage(outBytes);
+        if (st) {
+            VS_HIP(hipMemcpyAsync(st, mem.p + oD, outBytes, hipMemcpyDeviceToHost, ps));
+            VS_HIP(hipStreamSynchronize(ps));
+            memcpy(depth_out, st, n_pairs * sizeof(float)); memcpy(close_out, st + (oC - oD), n_pairs); memcpy(updated_out, st + (oU - oD), n_pairs);
+            VS_HIP(pool->sync());       // (recycles the arena - and may re-allocate it, hence after the copies)
+        } else {
+            VS_HIP(pool->d2h(depth_out, mem.p + oD, n_pairs * sizeof(float)));
+            VS_HIP(pool->d2h(close_out, mem.p + oC, n_pairs));
+            VS_HIP(pool->d2h(updated_out, mem.p + oU, n_pairs));
+            VS_HIP(pool->sync());
+        }
+    }
     return VSLAM_OK;
 }
 }  // namespace vslam
@@ -4097,58 +4169,52 @@ vslam_status vslam_ba_refresh_depth(const vslam_rig* rig, int32_t n_kf, const do
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
     if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
     if (n_pairs == 0) return VSLAM_OK;
-    VS_HIP(hipSetDevice(device));
-    std::vector<DPose> Tcw(n_kf);
-    for (int k = 0; k < n_kf; k++) { DPose T; pose_from_rm16(kf_pose_wc + 16 * (size_t)k, T); pose_inverse(T, Tcw[k]); }
-    // one device block for all operands, from the calling thread's block cache (no hipMalloc / hipFree in the steady state)
-    DevPool* pool = thread_pool(device);
-    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
-    hipStream_t ps = pool->stream;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t oT = take(n_kf * sizeof(DPose)), oLm = take((size_t)3 * std::max(n_lm, 1) * sizeof(double)), oO = take(std::max(n_lm, 1)),
-                 oKf = take(n_pairs * sizeof(int)), oL = take(n_pairs * sizeof(int)), oW = take(n_pairs), oCur = take(n_pairs * sizeof(float)),
-                 oD = take(n_pairs * sizeof(float)), oC = take(n_pairs), oU = take(n_pairs);
-    PoolBuf<uint8_t> mem(pool);
-    VS_HIP(mem.alloc(off));
-    // ONE upload for the seven inputs (they are laid out back to back, oT .. oCur: staged in the pool's pinned arena in the
-    // device layout) and ONE download for the three outputs (oD .. oU): every copy is a blit launch that queues behind the
-    // lockstep groups' wide kernels, and a mapping pass had ~37 of them
-    {
-        const size_t inBytes = oD;
-        uint8_t* st = pool->stage(inBytes);
-        auto put = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
-            if (!bytes) return hipSuccess;
-            if (st) { memcpy(st + at, src, bytes); return hipSuccess; }
-            return pool->h2d(mem.p + at, src, bytes);      // (no staging room yet: one copy per array)
-        };
-        VS_HIP(put(oT, Tcw.data(), n_kf * sizeof(DPose)));
-        if (n_lm) { VS_HIP(put(oLm, lm_xyz, (size_t)3 * n_lm * sizeof(double))); VS_HIP(put(oO, lm_outlier, n_lm)); }
-        VS_HIP(put(oKf, pair_kf, n_pairs * sizeof(int))); VS_HIP(put(oL, pair_lm, n_pairs * sizeof(int)));
-        VS_HIP(put(oW, pair_wrong, n_pairs)); VS_HIP(put(oCur, cur_depth, n_pairs * sizeof(float)));
-        if (st) VS_HIP(hipMemcpyAsync(mem.p, st, inBytes, hipMemcpyHostToDevice, ps));
+    return vslam::refresh_depth_sync(nullptr, vslam::refresh_close_th(*rig), n_kf, kf_pose_wc, n_lm, lm_xyz, lm_outlier, n_pairs, pair_kf, pair_lm,
+                                     pair_wrong, cur_depth, device, depth_out, close_out, updated_out);
+}
+
+// The merged form a lockstep group uses (batch.hip serve_requests) as a call of its own: n_req requests staged together - request r
+// brings req_n_kf[r] keyframe poses and its camera rigs[r]; kf_pose_wc / pair_kf index the concatenation - ONE launch, every pair
+// tested against the threshold of its own keyframe's camera.  Results are those of one vslam_ba_refresh_depth call per request.
+vslam_status vslam_ba_refresh_depth_merged(const vslam_rig* rigs, const int32_t* req_n_kf, int32_t n_req, const double* kf_pose_wc,
+                                           int32_t n_lm, const double* lm_xyz, const uint8_t* lm_outlier, int32_t n_pairs,
+                                           const int32_t* pair_kf, const int32_t* pair_lm, const uint8_t* pair_wrong,
+                                           const float* cur_depth, int32_t device, float* depth_out, uint8_t* close_out,
+                                           uint8_t* updated_out) {
+    if (!rigs || !req_n_kf || n_req < 1) { set_error("vslam_ba_refresh_depth_merged: invalid arguments"); return VSLAM_ERR_INVALID; }
+    std::vector<float> th;
+    for (int r = 0; r < n_req; r++) {
+        if (req_n_kf[r] < 0) { set_error("vslam_ba_refresh_depth_merged: invalid arguments"); return VSLAM_ERR_INVALID; }
+        th.insert(th.end(), (size_t)req_n_kf[r], vslam::refresh_close_th(rigs[r]));
     }
-    const float closeTh = rig->baseline * 40;
-    hipLaunchKernelGGL(k_ba_refresh_depth, dim3((n_pairs + 255) / 256), dim3(256), 0, ps, n_pairs, (const int*)(mem.p + oKf),
-                       (const int*)(mem.p + oL), (const uint8_t*)(mem.p + oW), (const uint8_t*)(mem.p + oO), (const float*)(mem.p + oCur),
-                       (const DPose*)(mem.p + oT), (const double*)(mem.p + oLm), closeTh, (float*)(mem.p + oD), mem.p + oC, mem.p + oU);
-    VS_HIP(hipGetLastError());
-    {
-        const size_t outBytes = off - oD;
-        uint8_t* st = pool->stage(outBytes);
-        if (st) {
-            VS_HIP(hipMemcpyAsync(st, mem.p + oD, outBytes, hipMemcpyDeviceToHost, ps));
-            VS_HIP(hipStreamSynchronize(ps));
-            memcpy(depth_out, st, n_pairs * sizeof(float)); memcpy(close_out, st + (oC - oD), n_pairs); memcpy(updated_out, st + (oU - oD), n_pairs);
-            VS_HIP(pool->sync());       // (recycles the arena - and may re-allocate it, hence after the copies)
-        } else {
-            VS_HIP(pool->d2h(depth_out, mem.p + oD, n_pairs * sizeof(float)));
-            VS_HIP(pool->d2h(close_out, mem.p + oC, n_pairs));
-            VS_HIP(pool->d2h(updated_out, mem.p + oU, n_pairs));
-            VS_HIP(pool->sync());
+    const int n_kf = (int)th.size();
+    if (n_kf < 1 || n_lm < 0 || n_pairs < 0 || !kf_pose_wc || (n_lm > 0 && (!lm_xyz || !lm_outlier)) ||
+        (n_pairs > 0 && (!pair_kf || !pair_lm || !pair_wrong || !cur_depth || !depth_out || !close_out || !updated_out))) {
+        set_error("vslam_ba_refresh_depth_merged: invalid arguments");
+        return VSLAM_ERR_INVALID;
+    }
+    for (int p = 0; p < n_pairs; p++)
+        if (pair_kf[p] < 0 || pair_kf[p] >= n_kf || pair_lm[p] < 0 || pair_lm[p] >= n_lm) { set_error("vslam_ba_refresh_depth_merged: pair index out of range"); return VSLAM_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    if (n_pairs == 0) return VSLAM_OK;
+    vslam::RefreshTicket tk{};
+    vslam_status st = VSLAM_ERR_CAPACITY;
+    for (int attempt = 0; attempt < 2 && st == VSLAM_ERR_CAPACITY; attempt++) {
+        st = vslam::refresh_depth_enqueue(th.data(), n_kf, kf_pose_wc, n_lm, lm_xyz, lm_outlier, n_pairs, pair_kf, pair_lm, pair_wrong, cur_depth, device, &tk);
+        vslam::DevPool* pool = vslam::thread_pool(device);
+        if (!pool) return VSLAM_ERR_HIP;
+        if (st == VSLAM_OK) {
+            VS_HIP(hipStreamSynchronize(pool->stream));
+            memcpy(depth_out, tk.dep, n_pairs * sizeof(float)); memcpy(close_out, tk.clo, n_pairs); memcpy(updated_out, tk.up, n_pairs);
         }
+        if (st == VSLAM_OK || st == VSLAM_ERR_CAPACITY) VS_HIP(pool->sync());      // (recycles the arena; grows it when there was no room)
     }
-    return VSLAM_OK;
+    if (st == VSLAM_ERR_CAPACITY)
+        return vslam::refresh_depth_sync(th.data(), 0.f, n_kf, kf_pose_wc, n_lm, lm_xyz, lm_outlier, n_pairs, pair_kf, pair_lm, pair_wrong, cur_depth,
+                                         device, depth_out, close_out, updated_out);
+    return st;
 }
 
 }  // extern "C"

@@ -21,6 +21,11 @@
 //
 // A lane's results are bit-identical to the same sequence run through a single vslam_system (tests/test_gpu_batch.py):
 // the batched kernels are the one-session kernels' bodies, fed per-lane argument blocks built by the same host code.
+//
+// A lane is one robot: its own camera (rig intrinsics and baseline are per lane - every lane's matcher, TrackGeom and mapping
+// problems are built from its own config; only image size, extractor parameters, device, IMU and mapping mode are the group's),
+// its own start (frame number 0 initialises its map) and its own end (restart_lane: a new session in the lane's place, the key
+// slabs of the old one back on the group's free list).
 #include "system.hpp"
 #include "pose_dev.hpp"
 #include "imu_dev.hpp"
@@ -154,6 +159,9 @@ struct vslam_batch {
     double* d_res = nullptr; double* h_res = nullptr;                        // [B][64] result blocks
     uint8_t* d_zero = nullptr; size_t zeroCap = 0;                           // MapPoint::GetIsOutlier of uploaded points: all 0
     BaPool pool;                                                             // host phases
+    vslam_system_config shared{};                                            // lane 0's config at creation: the fields every lane shares
+    vslam::SlabPool slabs;                                                   // the lanes' keyframe key slabs (HBM) + those handed back by restarts
+    std::vector<uint8_t> needFirst;                                          // lane restarted: its next frame must carry frame number 0
     // mapping engine (shared by the groups of this device); the jobs of the current host phase wait here for kick()
     std::shared_ptr<MapEngine> eng;
     std::deque<vslam_system*> npPend, baPend;
@@ -168,6 +176,9 @@ struct vslam_batch {
     long long nSteps = 0;
 
     vslam_status init(const vslam_system_config* cfgs, int n, int hostThreads, int mapThreads);
+    bool shares(const vslam_system_config& c) const;
+    vslam_status make_lane(int b, const vslam_system_config& c, vslam_system** out);
+    vslam_status restart_lane(int lane, const vslam_system_config* c);
     void release();
     vslam_status ensure_up(size_t bytes);
     vslam_status ensure_dn(size_t bytes);
@@ -201,17 +212,40 @@ struct vslam_batch {
     }
 };
 
+// what the lanes of a group share: the extractor (image size, parameters), the device and its streams, the schedule.  The camera
+// behind the images - fx, fy, cx, cy, baseline - is the lane's own.
+bool vslam_batch::shares(const vslam_system_config& c) const {
+    return c.device == shared.device && (c.use_imu != 0) == (shared.use_imu != 0) && c.rig.width == shared.rig.width &&
+           c.rig.height == shared.rig.height && !memcmp(&c.fe, &shared.fe, sizeof(c.fe)) && c.local_mapping == shared.local_mapping &&
+           c.mapping_delay == shared.mapping_delay && c.mapping_np_delay == shared.mapping_np_delay;
+}
+static const char* const kSharedRule = "lanes must share device, image size (rig width x height), extractor parameters, IMU mode and mapping mode / "
+                                       "delays; rig intrinsics and baseline are per lane";
+
+// a lane's session on the group's shared objects: extractor images 2b / 2b + 1, stream, result-block slices, mapping engine, slabs
+vslam_status vslam_batch::make_lane(int b, const vslam_system_config& c, vslam_system** out) {
+    vslam_system* s = new (std::nothrow) vslam_system();
+    if (!s) return VSLAM_ERR_INVALID;
+    *out = s;
+    VS_CHECK(s->init(&c, fe, 2 * b, stream));
+    vslam_matcher* m = s->fm;
+    m->resExternal = true;
+    m->d_res = d_res + (size_t)b * 64; m->h_res = h_res + (size_t)b * 64;
+    m->d_poseIO = m->d_res; m->imuIo = m->d_res + 32; m->d_poseOut = (int*)(m->d_res + 48); m->d_trCount = (int*)(m->d_res + 52);
+    m->trExternal = true;
+    s->mapExec = &vslam_batch::submit_mapping; s->mapExecArg = this;
+    s->slabPool = &slabs;
+    return VSLAM_OK;
+}
+
 vslam_status vslam_batch::init(const vslam_system_config* cfgs, int n, int hostThreads, int nMapThreads) {
     if (!cfgs || n <= 0 || n > 256) { set_error("vslam_batch: 1..256 lanes"); return VSLAM_ERR_INVALID; }
     B = n; device = cfgs[0].device; useImu = cfgs[0].use_imu != 0;
-    for (int b = 1; b < B; b++) {
-        const vslam_system_config& c = cfgs[b];
-        if (c.device != device || (c.use_imu != 0) != useImu || memcmp(&c.rig, &cfgs[0].rig, sizeof(c.rig)) || memcmp(&c.fe, &cfgs[0].fe, sizeof(c.fe)) ||
-            c.local_mapping != cfgs[0].local_mapping || c.mapping_delay != cfgs[0].mapping_delay || c.mapping_np_delay != cfgs[0].mapping_np_delay) {
-            set_error("vslam_batch: lanes must share device, rig, extractor parameters, IMU mode and mapping mode / delay");
-            return VSLAM_ERR_INVALID;
-        }
-    }
+    shared = cfgs[0];
+    for (int b = 1; b < B; b++)
+        if (!shares(cfgs[b])) { set_error("vslam_batch: %s", kSharedRule); return VSLAM_ERR_INVALID; }
+    slabs.alloc = [](size_t bytes) -> void* { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; };
+    slabs.dealloc = [](void* p) { hipFree(p); };
     VS_HIP(hipSetDevice(device));
     {
         // Every keyframe keeps ~200 KB of key arrays on the host; by default glibc serves blocks of that size with one mmap each,
@@ -230,25 +264,15 @@ vslam_status vslam_batch::init(const vslam_system_config* cfgs, int n, int hostT
     timer.stream = stream; timer.multi = true;
     VS_HIP(vslam::create_main_stream(&imuStream));
     for (hipEvent_t* e : {&evTab, &evImu0, &evSolve0, &evImu1}) VS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    VS_CHECK(vslam_extractor_create(&cfgs[0].fe, cfgs[0].rig.width, cfgs[0].rig.height, 2 * B, device, &fe));
+    VS_CHECK(vslam_extractor_create(&shared.fe, shared.rig.width, shared.rig.height, 2 * B, device, &fe));
     VS_CHECK(fe->enable_double_output());
     VS_HIP(hipMalloc(&d_res, (size_t)B * 64 * sizeof(double)));
     VS_HIP(vslam::memset_sync(d_res, 0, (size_t)B * 64 * sizeof(double)));
     VS_HIP(hipHostMalloc(&h_res, (size_t)B * 64 * sizeof(double), hipHostMallocDefault));
     sys.assign(B, nullptr);
     ls.assign(B, LaneStep{});
-    for (int b = 0; b < B; b++) {
-        vslam_system* s = new (std::nothrow) vslam_system();
-        if (!s) return VSLAM_ERR_INVALID;
-        sys[b] = s;
-        VS_CHECK(s->init(&cfgs[b], fe, 2 * b, stream));
-        vslam_matcher* m = s->fm;
-        m->resExternal = true;
-        m->d_res = d_res + (size_t)b * 64; m->h_res = h_res + (size_t)b * 64;
-        m->d_poseIO = m->d_res; m->imuIo = m->d_res + 32; m->d_poseOut = (int*)(m->d_res + 48); m->d_trCount = (int*)(m->d_res + 52);
-        m->trExternal = true;
-        s->mapExec = &vslam_batch::submit_mapping; s->mapExecArg = this;
-    }
+    needFirst.assign(B, 0);
+    for (int b = 0; b < B; b++) VS_CHECK(make_lane(b, cfgs[b], &sys[b]));
     // argument tables
     size_t off = 0;
     auto place = [&](size_t elem) { const size_t o = off; off = up256(off + elem * (size_t)B); return o; };
@@ -269,7 +293,7 @@ vslam_status vslam_batch::init(const vslam_system_config* cfgs, int n, int hostT
     if (hostThreads < 0) hostThreads = std::min(B, 8);
     pool.onExit = []() { vslam::thread_release(); };
     if (hostThreads > 1) pool.start(hostThreads - 1);
-    if (cfgs[0].local_mapping == 2) {
+    if (shared.local_mapping == 2) {
         // mapping_threads = the engine's threads for the cohorts' batched local BAs (a second cohort may start while one is in its
         // last rounds), + its thread(s) for the cohorts' batched new-point searches
         if (nMapThreads <= 0) nMapThreads = getenv("VSLAM_BATCH_MAP_THREADS") ? std::max(1, atoi(getenv("VSLAM_BATCH_MAP_THREADS"))) : 3;
@@ -309,6 +333,7 @@ void vslam_batch::release() {
     for (vslam_system* s : sys) if (s) { s->release(); delete s; }
     sys.clear();
     eng.reset();                                   // (the last group of the device stops the engine's threads)
+    slabs.destroy();                               // (the sessions handed their key slabs back: everything the group allocated)
     if (stream) hipStreamSynchronize(stream);
     if (imuStream) { hipStreamSynchronize(imuStream); hipStreamDestroy(imuStream); imuStream = nullptr; }
     for (hipEvent_t e : {evTab, evImu0, evSolve0, evImu1}) if (e) hipEventDestroy(e);
@@ -346,7 +371,7 @@ vslam_status vslam_batch::serve_requests() {
     // ---- gather: MapPoint::updatePos depth / close refresh ----------------------------------------------------------------------
     size_t nPair = 0; int nKf = 0, nLm = 0;
     for (vslam_system* s : sys) if (s->refReq.pending) { nPair += s->refReq.rk.size(); nKf += s->refReq.nKf; nLm += s->refReq.nLm; }
-    std::vector<int> rk, rl; std::vector<float> cur, dep; std::vector<double> pose, lm;
+    std::vector<int> rk, rl; std::vector<float> cur, dep, kfTh; std::vector<double> pose, lm;
     std::vector<uint8_t> zeroW, zeroO, clo, up;
     if (nPair) {
         cur.resize(nPair); dep.resize(nPair); pose.resize((size_t)nKf * 16); lm.resize((size_t)nLm * 3);
@@ -358,6 +383,7 @@ vslam_status vslam_batch::serve_requests() {
             if (!r.pending) continue;
             for (size_t i = 0; i < r.rk.size(); i++) { rk.push_back(r.rk[i] + ak); rl.push_back(r.rl[i] + al); cur[ap + i] = r.cur[i]; }
             memcpy(pose.data() + (size_t)ak * 16, r.rpose.data(), (size_t)r.nKf * 16 * sizeof(double));
+            kfTh.insert(kfTh.end(), (size_t)r.nKf, vslam::refresh_close_th(s->cfg.rig));      // (the lane's own camera: close = depth <= 40 x ITS baseline)
             memcpy(lm.data() + (size_t)al * 3, r.rlm.data(), (size_t)r.nLm * 3 * sizeof(double));
             ap += r.rk.size(); ak += r.nKf; al += r.nLm;
         }
@@ -372,7 +398,7 @@ vslam_status vslam_batch::serve_requests() {
         vslam_status sd = wantDesc ? vslam::calc_descriptors_enqueue(rqDescs.data(), rqStart.data(), (int)nMp, device, &bestP) : VSLAM_OK;
         vslam_status sr = VSLAM_OK;
         if (wantRef && (sd == VSLAM_OK || sd == VSLAM_ERR_CAPACITY))
-            sr = vslam::refresh_depth_enqueue(&sys[0]->cfg.rig, nKf, pose.data(), nLm, lm.data(), zeroO.data(), (int)nPair, rk.data(), rl.data(), zeroW.data(),
+            sr = vslam::refresh_depth_enqueue(kfTh.data(), nKf, pose.data(), nLm, lm.data(), zeroO.data(), (int)nPair, rk.data(), rl.data(), zeroW.data(),
                                               cur.data(), device, &tk);
         if (sd != VSLAM_OK && sd != VSLAM_ERR_CAPACITY) return sd;
         if (sr != VSLAM_OK && sr != VSLAM_ERR_CAPACITY) return sr;
@@ -384,8 +410,8 @@ vslam_status vslam_batch::serve_requests() {
         VS_HIP(pool->sync());          // (recycles the arena; may re-allocate it - after the copies)
         if (wantDesc && sd == VSLAM_ERR_CAPACITY) VS_CHECK(vslam_calc_descriptors(rqDescs.data(), rqStart.data(), (int)nMp, device, rqBest.data()));
         if (wantRef && sr == VSLAM_ERR_CAPACITY)
-            VS_CHECK(vslam_ba_refresh_depth(&sys[0]->cfg.rig, nKf, pose.data(), nLm, lm.data(), zeroO.data(), (int)nPair, rk.data(), rl.data(), zeroW.data(),
-                                            cur.data(), device, dep.data(), clo.data(), up.data()));
+            VS_CHECK(vslam::refresh_depth_sync(kfTh.data(), 0.f, nKf, pose.data(), nLm, lm.data(), zeroO.data(), (int)nPair, rk.data(), rl.data(), zeroW.data(),
+                                               cur.data(), device, dep.data(), clo.data(), up.data()));
     }
     // ---- scatter ----------------------------------------------------------------------------------------------------------------
     if (nMp) {
@@ -487,6 +513,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
         if (!q.on) continue;
         if (!L[b] || !R[b]) { set_error("vslam_batch: lane %d has no images", b); return VSLAM_ERR_INVALID; }
         q.first = frames[b] == 0;
+        if (needFirst[b] && !q.first) { set_error("vslam_batch: lane %d was restarted, its next frame must carry frame number 0 (got %d)", b, frames[b]); return VSLAM_ERR_INVALID; }
         nOn++;
     }
     if (!nOn) return VSLAM_OK;
@@ -711,7 +738,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
 
     // ---- device: every stage once for all lanes --------------------------------------------------------------------------------
     int t;
-    launch_stereo_batch(stream, dt.stereo, B, maxL, maxR, sys[0]->cfg.rig.height, &timer);
+    launch_stereo_batch(stream, dt.stereo, B, maxL, maxR, shared.rig.height, &timer);      // (image height: shared; the lanes' fx / baseline are in their StereoLane)
     // (stage timing brackets launches with events on the main stream: keep the pre-integrations there when it is on)
     static const bool sideEnv = getenv("VSLAM_BATCH_IMU_SIDE") ? atoi(getenv("VSLAM_BATCH_IMU_SIDE")) != 0 : true;
     const bool side = useImu && !timer.enabled && sideEnv;
@@ -825,12 +852,73 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
     });
     kick();                                        // the new-point searches of the lanes that inserted a keyframe
     VS_CHECK(first_error());
+    for (int b = 0; b < B; b++) if (ls[b].on) needFirst[b] = 0;      // (a restarted lane's frame 0 has been tracked)
     sub(5, ts);
     lap(6);
     return VSLAM_OK;
 }
 
+// Ends a lane's session and starts a new one in its place, between two steps, on the thread that drives the group.  Nothing on the
+// device is allocated or freed (a device free waits for every group's kernels, and a service whose lanes restart for ever is the steady
+// state): the new session takes over the old one's matcher - same extractor images, stream and result-block slices; its rig and
+// host-side frame state are reset (vslam_matcher::reset_session) - and the old session's key slabs go to the group's free list.  Order:
+//   1. validate: nothing has changed when this fails;
+//   2. the old session's mapping job: taken back from the group's pending lists or the engine's queues if no thread has picked it
+//      up, else waited for (finish_job notifies under the session's mutex, so the session can go once the flag is seen);
+//   3. the old session hands over its matcher and is released (slabs -> free list); the new one is initialised on that matcher;
+//   4. the lane's per-step state, result-block slices and the prefetch are reset.
+vslam_status vslam_batch::restart_lane(int lane, const vslam_system_config* config) {
+    if (lane < 0 || lane >= B) { set_error("vslam_batch_restart_lane: lane %d of %d", lane, B); return VSLAM_ERR_INVALID; }
+    const vslam_system_config c = config ? *config : sys[lane]->cfg;
+    if (!shares(c)) { set_error("vslam_batch_restart_lane: %s", kSharedRule); return VSLAM_ERR_INVALID; }
+    if (c.window > 16) { set_error("vslam_system: window > 16 keyframes is not supported by the new-point pipeline"); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(device));
+    VS_HIP(hipStreamSynchronize(stream));          // (between steps the stream is idle; the slabs are written by the step's pack kernel)
+    vslam_system* s = new (std::nothrow) vslam_system();
+    if (!s) return VSLAM_ERR_INVALID;
+    vslam_system* old = sys[lane];
+    bool queued = false;
+    {
+        std::lock_guard<std::mutex> lk(pendMu);
+        for (std::deque<vslam_system*>* q : {&npPend, &baPend})
+            for (auto it = q->begin(); it != q->end();) { if (*it == old) { it = q->erase(it); queued = true; } else ++it; }
+    }
+    if (!queued && eng) queued = eng->eng.cancel(old);
+    if (queued) old->finish_job(VSLAM_OK, "");     // (never ran: nobody else knows the job any more)
+    old->wait_idle();                              // a job that an engine thread has taken: finished, its result dropped with the session
+    vslam_matcher* fm = old->fm;
+    old->fm = nullptr;                             // (kept: release() below frees nothing on the device)
+    old->release();                                // slabs -> free list
+    delete old;
+    sys[lane] = s;
+    ls[lane] = LaneStep{};
+    needFirst[lane] = 1;
+    prefetched.clear();                            // a prefetched extraction may hold the old session's next frame
+    const vslam_status is = s->init(&c, fe, 2 * lane, stream, fm);
+    if (is != VSLAM_OK) {                          // (cannot happen after the checks above; the lane then has no tracker until it is restarted)
+        if (!s->fm) vslam_matcher_destroy(fm);
+        return is;
+    }
+    s->mapExec = &vslam_batch::submit_mapping; s->mapExecArg = this;
+    s->slabPool = &slabs;
+    VS_HIP(hipMemsetAsync(d_res + (size_t)lane * 64, 0, 64 * sizeof(double), stream));
+    VS_HIP(hipStreamSynchronize(stream));
+    memset(h_res + (size_t)lane * 64, 0, 64 * sizeof(double));
+    return VSLAM_OK;
+}
+
 extern "C" {
+
+vslam_status vslam_batch_restart_lane(vslam_batch* b, int32_t lane, const vslam_system_config* config) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->restart_lane(lane, config);
+}
+
+vslam_status vslam_batch_memory(vslam_batch* b, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free) {
+    if (!b) return VSLAM_ERR_INVALID;
+    b->slabs.stats(key_slab_bytes, slabs_in_use, slabs_free);
+    return VSLAM_OK;
+}
 
 vslam_status vslam_batch_create(const vslam_system_config* configs, int32_t lanes, int32_t host_threads, int32_t mapping_threads,
                                 vslam_batch** out) {
@@ -894,7 +982,7 @@ vslam_status vslam_batch_track_stereo_prefetch_color(vslam_batch* b, const uint8
 vslam_status vslam_batch_set_rectifiers(vslam_batch* b, int32_t lane, const vslam_rectifier* left, const vslam_rectifier* right) {
     if (!b) return VSLAM_ERR_INVALID;
     if (lane < -1 || lane >= b->B) { set_error("vslam_batch_set_rectifiers: lane %d of %d (-1 = every lane)", lane, b->B); return VSLAM_ERR_INVALID; }
-    // (all lanes share rig and device: what one lane accepts, every lane accepts)
+    // (all lanes share image size and device: what one lane accepts, every lane accepts)
     for (int k = 0; k < b->B; k++) if (lane < 0 || k == lane) VS_CHECK(b->sys[k]->set_rectifiers(left, right, "vslam_batch_set_rectifiers"));
     b->prefetched.clear();      // a prefetched extraction went through the rectifiers bound before
     return VSLAM_OK;

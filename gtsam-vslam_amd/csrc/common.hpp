@@ -233,9 +233,14 @@ struct RefreshTicket { const float* dep; const uint8_t* clo; const uint8_t* up; 
 struct KfUpdTicket { const uint8_t* drop_l; const uint8_t* drop_r; const double* lm_xyz; };
 vslam_status kf_update_pose_enqueue(const vslam_kf_update_problem* P, int32_t device, KfUpdTicket* out);
 vslam_status calc_descriptors_enqueue(const uint8_t* descs, const int32_t* start, int32_t n_mp, int32_t device, const int** best_out);
-vslam_status refresh_depth_enqueue(const vslam_rig* rig, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
+// (kf_close_th: one close threshold per staged keyframe pose - the requests of a group's lanes may come from different cameras)
+inline float refresh_close_th(const vslam_rig& rig) { return rig.baseline * 40; }      // closeNumber, include/FeatureMatcher.h:36
+vslam_status refresh_depth_enqueue(const float* kf_close_th, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
                                    const uint8_t* lm_outlier, int n_pairs, const int* pair_kf, const int* pair_lm, const uint8_t* pair_wrong,
                                    const float* cur_depth, int device, RefreshTicket* out);
+vslam_status refresh_depth_sync(const float* kf_close_th, float closeTh, int n_kf, const double* kf_pose_wc, int n_lm, const double* lm_xyz,
+                                const uint8_t* lm_outlier, int n_pairs, const int* pair_kf, const int* pair_lm, const uint8_t* pair_wrong,
+                                const float* cur_depth, int device, float* depth_out, uint8_t* close_out, uint8_t* updated_out);
 inline void thread_pool_release() { DevPool& p = thread_pool_slot(); if (p.device >= 0) { p.release(); p.device = -1; } }
 // RAII device array drawn from the thread's pool
 template <class T>

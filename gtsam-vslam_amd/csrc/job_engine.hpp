@@ -37,6 +37,17 @@ struct JobEngine {
         if (na) lanes[0].cv.notify_one();
         if (nb) lanes[1].cv.notify_one();
     }
+    // takes a released job back before a thread has picked it up (its owner goes away); false: not queued - it is running in a
+    // cohort or has finished, and the owner waits for it as usual
+    bool cancel(const Job& j) {
+        std::lock_guard<std::mutex> lk(mu);
+        bool found = false;
+        for (Lane& L : lanes)
+            for (auto it = L.queue.begin(); it != L.queue.end();) {
+                if (*it == j) { it = L.queue.erase(it); found = true; } else ++it;
+            }
+        return found;
+    }
     void loop(int kind) {
         if (onThreadStart) onThreadStart();
         Lane& L = lanes[kind];

@@ -154,6 +154,10 @@ struct vslam_matcher {
 
     vslam_status init(const vslam_rig* r, vslam_extractor* l, int il, vslam_extractor* rr, int ir);
     void release();
+    // a new session on this matcher (vslam_batch_restart_lane: same extractor images, same stream): the new camera's rig, the
+    // host-side frame state as after init.  Device buffers and their capacities stay - nothing is allocated or freed; no kernel
+    // reads a buffer before the session's own frames have written it, except d_trVisL, which is refilled here.
+    vslam_status reset_session(const vslam_rig* r);
     vslam_status ensure_cap(int n);
     vslam_status refresh_keys(bool waitStream = true);
     vslam_status stereo_match();

@@ -557,6 +557,22 @@ void vslam_matcher::release() {
     stream = nullptr;
 }
 
+vslam_status vslam_matcher::reset_session(const vslam_rig* r) {
+    if (!r || r->width != rig.width || r->height != rig.height) { set_error("matcher: a session's rig keeps the image size"); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(device));
+    rig = *r;
+    stereoDone = false;
+    overridden[0] = overridden[1] = false;
+    nKeys[0] = nKeys[1] = 0; d_kps[0] = d_kps[1] = nullptr; d_desc[0] = d_desc[1] = nullptr;
+    trN = 0; actN = 0; trNub = 0;
+    if (trExternal) { d_trXyz = nullptr; d_trDesc = nullptr; d_trMsd = nullptr; d_trOutlier = nullptr; }      // (views into the batch's upload block)
+    memset(trPredInv, 0, sizeof(trPredInv)); trRad = 10.f; trImu = false; trRetried = false;
+    memset(imuParams, 0, sizeof(imuParams)); memset(imuSi, 0, sizeof(imuSi)); memset(imuBiasPrev, 0, sizeof(imuBiasPrev));
+    imuPending = false; imuN = 0;
+    if (d_trVisL && trCap) { VS_HIP(hipMemsetAsync(d_trVisL, 1, (size_t)trCap, stream)); VS_HIP(hipStreamSynchronize(stream)); }      // (as ensure_track_cap leaves it)
+    return VSLAM_OK;
+}
+
 vslam_status vslam_matcher::adopt_stream(hipStream_t s) {
     if (!s) return VSLAM_ERR_INVALID;
     VS_HIP(hipSetDevice(device));

@@ -31,15 +31,24 @@ void vslam_system::backproject(const SysKeys& k, int i, const M4& pose, double* 
     for (int c = 0; c < 3; c++) out[c] = (pose[4 * c] * xp + pose[4 * c + 1] * yp + pose[4 * c + 2] * zp) + pose[4 * c + 3];
 }
 
-vslam_status vslam_system::init(const vslam_system_config* c, vslam_extractor* sharedFe, int imgBase, hipStream_t sharedStream) {
+vslam_status vslam_system::wait_idle() {
+    std::unique_lock<std::mutex> lk(wMu);
+    wCv.wait(lk, [&] { return !mappingBusy; });
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system::init(const vslam_system_config* c, vslam_extractor* sharedFe, int imgBase, hipStream_t sharedStream, vslam_matcher* adoptFm) {
     if (!c) return VSLAM_ERR_INVALID;
     cfg = *c;
     if (cfg.window <= 0) cfg.window = 10;
     if (cfg.window > 16) { set_error("vslam_system: window > 16 keyframes is not supported by the new-point pipeline"); return VSLAM_ERR_INVALID; }
     if (sharedFe) { fe = sharedFe; ownsFe = false; img0 = imgBase; }
     else VS_CHECK(vslam_extractor_create(&cfg.fe, cfg.rig.width, cfg.rig.height, 2, cfg.device, &fe));
-    VS_CHECK(vslam_matcher_create(&cfg.rig, fe, img0, fe, img0 + 1, &fm));
-    if (sharedStream) VS_CHECK(fm->adopt_stream(sharedStream));
+    if (adoptFm) { VS_CHECK(adoptFm->reset_session(&cfg.rig)); fm = adoptFm; }
+    else {
+        VS_CHECK(vslam_matcher_create(&cfg.rig, fe, img0, fe, img0 + 1, &fm));
+        if (sharedStream) VS_CHECK(fm->adopt_stream(sharedStream));
+    }
     nLev = cfg.fe.n_levels;
     scalePyr.resize(nLev); sigmaF.resize(nLev); invSigmaF.resize(nLev);
     VS_CHECK(vslam_extractor_tables(fe, scalePyr.data(), nullptr, sigmaF.data(), invSigmaF.data(), nullptr, nullptr));
@@ -69,7 +78,7 @@ void vslam_system::release() {
     if (h_up) hipHostFree(h_up);
     if (h_dn) hipHostFree(h_dn);
     h_up = h_dn = nullptr;
-    for (uint8_t* slab : keySlabs) hipFree(slab);
+    for (uint8_t* slab : keySlabs) { if (slabPool) slabPool->give(slab); else hipFree(slab); }
     keySlabs.clear();
 }
 
@@ -222,7 +231,10 @@ void* vslam_system::reserve_key_slot(int nL, int nR) {
     if (need > keySlot) return nullptr;           // (an unusually large frame: its arrays travel with every pass, as before)
     if (keySlotsUsed == keySlotsPerSlab) {
         uint8_t* slab = nullptr;
-        if (hipSetDevice(cfg.device) != hipSuccess || hipMalloc((void**)&slab, keySlot * (size_t)keySlotsPerSlab) != hipSuccess) return nullptr;
+        if (hipSetDevice(cfg.device) != hipSuccess) return nullptr;
+        if (slabPool) slab = (uint8_t*)slabPool->take(keySlot * (size_t)keySlotsPerSlab);
+        else if (hipMalloc((void**)&slab, keySlot * (size_t)keySlotsPerSlab) != hipSuccess) return nullptr;
+        if (!slab) return nullptr;
         keySlabs.push_back(slab); keySlotsUsed = 0;
     }
     return keySlabs.back() + keySlot * (size_t)keySlotsUsed;
@@ -742,8 +754,10 @@ void vslam_system::run_mapping() {
         std::lock_guard<std::mutex> lk(wMu);
         if (s != VSLAM_OK && workerStatus == VSLAM_OK) { workerStatus = s; snprintf(workerError, sizeof(workerError), "%s", vslam_last_error()); }
         mappingBusy = false;
+        // (under wMu: a waiter may destroy this session - vslam_batch_restart_lane - as soon as it sees the flag; it cannot before the
+        //  lock is dropped, and by then the condition variable is no longer touched here)
+        wCv.notify_all();
     }
-    wCv.notify_all();
 }
 
 // the batch's mapping engine ran this session's job as part of a cohort
@@ -752,8 +766,10 @@ void vslam_system::finish_job(vslam_status s, const char* err) {
         std::lock_guard<std::mutex> lk(wMu);
         if (s != VSLAM_OK && workerStatus == VSLAM_OK) { workerStatus = s; snprintf(workerError, sizeof(workerError), "%s", err ? err : ""); }
         mappingBusy = false;
+        // (under wMu: a waiter may destroy this session - vslam_batch_restart_lane - as soon as it sees the flag; it cannot before the
+        //  lock is dropped, and by then the condition variable is no longer touched here)
+        wCv.notify_all();
     }
-    wCv.notify_all();
 }
 
 void vslam_system::worker_loop() {

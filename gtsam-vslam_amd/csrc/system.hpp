@@ -2,6 +2,7 @@
 #pragma once
 #include "matcher.hpp"
 #include "dmath.hpp"
+#include "slab_pool.hpp"
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -221,6 +222,7 @@ struct vslam_system {
     bool deferDevice = false;          // (set by vslam_batch around the first half of a host phase)
     // keyframe key arrays resident in HBM: fixed-size slots carved from slabs (no hipMalloc / hipFree per keyframe)
     std::vector<uint8_t*> keySlabs; size_t keySlot = 0; int keySlotsPerSlab = 0, keySlotsUsed = 0;
+    vslam::SlabPool* slabPool = nullptr;      // lane of a vslam_batch: slabs come from / go back to the group's free list (null: hipMalloc / hipFree)
     std::vector<int> lcaWhere;         // scratch of kf_update_pose: map-point index -> slot (entries reset after use)
     // device work of the pass in flight (local_mapping == 2): the session's own thread, or the batch's mapping threads
     std::thread worker;
@@ -233,7 +235,10 @@ struct vslam_system {
     bool ownsFe = true; int img0 = 0;
     void (*mapExec)(void*, vslam_system*) = nullptr; void* mapExecArg = nullptr;      // mapping jobs go to the batch's threads
     SysFrameCtx ctx;
-    vslam_status init(const vslam_system_config* c, vslam_extractor* sharedFe = nullptr, int imgBase = 0, hipStream_t sharedStream = nullptr);
+    // adoptFm: the matcher (and adoptUp / adoptDn: the pinned staging) of the session this one replaces in its lane - reset, not rebuilt
+    vslam_status init(const vslam_system_config* c, vslam_extractor* sharedFe = nullptr, int imgBase = 0, hipStream_t sharedStream = nullptr,
+                      vslam_matcher* adoptFm = nullptr);
+    vslam_status wait_idle();          // waits for the mapping job in flight (if any); its result stays unread
     void release();
     vslam_status frame_begin(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu);      // = _a, the deferred device calls, _b
     vslam_status frame_begin_a(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu);

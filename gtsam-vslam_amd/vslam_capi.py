@@ -385,9 +385,11 @@ def local_ba(rig, sigma_factor, inv_sigma_factor, prob, device=0, comm=None):
 
 
 def local_ba_batch(rig, sigma_factor, inv_sigma_factor, probs, device=0):
-    """vslam_local_ba_batch: the problems optimised together, one launch per stage for all of them"""
+    """vslam_local_ba_batch: the problems optimised together, one launch per stage for all of them (rig: one dict for all
+    problems, or a list with one rig per problem - the lanes of a cohort may have different cameras)"""
     n = len(probs)
-    built = [ba_problem_structs(rig, sigma_factor, inv_sigma_factor, pr) for pr in probs]
+    rigs = list(rig) if isinstance(rig, (list, tuple)) else [rig] * n
+    built = [ba_problem_structs(rigs[i], sigma_factor, inv_sigma_factor, pr) for i, pr in enumerate(probs)]
     PP = (C.POINTER(BaProblem) * n)(*[C.pointer(b[0]) for b in built])
     RR = (C.POINTER(BaResult) * n)(*[C.pointer(b[1]) for b in built])
     _chk(lib().vslam_local_ba_batch(PP, RR, n, int(device)))
@@ -459,6 +461,23 @@ def ba_refresh_depth(rig, kf_pose_wc, lm_xyz, lm_outlier, pair_kf, pair_lm, pair
     r = make_rig(rig)
     _chk(lib().vslam_ba_refresh_depth(C.byref(r), len(T), _p(T), len(lm), _p(lm), _p(lo), n, _p(pk), _p(pl), _p(pw), _p(cd), int(device),
                                       _p(d), _p(c), _p(u)))
+    return d[:n], c[:n], u[:n]
+
+
+def ba_refresh_depth_merged(rigs, n_kfs, kf_pose_wc, lm_xyz, lm_outlier, pair_kf, pair_lm, pair_wrong, cur_depth, device=0):
+    """the same for requests of different cameras staged together (vslam_ba_refresh_depth_merged, the lockstep group's form):
+    request r has n_kfs[r] keyframe poses and the rig rigs[r]; poses, landmarks and pairs are the concatenations."""
+    T = np.ascontiguousarray(kf_pose_wc, np.float64).reshape(-1, 16)
+    lm = np.ascontiguousarray(lm_xyz, np.float64).reshape(-1, 3); lo = np.ascontiguousarray(lm_outlier, np.uint8)
+    pk = np.ascontiguousarray(pair_kf, np.int32); pl = np.ascontiguousarray(pair_lm, np.int32)
+    pw = np.ascontiguousarray(pair_wrong, np.uint8); cd = np.ascontiguousarray(cur_depth, np.float32)
+    n = len(pk)
+    d = np.zeros(max(n, 1), np.float32); c = np.zeros(max(n, 1), np.uint8); u = np.zeros(max(n, 1), np.uint8)
+    rg = (Rig * len(rigs))(*[make_rig(r) for r in rigs])
+    nk = np.ascontiguousarray(n_kfs, np.int32)
+    assert len(nk) == len(rigs) and int(nk.sum()) == len(T)
+    _chk(lib().vslam_ba_refresh_depth_merged(rg, _p(nk), len(rigs), _p(T), len(lm), _p(lm), _p(lo), n, _p(pk), _p(pl), _p(pw), _p(cd),
+                                             int(device), _p(d), _p(c), _p(u)))
     return d[:n], c[:n], u[:n]
 
 
@@ -1195,28 +1214,66 @@ class _BorrowedSystem(System):
 
 
 class Batch:
-    """vslam_batch: `lanes` sessions tracked in lockstep.  T0s: per-lane initial poses (or None), velocities: per-lane (IMU)."""
+    """vslam_batch: `lanes` sessions tracked in lockstep.  T0s: per-lane initial poses (or None), velocities: per-lane (IMU).
+    rig: the camera of every lane; rigs=[...]: one rig dict per lane (a lane per robot: fx, fy, cx, cy, bl may differ, the image
+    size may not; `rig` may then be None)."""
 
     def __init__(self, rig, nfeatures, lanes, T0s=None, imu=None, velocities=None, local_mapping=1, window=10, device=0,
-                 host_threads=-1, mapping_threads=0, mapping_delay=0, mapping_np_delay=0):
+                 host_threads=-1, mapping_threads=0, mapping_delay=0, mapping_np_delay=0, rigs=None):
         self.L = lib()
         self.L.vslam_batch_system.restype = C.c_void_p
         self.lanes = lanes
+        if rigs is not None and len(rigs) != lanes:
+            raise ValueError("Batch: rigs needs one rig per lane")
+        self.rigs = list(rigs) if rigs is not None else [rig] * lanes
+        rig = self.rigs[0]
+        self._cfg = dict(nfeatures=nfeatures, imu=imu, local_mapping=local_mapping, window=window, device=device, mapping_delay=mapping_delay,
+                         mapping_np_delay=mapping_np_delay)
         cfgs = (SystemConfig * lanes)()
         for b in range(lanes):
-            im = None
-            if imu is not None:
-                im = dict(imu)
-                if velocities is not None:
-                    im["velocity"] = velocities[b]
-            c = system_config(rig, nfeatures, imu=im, local_mapping=local_mapping, window=window, device=device, mapping_delay=mapping_delay,
-                              mapping_np_delay=mapping_np_delay)
-            if T0s is not None and T0s[b] is not None:
-                c.T_wc_init = (C.c_double * 16)(*np.asarray(T0s[b], np.float64).reshape(16))
-            cfgs[b] = c
+            cfgs[b] = self._config(self.rigs[b], T0s[b] if T0s is not None else None, velocities[b] if velocities is not None else None)
         self.w, self.h = rig["w"], rig["h"]
         self.h_b = C.c_void_p()
         _chk(self.L.vslam_batch_create(cfgs, lanes, host_threads, mapping_threads, C.byref(self.h_b)))
+
+    def _config(self, rig, T0, velocity, **over):
+        """a lane's vslam_system_config (over: fields set after the defaults, e.g. mapping_delay)"""
+        kw = dict(self._cfg)
+        nfeatures = over.pop("nfeatures", kw.pop("nfeatures"))
+        im = None
+        if kw["imu"] is not None:
+            im = dict(kw["imu"])
+            if velocity is not None:
+                im["velocity"] = velocity
+        kw["imu"] = over.pop("imu", im)
+        kw.update(over)
+        c = system_config(rig, nfeatures, **kw)
+        if T0 is not None:
+            c.T_wc_init = (C.c_double * 16)(*np.asarray(T0, np.float64).reshape(16))
+        return c
+
+    def restart_lane(self, lane, rig=None, T0=None, velocity=None, **over):
+        """ends lane `lane`'s session and starts a new one in its place (vslam_batch_restart_lane), between two track() calls.
+        rig: the new session's camera (None: the lane's previous one); T0 / velocity: its initial pose / velocity.  over: other
+        config fields (nfeatures, imu, local_mapping, mapping_delay, mapping_np_delay) - the batch refuses what differs from its
+        shared settings.  The lane's next frame carries frame number 0; rectifiers must be bound again for raw frames.
+        With no argument but the lane, the library restarts it on its previous configuration (config = NULL: same rig, same
+        initial pose and velocity).  As soon as anything is given, a whole new config is built: T0 = None is then the identity
+        and velocity = None zero, not the previous session's."""
+        lane = int(lane)
+        if rig is None and T0 is None and velocity is None and not over:
+            _chk(self.L.vslam_batch_restart_lane(self.h_b, lane, None))
+            return
+        r = rig if rig is not None else (self.rigs[lane] if 0 <= lane < self.lanes else self.rigs[0])
+        c = self._config(r, T0, velocity, **over)
+        _chk(self.L.vslam_batch_restart_lane(self.h_b, lane, C.byref(c)))
+        self.rigs[lane] = r
+
+    def memory(self):
+        """key slabs (HBM) the batch has allocated in total, and how many of them sessions hold / its free list holds"""
+        nb = C.c_int64(); u = C.c_int32(); f = C.c_int32()
+        _chk(self.L.vslam_batch_memory(self.h_b, C.byref(nb), C.byref(u), C.byref(f)))
+        return dict(key_slab_bytes=nb.value, slabs_in_use=u.value, slabs_free=f.value)
 
     def close(self):
         if self.h_b:

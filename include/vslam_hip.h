@@ -375,6 +375,15 @@ vslam_status vslam_ba_refresh_depth(const vslam_rig* rig, int32_t n_kf, const do
                                     const int32_t* pair_kf, const int32_t* pair_lm, const uint8_t* pair_wrong,
                                     const float* cur_depth, int32_t device, float* depth_out, uint8_t* close_out,
                                     uint8_t* updated_out);
+/* The same for n_req requests of DIFFERENT cameras staged together, as a lockstep group serves the write-backs of its
+ * lanes: request r brings req_n_kf[r] keyframe poses and its rig rigs[r]; kf_pose_wc is the concatenation (pair_kf
+ * indexes it), landmarks and pairs likewise.  ONE launch; every pair is tested against 40 * baseline of its own
+ * keyframe's camera.  Outputs equal those of one vslam_ba_refresh_depth call per request. */
+vslam_status vslam_ba_refresh_depth_merged(const vslam_rig* rigs, const int32_t* req_n_kf, int32_t n_req, const double* kf_pose_wc,
+                                           int32_t n_lm, const double* lm_xyz, const uint8_t* lm_outlier, int32_t n_pairs,
+                                           const int32_t* pair_kf, const int32_t* pair_lm, const uint8_t* pair_wrong,
+                                           const float* cur_depth, int32_t device, float* depth_out, uint8_t* close_out,
+                                           uint8_t* updated_out);
 
 /* KeyFrame::updatePose(keyPose) (src/KeyFrame.cpp:6-76) — the per-keyframe step of FeatureTracker::changePosesLCA
  * (src/FeatureTracker.cpp:884-908), applied along the keyframe chain after a local BA / loop closure moved an earlier
@@ -455,7 +464,8 @@ typedef struct vslam_ba_lane_shape {
     int32_t n_pairs;        /* the problem's (keyframe, landmark) pairs */
     int32_t max_slots;      /* most free keyframes observing one landmark */
     int32_t max_factors;    /* most factors of one landmark (fixed keyframes included) */
-    int32_t own_rig;        /* 1: rig or pyramid differs from the first problem's */
+    int32_t own_rig;        /* 1: the problem runs on its own (vslam_local_ba_batch sets it for a pyramid depth other than the first
+                             * problem's; camera rigs may differ between the problems of a batch) */
 } vslam_ba_lane_shape;
 
 typedef struct vslam_ba_batch_shape {
@@ -780,8 +790,12 @@ vslam_status vslam_system_ba_timings(vslam_system* sys, const char** names, floa
  * per-lane table), because one sequence's frame is a chain of mostly one-workgroup kernels that cannot fill the GPU.
  * Each lane is a complete vslam_system (own map, keyframes, local mapping); its results are identical to the same
  * sequence run through vslam_system_track_stereo.  Local mapping of the lanes runs on `mapping_threads` library threads
- * (local_mapping = 2) or inside the step (1).  All lanes share rig, extractor parameters, device, IMU and mapping mode;
- * T_wc_init / velocity_init may differ.
+ * (local_mapping = 2) or inside the step (1).
+ * A lane is one robot.  Shared by all lanes of a batch (checked by vslam_batch_create and vslam_batch_restart_lane): device,
+ * image size (rig.width x rig.height), extractor parameters (fe), IMU mode, mapping mode and mapping_delay /
+ * mapping_np_delay - the extractor, the streams and the schedule are shared objects.  Per lane: the camera behind the
+ * images (rig.fx, fy, cx, cy, baseline - with the lane's rectifiers for raw frames), T_wc_init, velocity_init, the IMU
+ * constants, and the session's life: frame number 0 starts it, vslam_batch_restart_lane ends it and starts the next.
  * ------------------------------------------------------------------------- */
 typedef struct vslam_batch vslam_batch;
 /* host_threads: threads for the per-lane host phases (< 0: min(lanes, 8)); mapping_threads: <= 0: min(lanes, 3) */
@@ -832,7 +846,22 @@ vslam_status vslam_batch_track_stereo_prefetch_raw(vslam_batch* batch, const uin
                                                    const vslam_imu_bucket* imu, const uint8_t* lane_mask, double* T_wc_out,
                                                    vslam_frame_report* reports, const uint8_t* const* next_left,
                                                    const uint8_t* const* next_right, const uint8_t* next_mask);
-/* a lane's session (borrowed: valid until vslam_batch_destroy) for the vslam_system_* read-outs */
+/* Ends lane `lane`'s session and starts a new one in its place: new map, keyframes, trajectory, tracker state, IMU state.
+ * config: the new session's configuration (NULL = the lane's previous one).  Same shared fields as vslam_batch_create
+ * (device, width x height, fe, IMU mode, mapping mode / delays), else VSLAM_ERR_INVALID and the lane is left as it was;
+ * rig intrinsics / baseline, T_wc_init, velocity_init and the IMU constants may differ.
+ * Waits for THIS lane's mapping job in flight (its result is discarded); other lanes, their maps and their jobs are not
+ * touched.  Discards a pending prefetch (as vslam_batch_set_rectifiers does) and unbinds the lane's rectifiers.  The
+ * lane's next frame must carry frame_number 0.  A vslam_system* from vslam_batch_system(lane) is invalid afterwards.
+ * Call it between two steps, on the thread that drives the batch.  A restart allocates and frees nothing on the device
+ * (no hipFree / hipHostFree: they would wait for the kernels of every group on the device): the new session takes over
+ * the lane's matcher buffers, and the old session's key slabs (HBM) go to a free list of the batch, from which the
+ * sessions of all lanes take before new memory is allocated; vslam_batch_destroy frees it. */
+vslam_status vslam_batch_restart_lane(vslam_batch* batch, int32_t lane, const vslam_system_config* config);
+/* key slabs the batch has allocated in total (bytes), and how many of them sessions hold / the free list holds; any
+ * pointer may be NULL */
+vslam_status vslam_batch_memory(vslam_batch* batch, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free);
+/* a lane's session (borrowed: valid until vslam_batch_destroy or the lane's restart) for the vslam_system_* read-outs */
 vslam_system* vslam_batch_system(vslam_batch* batch, int32_t lane);
 int32_t vslam_batch_lanes(const vslam_batch* batch);
 vslam_status vslam_batch_wait_mapping(vslam_batch* batch);
