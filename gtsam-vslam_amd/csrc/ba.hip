@@ -26,6 +26,7 @@
 #include "comm.hpp"
 #include "dmath.hpp"
 #include "ba_pool.hpp"
+#include "ba_packed.hpp"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -746,18 +747,65 @@ __device__ __forceinline__ void ba2_w_row(const Ba2Region& g, const Ba2Roles& R,
     }
 }
 
-__global__ __launch_bounds__(1024) void k_ba_schur2(const BaDev* __restrict__ tab, int maxSlots, int maxFac) {
+// Layout of the workgroup's LDS copy of the system (and of the partial it writes out):
+//   BA2_PACKED     upper 6x6 blocks only, block pitch BA_PACKED_PITCH (ba_packed.hpp) - the production form: 2 095 instead of 3 660
+//                  doubles to zero, flush, write and sum at F = 10, and block bases spread over the LDS banks;
+//   BA2_ROWMAJOR   n x n row-major with pitch n (the form of D.S; k_ba_schur's);  BA2_ROWMAJOR1  the same with LDS pitch n + 1 (the
+//                  bank effect alone; written out with pitch n).  Developer overrides: VSLAM_BA_SCHUR2_LAYOUT = 0 / 1.
+enum { BA2_ROWMAJOR = 0, BA2_ROWMAJOR1 = 1, BA2_PACKED = 2 };
+__host__ __device__ inline int ba2_sys_doubles(int n, int layout) {       // LDS doubles of the system copy (even: the staging regions follow)
+    return layout == BA2_PACKED ? (ba_packed_doubles(n / 6) + 1) & ~1 : layout == BA2_ROWMAJOR1 ? n * (n + 1) + n : n * n + n;
+}
+__host__ __device__ inline int ba2_part_doubles(int n, int layout) {      // doubles of one partial in Spart
+    return layout == BA2_PACKED ? ba_packed_doubles(n / 6) : n * n + n;
+}
+// the block phase: two lanes own one 6x6 block (s1 <= s2), three rows each; 32 blocks per pass.  One base address per lane, the 18
+// atomics at constant offsets from it (PACKED: row pitch 6 - all of them immediates; else the rows are ld apart).
+template <bool PACKED>
+__device__ __forceinline__ void ba2_blocks(double* Sloc, const double* W, const double* WH, const int* sfi, int ns, int lane, int F, int ld) {
+    const int nb = ns * (ns + 1) / 2, half = lane & 1;
+    for (int b0 = 0; b0 < nb; b0 += 32) {
+        int b = b0 + (lane >> 1), s1 = 0;
+        if (b >= nb) continue;
+        while (b >= ns - s1) { b -= ns - s1; s1++; }
+        const int s2 = s1 + b;
+        const double* A = WH + s1 * 18 + half * 9;
+        const double* B = W + s2 * 18;
+        double aa[9];
+#pragma unroll
+        for (int q = 0; q < 9; q++) aa[q] = A[q];
+        double* d0 = Sloc + (PACKED ? ba_packed_block(F, sfi[s1], sfi[s2]) * BA_PACKED_PITCH + 18 * half : (6 * sfi[s1] + 3 * half) * ld + 6 * sfi[s2]);
+        // (the lane's three A rows stay in registers; B goes through them three columns at a time)
+#pragma unroll
+        for (int jh = 0; jh < 2; jh++) {
+            double bb[9];
+#pragma unroll
+            for (int q = 0; q < 9; q++) bb[q] = B[9 * jh + q];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                double* dr = d0 + i * (PACKED ? 6 : ld) + 3 * jh;
+#pragma unroll
+                for (int j = 0; j < 3; j++) atomicAdd(dr + j, -(aa[3 * i] * bb[3 * j] + aa[3 * i + 1] * bb[3 * j + 1] + aa[3 * i + 2] * bb[3 * j + 2]));
+            }
+        }
+    }
+}
+
+template <bool PACKED>
+__device__ __forceinline__ void ba2_schur(const BaDev* __restrict__ tab, int maxSlots, int maxFac, int layout) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the cohort)
     extern __shared__ double sm[];
     if (!ba_enter(D, BA_TRY, blockIdx.y)) return;
-    const int n = D.n;
-    const int sys = n * n + n;
+    const int n = D.n, F = n / 6;                // the lane's own system, not the cohort's largest
+    constexpr bool packed = PACKED;
+    const int ld = layout == BA2_ROWMAJOR1 ? n + 1 : n;
+    const int sys = ba2_sys_doubles(n, layout);
     double* const Sloc = sm;
-    double* const racc = Sloc + (size_t)n * n;
+    double* const racc = Sloc + (packed ? ba_packed_rhs(F) : ld * n);
     const int lane = threadIdx.x & 63;
     const int unit = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nu = blockDim.x >> 6, nt = blockDim.x;
     const Ba2Region g = ba2_region(sm + sys + (size_t)unit * ba2_stage_doubles(maxFac, maxSlots), maxFac, maxSlots);
-    double* const F = g.F; double* const W = g.W; double* const WH = g.WH;
+    double* const F_ = g.F; double* const W = g.W; double* const WH = g.WH;
     int* const ffi = g.ffi; int* const sfi = g.sfi;
     const double lam = D.lambda;
     Ba2Roles R;
@@ -783,29 +831,8 @@ __global__ __launch_bounds__(1024) void k_ba_schur2(const BaDev* __restrict__ ta
             atomicAdd(&racc[6 * sfi[R.ws] + R.wi], -(g0 * h[6] + g1 * h[7] + g2 * h[8]));
         }
         ba_wave_fence();
-        // ---- blocks: two lanes own one 6x6 block (s1 <= s2), three rows each; 32 blocks per pass ----
-        {
-            const int nb = ns * (ns + 1) / 2, half = lane & 1;
-            for (int b0 = 0; b0 < nb; b0 += 32) {
-                int b = b0 + (lane >> 1), s1 = 0;
-                if (b >= nb) continue;
-                while (b >= ns - s1) { b -= ns - s1; s1++; }
-                const int s2 = s1 + b;
-                const double* A = WH + s1 * 18 + half * 9;
-                const double* B = W + s2 * 18;
-                double bb[18];
-#pragma unroll
-                for (int q = 0; q < 18; q++) bb[q] = B[q];
-                double* d0 = Sloc + (6 * sfi[s1] + 3 * half) * n + 6 * sfi[s2];
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    const double a0 = A[3 * i], a1 = A[3 * i + 1], a2 = A[3 * i + 2];
-                    double* dr = d0 + i * n;
-#pragma unroll
-                    for (int j = 0; j < 6; j++) atomicAdd(dr + j, -(a0 * bb[3 * j] + a1 * bb[3 * j + 1] + a2 * bb[3 * j + 2]));
-                }
-            }
-        }
+        // ---- blocks ----
+        ba2_blocks<PACKED>(Sloc, W, WH, sfi, ns, lane, F, ld);
         // ---- Hpp and bp of the factors of free keyframes: lane (f, i), ten factors per pass ----
         if (pf < 10)
             for (int fb = 0; fb < nf; fb += 10) {
@@ -813,18 +840,26 @@ __global__ __launch_bounds__(1024) void k_ba_schur2(const BaDev* __restrict__ ta
                 if (f >= nf) break;
                 const int fi = ffi[f];
                 if (fi < 0) continue;
-                const double* o = F + f * 20;
+                const double* o = F_ + f * 20;
                 const double a0 = o[2 + pi], a1 = o[8 + pi];
-                double* dr = Sloc + (6 * fi + pi) * n + 6 * fi;
+                double* dr = Sloc + (packed ? ba_packed_block(F, fi, fi) * BA_PACKED_PITCH + 6 * pi : (6 * fi + pi) * ld + 6 * fi);
                 for (int j = pi; j < 6; j++) atomicAdd(dr + j, a0 * o[2 + j] + a1 * o[8 + j]);
                 atomicAdd(&racc[6 * fi + pi], -(a0 * o[0] + a1 * o[1]));
             }
         ba_wave_fence();        // the region is rewritten for the next landmark
     }
     __syncthreads();
-    double* dst = D.Spart + (size_t)blockIdx.x * sys;
-    for (int i = threadIdx.x; i < sys; i += nt) dst[i] = Sloc[i];
+    const int part = ba2_part_doubles(n, layout);
+    double* dst = D.Spart + (size_t)blockIdx.x * part;
+    if (layout == BA2_ROWMAJOR1) {
+        for (int i = threadIdx.x; i < part; i += nt) dst[i] = Sloc[i + i / n];      // pitch n + 1 -> n (the rhs is row n)
+    } else {
+        for (int i = threadIdx.x; i < part; i += nt) dst[i] = Sloc[i];
+    }
 }
+__global__ __launch_bounds__(1024) void k_ba_schur2(const BaDev* __restrict__ tab, int maxSlots, int maxFac) { ba2_schur<true>(tab, maxSlots, maxFac, BA2_PACKED); }
+// the row-major forms behind the developer switch (layout = BA2_ROWMAJOR / BA2_ROWMAJOR1)
+__global__ __launch_bounds__(1024) void k_ba_schur2_rm(const BaDev* __restrict__ tab, int maxSlots, int maxFac, int layout) { ba2_schur<false>(tab, maxSlots, maxFac, layout); }
 
 // Back-substitution on the same staged front part: dl = (Hll + lambda I)^-1 (bl - sum_s W_s^T dP_s) per candidate, trial landmark positions.
 // Lane (s, i) multiplies its W row by its entry of the slot's pose update; the three sums over the <= 60 lanes finish with two DPP quad
@@ -879,36 +914,45 @@ __global__ __launch_bounds__(512) void k_ba_back2(const BaDev* __restrict__ tab,
 // before the solve.  A workgroup owns 32 entries; 8 thread groups sum slices of the partials, the 8 slice sums are
 // then added in slice order through LDS - a fixed summation order, no atomics: the reduced system is bit-identical
 // from run to run.
-__global__ __launch_bounds__(256) void k_ba_reduce(const BaDev* __restrict__ tab, int nPart) {
+__global__ __launch_bounds__(256) void k_ba_reduce(const BaDev* __restrict__ tab, int nPart, int packed) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the batch)
     __shared__ double sSl[8][33];
     if (!ba_enter(D, BA_TRY, blockIdx.y)) return;
-    const int total = D.n * D.n + D.n;
+    const int total = D.n * D.n + D.n, F = D.n / 6;
+    // packed partials (k_ba_schur2, ba_packed.hpp): the workgroup's 32 slots are 32 consecutive packed offsets, read as they lie; the
+    // slots behind the packed size own the entries below the block diagonal - in no partial, they get the edge term alone (what the
+    // sum of their zeros gave)
+    const int nSum = packed ? ba_packed_doubles(F) : total;            // slots with partials = doubles of one partial
+    const int nSlots = packed ? ba_packed_reduce_slots(F) : total;
     const int e = threadIdx.x & 31, y = threadIdx.x >> 5;
     const int i = blockIdx.x * 32 + e;
-    const size_t stride = (size_t)total;
     double s = 0;
-    if (i < total) {
+    if (i < nSum) {
         const int per = (nPart + 7) / 8;
         const int p0 = y * per, p1 = min(nPart, p0 + per);
         double s0 = 0, s1 = 0, s2 = 0, s3 = 0;      // 4 independent accumulators keep the strided loads in flight
+        // (int offsets: the partials of a candidate, at most a few hundred of <= 3 660 doubles, stay far below 2^31)
         int p = p0;
         for (; p + 3 < p1; p += 4) {
-            s0 += D.Spart[(size_t)p * stride + i];
-            s1 += D.Spart[(size_t)(p + 1) * stride + i];
-            s2 += D.Spart[(size_t)(p + 2) * stride + i];
-            s3 += D.Spart[(size_t)(p + 3) * stride + i];
+            s0 += D.Spart[p * nSum + i];
+            s1 += D.Spart[(p + 1) * nSum + i];
+            s2 += D.Spart[(p + 2) * nSum + i];
+            s3 += D.Spart[(p + 3) * nSum + i];
         }
-        for (; p < p1; p++) s0 += D.Spart[(size_t)p * stride + i];
+        for (; p < p1; p++) s0 += D.Spart[p * nSum + i];
         s = (s0 + s1) + (s2 + s3);
     }
     sSl[y][e] = s;
     __syncthreads();
-    if (y == 0 && i < total) {
-        double t = D.Sedge[i];           // BetweenFactor blocks of this linearisation
-        for (int q = 0; q < 8; q++) t += sSl[q][e];
-        if (D.specLin) D.Sedge2[i] = 0;  // the trial's speculative linearisation accumulates here
-        if (i < D.n * D.n) D.S[i] = t; else D.rhs[i - D.n * D.n] = t;
+    const int slot = blockIdx.x * 32 + threadIdx.x;      // = i in slice 0
+    if (y == 0 && slot < nSlots) {
+        const int io = packed ? ba_packed_reduce_entry(F, slot) : slot;      // the slot's row-major entry
+        if (io >= 0) {
+            double t = D.Sedge[io];          // BetweenFactor blocks of this linearisation
+            for (int q = 0; q < 8; q++) t += sSl[q][threadIdx.x];
+            if (D.specLin) D.Sedge2[io] = 0; // the trial's speculative linearisation accumulates here
+            if (io < D.n * D.n) D.S[io] = t; else D.rhs[io - D.n * D.n] = t;
+        }
     }
 }
 
@@ -2668,8 +2712,8 @@ static vslam_status ba_kernel_attributes() {
         const int cap = BA_LDS_BYTES;
         const void* fns[] = {(const void*)k_ba_schur, (const void*)k_ba_schur_win, (const void*)k_ba_solve, (const void*)k_ba_back,
                              (const void*)k_ba_solve_mfma, (const void*)k_ba_chol_col, (const void*)k_ba_chol_back, (const void*)k_ba_lm_prep,
-                             (const void*)k_ba_schur2, (const void*)k_ba_back2};
-        const void* batchFns[] = {(const void*)k_ba_schur, (const void*)k_ba_schur2, (const void*)k_ba_back, (const void*)k_ba_back2, (const void*)k_ba_solve_mfma};
+                             (const void*)k_ba_schur2, (const void*)k_ba_schur2_rm, (const void*)k_ba_back2};
+        const void* batchFns[] = {(const void*)k_ba_schur, (const void*)k_ba_schur2, (const void*)k_ba_schur2_rm, (const void*)k_ba_back, (const void*)k_ba_back2, (const void*)k_ba_solve_mfma};
         for (const void* f : fns) {
             hipFuncAttributes fa{};      // (the limit is on static + dynamic LDS together)
             hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -3244,7 +3288,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             g_baTimer.end(t);
             t = g_baTimer.begin("ba_solve");
             if (n > 0) {     // sum of the partial systems + BetweenFactor blocks
-                if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, lmBlocks);
+                if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, lmBlocks, 0);
                 else hipLaunchKernelGGL(k_ba_reduce_win, dim3(Wn.nWin, NB), dim3(256), 0, stream, dD, Wn);
             }
             // the NB candidates' systems are contiguous (sysStride apart): one all-reduce for all of them
@@ -3449,7 +3493,7 @@ static std::atomic<long long> g_bbsNs[12], g_bbsCalls{0}, g_bbsPolls{0};
 static const char* g_bbsName[12] = {"check+count", "arena fill", "tables+upload", "lm pass 1", "chi2 1", "second-pass prep", "lm pass 2", "chi2 2 + fetch", "results", nullptr, nullptr, nullptr};
 
 // ---- launch plan of the batch: a pure function of the cohort's shape (no device calls; exported as vslam_local_ba_batch_plan) -----
-struct BaPlanKnobs { bool schur2, back2, sharedW; int s2Waves, b2Waves, schurWaves, lmBlocks; };
+struct BaPlanKnobs { bool schur2, back2, sharedW; int s2Waves, b2Waves, schurWaves, lmBlocks, s2Layout; };
 static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the environment (none set: the production plan)
     static const bool s2Env = !(getenv("VSLAM_BA_SCHUR2") && atoi(getenv("VSLAM_BA_SCHUR2")) == 0);
     static const bool b2Env = !(getenv("VSLAM_BA_BACK2") && atoi(getenv("VSLAM_BA_BACK2")) == 0);
@@ -3462,6 +3506,8 @@ static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the enviro
     //  finds a CU sooner: 8 waves here, 4 for the back-substitution - ba_back 15.7 -> 10.6 us per tracked frame)
     k.s2Waves = getenv("VSLAM_BA_SCHUR2_WAVES") ? atoi(getenv("VSLAM_BA_SCHUR2_WAVES")) : 8;
     k.b2Waves = getenv("VSLAM_BA_BACK2_WAVES") ? atoi(getenv("VSLAM_BA_BACK2_WAVES")) : 4;
+    // k_ba_schur2's LDS system: packed upper blocks; 0 / 1: the row-major forms (pitch n, n + 1) for comparison
+    k.s2Layout = getenv("VSLAM_BA_SCHUR2_LAYOUT") ? std::max(0, std::min((int)BA2_PACKED, atoi(getenv("VSLAM_BA_SCHUR2_LAYOUT")))) : (int)BA2_PACKED;
     return k;
 }
 static inline int ba_batch_solve_kind(int n, bool useMfma) { return (n <= 64 && useMfma) ? BA_SOLVE_MFMA64 : n <= BA_WAVE_N ? BA_SOLVE_WAVE : BA_SOLVE_MFMA; }
@@ -3520,7 +3566,8 @@ static void ba_batch_plan(const vslam_ba_batch_shape& S, const BaPlanKnobs& kn, 
     p.schur_waves = useSchur2 ? s2Waves : schurWaves;
     p.schur_shared_w = useSchur2 ? 0 : sharedW;
     p.schur_blocks = lmBlocks;
-    p.schur_lds = (int)(useSchur2 ? s2Lds : schurLds);
+    // (the rules above keep computing with the row-major size: the plans per shape stay; only the LDS asked for follows the layout)
+    p.schur_lds = (int)(useSchur2 ? (size_t)ba2_sys_doubles(nMax, kn.s2Layout) * sizeof(double) + (size_t)s2Waves * s2StageB : schurLds);
     p.back_kernel = useBack2 ? VSLAM_BA_KERNEL_BACK2 : VSLAM_BA_KERNEL_BACK;
     if (useBack2) {
         p.back_waves = b2Waves; p.back_shared = 1; p.back_lds = (int)b2Lds;
@@ -3703,6 +3750,10 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     const size_t sysMax = (size_t)nMax * nMax + nMax;
     const int maxSlots = plan.max_slots, maxFac = plan.max_factors, lmBlocks = plan.schur_blocks;
     const bool useSchur2 = plan.schur_kernel == VSLAM_BA_KERNEL_SCHUR2, useBack2 = plan.back_kernel == VSLAM_BA_KERNEL_BACK2;
+    const int s2Layout = ba_plan_knobs().s2Layout;
+    const bool packedS = useSchur2 && s2Layout == BA2_PACKED;
+    const int reduceSlots = packedS ? ba_packed_reduce_slots(nMax / 6) : (int)sysMax;      // k_ba_reduce: 32 slots per workgroup
+    auto part_doubles = [&](int n) { return (size_t)(useSchur2 ? ba2_part_doubles(n, s2Layout) : n * n + n); };      // one workgroup's partial in Spart
     const bool anyMfma64 = plan.solve_kinds & (1 << BA_SOLVE_MFMA64), anyWave = plan.solve_kinds & (1 << BA_SOLVE_WAVE),
                anyMfma = plan.solve_kinds & (1 << BA_SOLVE_MFMA);
     VS_CHECK(ba_kernel_attributes());
@@ -3723,11 +3774,11 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     for (int a = 0; a < NL; a++) {
         const Lane& q = lanes[act[a]];
         const BaPassHost& H = q.H;
-        const size_t sysStride = (size_t)H.n * H.n + 2 * H.n + 8, sysD = (size_t)H.n * H.n + H.n;
+        const size_t sysStride = (size_t)H.n * H.n + 2 * H.n + 8;
         off[a].poseS = dtake((size_t)nSlots * q.K * sizeof(DPose)); off[a].lmS = dtake((size_t)nSlots * 3 * q.L * 8);
         off[a].facJ = dtake((size_t)20 * H.NF * nSlots * 8); off[a].dP = dtake((size_t)NB * H.n * 8); off[a].dL = dtake((size_t)NB * 3 * H.Lp * 8);
         off[a].S = dtake(sysStride * NB * 8); off[a].partial = dtake(((size_t)2 * obsBlocks + 2 * (size_t)std::max(H.NE, 1)) * NB * 8);
-        off[a].spart = dtake(sysD * lmBlocks * NB * 8); off[a].sums = dtake(32 * 8);
+        off[a].spart = dtake(part_doubles(H.n) * lmBlocks * NB * 8); off[a].sums = dtake(32 * 8);
         off[a].Lg = (H.n > 64 || !useMfma) && H.n > BA_WAVE_N ? dtake((size_t)BA_MFMA_N * BA_MFMA_N * NB * 8) : 0;
     }
     VS_HIP(W.d_mem.alloc(dBytes));
@@ -3771,7 +3822,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         D.facJBase = q.d_facJ; D.facJStride = (size_t)20 * H.NF; D.SedgeBase = q.d_Sedge; D.edgesBase = A.dev(H.h_edges);
         D.sysStride = (size_t)n * n + 2 * n + 8; D.dLStride = (size_t)3 * H.Lp;
         D.partialStride = (size_t)2 * obsBlocks + 2 * (size_t)std::max(H.NE, 1); D.partial = q.d_partial;
-        D.spartStride = ((size_t)n * n + n) * lmBlocks; D.Spart = q.d_Spart;
+        D.spartStride = part_doubles(n) * lmBlocks; D.Spart = q.d_Spart;
         D.solveKind = ba_batch_solve_kind(n, useMfma);
         D.Lg = q.d_Lg;
         D.ctlHost = (double*)(W.h_back + oBackCtl) + (size_t)CTL_DOUBLES * a;
@@ -3803,11 +3854,12 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
             g_baTimer.end(t);
         }
         t = g_baTimer.begin("ba_schur");
-        if (useSchur2) hipLaunchKernelGGL(k_ba_schur2, dim3(lmBlocks, NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, maxFac);
+        if (useSchur2 && s2Layout == BA2_PACKED) hipLaunchKernelGGL(k_ba_schur2, dim3(lmBlocks, NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, maxFac);
+        else if (useSchur2) hipLaunchKernelGGL(k_ba_schur2_rm, dim3(lmBlocks, NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, maxFac, s2Layout);
         else hipLaunchKernelGGL(k_ba_schur, dim3(lmBlocks, plan.schur_shared_w ? 1 : NB, NL), dim3(64 * plan.schur_waves), plan.schur_lds, stream, dTab, maxSlots, plan.schur_shared_w);
         g_baTimer.end(t);
         t = g_baTimer.begin("ba_solve");
-        hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysMax + 31) / 32, NB, NL), dim3(256), 0, stream, dTab, lmBlocks);
+        hipLaunchKernelGGL(k_ba_reduce, dim3((reduceSlots + 31) / 32, NB, NL), dim3(256), 0, stream, dTab, lmBlocks, packedS ? 1 : 0);
         if (anyMfma64) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB, 1, NL), dim3(64), 0, stream, dTab);
         if (anyWave) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB, 1, NL), dim3(64), 0, stream, dTab);
         if (anyMfma) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB, 1, NL), dim3(64 * BA_MFMA_NW), plan.solve_lds, stream, dTab, (double*)nullptr);
