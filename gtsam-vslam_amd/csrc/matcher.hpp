@@ -67,6 +67,9 @@ struct vslam_matcher {
     vslam_status proj_enqueue(int M, float rad, const int* Mdev = nullptr, const int* gate = nullptr, int gateMin = 0, int mode = 0);
     void proj_lane(vslam::ProjLane& L, int M, float rad, const int* Mdev, const int* gate, int gateMin, int mode);
     bool mono = false;               // created without a right extractor: left-only operations
+    uint8_t* d_win = nullptr; size_t winCap = 0;     // work block of match_radius_window (lane table, views, per-target lists, claim table)
+    vslam_status match_radius_window(const void* lastKeys, int nLast, const void* const* targetKeys, const int* nTarget, int nTargets,
+                                     float rad, int* matchedL, int nMatched, int* matchOut, int* nMatches);
     vslam_status match_projection(const vslam_mappoint_view* mps, int M, float rad, int* mL, int* mR,
                                   int* matches, int* nMatches, long long* nCand, int mode = 0);
 

@@ -17,6 +17,7 @@
 // the window is (cell row, cell col, index).
 #include "matcher.hpp"
 #include "proj_dev.hpp"
+#include "track_dev.hpp"
 
 namespace vslam {
 
@@ -661,4 +662,125 @@ extern "C" vslam_status vslam_match_by_radius(vslam_matcher* m, const vslam_keyp
     if (s != VSLAM_OK) return s;
     for (int i = 0; i < n_last; i++) match_out[i] = mt[2 * (size_t)i];
     return VSLAM_OK;
+}
+
+// ---- matchByRadius from one key set into several resident key sets (addMappointsMono, src/FeatureTracker.cpp:1512-1519) ----------
+// The query keypoints become map-point views on the device (the only new device code: every other step is a kernel above, fed
+// from the key blocks): k_proj_cells_b and k_proj_candidates_b run once with the target as grid dimension (the candidate lists do
+// not depend on the claims), then k_proj_resolve walks the targets in order on ONE claim table - a claim at index j made in one
+// target blocks index j in the later ones, as the reference's shared matchedIdxsL does.
+namespace vslam {
+__global__ __launch_bounds__(256) void k_radius_views(const vslam_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc, int n,
+                                                      vslam_mappoint_view* __restrict__ mpv) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    static_assert(sizeof(vslam_mappoint_view) == 60, "view written as 15 words");
+    const uint32_t* d = (const uint32_t*)(desc + (size_t)i * 32);
+    uint32_t* o = (uint32_t*)(mpv + i);
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = d[k];
+    o[8] = __float_as_uint(kps[i].x); o[9] = __float_as_uint(kps[i].y);      // pred_l = the keypoint itself
+    o[10] = 0; o[11] = 0;
+    o[12] = (uint32_t)kps[i].octave; o[13] = 0;                              // scale_level_l / _r
+    o[14] = 1;                                                               // in_frame = 1, in_frame_r = 0
+}
+}  // namespace vslam
+
+vslam_status vslam_matcher::match_radius_window(const void* lastKeys, int nLast, const void* const* targetKeys, const int* nTarget,
+                                                int nTargets, float rad, int* matchedL, int nMatched, int* matchOut, int* nMatches) {
+    constexpr int MAX_TARGETS = 64;
+    if (nLast < 0 || nTargets < 0 || nMatched < 0 || nTargets > MAX_TARGETS || nLast > 65535 || (nLast > 0 && !lastKeys) ||
+        (nTargets > 0 && (!targetKeys || !nTarget)) || (nMatched > 0 && !matchedL) || ((size_t)nLast * nTargets > 0 && !matchOut)) {
+        set_error("vslam_match_by_radius_window: bad argument");
+        return VSLAM_ERR_INVALID;
+    }
+    int maxT = 0;
+    for (int t = 0; t < nTargets; t++) {
+        if (nTarget[t] < 0 || (nTarget[t] > 0 && !targetKeys[t])) { set_error("vslam_match_by_radius_window: bad target %d", t); return VSLAM_ERR_INVALID; }
+        if (nTarget[t] > nMatched) {
+            set_error("vslam_match_by_radius_window: the claim table has %d entries, target %d has %d keys", nMatched, t, nTarget[t]);
+            return VSLAM_ERR_INVALID;
+        }
+        maxT = std::max(maxT, nTarget[t]);
+    }
+    if (maxT > 65535 || proj_resolve_lds(maxT, 0, 32) > PROJ_LDS_CAP) {
+        set_error("vslam_match_by_radius_window: %d keys in one target exceed the claim tables' room", maxT);
+        return VSLAM_ERR_CAPACITY;
+    }
+    if (nMatches) for (int t = 0; t < nTargets; t++) nMatches[t] = 0;
+    for (size_t k = 0; k < (size_t)nLast * nTargets; k++) matchOut[k] = -1;
+    if (nLast == 0 || nTargets == 0) return VSLAM_OK;          // (no query, or no target: nothing is claimed)
+    VS_HIP(hipSetDevice(device));
+    // one work block: lane table | views | claim table | resolve outputs | per target: matches, top lists, cell starts, cell indices
+    size_t at = 0;
+    auto put = [&](size_t bytes) { const size_t a = at; at = (at + bytes + 255) & ~(size_t)255; return a; };
+    const size_t oLanes = put((size_t)nTargets * sizeof(ProjLane)), oMpv = put((size_t)nLast * sizeof(vslam_mappoint_view));
+    const size_t oTab = put((size_t)nMatched * sizeof(int)), oOut = put((size_t)nTargets * 4 * sizeof(int)), oStats = put(4 * sizeof(unsigned long long));
+    const size_t oMt = put((size_t)nTargets * nLast * 2 * sizeof(int));
+    const size_t oTopk = put((size_t)nTargets * nLast * 2 * PROJ_K * sizeof(unsigned long long));
+    const size_t oCs = put((size_t)nTargets * (PROJ_MAX_CELLS + 1) * sizeof(int));
+    std::vector<size_t> oCi(nTargets);
+    for (int t = 0; t < nTargets; t++) oCi[t] = put((size_t)std::max(nTarget[t], 1) * sizeof(unsigned short));
+    if (at > winCap) {
+        VS_HIP(hipStreamSynchronize(stream));
+        hipFree(d_win); d_win = nullptr; winCap = 0;
+        VS_HIP(hipMalloc((void**)&d_win, at));
+        winCap = at;
+    }
+    uint8_t* w = d_win;
+    vslam_mappoint_view* mpv = (vslam_mappoint_view*)(w + oMpv);
+    int* tab = (int*)(w + oTab);
+    std::vector<ProjLane> lanes(nTargets);
+    const KeyBlockLayout ol = key_block_layout(nLast, 0);
+    for (int t = 0; t < nTargets; t++) {
+        ProjLane& L = lanes[t];
+        proj_lane(L, nLast, rad, nullptr, nullptr, 0, PROJ_RADIUS);          // the matcher's geometry (grid, scalePyr)
+        ProjArgs& A = L.A;
+        const KeyBlockLayout o = key_block_layout(nTarget[t], 0);
+        const uint8_t* blk = (const uint8_t*)targetKeys[t];
+        A.kps[0] = nTarget[t] ? (const vslam_keypoint*)(blk + o.kpsL) : nullptr; A.desc[0] = nTarget[t] ? blk + o.descL : nullptr; A.n[0] = nTarget[t];
+        A.kps[1] = nullptr; A.desc[1] = nullptr; A.n[1] = 0;
+        A.mpv = mpv; A.rightIdxs = nullptr; A.leftIdxs = nullptr;
+        const bool bucketed = A.xGrids * A.yGrids <= PROJ_MAX_CELLS;
+        A.cellStart[0] = bucketed ? (int*)(w + oCs) + (size_t)t * (PROJ_MAX_CELLS + 1) : nullptr;
+        A.cellIdx[0] = bucketed ? (unsigned short*)(w + oCi[t]) : nullptr;
+        A.cellStart[1] = nullptr; A.cellIdx[1] = nullptr;
+        L.matches = (int*)(w + oMt) + (size_t)t * nLast * 2;
+        L.topk = (unsigned long long*)(w + oTopk) + (size_t)t * nLast * 2 * PROJ_K;
+        L.stats = (unsigned long long*)(w + oStats);
+        L.matchedL = tab; L.matchedR = tab; L.out = (int*)(w + oOut) + 4 * t;
+    }
+    VS_HIP(hipMemcpyAsync(w + oLanes, lanes.data(), (size_t)nTargets * sizeof(ProjLane), hipMemcpyHostToDevice, stream));
+    VS_HIP(hipMemcpyAsync(tab, matchedL, (size_t)nMatched * sizeof(int), hipMemcpyHostToDevice, stream));
+    VS_HIP(hipMemsetAsync(w + oMt, 0xff, (size_t)nTargets * nLast * 2 * sizeof(int), stream));       // matchesIdxs: all (-1, -1)
+    VS_HIP(hipMemsetAsync(w + oStats, 0, 4 * sizeof(unsigned long long), stream));
+    VS_HIP(hipMemsetAsync(w + oOut, 0, (size_t)nTargets * 4 * sizeof(int), stream));
+    const uint8_t* lb = (const uint8_t*)lastKeys;
+    hipLaunchKernelGGL(k_radius_views, dim3((nLast + 255) / 256), dim3(256), 0, stream, (const vslam_keypoint*)(lb + ol.kpsL), lb + ol.descL, nLast, mpv);
+    const ProjLane* dLanes = (const ProjLane*)(w + oLanes);
+    proj_attrs();
+    if (lanes[0].A.cellStart[0])
+        hipLaunchKernelGGL(k_proj_cells_b, dim3(1, nTargets), dim3(PROJ_CELLS_NT), (size_t)PROJ_MAX_CELLS * sizeof(int), stream, dLanes);
+    hipLaunchKernelGGL(k_proj_candidates_b, dim3((2 * nLast + 3) / 4, nTargets), dim3(256), 0, stream, dLanes);
+    for (int t = 0; t < nTargets; t++)          // in list order, the claim table carried from target to target
+        launch_proj_resolve(stream, lanes[t].A, lanes[t].topk, tab, tab, lanes[t].matches, lanes[t].out);
+    VS_HIP(hipGetLastError());
+    std::vector<int> mt((size_t)nTargets * nLast * 2), outs((size_t)nTargets * 4);
+    VS_HIP(hipMemcpyAsync(mt.data(), w + oMt, mt.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(outs.data(), w + oOut, outs.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipMemcpyAsync(matchedL, tab, (size_t)nMatched * sizeof(int), hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipStreamSynchronize(stream));       // the call's one host wait
+    for (int t = 0; t < nTargets; t++) {
+        for (int i = 0; i < nLast; i++) matchOut[(size_t)t * nLast + i] = mt[((size_t)t * nLast + i) * 2];
+        if (nMatches) nMatches[t] = outs[4 * (size_t)t];
+    }
+    return VSLAM_OK;
+}
+
+extern "C" vslam_status vslam_match_by_radius_window(vslam_matcher* m, const void* last_keys, int32_t n_last,
+                                                     const void* const* target_keys, const int32_t* n_target, int32_t n_targets,
+                                                     float rad, int32_t* matched_idxs_l, int32_t n_matched,
+                                                     int32_t* match_out, int32_t* n_matches) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->match_radius_window(last_keys, n_last, target_keys, n_target, n_targets, rad, matched_idxs_l, n_matched, match_out, n_matches);
 }

@@ -553,6 +553,7 @@ void vslam_matcher::release() {
     hipFree(d_trVisL);
     hipFree(d_mpv); hipFree(d_topk); hipFree(d_matches); hipFree(d_matchedL); hipFree(d_matchedR); hipFree(d_projOut);
     for (int s = 0; s < 2; s++) { hipFree(d_cellStart[s]); hipFree(d_cellIdx[s]); }
+    hipFree(d_win); d_win = nullptr; winCap = 0;
     if (stream && ownsStream) hipStreamDestroy(stream);
     stream = nullptr;
 }

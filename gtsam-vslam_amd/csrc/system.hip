@@ -683,6 +683,7 @@ vslam_status vslam_system::raw_args(int stride, int channels, const char* fn) co
 vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame,
                                  const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* rep, bool raw) {
     if (!L || !R || !T_wc_out) return VSLAM_ERR_INVALID;
+    if (monoMode) { set_error("vslam_system: a mono session takes vslam_system_track_mono_imu"); return VSLAM_ERR_INVALID; }
     if (raw) VS_CHECK(raw_args(stride, channels, "vslam_system_track_stereo_raw"));
     SysFrameCtx& c = ctx;
     VS_CHECK(frame_begin(c, frame, imu));

@@ -268,6 +268,21 @@ struct vslam_system {
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);
     vslam_status raw_args(int stride, int channels, const char* fn) const;      // a raw call's arguments against the bound rectifiers
     vslam_status fetch_keys(SysKeys& k);
+    // ---- mono + IMU session (system_mono.hip): FeatureTracker::TrackImageMonoIMU (src/FeatureTracker.cpp:1280-1495) --------------
+    bool monoMode = false, monoInitialized = false;
+    double monoFps = 0;                // zedPtr->mFps
+    int kfsUntilInitialized = 0;       // KFsUntilInitialized (bootstrap keyframes so far)
+    double predVelocity[3] = {0, 0, 0};      // FeatureTracker::predVelocity: advanced by every PredictNextPoseIMU, never synchronised with `velocity`
+    vslam_status init_mono(const vslam_system_config* c, double fps);
+    vslam_status track_mono(const uint8_t* L, int stride, int channels, bool onDevice, int frame, const vslam_imu_bucket* imu,
+                            double* T_wc_out, vslam_mono_frame_report* rep);
+    vslam_status fetch_keys_mono(SysKeys& k);
+    void update_poses(const M4& poseEst);                                        // updatePoses (:1699-1708)
+    void insert_keyframe_mono(SysKeys& keys, const M4& estimPose, int frame, bool first);      // initializeMono (:125-145) / insertKeyFrameMono (:844-869)
+    vslam_status upload_keys_block(const SysKeys& keys, void** slot);
+    void undo_keyframe_mono(int prevLatest, const M4& prevLastKFPoseInv);
+    vslam_status add_mappoints_mono(const std::vector<int>& actKeyF, std::vector<int>& matchedL, int* newPoints, int* radiusMatches);
+    int key_slots_total() const { return keySlabs.empty() ? 0 : ((int)keySlabs.size() - 1) * keySlotsPerSlab + keySlotsUsed; }
     void mp_update(SysMP& mp, int kfNumb, std::vector<int>& needDesc, int mpIndex);
     vslam_status calc_descriptors(const std::vector<int>& mps);
     void backproject(const SysKeys& k, int i, const M4& pose, double* out) const;

@@ -418,6 +418,76 @@ def imu_samples(t0, t1, fps=20.0, hz=200, T_bs=T_BC1, gravity=(0.0, 9.81, 0.0), 
     return samples, dts, g
 
 
+# ---- mono + IMU sequence (C4) -----------------------------------------------------------------------------------------------
+# The reference's mono mode only initialises and tracks on a trajectory shaped for it:
+#   * its movement gate wants >= 0.1 m AND >= 5 degrees between the camera pose and ONE bucket's IMU prediction, and
+#     predVelocity starts at zero and is only ever advanced by the buckets' velocity increments - so the camera starts at rest;
+#   * a refused call leaves the camera pose where it was, so whatever the camera really did during that bucket is missing from
+#     every later prediction: a refused bucket may hold a pure translation before the first keyframe (the map is then shifted
+#     as a whole) or no motion at all, nothing else;
+#   * its mono reprojection check projects with K * T_wc[:3] instead of the inverse (vslam_mono_new_points keeps that), which
+#     agrees with the true projection only where T_wc is its own inverse: T_wc = Rz(pi) * [Ry(yaw) | (0, y, 0)] is (an
+#     upside-down camera that yaws about, and travels along, the world's vertical axis through the origin);
+#   * tracked calls match at a radius of 1200 px, i.e. by descriptor over the whole image with a threshold of 150, the pose solve
+#     has no robust kernel and the map never grows: one map point whose keypoint is not found again yields a gross false match,
+#     and a handful of those make the solve diverge.  Tracking only holds where every map point's keypoint reappears - the
+#     camera is back at the first keyframe's pose whenever a tracked call is made, and the frames carry no sensor noise.
+# mono_arc_pose is such a trajectory through make_scene's room: swings of the yaw angle and the height between knots at which
+# the camera is at rest (cosine ease between them, so velocities are continuous), calls at knots.
+MONO_FPS = 20.0
+_KF0 = (7.0, 0.27)
+# (frame, yaw [degrees], lift [m]) knots: lift from rest | first keyframe | second | dwell | third | initialisation | swings that
+# return to the first keyframe's pose for every tracked call but the last
+MONO_KNOTS = ((0, 0.0, 0.0), (12, 0.0, 0.13), (22,) + _KF0, (32, 0.0, 0.13), (34, 0.0, 0.13), (44, 8.5, 0.29), (54, 2.0, 0.16)) + \
+    tuple(k for j, away in enumerate(((3.0, 0.20), (10.0, 0.33), (5.0, 0.22), (9.0, 0.30), (4.0, 0.35), (11.0, 0.21), (6.0, 0.19),
+                                      (2.5, 0.31), (9.5, 0.24), (4.5, 0.28)))
+          for k in ((58 + 8 * j,) + away, (62 + 8 * j,) + _KF0)) + ((138, 4.0, 0.24), (142, 7.01, 0.2702)) + \
+    ((160, 35.0, 0.27), (178, -22.0, 0.10), (180, -22.0, 0.10))      # (after the last call: two wide views for the matching tests)
+# frames at which TrackMonoIMU is called (the bucket of a call = the IMU samples since the previous one, the first from frame 0):
+# refused (rotation only) | keyframe | keyframe | refused (no motion) | keyframe | initialisation | ten tracked calls at the first
+# keyframe's pose | one tracked call 0.01 degrees and 0.2 mm beside it: enough for a few keypoints not to reappear, so the solve loses
+# the pose, every retry round runs and the call's map points end as outliers
+MONO_CALLS = (12, 22, 32, 34, 44, 54) + tuple(62 + 8 * j for j in range(10)) + (142,)
+
+
+def mono_arc_pose(i, fps=MONO_FPS):
+    """world <- camera at frame i (fractional frames allowed) of the mono + IMU sequence described above"""
+    f = min(max(i * MONO_FPS / fps, 0.0), float(MONO_KNOTS[-1][0]))
+    k = 0
+    while k + 2 < len(MONO_KNOTS) and f >= MONO_KNOTS[k + 1][0]:
+        k += 1
+    (f0, y0, l0), (f1, y1, l1) = MONO_KNOTS[k], MONO_KNOTS[k + 1]
+    e = 0.5 * (1.0 - np.cos(np.pi * (f - f0) / (f1 - f0)))
+    yaw, lift = np.radians(y0 + (y1 - y0) * e), l0 + (l1 - l0) * e
+    c, sn = np.cos(yaw), np.sin(yaw)
+    Ry = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]])
+    T = np.eye(4)
+    T[:3, :3] = np.diag([-1.0, -1.0, 1.0]) @ Ry
+    T[:3, 3] = [0.0, 0.4 - lift, 0.0]
+    return T
+
+
+_MONO_CACHE = {}
+
+
+def mono_frame(i, rig_name="euroc", scene_seed=7, tex_seed=0xC0FFEE, noise=False):
+    """left u8 image of frame i of the mono sequence (no sensor noise: see above) plus the ground-truth pose"""
+    key = (i, rig_name, scene_seed, tex_seed, noise)
+    if key not in _MONO_CACHE:
+        T = mono_arc_pose(i, MONO_FPS)
+        img, _ = render(make_scene(scene_seed), texture(tex_seed), RIGS[rig_name], T, noise_seed=(5000 + i) if noise else None)
+        _MONO_CACHE[key] = (img, T)
+    img, T = _MONO_CACHE[key]
+    return img.copy(), T.copy()
+
+
+def mono_bucket(k):
+    """IMU bucket of call k of MONO_CALLS: (samples [n,6] acc | gyro, dts [n], timestamps_ns [n])"""
+    f0 = MONO_CALLS[k - 1] if k else 0
+    S, dts, _ = imu_samples(f0, MONO_CALLS[k], fps=MONO_FPS, pose_fn=mono_arc_pose)
+    return S, dts, np.arange(len(dts)) * 5e6
+
+
 def make_mono_points_problem(rig_name="euroc", n_kf=4, n_points=400, seed=0x4D4F, trans_sigma=0.01, rot_sigma=0.002,
                              pix_noise=0.3, outlier_frac=0.1):
     """Input of FeatureTracker::addMappointsMono after its matchByRadius passes: n_kf keyframes a few centimetres apart

@@ -1065,6 +1065,118 @@ class System:
     def save_trajectory(self, path, path_positions=None):
         _chk(self.L.vslam_system_save_trajectory(self.h_sys, path.encode(), path_positions.encode() if path_positions else None))
 
+    def map_points(self):
+        n = C.c_int32(self.counts()["map_points"])
+        xyz = np.zeros((max(n.value, 1), 3)); ol = np.zeros(max(n.value, 1), np.uint8)
+        _chk(self.L.vslam_system_map_points(self.h_sys, max(n.value, 1), C.byref(n), _p(xyz), _p(ol)))
+        return xyz[:n.value].copy(), ol[:n.value].copy()
+
+
+class MonoFrameReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("frame", "state", "keyframe_inserted", "n_active", "n_inliers", "rounds", "lm_iterations")] + \
+               [("last_radius", C.c_float)] + \
+               [(n, C.c_int32) for n in ("new_points", "radius_matches", "n_keyframes", "n_map_points", "n_active_after")]
+
+
+MONO_REFUSED, MONO_BOOTSTRAP, MONO_INITIALISED, MONO_TRACKED = 0, 1, 2, 3
+
+
+class MonoSystem(System):
+    """vslam_system in mono + IMU mode (VSlamSystem::TrackMonoIMU): a batch-1 extractor, a mono matcher, no local mapper.
+    imu: dict(gravity, noise=(gyro density, gyro walk, acc density, acc walk), T_bs, hz[, velocity]); fps = the camera's rate."""
+
+    def __init__(self, rig, nfeatures, fps, T0=None, imu=None, device=0, nlevels=8, scale=1.2, local_mapping=0, window=10):
+        self.L = lib()
+        cfg = SystemConfig()
+        cfg.fe = FeParams(nfeatures, nlevels, scale, 19, 31, 20, 7)
+        cfg.rig = make_rig(rig)
+        cfg.device = device; cfg.local_mapping = local_mapping; cfg.window = window
+        if T0 is not None:
+            cfg.T_wc_init = (C.c_double * 16)(*np.asarray(T0, np.float64).reshape(16))
+        if imu is not None:
+            cfg.use_imu = 1
+            cfg.gravity = (C.c_double * 3)(*imu["gravity"])
+            cfg.gyro_noise_density, cfg.gyro_random_walk, cfg.accel_noise_density, cfg.accel_random_walk = imu["noise"]
+            cfg.T_body_sensor = (C.c_double * 16)(*np.asarray(imu["T_bs"], np.float64).reshape(16))
+            cfg.imu_hz = int(imu["hz"])
+            if "velocity" in imu:
+                cfg.velocity_init = (C.c_double * 3)(*imu["velocity"])
+        self.w, self.h = rig["w"], rig["h"]
+        self.h_sys = C.c_void_p()
+        _chk(self.L.vslam_system_create_mono(C.byref(cfg), C.c_double(fps), C.byref(self.h_sys)))
+
+    def track(self, left, frame_number, imu_bucket, channels=1, on_device=False, stride=None):
+        """left: u8 array ((H, W) gray, (H, W, 3) BGR, (H, W, 4) BGRA) or a device pointer (on_device, with `channels`);
+        imu_bucket: (acc (n,3), gyro (n,3), timestamps_ns (n)) since the previous call, or None (an error)."""
+        T = np.zeros((4, 4))
+        rep = MonoFrameReport()
+        b = None
+        keep = []
+        if imu_bucket is not None:
+            acc, gyr, ts = (np.ascontiguousarray(a, np.float64) for a in imu_bucket)
+            keep = [acc, gyr, ts]
+            b = ImuBucket(len(ts), _p(acc), _p(gyr), _p(ts))
+        if on_device:
+            lp, st, ch = C.c_void_p(left), stride or self.w * channels, channels
+        else:
+            left, ch, st = _image(left, self.h, self.w)
+            keep.append(left)
+            lp = _p(left)
+        _chk(self.L.vslam_system_track_mono_imu(self.h_sys, lp, int(st), int(ch), int(on_device), int(frame_number),
+                                                C.byref(b) if b is not None else None, _p(T), C.byref(rep)))
+        return T, {f[0]: getattr(rep, f[0]) for f in MonoFrameReport._fields_}
+
+    def memory(self):
+        n, b = C.c_int32(), C.c_int64()
+        _chk(self.L.vslam_system_memory(self.h_sys, C.byref(n), C.byref(b)))
+        return dict(key_slots_used=n.value, key_slab_bytes=b.value)
+
+
+class KeyBlock:
+    """a key set (keypoints + descriptors, no right keys) resident in a device block, as vslam_kf_keys_upload writes it"""
+
+    def __init__(self, kps, desc, device=0):
+        self.L = lib()
+        self.L.vslam_device_alloc.argtypes = [C.c_int32, C.c_size_t, C.POINTER(C.c_void_p)]
+        self.L.vslam_device_free.argtypes = [C.c_int32, C.c_void_p]
+        self.L.vslam_device_free.restype = None
+        self.device = device
+        self.n = len(kps)
+        p = C.c_void_p()
+        _chk(self.L.vslam_device_alloc(device, kf_keys_bytes(self.n, 0), C.byref(p)))
+        self.ptr = p.value
+        e = np.zeros(0, np.int32)
+        kf_keys_upload(dict(T_wc=np.eye(4), id=0, kpsL=kps, descL=np.ascontiguousarray(desc, np.uint8).reshape(-1, 32),
+                            kpsR=np.zeros(0, KP_DTYPE), descR=np.zeros((0, 32), np.uint8), rightIdxs=np.full(self.n, -1, np.int32),
+                            leftIdxs=e, unF=e, unFR=e), self.ptr, device)
+
+    def free(self):
+        if self.ptr:
+            self.L.vslam_device_free(self.device, self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def match_by_radius_window(matcher, last, targets, rad, matchedL):
+    """matchByRadius from the KeyBlock `last` into the KeyBlocks `targets` in order on one claim table (addMappointsMono);
+    returns (n_matches per target, matchedL, match_out [n_targets][n_last])."""
+    nT = len(targets)
+    ptrs = (C.c_void_p * max(nT, 1))(*[t.ptr for t in targets])
+    nt = np.array([t.n for t in targets], np.int32)
+    mL = np.array(matchedL, np.int32, copy=True)
+    out_c = np.full(max(nT * last.n, 1), -1, np.int32)
+    nm = np.zeros(max(nT, 1), np.int32)
+    matcher.L.vslam_match_by_radius_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
+                                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    _chk(matcher.L.vslam_match_by_radius_window(matcher.h, last.ptr, last.n, ptrs if nT else None, _p(nt) if nT else None, nT,
+                                                C.c_float(rad), _p(mL) if len(mL) else None, len(mL), _p(out_c), _p(nm)))
+    return nm[:nT].copy(), mL, out_c[:nT * last.n].reshape(nT, last.n).copy()
+
 
 class DeviceImage:
     """a u8 image uploaded into a device buffer of the library's allocator (vslam_device_alloc); .ptr for the *_device calls"""

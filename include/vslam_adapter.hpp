@@ -10,9 +10,13 @@
 //   * -DVSLAM_WITH_OPENCV  : adds the cv::Mat / cv::KeyPoint overloads with the reference's exact
 //                            signatures (needs OpenCV + Eigen; tests/native/adapter_color.cpp compiles this branch
 //                            against a minimal stand-in of the two headers and runs it on the GPU).
+// Mono + IMU (slamMode 2): a FeatureTracker built on a StereoCamera without a right camera, as VSlamSystem::InitializeMonocular
+// does (src/System.cpp:27-34), owns a mono session; TrackImageMonoIMU is the whole of src/FeatureTracker.cpp:1280-1495
+// (tests/native/adapter_mono_link.cpp).
 // Colour frames (cv::imread IMREAD_COLOR in the reference's loop) are converted to gray on the device: the cv::Mat
 // overloads dispatch on channels() as TrackImage does (src/FeatureTracker.cpp:1130-1144), the POD forms take `channels`.
 #pragma once
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -260,6 +264,11 @@ class Map {
         if (h_) throw std::runtime_error("Map: the session exists already");
         vs_check(vslam_system_create(&cfg, &h_), "vslam_system_create");
     }
+    // the mono + IMU session (VSlamSystem::InitializeMonocular): fps = zedPtr->mFps
+    void createMono(const vslam_system_config& cfg, double fps) {
+        if (h_) throw std::runtime_error("Map: the session exists already");
+        vs_check(vslam_system_create_mono(&cfg, fps, &h_), "vslam_system_create_mono");
+    }
     ~Map() { vslam_system_destroy(h_); }
     Map(const Map&) = delete;
     Map& operator=(const Map&) = delete;
@@ -292,7 +301,11 @@ class FeatureTracker {
             vslam_system_config cfg{};
             cfg.fe = feLeft->params();
             cfg.rig = zedPtr->rig();
-            cfg.device = device; cfg.local_mapping = localMapping; cfg.window = 10;
+            // no right camera: the monocular system (src/System.cpp:27-34: right extractor null, mFps from the camera) - no LocalMapper
+            // exists in that mode (:11-20), and TrackImageMonoIMU needs the IMU constants
+            mono = !zedPtr->mCameraRight;
+            if (mono && !zedPtr->mCameraLeft->mIMUData) throw std::runtime_error("FeatureTracker: the monocular mode is mono + IMU: the left camera needs mIMUData");
+            cfg.device = device; cfg.local_mapping = mono ? 0 : localMapping; cfg.window = 10;
             cfg.mapping_delay = mappingDelay; cfg.mapping_np_delay = mappingNpDelay;
             std::memcpy(cfg.T_wc_init, zedPtr->mCameraPose.pose, sizeof(cfg.T_wc_init));
             const Camera& cl = *zedPtr->mCameraLeft;
@@ -304,7 +317,8 @@ class FeatureTracker {
                 std::memcpy(cfg.T_body_sensor, cl.TBodyToCam, sizeof(cfg.T_body_sensor));
                 cfg.imu_hz = cl.mIMUData->mHz;
             }
-            map->create(cfg);
+            if (mono) map->createMono(cfg, (double)zedPtr->mFps);
+            else map->create(cfg);
         }
     }
     std::shared_ptr<Map> map;
@@ -312,6 +326,8 @@ class FeatureTracker {
     std::shared_ptr<FeatureExtractor> feLeft{nullptr}, feRight{nullptr};
     double lastPose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};    // zedPtr->mCameraPose->pose after the last frame
     vslam_frame_report lastReport{};
+    vslam_mono_frame_report lastMonoReport{};          // of the last TrackImageMonoIMU call
+    bool mono = false;                                 // the session is a mono + IMU one
 
     // TrackImage (include/FeatureTracker.h:90): u8 row-major rectified images; IMUDataptr as in the reference (nullptr
     // in stereo-only mode).  Extraction, stereo match, projection matching, the pose solves, the keyframe rule and
@@ -335,6 +351,32 @@ class FeatureTracker {
                                                  IMUDataptr ? &b : nullptr, lastPose, &lastReport), "vslam_system_track_stereo_color");
         if (zedPtr) std::memcpy(zedPtr->mCameraPose.pose, lastPose, sizeof(lastPose));
     }
+    // TrackImageMonoIMU (include/FeatureTracker.h:96, src/FeatureTracker.cpp:1280-1495): a u8 row-major rectified gray image and the
+    // IMU samples since the previous call.  Everything of the reference's function happens behind this call - the IMU prediction,
+    // the movement gate, the bootstrap keyframes, the initialisation, tracking, the keyframe per tracked call; what stays with the
+    // caller is image decoding and IMU bucketing.  lastMonoReport.state says what the call did (0 = refused by the gate: nothing
+    // was extracted and the pose is unchanged).
+    void TrackImageMonoIMU(const uint8_t* leftRect, int stride, const int frameNumb, std::shared_ptr<IMUData> IMUDataptr, bool onDevice = false) {
+        TrackImageMonoIMUChannels(leftRect, stride, 1, frameNumb, IMUDataptr, onDevice);
+    }
+    // the same for gray (1), BGR (3) or BGRA (4) images (the cvtColor of :1292-1303 on the device)
+    void TrackImageMonoIMUChannels(const uint8_t* leftRect, int stride, int channels, const int frameNumb, std::shared_ptr<IMUData> IMUDataptr,
+                                   bool onDevice = false) {
+        vslam_imu_bucket b{};
+        if (IMUDataptr) b = IMUDataptr->bucket();
+        vs_check(vslam_system_track_mono_imu(map->handle(), leftRect, stride, channels, onDevice ? 1 : 0, frameNumb, IMUDataptr ? &b : nullptr,
+                                             lastPose, &lastMonoReport), "vslam_system_track_mono_imu");
+        if (zedPtr) std::memcpy(zedPtr->mCameraPose.pose, lastPose, sizeof(lastPose));
+    }
+#ifdef VSLAM_WITH_OPENCV
+    // the reference signature (include/FeatureTracker.h:96): dispatched on channels() as src/FeatureTracker.cpp:1292-1303 does
+    void TrackImageMonoIMU(const cv::Mat& leftRect, const int frameNumb, std::shared_ptr<IMUData> IMUDataptr) {
+        if (leftRect.depth() != CV_8U) throw std::runtime_error("TrackImageMonoIMU: the image is not 8-bit");
+        const int cn = leftRect.channels();
+        if (cn != 1 && cn != 3 && cn != 4) throw std::runtime_error("TrackImageMonoIMU: images of 1, 3 (BGR) or 4 (BGRA) channels only");
+        TrackImageMonoIMUChannels(leftRect.ptr<uint8_t>(), (int)leftRect.step, cn, frameNumb, IMUDataptr);
+    }
+#endif
 #ifdef VSLAM_WITH_OPENCV
     // the reference signature (include/FeatureTracker.h:90): 8-bit images of 1, 3 (BGR) or 4 (BGRA) channels, dispatched on
     // channels() as src/FeatureTracker.cpp:1130-1144 does; left and right must agree in size, channels and row stride
@@ -369,7 +411,8 @@ class LocalMapper {
     std::shared_ptr<Map> map;
     std::shared_ptr<StereoCamera> zedPtr{nullptr};
     std::shared_ptr<FeatureMatcher> fm{nullptr};
-    bool stopRequested{false};      // (the reference's flag of the same name, include/OptimizationBA.h:84; set it, then join the thread)
+    std::atomic<bool> stopRequested{false};      // (the reference's flag of the same name, include/OptimizationBA.h:84 - a plain bool there;
+                                                 //  it is set on one thread and polled on another: set it, then join the thread)
     // beginLocalMapping (:87).  The session runs the optimizer's passes on its own library thread (local_mapping = 2), so this
     // has nothing to compute.  Constructed the reference's way it is the body of `std::thread(&LocalMapper::beginLocalMapping,
     // mLocalMapper)` (src/System.cpp:19): it stays alive like the reference's 20 ms polling loop until stopRequested, then waits

@@ -228,6 +228,20 @@ vslam_status vslam_match_projection_mono(vslam_matcher* m, const vslam_mappoint_
 vslam_status vslam_match_by_radius(vslam_matcher* m, const vslam_keypoint* last_kps, const uint8_t* last_desc,
                                    int32_t n_last, float rad, int32_t* matched_idxs_l, int32_t* match_out,
                                    int32_t* n_matches);
+/* matchByRadius (src/FeatureMatcher.cpp:458-526) from one key set into n_targets key sets IN ORDER, sharing one claim table:
+ * what addMappointsMono (src/FeatureTracker.cpp:1512-1519) does.  last_keys / target_keys[t]: device key blocks
+ * (vslam_kf_keys_bytes(n, 0) bytes as written by vslam_kf_keys_upload, or a session's key slot), no right keys.
+ * matched_idxs_l: in/out, n_matched entries, indexed by TARGET key index - a claim at index j made in one target blocks index j
+ * in every later target; n_matched >= every n_target[t], else VSLAM_ERR_INVALID.  match_out[t * n_last + i] = index in target t
+ * that the reference appends to keyframeIdxMatchs[i], or -1; n_matches[t] (may be NULL) = the call's return value for target t.
+ * Grid and scalePyramid are the matcher's, as for vslam_match_by_radius; the matcher's current frame is neither read nor
+ * changed.  Everything is enqueued on the matcher's stream: one launch builds all targets' cell buckets, one scans all
+ * targets' candidates, the resolve runs per target on the shared table; the call waits once, at its end.  At most 64
+ * targets. */
+vslam_status vslam_match_by_radius_window(vslam_matcher* m, const void* last_keys, int32_t n_last,
+                                          const void* const* target_keys, const int32_t* n_target, int32_t n_targets,
+                                          float rad, int32_t* matched_idxs_l, int32_t n_matched,
+                                          int32_t* match_out, int32_t* n_matches);
 
 /* ---------------------------------------------------------------------------
  * Tracker steps — replace FeatureTracker::estimatePoseGTSAM (stereo-only branch) with
@@ -775,6 +789,48 @@ vslam_status vslam_system_counts(vslam_system* sys, int32_t* n_keyframes, int32_
                                  int32_t* n_frames);
 vslam_status vslam_system_keyframes(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* frame_idx, double* poses_wc);
 vslam_status vslam_system_last_frame(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* matches, uint8_t* mps_outliers);
+/* test tap: world positions (n x 3) and outlier flags of every map point, in creation order */
+vslam_status vslam_system_map_points(vslam_system* sys, int32_t cap, int32_t* n_out, double* xyz, uint8_t* is_outlier);
+/* key slots of the session's keyframes in HBM: slots handed out so far, bytes of the slabs they are carved from */
+vslam_status vslam_system_memory(vslam_system* sys, int32_t* key_slots_used, int64_t* key_slab_bytes);
+
+/* ---------------------------------------------------------------------------
+ * Mono + IMU session (slamMode 2): VSlamSystem::TrackMonoIMU -> FeatureTracker::TrackImageMonoIMU (src/System.cpp:82-85,
+ * src/FeatureTracker.cpp:1280-1495) behind the same handle; no LocalMapper exists in this mode (src/System.cpp:11-20).
+ * Per call, as the reference: PredictNextPoseIMU first (it advances predVelocity even on a refused call); until the map is
+ * initialised the movement gate (Converter::checkSufficientMovement: translation >= 0.1f m AND rotation >= 5 degrees between
+ * the camera pose and the prediction) refuses the call before anything is extracted; the first three accepted calls insert a
+ * keyframe at the predicted pose; the fourth inserts one, matches the FIRST keyframe by radius (120) into the other three on
+ * one claim table (vslam_match_by_radius_window) and triangulates the initial map (vslam_mono_new_points); every later call
+ * is tracked (vslam_tracker_track_mono_imu's block) and inserts a keyframe - the reference's keyframe rule is always true
+ * here - whose window is empty, so the map only shrinks.
+ * The claim table of the initialisation has max(current frame's keys, largest target) entries, all -1 (the reference sizes
+ * it by the current frame and reads past its end for a larger target).
+ * HBM: only keyframes that a later device step can read take a key slot - the bootstrap keyframes and the initialising one.
+ * Keyframes inserted by tracked calls keep their host keys only: nothing on the device ever reads them.
+ * ------------------------------------------------------------------------- */
+typedef struct vslam_mono_frame_report {
+    int32_t frame;
+    int32_t state;            /* 0 refused by the movement gate, 1 bootstrap keyframe, 2 initialised by this call, 3 tracked */
+    int32_t keyframe_inserted;
+    int32_t n_active, n_inliers, rounds, lm_iterations;   /* state 3: as vslam_track_report */
+    float   last_radius;
+    int32_t new_points;       /* map points this call created */
+    int32_t radius_matches;   /* state 2: summed matchByRadius matches over the targets */
+    int32_t n_keyframes, n_map_points, n_active_after;
+} vslam_mono_frame_report;
+
+/* config->use_imu must be 1 and local_mapping 0, fps (zedPtr->mFps) > 0, else VSLAM_ERR_INVALID; rig.baseline is ignored.
+ * The session owns a batch-1 extractor and a mono matcher. */
+vslam_status vslam_system_create_mono(const vslam_system_config* config, double fps, vslam_system** out);
+/* channels 1 / 3 / 4 (gray, BGR, BGRA: the extractor's gray / colour load), stride >= width x channels.  imu: the bucket since
+ * the previous call, non-NULL with n >= 1, else VSLAM_ERR_INVALID with nothing changed.  A refused call extracts nothing and
+ * returns the unchanged camera pose (state 0).  The stereo entry points on a mono session and this one on a stereo session
+ * return VSLAM_ERR_INVALID with nothing changed.  vslam_system_counts / _keyframes / _last_frame / _save_trajectory work as
+ * for a stereo session; n_frames counts accepted calls only. */
+vslam_status vslam_system_track_mono_imu(vslam_system* sys, const uint8_t* left, int32_t stride, int32_t channels,
+                                         int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
+                                         double* T_wc_out, vslam_mono_frame_report* report);
 
 /* per-kernel-group HIP-event timing of a session: extraction and tracking groups of the LAST frame, local-BA groups summed
  * over the ba_calls local BAs that completed since the previous read */
