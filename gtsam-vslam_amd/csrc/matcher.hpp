@@ -120,6 +120,27 @@ struct vslam_matcher {
     vslam_status imu_predict(const vslam_imu_input* imu, const double* predVelocity, double lastDt, double* T_wc_out, double* vel_out);
     vslam_status estimate_pose(vslam_pose_problem* prob, int* nIn, int* nStereo, vslam_lm_report* rep);
 
+    // relocalisation (reloc.hip): global descriptor match of a map against the current frame, pose hypotheses, refinement
+    int rlCap = 0;                   // map-point capacity of d_rlPts / d_rlDesc / d_rlD / d_rlPairs
+    double* d_rlPts = nullptr;       // [N][3]
+    uint8_t* d_rlDesc = nullptr;     // [N][32]
+    int* d_rlD = nullptr;            // [N][3]: d1, i1, d2
+    int* d_rlPairs = nullptr;        // [N]: key index of the point's correspondence or -1
+    unsigned long long* d_rlKeyWin = nullptr;   // [RELOC_MAX_KEYS]: (d1 << 32 | point) of the key's best proposer
+    int* d_rlKeyWinner = nullptr;    // [RELOC_MAX_KEYS]: that point or -1
+    void* d_rlRec = nullptr;         // [RELOC_MAX_KEYS] correspondence records
+    uint8_t* d_rlFlags = nullptr;    // [RELOC_MAX_KEYS] the winner's inlier flags
+    int* d_rlCounts = nullptr;       // [RELOC_MAX_HYP]
+    double* d_rlPoses = nullptr;     // [RELOC_MAX_HYP][12]: R row-major, t
+    double* d_rlOut = nullptr;       // T_cw[16] of the winner, then ints {C, best hypothesis, best count}
+    int rlLast[4] = {0, 0, 0, 0};    // sizes of the last call: points, keys, hypotheses, correspondences
+    std::vector<uint8_t> rlHost;     // download block of the last call
+    vslam_status ensure_reloc_cap(int n);
+    vslam_status relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
+                            int32_t* pairsOut, vslam_reloc_report* rep);
+    vslam_status relocalize_debug(int32_t* d3, int capPoints, int32_t* keyWinner, int capKeys, int32_t* counts, int capHyp,
+                                  uint8_t* flags, int capPairs, int32_t* sizes4);
+
     // tracker state (FeatureTracker's activeMapPoints, flattened and device-resident)
     int trCap = 0, trN = 0;
     double* d_trXyz = nullptr;       // [N][3]

@@ -183,12 +183,19 @@ __device__ __forceinline__ void block_reduce(double (&v)[NV], double* red, doubl
     __syncthreads();
 }
 
-__device__ __forceinline__ bool check2d(const double* pc, float ox, float oy, const PoseArgs& A, double weight) {
-    if (pc[2] <= 0) return true;
+// pixel residual (observed - projected) of a camera-frame point with pc[2] > 0: the residual of the chi2 tests below and of
+// the relocalisation score (reloc.hip)
+__device__ __forceinline__ void reproj_residual(const double* pc, float ox, float oy, const PoseArgs& A, double& eu, double& ev) {
     const double invZ = 1.0 / pc[2];
     const double u = A.fx * pc[0] * invZ + A.cx;
     const double v = A.fy * pc[1] * invZ + A.cy;
-    const double eu = (double)ox - u, ev = (double)oy - v;
+    eu = (double)ox - u; ev = (double)oy - v;
+}
+
+__device__ __forceinline__ bool check2d(const double* pc, float ox, float oy, const PoseArgs& A, double weight) {
+    if (pc[2] <= 0) return true;
+    double eu, ev;
+    reproj_residual(pc, ox, oy, A, eu, ev);
     return (eu * eu + ev * ev) * weight > A.thres;
 }
 

@@ -1,0 +1,376 @@
+// Relocalisation on gfx950: recover the pose of the matcher's current stereo frame from a map WITHOUT a pose prior.
+// This stage has no counterpart in the reference; its definition is the one in include/vslam_hip.h,
+// restated on the CPU by tests/reloc_ref.py.
+//   k_reloc_match   brute-force 256-bit Hamming search of every map point against every left key: one lane owns one map
+//                   point (eight descriptor dwords in registers), a workgroup stages the frame's descriptors through LDS in
+//                   tiles of 2048 (64 KB: two workgroups per CU), every lane reads the same LDS address (a broadcast);
+//                   best / second-best distance, the acceptance tests, one 64-bit atomicMin per proposal
+//   k_reloc_pairs   one workgroup: winning pairs whose key has stereo depth, compacted in ascending key index
+//   k_reloc_ransac  one wave per hypothesis: three sampled correspondences -> rigid pose (fp64), scored over all records
+//   k_reloc_best    one wave: the winning hypothesis and its inlier flags
+// The winner's inliers are refined by the existing motion-only LM (vslam_matcher::estimate_pose).
+#include "pose_dev.hpp"
+#include "track_dev.hpp"
+
+namespace vslam {
+
+constexpr int RELOC_TILE = 2048;              // left keys staged per LDS tile (32 B each)
+constexpr int RELOC_MAX_POINTS = 65536;
+constexpr int RELOC_MAX_KEYS = 7680;          // the matcher's left-key limit (stereo staging)
+constexpr int RELOC_MAX_HYP = 1024;
+constexpr int RELOC_DRAWS = 16;               // sample indices tried per hypothesis
+
+struct RelocRec {            // one correspondence: map point p <-> left key i
+    double Xw[3], Xc[3];     // world position of p; key i back-projected with its depth (camera frame)
+    float kx, ky, kxr;       // left keypoint, x of the matched right keypoint
+    int octave, p, i;
+};
+static_assert(sizeof(RelocRec) == 72, "records are downloaded as plain bytes");
+
+__device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+__global__ __launch_bounds__(256) void k_reloc_match(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
+                                                     int maxHamming, int ratioPct, int* __restrict__ dOut,
+                                                     unsigned long long* __restrict__ keyWin) {
+    __shared__ uint4 tile[RELOC_TILE * 2];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
+    if (p < nP) { a0 = descP[2 * (size_t)p]; a1 = descP[2 * (size_t)p + 1]; }
+    int d1 = 257, d2 = 257, i1 = -1;
+    for (int base = 0; base < nL; base += RELOC_TILE) {
+        const int cnt = min(RELOC_TILE, nL - base);
+        __syncthreads();                          // the previous tile has been consumed
+        for (int q = threadIdx.x; q < 2 * cnt; q += 256) tile[q] = descL[2 * (size_t)base + q];
+        __syncthreads();
+        // ascending key index: the first key attaining d1 keeps it, a tie goes to d2.  Eight keys per trip: sixteen 16-byte LDS
+        // reads are in flight before the first is consumed (a workgroup has one wave per SIMD, nothing else hides their latency)
+#pragma unroll 8
+        for (int k = 0; k < cnt; k++) {
+            const int d = hamming256(a0, a1, tile[2 * k], tile[2 * k + 1]);
+            if (d < d1) { d2 = d1; d1 = d; i1 = base + k; }
+            else if (d < d2) d2 = d;
+        }
+    }
+    if (p >= nP) return;
+    dOut[3 * (size_t)p] = d1; dOut[3 * (size_t)p + 1] = i1; dOut[3 * (size_t)p + 2] = d2;
+    if (i1 >= 0 && d1 <= maxHamming && 100 * d1 < ratioPct * d2)
+        atomicMin(&keyWin[i1], ((unsigned long long)d1 << 32) | (unsigned)p);
+}
+
+__global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned long long* __restrict__ keyWin,
+                                                      const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
+                                                      const float* __restrict__ depth, const int* __restrict__ rightIdxs,
+                                                      const double* __restrict__ pts, double fx, double fy, double cx, double cy,
+                                                      RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
+                                                      int* __restrict__ out) {
+    __shared__ int wsum[16];
+    int run = 0;
+    for (int base = 0; base < nL; base += 1024) {
+        const int i = base + threadIdx.x;
+        int p = -1, ri = -1;
+        float z = 0.f;
+        if (i < nL) {
+            const unsigned long long w = keyWin[i];
+            if (w != ~0ull) p = (int)(unsigned)(w & 0xFFFFFFFFull);
+            keyWinner[i] = p;
+            z = depth[i]; ri = rightIdxs[i];
+        }
+        const bool keep = p >= 0 && z > 0 && ri >= 0;       // a winner on a key without depth is dropped; the key stays lost to the loser
+        int tot;
+        const int pos = run + block_excl_scan_1024(keep, wsum, tot);
+        if (keep) {
+            const vslam_keypoint k = kpsL[i];
+            RelocRec r;
+            r.Xw[0] = pts[3 * (size_t)p]; r.Xw[1] = pts[3 * (size_t)p + 1]; r.Xw[2] = pts[3 * (size_t)p + 2];
+            const double zp = (double)z;                    // back-projection exactly as k_init_map
+            r.Xc[0] = ((double)k.x - cx) * zp / fx;
+            r.Xc[1] = ((double)k.y - cy) * zp / fy;
+            r.Xc[2] = zp;
+            r.kx = k.x; r.ky = k.y; r.kxr = kpsR[ri].x;
+            r.octave = k.octave; r.p = p; r.i = i;
+            rec[pos] = r;
+            pairs[p] = i;
+        }
+        run += tot;
+    }
+    if (threadIdx.x == 0) out[0] = run;
+}
+
+__device__ __forceinline__ unsigned reloc_mix(unsigned s, unsigned h, unsigned j) {
+    unsigned x = s ^ (h * 0x9E3779B9u) ^ (j * 0x85EBCA6Bu);
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+
+// right-handed orthonormal frame of a point triple: e1 along P1 - P0, e3 along e1 x (P2 - P0), e2 = e3 x e1
+__device__ __forceinline__ bool reloc_frame(const double* P0, const double* P1, const double* P2, double* e1, double* e2, double* e3) {
+    const double a[3] = {P1[0] - P0[0], P1[1] - P0[1], P1[2] - P0[2]};
+    const double na2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+    if (na2 < 1e-12) return false;
+    const double na = sqrt(na2);
+    e1[0] = a[0] / na; e1[1] = a[1] / na; e1[2] = a[2] / na;
+    const double c[3] = {P2[0] - P0[0], P2[1] - P0[1], P2[2] - P0[2]};
+    const double n[3] = {e1[1] * c[2] - e1[2] * c[1], e1[2] * c[0] - e1[0] * c[2], e1[0] * c[1] - e1[1] * c[0]};
+    const double nn2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    if (nn2 < 1e-12) return false;
+    const double nn = sqrt(nn2);
+    e3[0] = n[0] / nn; e3[1] = n[1] / nn; e3[2] = n[2] / nn;
+    e2[0] = e3[1] * e1[2] - e3[2] * e1[1]; e2[1] = e3[2] * e1[0] - e3[0] * e1[2]; e2[2] = e3[0] * e1[1] - e3[1] * e1[0];
+    return true;
+}
+
+// hypothesis h: camera <- world pose from three sampled correspondences; false = void
+__device__ __forceinline__ bool reloc_hypothesis(const RelocRec* __restrict__ rec, int C, unsigned seed, int h, DPose& T) {
+    if (C < 3) return false;
+    int idx[3] = {-1, -1, -1};
+    int got = 0;
+#pragma unroll
+    for (int j = 0; j < RELOC_DRAWS; j++) {
+        const int v = (int)(((unsigned long long)reloc_mix(seed, (unsigned)h, (unsigned)j) * (unsigned long long)C) >> 32);
+        const bool fresh = got < 3 && v != idx[0] && v != idx[1];
+        if (fresh) {                              // (written without a dynamic index: idx stays in registers)
+            if (got == 0) idx[0] = v; else if (got == 1) idx[1] = v; else idx[2] = v;
+            got++;
+        }
+    }
+    if (got < 3) return false;
+    const RelocRec &r0 = rec[idx[0]], &r1 = rec[idx[1]], &r2 = rec[idx[2]];
+    double e1[3], e2[3], e3[3], f1[3], f2[3], f3[3];
+    if (!reloc_frame(r0.Xw, r1.Xw, r2.Xw, e1, e2, e3)) return false;
+    if (!reloc_frame(r0.Xc, r1.Xc, r2.Xc, f1, f2, f3)) return false;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) T.R[3 * r + c] = f1[r] * e1[c] + f2[r] * e2[c] + f3[r] * e3[c];
+    double ra[3];
+    mat3_vec(T.R, r0.Xw, ra);
+#pragma unroll
+    for (int r = 0; r < 3; r++) T.t[r] = r0.Xc[r] - ra[r];
+    return true;
+}
+
+// stereo chi2 test of one correspondence under T (camera <- world): left u, left v, right u
+__device__ __forceinline__ bool reloc_inlier(const RelocRec& r, const DPose& T, const PoseArgs& A, const float* lvl) {
+    double pc[3];
+    mat3_vec(T.R, r.Xw, pc);
+#pragma unroll
+    for (int k = 0; k < 3; k++) pc[k] += T.t[k];
+    if (!(pc[2] > 0)) return false;
+    const double pr[3] = {pc[0] - A.b, pc[1], pc[2]};
+    double eu, ev, eur, evr;
+    reproj_residual(pc, r.kx, r.ky, A, eu, ev);
+    reproj_residual(pr, r.kxr, r.ky, A, eur, evr);
+    return !((eu * eu + ev * ev + eur * eur) * (double)lvl[r.octave] > A.thres);
+}
+
+__global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
+                                                     unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
+    __shared__ float sLvl[MAX_LEVELS];
+    pose_stage_levels(A, sLvl);
+    const int h = blockIdx.x, lane = threadIdx.x;
+    const int C = *nRec;
+    DPose T;
+    int count = 0;
+    const bool valid = reloc_hypothesis(rec, C, seed, h, T);      // (the same value in every lane)
+    if (valid) {
+        for (int base = 0; base < C; base += 64) {
+            const int c = base + lane;
+            const bool in = c < C && reloc_inlier(rec[c], T, A, sLvl);
+            count += __popcll(__ballot(in));
+        }
+    }
+    if (lane == 0) {
+        counts[h] = count;
+        double* o = poses + 12 * (size_t)h;
+        for (int k = 0; k < 9; k++) o[k] = valid ? T.R[k] : 0.0;
+        for (int k = 0; k < 3; k++) o[9 + k] = valid ? T.t[k] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
+                                                   const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
+    __shared__ float sLvl[MAX_LEVELS];
+    pose_stage_levels(A, sLvl);
+    const int lane = threadIdx.x;
+    int* outI = (int*)(out + 16);
+    const int C = outI[0];
+    unsigned long long best = 0;                  // (count << 32 | 0xFFFFFFFF - h): the lowest h wins a tie
+    for (int h = lane; h < nHyp; h += 64) {
+        const unsigned long long v = ((unsigned long long)(unsigned)counts[h] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h);
+        best = v > best ? v : best;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(best, d);
+        best = o > best ? o : best;
+    }
+    const int bh = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+    const int bc = (int)(best >> 32);
+    DPose T;
+    const double* o = poses + 12 * (size_t)bh;
+#pragma unroll
+    for (int k = 0; k < 9; k++) T.R[k] = o[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) T.t[k] = o[9 + k];
+    for (int c = lane; c < C; c += 64) flags[c] = bc > 0 && reloc_inlier(rec[c], T, A, sLvl) ? 1 : 0;
+    if (lane == 0) {
+        pose_to_rm16(T, out);
+        outI[1] = bh; outI[2] = bc;
+    }
+}
+
+}  // namespace vslam
+
+using namespace vslam;
+
+vslam_status vslam_matcher::ensure_reloc_cap(int n) {
+    if (!d_rlKeyWin) {
+        VS_HIP(poison_malloc(&d_rlKeyWin, (size_t)RELOC_MAX_KEYS * sizeof(unsigned long long)));
+        VS_HIP(poison_malloc(&d_rlKeyWinner, (size_t)RELOC_MAX_KEYS * sizeof(int)));
+        VS_HIP(poison_malloc(&d_rlRec, (size_t)RELOC_MAX_KEYS * sizeof(RelocRec)));
+        VS_HIP(poison_malloc(&d_rlFlags, (size_t)RELOC_MAX_KEYS));
+        VS_HIP(poison_malloc(&d_rlCounts, (size_t)RELOC_MAX_HYP * sizeof(int)));
+        VS_HIP(poison_malloc(&d_rlPoses, (size_t)RELOC_MAX_HYP * 12 * sizeof(double)));
+        VS_HIP(poison_malloc(&d_rlOut, 20 * sizeof(double)));
+    }
+    if (n <= rlCap) return VSLAM_OK;
+    hipFree(d_rlPts); hipFree(d_rlDesc); hipFree(d_rlD); hipFree(d_rlPairs);
+    d_rlPts = nullptr; d_rlDesc = nullptr; d_rlD = nullptr; d_rlPairs = nullptr; rlCap = 0;
+    const int cap2 = vslam::align_up(std::max(n, 1), 1024);
+    VS_HIP(poison_malloc(&d_rlPts, (size_t)cap2 * 3 * sizeof(double)));
+    VS_HIP(poison_malloc(&d_rlDesc, (size_t)cap2 * 32));
+    VS_HIP(poison_malloc(&d_rlD, (size_t)cap2 * 3 * sizeof(int)));
+    VS_HIP(poison_malloc(&d_rlPairs, (size_t)cap2 * sizeof(int)));
+    rlCap = cap2;
+    return VSLAM_OK;
+}
+
+vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
+                                       int32_t* pairsOut, vslam_reloc_report* rep) {
+    if (n < 0 || (n > 0 && (!xyz || !desc)) || !T_cw_out || !rep) { set_error("relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
+    if (mono) { set_error("relocalize on a mono matcher"); return VSLAM_ERR_INVALID; }
+    vslam_reloc_params P = prm ? *prm : vslam_reloc_params{};
+    if (!P.max_hamming) P.max_hamming = 50;                 // a zero field takes its default
+    if (!P.ratio_pct) P.ratio_pct = 80;
+    if (!P.n_hypotheses) P.n_hypotheses = 256;
+    if (!P.seed) P.seed = 0x52454C4Fu;
+    if (!P.min_inliers) P.min_inliers = 50;
+    if (P.max_hamming < 0 || P.max_hamming > 256 || P.ratio_pct < 0 || P.ratio_pct > 100 || P.n_hypotheses < 1 || P.n_hypotheses > RELOC_MAX_HYP ||
+        P.min_inliers < 0) {
+        set_error("relocalize: parameters out of range (max_hamming 0..256, ratio_pct 0..100, n_hypotheses 1..%d, min_inliers >= 0)", RELOC_MAX_HYP);
+        return VSLAM_ERR_INVALID;
+    }
+    if (!stereoDone) { set_error("relocalize needs a completed stereo match"); return VSLAM_ERR_INVALID; }
+    if (n > RELOC_MAX_POINTS) { set_error("relocalize: %d map points exceed the limit (%d)", n, RELOC_MAX_POINTS); return VSLAM_ERR_CAPACITY; }
+    VS_HIP(hipSetDevice(device));
+    const int H = P.n_hypotheses;
+    int nL = 0;
+    {
+        UseMark mark{this};
+        VS_CHECK(refresh_keys());
+        nL = nKeys[0];
+        if (nL > RELOC_MAX_KEYS) { set_error("relocalize: %d left keypoints exceed the limit (%d)", nL, RELOC_MAX_KEYS); return VSLAM_ERR_CAPACITY; }
+        VS_CHECK(ensure_reloc_cap(n));
+        *rep = vslam_reloc_report{};
+        rep->n_points = n;
+        rlLast[0] = n; rlLast[1] = nL; rlLast[2] = H; rlLast[3] = 0;
+        if (n) {
+            VS_HIP(hipMemcpyAsync(d_rlPts, xyz, (size_t)n * 24, hipMemcpyHostToDevice, stream));
+            VS_HIP(hipMemcpyAsync(d_rlDesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, stream));
+            VS_HIP(hipMemsetAsync(d_rlPairs, 0xFF, (size_t)n * sizeof(int), stream));
+        }
+        if (nL) VS_HIP(hipMemsetAsync(d_rlKeyWin, 0xFF, (size_t)nL * sizeof(unsigned long long), stream));
+        PoseArgs A{};
+        A.fx = rig.fx; A.fy = rig.fy; A.cx = rig.cx; A.cy = rig.cy; A.b = (double)rig.baseline; A.thres = 7.815;
+        for (int l = 0; l < feL->nLevels; l++) A.invSigma[l] = feL->InvSigmaFactor[l];
+        int* outI = (int*)(d_rlOut + 16);
+        int t = timer.begin("reloc_match");
+        if (n) hipLaunchKernelGGL(k_reloc_match, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const uint4*)d_rlDesc, nL, (const uint4*)d_desc[0],
+                                  P.max_hamming, P.ratio_pct, d_rlD, d_rlKeyWin);
+        timer.end(t);
+        t = timer.begin("reloc_pairs");
+        hipLaunchKernelGGL(k_reloc_pairs, dim3(1), dim3(1024), 0, stream, nL, d_rlKeyWin, d_kps[0], d_kps[1], d_depth, d_rightIdxs, d_rlPts,
+                           rig.fx, rig.fy, rig.cx, rig.cy, (RelocRec*)d_rlRec, d_rlPairs, d_rlKeyWinner, outI);
+        timer.end(t);
+        t = timer.begin("reloc_ransac");
+        hipLaunchKernelGGL(k_reloc_ransac, dim3(H), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, outI, P.seed, d_rlCounts, d_rlPoses);
+        hipLaunchKernelGGL(k_reloc_best, dim3(1), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, H, d_rlCounts, d_rlPoses, d_rlOut, d_rlFlags);
+        timer.end(t);
+        VS_HIP(hipGetLastError());
+        // one download block: out (T_cw, ints) | records | rightIdxs | flags
+        const size_t oRec = 20 * sizeof(double), oRi = oRec + (size_t)nL * sizeof(RelocRec), oFl = oRi + (size_t)nL * sizeof(int);
+        rlHost.resize(oFl + (size_t)nL + 8);
+        VS_HIP(hipMemcpyAsync(rlHost.data(), d_rlOut, 20 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (nL) {
+            VS_HIP(hipMemcpyAsync(rlHost.data() + oRec, d_rlRec, (size_t)nL * sizeof(RelocRec), hipMemcpyDeviceToHost, stream));
+            VS_HIP(hipMemcpyAsync(rlHost.data() + oRi, d_rightIdxs, (size_t)nL * sizeof(int), hipMemcpyDeviceToHost, stream));
+            VS_HIP(hipMemcpyAsync(rlHost.data() + oFl, d_rlFlags, (size_t)nL, hipMemcpyDeviceToHost, stream));
+        }
+        if (pairsOut && n) VS_HIP(hipMemcpyAsync(pairsOut, d_rlPairs, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream));
+        VS_HIP(hipStreamSynchronize(stream));
+    }
+    const double* hT = (const double*)rlHost.data();
+    const int* hI = (const int*)(rlHost.data() + 16 * sizeof(double));
+    const RelocRec* hRec = (const RelocRec*)(rlHost.data() + 20 * sizeof(double));
+    const int* rIdx = (const int*)(hRec + nL);
+    const uint8_t* hFl = (const uint8_t*)(rIdx + nL);
+    const int C = hI[0];
+    rlLast[3] = C;
+    rep->n_pairs = C; rep->best_hypothesis = hI[1]; rep->best_count = hI[2];
+    if (C < 3 || hI[2] <= 0) return VSLAM_OK;               // success = 0
+    // ---- refinement: the winner's inliers, in correspondence order, through the motion-only LM -----------------------------------
+    std::vector<double> pts; std::vector<int> mt;
+    for (int c = 0; c < C; c++) {
+        if (!hFl[c]) continue;
+        pts.insert(pts.end(), hRec[c].Xw, hRec[c].Xw + 3);
+        mt.push_back(hRec[c].i); mt.push_back(rIdx[hRec[c].i]);
+    }
+    const int M = (int)mt.size() / 2;
+    std::vector<uint8_t> ones((size_t)M, 1), zeros((size_t)M, 0), outl((size_t)M, 0);
+    vslam_pose_problem prob{};
+    prob.n_mps = M; prob.points_xyz = pts.data(); prob.in_frame = ones.data(); prob.in_frame_r = ones.data();
+    prob.mp_is_outlier = zeros.data(); prob.matches = mt.data(); prob.mps_outliers = outl.data();
+    memcpy(prob.T_cw, hT, 16 * sizeof(double));
+    int nIn = 0, nSt = 0;
+    VS_CHECK(estimate_pose(&prob, &nIn, &nSt, &rep->lm));
+    rep->n_inliers = nIn; rep->n_stereo = nSt;
+    rep->success = nIn >= P.min_inliers ? 1 : 0;
+    if (rep->success) memcpy(T_cw_out, prob.T_cw, 16 * sizeof(double));
+    return VSLAM_OK;
+}
+
+vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t* keyWinner, int capKeys, int32_t* counts, int capHyp,
+                                             uint8_t* flags, int capPairs, int32_t* sizes4) {
+    const int n = rlLast[0], nL = rlLast[1], H = rlLast[2], C = rlLast[3];
+    if (sizes4) for (int k = 0; k < 4; k++) sizes4[k] = rlLast[k];
+    if ((d3 && capPoints < n) || (keyWinner && capKeys < nL) || (counts && capHyp < H) || (flags && capPairs < C)) {
+        set_error("relocalize_debug: capacity"); return VSLAM_ERR_CAPACITY;
+    }
+    if (!d_rlKeyWin) return VSLAM_OK;                       // no call yet: all sizes 0
+    VS_HIP(hipSetDevice(device));
+    if (d3 && n) VS_HIP(hipMemcpyAsync(d3, d_rlD, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
+    if (keyWinner && nL) VS_HIP(hipMemcpyAsync(keyWinner, d_rlKeyWinner, (size_t)nL * 4, hipMemcpyDeviceToHost, stream));
+    if (counts && H) VS_HIP(hipMemcpyAsync(counts, d_rlCounts, (size_t)H * 4, hipMemcpyDeviceToHost, stream));
+    if (flags && C) VS_HIP(hipMemcpyAsync(flags, d_rlFlags, (size_t)C, hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipStreamSynchronize(stream));
+    return VSLAM_OK;
+}
+
+extern "C" {
+
+vslam_status vslam_relocalize(vslam_matcher* m, const double* points_xyz, const uint8_t* desc, int32_t n_points,
+                              const vslam_reloc_params* params, double* T_cw_out, int32_t* pairs_out, vslam_reloc_report* report) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->relocalize(points_xyz, desc, n_points, params, T_cw_out, pairs_out, report);
+}
+
+vslam_status vslam_relocalize_debug(vslam_matcher* m, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner, int32_t cap_keys,
+                                    int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags, int32_t cap_pairs, int32_t* sizes4) {
+    if (!m) return VSLAM_ERR_INVALID;
+    return m->relocalize_debug(d1_i1_d2, cap_points, key_winner, cap_keys, hyp_counts, cap_hypotheses, inlier_flags, cap_pairs, sizes4);
+}
+
+}  // extern "C"

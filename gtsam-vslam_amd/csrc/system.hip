@@ -735,6 +735,65 @@ vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride,
     return frame_post(c, st, T_wc_out, rep);
 }
 
+// Relocalisation (no reference counterpart): the frame's front end as track() runs it, vslam_matcher::relocalize over the
+// session's non-outlier map points, then - on success only - the pose state of a frame tracked with zero predicted motion.
+vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_reloc_params* prm,
+                                      double* T_wc_out, vslam_reloc_report* rep) {
+    if (!L || !R || !T_wc_out || !rep) return VSLAM_ERR_INVALID;
+    if (monoMode) { set_error("vslam_system_relocalize: a mono session cannot relocalise (stereo depth is needed)"); return VSLAM_ERR_INVALID; }
+    if (cfg.use_imu) {
+        set_error("vslam_system_relocalize: an IMU session cannot relocalise yet (its velocity would need re-initialising)");
+        return VSLAM_ERR_INVALID;
+    }
+    if (keyFrames.empty()) { set_error("vslam_system_relocalize: the session has no map (track frame 0 first)"); return VSLAM_ERR_INVALID; }
+    SysFrameCtx& c = ctx;
+    VS_CHECK(frame_begin(c, frame, nullptr));
+    VS_CHECK(frame_mid());
+    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
+    else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
+    VS_CHECK(vslam_extractor_run(fe));
+    VS_CHECK(fm->stereo_match());
+    // every map point that is not an outlier, in creation order; the most recent 65536 if there are more
+    std::vector<int> ids;
+    std::vector<double> xyz; std::vector<uint8_t> desc; std::vector<float> msd;
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        for (int m = 0; m < (int)mapPoints.size(); m++) if (!mpOutlier[m]) ids.push_back(m);
+        if (ids.size() > 65536) ids.erase(ids.begin(), ids.end() - 65536);
+        const size_t n = ids.size();
+        xyz.resize(3 * n); desc.resize(32 * n); msd.resize(n);
+        for (size_t j = 0; j < n; j++) {
+            const SysMP& mp = mapPoints[ids[j]];
+            xyz[3 * j] = mp.wp[0]; xyz[3 * j + 1] = mp.wp[1]; xyz[3 * j + 2] = mp.wp[2];
+            memcpy(desc.data() + 32 * j, mp.desc, 32);
+            msd[j] = mp.maxScaleDist;
+        }
+    }
+    double T_cw[16];
+    VS_CHECK(fm->relocalize(xyz.data(), desc.data(), (int)ids.size(), prm, T_cw, nullptr, rep));
+    if (!rep->success) { memcpy(T_wc_out, camPose.data(), sizeof(double) * 16); return VSLAM_OK; }
+    // the map points the new pose places inside the left image
+    const size_t n = ids.size();
+    std::vector<float> pl(2 * n), pr(2 * n); std::vector<int> ll(n), lr(n); std::vector<uint8_t> inF(n), inFR(n);
+    VS_CHECK(vslam_world_to_frame(fm, T_cw, (int)n, xyz.data(), msd.data(), (float)std::log((double)cfg.fe.scale), pl.data(), pr.data(),
+                                  ll.data(), lr.data(), inF.data(), inFR.data()));
+    const M4 poseEst = m4_rigid_inv(m4_from(T_cw));
+    std::lock_guard<std::mutex> lk(mapMutex);
+    allFrames.push_back({false, -1, latestKF, m4_mul(keyFrames[latestKF].poseInv, poseEst)});      // addFrame
+    camRefPose = m4_mul(lastKFPoseInv, poseEst);
+    camPose = poseEst; camPoseInv = m4_affine_inv(poseEst);
+    predNPoseRef = m4_identity();
+    predNPose = poseEst; predNPoseInv = camPoseInv;
+    active.clear();
+    for (size_t j = 0; j < n; j++) {
+        mpInFrame[ids[j]] = inF[j];
+        if (inF[j]) active.push_back(ids[j]);
+    }
+    lastMatches.clear(); lastOutliers.clear();
+    memcpy(T_wc_out, camPose.data(), sizeof(double) * 16);
+    return VSLAM_OK;
+}
+
 // ---- the local-mapping pass on its schedule ---------------------------------------------------------------------------------
 // local_mapping = 1: the whole pass inside frame_post of the frame that inserted the keyframe.
 // local_mapping = 2, mapping_delay = k:   frame_post(f)       window, np_collect, NEW_POINTS job submitted
@@ -1251,6 +1310,12 @@ vslam_status vslam_system_track_stereo_raw(vslam_system* s, const uint8_t* left,
                                            vslam_frame_report* report) {
     if (!s) return VSLAM_ERR_INVALID;
     return s->track(left, right, stride, channels, on_device != 0, frame_number, imu, T_wc_out, report, true);
+}
+
+vslam_status vslam_system_relocalize(vslam_system* s, const uint8_t* left, const uint8_t* right, int32_t stride, int32_t on_device,
+                                     int32_t frame_number, const vslam_reloc_params* params, double* T_wc_out, vslam_reloc_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->relocalize(left, right, stride, on_device != 0, frame_number, params, T_wc_out, report);
 }
 
 vslam_status vslam_system_wait_mapping(vslam_system* s) {

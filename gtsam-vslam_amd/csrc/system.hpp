@@ -263,6 +263,9 @@ struct vslam_system {
     // raw: L / R are unrectified frames (stride / channels describe them), rectified through rectL / rectR on the way into level 0
     vslam_status track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame, const vslam_imu_bucket* imu,
                        double* T_wc_out, vslam_frame_report* rep, bool raw = false);
+    // relocalisation from the session's own map, without a pose prior (no reference counterpart; vslam_hip.h)
+    vslam_status relocalize(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_reloc_params* prm,
+                            double* T_wc_out, vslam_reloc_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

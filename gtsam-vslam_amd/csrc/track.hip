@@ -11,20 +11,6 @@
 
 namespace vslam {
 
-// order-preserving compaction helper: exclusive scan of a 0/1 flag over one 1024-thread workgroup
-__device__ __forceinline__ int block_excl_scan_1024(int flag, int* wsum, int& total) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long bal = __ballot(flag);
-    const int lanePrefix = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int k = 0; k < 16; k++) { const int v = wsum[k]; if (k < wave) off += v; tot += v; }
-    __syncthreads();
-    total = tot;
-    return off + lanePrefix;
-}
-
 // initializeMap: one map point per left keypoint with estimatedDepth > 0, in keypoint order
 __global__ __launch_bounds__(1024) void k_init_map(int nL, const vslam_keypoint* __restrict__ kps,
                                                    const uint8_t* __restrict__ desc,

@@ -256,11 +256,59 @@ class Matcher:
         _chk(self.L.vslam_matcher_bind_extractors(self.h, feL.h, iL, feR.h, iR))
         self.fe = (feL, feR)      # keep them alive
 
+    def relocalize(self, points, desc, pairs=True, **params):
+        """vslam_relocalize on the matcher's current frame: (T_cw or None, report dict, pairs or None).  params: the
+        fields of RelocParams (max_hamming, ratio_pct, n_hypotheses, seed, min_inliers; 0 / absent = default)."""
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(desc) == len(points)
+        n = len(points)
+        prm = RelocParams(**{k: int(v) for k, v in params.items()})
+        T = np.zeros((4, 4))
+        rep = RelocReport()
+        po = np.full(max(n, 1), -1, np.int32) if pairs else None
+        _chk(self.L.vslam_relocalize(self.h, _p(points), _p(desc), n, C.byref(prm), _p(T), _p(po) if pairs else None, C.byref(rep)))
+        d = _reloc_report_dict(rep)
+        return (T if d["success"] else None), d, (po[:n] if pairs else None)
+
+    def relocalize_debug(self):
+        """(d1, i1, d2) per map point, winning map point per left key, count per hypothesis and the winner's inlier flag
+        per correspondence of the last relocalize call (test tap)"""
+        sz = np.zeros(4, np.int32)
+        _chk(self.L.vslam_relocalize_debug(self.h, None, 0, None, 0, None, 0, None, 0, _p(sz)))
+        n, nL, H, Cn = (int(v) for v in sz)
+        d3 = np.zeros((max(n, 1), 3), np.int32); kw = np.zeros(max(nL, 1), np.int32)
+        hc = np.zeros(max(H, 1), np.int32); fl = np.zeros(max(Cn, 1), np.uint8)
+        _chk(self.L.vslam_relocalize_debug(self.h, _p(d3), n, _p(kw), nL, _p(hc), H, _p(fl), Cn, _p(sz)))
+        return dict(d=d3[:n], key_winner=kw[:nL], counts=hc[:H], flags=fl[:Cn])
+
 
 MPV_DTYPE = np.dtype([("desc", "u1", 32), ("predLx", "<f4"), ("predLy", "<f4"), ("predRx", "<f4"),
                       ("predRy", "<f4"), ("scaleLevelL", "<i4"), ("scaleLevelR", "<i4"),
                       ("inFrame", "u1"), ("inFrameR", "u1"), ("_pad", "u1", 2)])
 assert MPV_DTYPE.itemsize == 60
+
+
+class LmReport(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("inner_iterations", C.c_int32), ("initial_error", C.c_double),
+                ("final_error", C.c_double), ("lam", C.c_double)]
+
+
+class RelocParams(C.Structure):
+    _fields_ = [("max_hamming", C.c_int32), ("ratio_pct", C.c_int32), ("n_hypotheses", C.c_int32), ("seed", C.c_uint32),
+                ("min_inliers", C.c_int32)]
+
+
+class RelocReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("success", "n_points", "n_pairs", "best_hypothesis", "best_count", "n_inliers", "n_stereo")] + \
+               [("lm", LmReport)]
+
+
+def _reloc_report_dict(rep):
+    d = {f[0]: getattr(rep, f[0]) for f in RelocReport._fields_ if f[0] != "lm"}
+    d["lm"] = dict(iterations=rep.lm.iterations, inner=rep.lm.inner_iterations, initialError=rep.lm.initial_error,
+                   finalError=rep.lm.final_error, lam=rep.lm.lam)
+    return d
 
 
 def match_projection(matcher, mps, rad, matchedL, matchedR, matches):
@@ -278,11 +326,6 @@ def match_projection(matcher, mps, rad, matchedL, matchedR, matches):
     _chk(matcher.L.vslam_match_projection(matcher.h, _p(mps), len(mps), C.c_float(rad), _p(mL), _p(mR), _p(mt),
                                           C.byref(n), C.byref(nc)))
     return n.value, mL[:len(matchedL)], mR[:len(matchedR)], mt, nc.value
-
-
-class LmReport(C.Structure):
-    _fields_ = [("iterations", C.c_int32), ("inner_iterations", C.c_int32), ("initial_error", C.c_double),
-                ("final_error", C.c_double), ("lam", C.c_double)]
 
 
 class PoseProblem(C.Structure):
@@ -1043,6 +1086,25 @@ class System:
         d["ba_report"] = [dict(iterations=r.iterations, inner=r.inner_iterations, initialError=r.initial_error,
                                finalError=r.final_error, lam=r.lam) for r in rep.ba_report]
         return T, d
+
+    def relocalize(self, left, right, frame_number, on_device=False, stride=None, **params):
+        """vslam_system_relocalize with gray frames: (T_wc, report dict); T_wc is the unchanged camera pose on failure"""
+        T = np.zeros((4, 4))
+        rep = RelocReport()
+        prm = RelocParams(**{k: int(v) for k, v in params.items()})
+        if on_device:
+            lp, rp, st = C.c_void_p(left), C.c_void_p(right), stride or self.w
+            keep = []
+        else:
+            left, ch, st = _image(left, self.h, self.w)
+            right, chr_, _ = _image(right, self.h, self.w)
+            if ch != 1 or chr_ != 1:
+                raise ValueError("relocalize takes gray frames")
+            keep = [left, right]
+            lp, rp = _p(left), _p(right)
+        _chk(self.L.vslam_system_relocalize(self.h_sys, lp, rp, int(st), int(on_device), int(frame_number), C.byref(prm), _p(T),
+                                            C.byref(rep)))
+        return T, _reloc_report_dict(rep)
 
     def wait_mapping(self):
         _chk(self.L.vslam_system_wait_mapping(self.h_sys))

@@ -336,6 +336,53 @@ vslam_status vslam_world_to_frame(vslam_matcher* m, const double* T_cw, int32_t 
                                   uint8_t* in_frame, uint8_t* in_frame_r);
 
 /* ---------------------------------------------------------------------------
+ * Relocalisation — NO reference counterpart (the reference has nothing that recovers a lost tracker; DESIGN.md section 6
+ * holds the exact rules, tests/reloc_ref.py restates them on the CPU).  Recovers the pose of the frame the matcher
+ * currently holds (a completed vslam_stereo_match: keypoints, descriptors, rightIdxs, estimatedDepth in HBM) from a map,
+ * without a pose prior:
+ *   A  k_reloc_match: every map point against every left key, 256-bit Hamming.  d1 = smallest distance, i1 = lowest key
+ *      index attaining it, d2 = smallest distance over all other keys (257 with a single key).  Point p proposes i1 iff
+ *      d1 <= max_hamming and 100 * d1 < ratio_pct * d2; key i goes to the proposer with the smallest (d1 << 32 | p).
+ *   B  k_reloc_pairs: winning pairs whose key has estimatedDepth > 0 and rightIdxs >= 0, in ascending key index, as
+ *      correspondences {X_w, X_c (the key back-projected with its depth), kx, ky, kxr, octave, p, i}; C of them.
+ *      C < 3: success = 0, status VSLAM_OK.
+ *   C  k_reloc_ransac / k_reloc_best: n_hypotheses poses, each from three correspondences sampled by a counter hash of
+ *      (seed, hypothesis, draw), built in fp64 from the two point triples' orthonormal frames; scored by the number of
+ *      correspondences with z > 0 whose (left u, left v, right u) residual, weighted by the octave's InvSigmaFactor,
+ *      passes the chi2 bound 7.815.  The winner is the largest (count << 32 | 0xFFFFFFFF - h).
+ *   D  the winner's inliers, in correspondence order, refined by vslam_estimate_pose from the hypothesis;
+ *      success = n_inliers >= min_inliers.  T_cw_out is written only on success.
+ * Everything is enqueued on the matcher's stream; the call waits once before the refinement and once at its end.
+ * n_points <= 65536 and at most 7680 left keys, else VSLAM_ERR_CAPACITY; no completed stereo match, n_hypotheses above
+ * 1024 or a negative parameter: VSLAM_ERR_INVALID.  Like vslam_estimate_pose, step D may clear the stereo match of a
+ * key whose right observation fails the chi2 test.
+ * ------------------------------------------------------------------------- */
+typedef struct vslam_reloc_params {   /* a zero field takes the default in brackets (all zero / NULL = all defaults) */
+    int32_t max_hamming;     /* [50]  accept a best distance <= this */
+    int32_t ratio_pct;       /* [80]  and 100*d1 < ratio_pct*d2 */
+    int32_t n_hypotheses;    /* [256] at most 1024 */
+    uint32_t seed;           /* [0x52454C4F] */
+    int32_t min_inliers;     /* [50]  the fleet's "lost" limit */
+} vslam_reloc_params;
+
+typedef struct vslam_reloc_report {
+    int32_t success, n_points, n_pairs, best_hypothesis, best_count;
+    int32_t n_inliers, n_stereo;
+    vslam_lm_report lm;
+} vslam_reloc_report;
+
+vslam_status vslam_relocalize(vslam_matcher* m, const double* points_xyz, const uint8_t* desc, int32_t n_points,
+                              const vslam_reloc_params* params, double* T_cw_out,
+                              int32_t* pairs_out /* n_points: key index of the point's correspondence or -1; may be NULL */,
+                              vslam_reloc_report* report);
+/* test tap: of the last vslam_relocalize call on this matcher, per map point (d1, i1, d2) [n_points][3], per left key the
+ * winning map point or -1, per hypothesis its count, per correspondence the winner's inlier flag.  sizes4 = {n_points, left
+ * keys, hypotheses, correspondences}; any array may be NULL; a capacity below its size: VSLAM_ERR_CAPACITY. */
+vslam_status vslam_relocalize_debug(vslam_matcher* m, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner, int32_t cap_keys,
+                                    int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags, int32_t cap_pairs,
+                                    int32_t* sizes4);
+
+/* ---------------------------------------------------------------------------
  * Local bundle adjustment — replaces the numerical core of LocalMapper::localBA
  * (include/OptimizationBA.h:75, src/OptimizationBA.cpp:543-873): GenericProjectionFactor
  * (left, and right with the stereo extrinsics) per observation, BetweenFactor<Pose3>
@@ -779,6 +826,20 @@ vslam_status vslam_system_set_rectifiers(vslam_system* sys, const vslam_rectifie
 vslam_status vslam_system_track_stereo_raw(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
                                            int32_t channels, int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
                                            double* T_wc_out, vslam_frame_report* report);
+/* Relocalisation of a stereo session (use_imu = 0; gray frames) from its own map, without a pose prior - for a session whose
+ * tracking is lost (fewer than 50 inliers).  No reference counterpart.  The call does what a tracked frame does first
+ * (mapping results due at frame_number land, extraction, stereo match), then runs vslam_relocalize over every map point not
+ * flagged an outlier, in creation order (the most recent 65536 if there are more).
+ * Failure (report->success = 0, VSLAM_OK): nothing else in the session changes, T_wc_out = the unchanged camera pose.
+ * Success: the camera pose is the result; the predicted motion is the identity (predNPose = camPose, predNPoseRef = I);
+ * camRefPose = lastKFPoseInv * pose; the frame is recorded as addFrame records a non-keyframe frame; activeMapPoints
+ * becomes, in creation order, every non-outlier map point that vslam_world_to_frame places inside the left image under the
+ * new pose (MapPoint::inFrame follows); the last frame's match tables are cleared; no keyframe is inserted, and the next
+ * vslam_system_track_stereo proceeds normally.  IMU sessions (their velocity would need re-initialising) and mono sessions:
+ * VSLAM_ERR_INVALID with nothing changed. */
+vslam_status vslam_system_relocalize(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
+                                     int32_t on_device, int32_t frame_number, const vslam_reloc_params* params,
+                                     double* T_wc_out, vslam_reloc_report* report);
 /* blocks until the device work of the pass in flight (local_mapping = 2) has finished; reports its failure, if any.
  * (Its results are still applied at the frames the schedule names.) */
 vslam_status vslam_system_wait_mapping(vslam_system* sys);

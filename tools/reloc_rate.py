@@ -1,0 +1,105 @@
+"""Time of one vslam_relocalize call on a resident frame: 1 500 left keys against 20 000 map points, 256 hypotheses.
+
+The frame is crafted (keys at random pixels with stereo depth, through set_keys + vslam_stereo_finalize_arrays) and stays in
+HBM; the map is 20 000 points of which 1 200 carry a key's descriptor with 0 .. 30 bits flipped - 60 % of those consistent
+with one camera pose, the rest gross outliers - and 18 800 random descriptors.  Every call uploads the map (20 000 x 56 B),
+runs the four kernels and the refinement, and downloads the result, as a caller's call does.
+Reported: the wall-clock time of a call (host clock around the call, which ends in a device synchronise) and the device time
+per kernel group from the matcher's HIP events (summed over a repetition's calls, divided by their number).  Five warm-up
+calls, then `reps` repetitions of `calls` calls each; median and range over the repetitions.  Beside it, as context only, the
+time of the numpy restatement (tests/reloc_ref.py, steps A - C and the CPU pose solve) on one core for the same input.
+usage: python tools/reloc_rate.py [out.json] [calls] [reps]"""
+import json, os, sys, time
+os.environ.setdefault("OMP_NUM_THREADS", "1")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("gtsam-vslam_amd", "tests", "oracle"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+import numpy as np
+import synth
+import vslam_capi as vc
+
+N_KEYS, N_POINTS, N_TRUE = 1500, 20000, 1200
+RIG = synth.RIGS["euroc"]
+
+
+def flip(desc, k, rng):
+    out = desc.copy()
+    for b in rng.choice(256, size=k, replace=False):
+        out[b >> 3] ^= np.uint8(1 << (b & 7))
+    return out
+
+
+def build(seed=1):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = N_KEYS
+    kL = np.zeros(n, vc.KP_DTYPE); kR = np.zeros(n, vc.KP_DTYPE)
+    u = rng.uniform(60, RIG["w"] - 40, n).astype(np.float32); v = rng.uniform(40, RIG["h"] - 40, n).astype(np.float32)
+    z = rng.uniform(2.0, 8.0, n).astype(np.float32)
+    kL["x"], kL["y"], kL["octave"] = u, v, rng.integers(0, 8, n)
+    kR["x"] = (u - RIG["fx"] * RIG["bl"] / z).astype(np.float32); kR["y"] = v; kR["octave"] = kL["octave"]
+    dL = rng.integers(0, 256, (n, 32), dtype=np.uint8); dR = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    w = np.array([0.3, -0.4, 0.2]); th = np.linalg.norm(w); K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / th
+    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K); t = np.array([0.8, -0.3, 1.1])
+    zp = z.astype(np.float64)
+    Xc = np.stack([(u - RIG["cx"]) * zp / RIG["fx"], (v - RIG["cy"]) * zp / RIG["fy"], zp], axis=1)
+    Xw_keys = (Xc - t) @ R
+    points = rng.uniform(-8, 8, (N_POINTS, 3)); desc = rng.integers(0, 256, (N_POINTS, 32), dtype=np.uint8)
+    where = rng.permutation(N_POINTS)[:N_TRUE]; keys = rng.permutation(n)[:N_TRUE]
+    for j, (p, k) in enumerate(zip(where, keys)):
+        desc[p] = flip(dL[k], int(rng.integers(0, 31)), rng)
+        if j % 5 < 3:
+            points[p] = Xw_keys[k]
+    return dict(kL=kL, dL=dL, kR=kR, dR=dR, best=np.arange(n, dtype=np.int32), depth=z, sad=np.full(n, 10, np.int32),
+                points=points, desc=desc)
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reloc_rate.json")
+    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    if vc.device_count() < 1:
+        raise RuntimeError("reloc_rate needs a GPU: a time taken anywhere else says nothing about the stage")
+    g = build()
+    ge = vc.Extractor(RIG["w"], RIG["h"], 1500, batch=2)
+    m = vc.Matcher(RIG, ge, 0, ge, 1)
+    m.stereo_finalize_arrays(g["best"], g["depth"], g["sad"], N_KEYS)
+    m.set_keys(0, g["kL"], g["dL"]); m.set_keys(1, g["kR"], g["dR"])
+    st = m.stereo_fetch(N_KEYS, N_KEYS)
+    for _ in range(5):
+        T, rep, _ = m.relocalize(g["points"], g["desc"], pairs=False)
+    m.timings()
+    wall, groups = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            m.relocalize(g["points"], g["desc"], pairs=False)
+        wall.append((time.perf_counter() - t0) / calls * 1e3)
+        groups.append({k: v / calls for k, v in m.timings().items()})
+    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, calls_per_repetition=calls, repetitions=reps,
+               report={k: rep[k] for k in ("success", "n_pairs", "best_count", "n_inliers", "n_stereo")},
+               hamming_tests_per_call=N_KEYS * N_POINTS,
+               wall_ms_per_call=dict(median=float(np.median(wall)), min=min(wall), max=max(wall)),
+               device_ms_per_call={k: dict(median=float(np.median([gr.get(k, 0.0) for gr in groups])), min=min(gr.get(k, 0.0) for gr in groups),
+                                           max=max(gr.get(k, 0.0) for gr in groups)) for k in sorted(groups[0])})
+    mt = res["device_ms_per_call"].get("reloc_match", {}).get("median", 0.0)
+    if mt > 0:
+        res["hamming_tests_per_second_in_k_reloc_match"] = N_KEYS * N_POINTS / (mt * 1e-3)
+    # context: the numpy restatement on one core (best of three)
+    import pyoracle, reloc_ref as rr
+    inv_sigma = pyoracle.Extractor(1500).InvSigmaFactor
+    cpu = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        ref = rr.relocalize(pyoracle, RIG, inv_sigma, g["points"], g["desc"], g["kL"], g["dL"], g["kR"], st)
+        cpu.append((time.perf_counter() - t0) * 1e3)
+    res["numpy_restatement_one_core_ms"] = dict(best=min(cpu), all=cpu)
+    res["same_result_as_restatement"] = bool(ref["n_pairs"] == rep["n_pairs"] and ref["best_count"] == rep["best_count"] and
+                                             ref["n_inliers"] == rep["n_inliers"] and ref["T_cw"] is not None and T is not None and
+                                             float(np.abs(ref["T_cw"] - T).max()) < 1e-7)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
