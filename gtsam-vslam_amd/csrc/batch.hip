@@ -183,6 +183,10 @@ struct vslam_batch {
     vslam_status ensure_up(size_t bytes);
     vslam_status ensure_dn(size_t bytes);
     vslam_status serve_requests();
+    vslam_status first_error();
+    vslam_status host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates);
+    vslam_status relocalize(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames, const uint8_t* mask,
+                            const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps);
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
     vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
@@ -494,35 +498,18 @@ vslam_status vslam_batch::enqueue_extraction(const uint8_t* const* L, const uint
     return fe->run();
 }
 
-vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
-                               const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
-                               const uint8_t* const* nextL, const uint8_t* const* nextR, const uint8_t* nextMask, bool raw) {
-    if (!L || !R || !frames || !T_wc_out) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
-    vslam::thread_pool_wants_priority() = true;      // this thread's pool serves the group's requests (serve_requests)
-    using clk = std::chrono::steady_clock;
-    auto t0 = clk::now();
-    auto lap = [&](int k) { const auto t1 = clk::now(); phase[k] = std::chrono::duration<double>(t1 - t0).count(); phaseSum[k] += phase[k]; t0 = t1; };
-    auto sub = [&](int k, clk::time_point& ts) { const auto t1 = clk::now(); subSum[k] += std::chrono::duration<double>(t1 - ts).count(); ts = t1; };
-    nSteps++;
-    int nOn = 0;
-    for (int b = 0; b < B; b++) {
-        LaneStep& q = ls[b];
-        q = LaneStep{};
-        q.on = !mask || mask[b];
-        if (!q.on) continue;
-        if (!L[b] || !R[b]) { set_error("vslam_batch: lane %d has no images", b); return VSLAM_ERR_INVALID; }
-        q.first = frames[b] == 0;
-        if (needFirst[b] && !q.first) { set_error("vslam_batch: lane %d was restarted, its next frame must carry frame number 0 (got %d)", b, frames[b]); return VSLAM_ERR_INVALID; }
-        nOn++;
-    }
-    if (!nOn) return VSLAM_OK;
-    auto first_error = [&]() -> vslam_status {
-        for (int b = 0; b < B; b++) if (ls[b].failed) { set_error("lane %d: %s", b, ls[b].err); return ls[b].st; }
-        return VSLAM_OK;
-    };
+vslam_status vslam_batch::first_error() {
+    for (int b = 0; b < B; b++) if (ls[b].failed) { set_error("lane %d: %s", b, ls[b].err); return ls[b].st; }
+    return VSLAM_OK;
+}
 
-    // ---- host: frame_begin + candidate lists --------------------------------------------------------------------------------
+// The host begin phase of the lanes that are on in ls[]: mapping results due at the lanes' frame numbers land (frame_begin_a, the
+// group's request service, frame_begin_b1, the merged changePosesLCA pass, frame_begin_b2).  candidates: the tracker's candidate
+// lists as well (a tracked step; a relocalisation gathers its own).
+vslam_status vslam_batch::host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates) {
+    using clk = std::chrono::steady_clock;
+    auto sub = [&](int k, clk::time_point& ts) { const auto t1 = clk::now(); subSum[k] += std::chrono::duration<double>(t1 - ts).count(); ts = t1; };
+
     auto ts = clk::now();
     pool.run(B, [&](int b) {
         LaneStep& q = ls[b];
@@ -547,7 +534,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
         const vslam_status bs = s->frame_begin_b1(s->ctx);
         s->deferLca = false;
         LANE_TRY(bs);
-        if (!s->lcaReq.pending && !q.first) q.N = s->frame_candidates(s->ctx);
+        if (candidates && !s->lcaReq.pending && !q.first) q.N = s->frame_candidates(s->ctx);
     });
     VS_CHECK(first_error());
     // changePosesLCA of the lanes whose local BA landed at this step: their KeyFrame::updatePose kernels enqueued back to back on this
@@ -582,12 +569,39 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
                 LaneStep& q = ls[b];
                 vslam_system* s = sys[b];
                 LANE_TRY(s->frame_begin_b2(s->ctx));
-                if (!q.first) q.N = s->frame_candidates(s->ctx);
+                if (candidates && !q.first) q.N = s->frame_candidates(s->ctx);
             });
             VS_CHECK(first_error());
         }
     }
     sub(2, ts);
+    return VSLAM_OK;
+}
+
+vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
+                               const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
+                               const uint8_t* const* nextL, const uint8_t* const* nextR, const uint8_t* nextMask, bool raw) {
+    if (!L || !R || !frames || !T_wc_out) return VSLAM_ERR_INVALID;
+    VS_HIP(hipSetDevice(device));
+    vslam::thread_pool_wants_priority() = true;      // this thread's pool serves the group's requests (serve_requests)
+    using clk = std::chrono::steady_clock;
+    auto t0 = clk::now();
+    auto lap = [&](int k) { const auto t1 = clk::now(); phase[k] = std::chrono::duration<double>(t1 - t0).count(); phaseSum[k] += phase[k]; t0 = t1; };
+    auto sub = [&](int k, clk::time_point& ts) { const auto t1 = clk::now(); subSum[k] += std::chrono::duration<double>(t1 - ts).count(); ts = t1; };
+    nSteps++;
+    int nOn = 0;
+    for (int b = 0; b < B; b++) {
+        LaneStep& q = ls[b];
+        q = LaneStep{};
+        q.on = !mask || mask[b];
+        if (!q.on) continue;
+        if (!L[b] || !R[b]) { set_error("vslam_batch: lane %d has no images", b); return VSLAM_ERR_INVALID; }
+        q.first = frames[b] == 0;
+        if (needFirst[b] && !q.first) { set_error("vslam_batch: lane %d was restarted, its next frame must carry frame number 0 (got %d)", b, frames[b]); return VSLAM_ERR_INVALID; }
+        nOn++;
+    }
+    if (!nOn) return VSLAM_OK;
+    VS_CHECK(host_begin(frames, imu, true));
     lap(0);
 
     // ---- device: images, extraction (already in flight when the previous step prefetched exactly these images) -----------
@@ -826,7 +840,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
     lap(5);
 
     // ---- host: frame_post (first frames: the one-session path on their own stereo result) ------------------------------------
-    ts = clk::now();
+    auto ts = clk::now();
     pool.run(B, [&](int b) {
         LaneStep& q = ls[b];
         if (!q.on) return;
@@ -855,6 +869,83 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
     for (int b = 0; b < B; b++) if (ls[b].on) needFirst[b] = 0;      // (a restarted lane's frame 0 has been tracked)
     sub(5, ts);
     lap(6);
+    return VSLAM_OK;
+}
+
+// Relocalisation of the masked lanes from their own maps, in lockstep: per lane what vslam_system::relocalize does, with one extraction
+// enqueue, one stereo launch set and one launch per relocalisation stage for all of them (reloc.hip: reloc_batch_run), the map points
+// gathered straight into the group's upload block.  One wait for the extraction's counts (as a step has), one at the end.
+vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames,
+                                     const uint8_t* mask, const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps) {
+    if (!L || !R || !frames || !T_wc_out || !reps) { set_error("vslam_batch_relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
+    // ---- refusals: nothing has changed when one of these returns ----------------------------------------------------------------
+    int nOn = 0;
+    for (int b = 0; b < B; b++) {
+        if (mask && !mask[b]) continue;
+        nOn++;
+        if (useImu) { set_error("vslam_batch_relocalize: lane %d: an IMU batch cannot relocalise yet (its velocity would need re-initialising)", b); return VSLAM_ERR_INVALID; }
+        if (!L[b] || !R[b]) { set_error("vslam_batch_relocalize: lane %d has no images", b); return VSLAM_ERR_INVALID; }
+        if (needFirst[b] || sys[b]->keyFrames.empty()) { set_error("vslam_batch_relocalize: lane %d has no map (track its frame 0 first)", b); return VSLAM_ERR_INVALID; }
+    }
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(prm, P));
+    if (!nOn) return VSLAM_OK;
+    VS_HIP(hipSetDevice(device));
+    vslam::thread_pool_wants_priority() = true;
+    for (int b = 0; b < B; b++) { ls[b] = LaneStep{}; ls[b].on = !mask || mask[b]; }
+    // ---- host: mapping results due at these frame numbers land as in a tracked step ------------------------------------------------
+    VS_CHECK(host_begin(frames, nullptr, false));
+    // ---- device: the frames' extraction; a prefetched one (for a tracked step's images) finishes first and is discarded ---------
+    prefetched.clear();
+    if (fe->countsPending) VS_CHECK(fe->wait_counts());
+    VS_CHECK(enqueue_extraction(L, R, mask, stride, 1, onDevice, false));
+    // ---- host, under the extraction: the local BAs' window collection, the candidate lists, the upload block --------------------
+    std::vector<RelocBatchLane> rl((size_t)B);
+    pool.run(B, [&](int b) {
+        LaneStep& q = ls[b];
+        if (!q.on) return;
+        hipSetDevice(device);
+        if (sys[b]->pass.collectDue) LANE_TRY(sys[b]->frame_mid());
+        rl[b].m = sys[b]->fm; rl[b].n = sys[b]->reloc_candidates(); rl[b].wantInFrame = true;
+    });
+    kick();
+    VS_CHECK(first_error());
+    RelocBatchPlan plan;
+    reloc_batch_plan(rl.data(), B, plan);
+    VS_CHECK(ensure_up(plan.upBytes));
+    VS_CHECK(ensure_dn(plan.dnBytes));
+    pool.run(B, [&](int b) {
+        if (!ls[b].on) return;
+        sys[b]->reloc_fill_upload((double*)(h_up + rl[b].oXyz), h_up + rl[b].oDesc, (float*)(h_up + rl[b].oMsd));
+    });
+    // ---- keys of the new frames (waits for the extraction's totals), stereo match of the masked pairs -----------------------------
+    VS_HIP(hipStreamWaitEvent(stream, fe->evDone, 0));
+    VS_CHECK(fe->wait_counts());
+    int maxL = 0, maxR = 0;
+    for (int b = 0; b < B; b++) {
+        StereoLane& S = ht.stereo[b];
+        if (!ls[b].on) { S.A.nL = 0; S.A.nR = 0; continue; }
+        vslam_matcher* m = sys[b]->fm;
+        VS_CHECK(m->refresh_keys(false));
+        VS_CHECK(m->stereo_lane(S));
+        m->stereoDone = true;
+        maxL = std::max(maxL, m->nKeys[0]); maxR = std::max(maxR, m->nKeys[1]);
+    }
+    VS_HIP(hipMemcpyAsync(dt.stereo, ht.stereo, (size_t)B * sizeof(StereoLane), hipMemcpyHostToDevice, stream));
+    launch_stereo_batch(stream, dt.stereo, B, maxL, maxR, shared.rig.height, &timer);
+    VS_CHECK(reloc_batch_check(rl.data(), B, device));
+    // ---- device: every relocalisation stage once for all lanes; one wait ----------------------------------------------------------
+    std::vector<double> Tcw((size_t)B * 16, 0.0);
+    const RelocBlocks blk{h_up, d_up, h_dn, d_dn};
+    VS_CHECK(reloc_batch_run(rl.data(), B, plan, blk, stream, P, (double)(float)std::log((double)shared.fe.scale), &timer, Tcw.data(), reps));
+    // ---- host: commit per lane (a failure changes nothing in its session) ----------------------------------------------------------
+    pool.run(B, [&](int b) {
+        if (!ls[b].on) return;
+        vslam_system* s = sys[b];
+        double* out = T_wc_out + 16 * (size_t)b;
+        if (reps[b].success) s->reloc_commit(Tcw.data() + 16 * (size_t)b, h_dn + rl[b].oInF, out);
+        else memcpy(out, s->camPose.data(), sizeof(double) * 16);
+    });
     return VSLAM_OK;
 }
 
@@ -912,6 +1003,21 @@ extern "C" {
 vslam_status vslam_batch_restart_lane(vslam_batch* b, int32_t lane, const vslam_system_config* config) {
     if (!b) return VSLAM_ERR_INVALID;
     return b->restart_lane(lane, config);
+}
+
+vslam_status vslam_batch_relocalize(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride, int32_t on_device,
+                                    const int32_t* frame_numbers, const uint8_t* lane_mask, const vslam_reloc_params* params, double* T_wc_out,
+                                    vslam_reloc_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->relocalize(left, right, stride, on_device != 0, frame_numbers, lane_mask, params, T_wc_out, reports);
+}
+
+vslam_status vslam_batch_relocalize_debug(vslam_batch* b, int32_t lane, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner,
+                                          int32_t cap_keys, int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags,
+                                          int32_t cap_pairs, int32_t* sizes4) {
+    if (!b) return VSLAM_ERR_INVALID;
+    if (lane < 0 || lane >= b->B) { set_error("vslam_batch_relocalize_debug: lane %d of %d", lane, b->B); return VSLAM_ERR_INVALID; }
+    return b->sys[lane]->fm->relocalize_debug(d1_i1_d2, cap_points, key_winner, cap_keys, hyp_counts, cap_hypotheses, inlier_flags, cap_pairs, sizes4);
 }
 
 vslam_status vslam_batch_memory(vslam_batch* b, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free) {

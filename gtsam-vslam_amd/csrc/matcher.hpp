@@ -121,7 +121,8 @@ struct vslam_matcher {
     vslam_status estimate_pose(vslam_pose_problem* prob, int* nIn, int* nStereo, vslam_lm_report* rep);
 
     // relocalisation (reloc.hip): global descriptor match of a map against the current frame, pose hypotheses, refinement
-    int rlCap = 0;                   // map-point capacity of d_rlPts / d_rlDesc / d_rlD / d_rlPairs
+    int rlCap = 0;                   // map-point capacity of d_rlPts / d_rlDesc / d_rlPairs
+    int rlDCap = 0;                  // map-point capacity of d_rlD
     double* d_rlPts = nullptr;       // [N][3]
     uint8_t* d_rlDesc = nullptr;     // [N][32]
     int* d_rlD = nullptr;            // [N][3]: d1, i1, d2
@@ -135,7 +136,9 @@ struct vslam_matcher {
     double* d_rlOut = nullptr;       // T_cw[16] of the winner, then ints {C, best hypothesis, best count}
     int rlLast[4] = {0, 0, 0, 0};    // sizes of the last call: points, keys, hypotheses, correspondences
     std::vector<uint8_t> rlHost;     // download block of the last call
-    vslam_status ensure_reloc_cap(int n);
+    vslam_status ensure_reloc_cap(int n, bool uploads = true);      // uploads: d_rlPts / d_rlDesc / d_rlPairs as well (the one-session call)
+    uint8_t* rlBlk[4] = {nullptr, nullptr, nullptr, nullptr}; size_t rlBlkCap[2] = {0, 0};      // vslam_relocalize_batch with this matcher first:
+                                                                                                  // pinned / device upload block, pinned / device download block
     vslam_status relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
                             int32_t* pairsOut, vslam_reloc_report* rep);
     vslam_status relocalize_debug(int32_t* d3, int capPoints, int32_t* keyWinner, int capKeys, int32_t* counts, int capHyp,
@@ -252,4 +255,27 @@ void launch_proj_candidates(hipStream_t s, const ProjArgs& A, const int* matches
                             unsigned long long* topk, unsigned long long* stats);
 void launch_proj_resolve(hipStream_t s, const ProjArgs& A, const unsigned long long* topk, int* matchedL, int* matchedR,
                          int* matches, int* out);
+
+// ---- batched relocalisation (reloc.hip): one launch per stage for all lanes ---------------------------------------------------
+// Both blocks are the caller's (vslam_relocalize_batch: the first matcher's; vslam_batch: the group's upload / download blocks).
+//   upload block    lane tables | per lane: xyz [n][3], descriptors [n][32], maxScaleDist [n] (if wanted) | per lane: key winners
+//                   (device side only); everything before the key winners goes up in ONE copy
+//   download block  per lane: summary | pairs [n] | in-frame bytes [n] (if wanted); comes down in ONE copy
+struct RelocBatchLane {
+    vslam_matcher* m = nullptr;      // null: the lane is idle
+    int n = 0;                       // map points
+    bool wantInFrame = false;        // the in-frame bytes under the refined pose (needs maxScaleDist in the upload block)
+    size_t oXyz = 0, oDesc = 0, oMsd = 0, oKeyWin = 0, oSum = 0, oPairs = 0, oInF = 0;      // byte offsets (reloc_batch_plan)
+    int nL = 0;                      // left keys (reloc_batch_run)
+};
+struct RelocBatchPlan { size_t oPose = 0, upCopyBytes = 0, upBytes = 0, dnBytes = 0; int maxN = 0, nOn = 0; };
+struct RelocBlocks { uint8_t* h_up; uint8_t* d_up; uint8_t* h_dn; uint8_t* d_dn; };
+vslam_status reloc_resolve_params(const vslam_reloc_params* prm, vslam_reloc_params& P);
+// per-lane argument checks of the batched call (limits and status rules of vslam_relocalize); nothing is changed
+vslam_status reloc_batch_check(const RelocBatchLane* lanes, int B, int device);
+void reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan);
+// The caller has filled the lanes' map arrays in h_up.  Keys are refreshed, capacities ensured, then tables, upload, the stages,
+// download and ONE wait on `stream`; reports and T_cw_out ([B][16], written per lane only on success) are filled per active lane.
+vslam_status reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
+                             const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps);
 }  // namespace vslam

@@ -192,22 +192,9 @@ __global__ __launch_bounds__(256) void k_world_to_frame(int n, const double* __r
     for (int k = 0; k < 3; k++) pc[k] += Tcw.t[k];
     for (int side = 0; side < 2; side++) {
         const double x = side ? pc[0] - b : pc[0], y = pc[1], z = pc[2];
-        bool vis = false;
         float uo = 0, vo = 0;
         int lvl = 0;
-        if (!(z <= 0.0)) {
-            const double invZ = 1.0 / z;
-            const double u = fx * x * invZ + cx, v = fy * y * invZ + cy;
-            if (!(u < 0 || v < 0 || u >= w || v >= h)) {
-                const float dist = (float)sqrt(x * x + y * y + z * z);
-                const float dif = maxScaleDist[i] / dist;
-                const double s = log((double)dif) / logScale;
-                int sc = (int)s;
-                sc += (sc < s);
-                if (sc < 0) sc = 0; else if (sc >= nLev) sc = nLev - 1;
-                vis = true; uo = (float)u; vo = (float)v; lvl = sc;
-            }
-        }
+        const bool vis = world_to_frame_cam(x, y, z, fx, fy, cx, cy, w, h, maxScaleDist + i, logScale, nLev, uo, vo, lvl);
         if (side == 0) { if (vis) { predL[2 * i] = uo; predL[2 * i + 1] = vo; lvlL[i] = lvl; } inF[i] = vis; }
         else { if (vis) { predR[2 * i] = uo; predR[2 * i + 1] = vo; lvlR[i] = lvl; } inFR[i] = vis; }
     }

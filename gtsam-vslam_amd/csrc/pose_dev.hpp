@@ -39,6 +39,27 @@ struct ImuLmArgs {
 };
 struct PoseLane { PoseArgs A; ImuLmArgs I; };      // one lane of the batched pose solves (I unused by the 6-dof kernel)
 
+// one lane of the batched relocalisation kernels (reloc.hip); the tables hold the call's active lanes only
+struct RelocRec;
+struct RelocLane {
+    int nP, nL;                                        // map points, left keys of the lane's current frame
+    const uint4* descP; const uint4* descL;            // their descriptors
+    const double* pts; const float* msd;               // world positions, MapPoint::maxScaleDist (null: no in-frame pass)
+    int maxHamming, ratioPct, nHyp, minInliers; unsigned seed;
+    int* dOut; unsigned long long* keyWin; int* keyWinner; int* pairs;
+    const vslam_keypoint* kpsL; const vslam_keypoint* kpsR; const float* depth; const int* rightIdxs;
+    RelocRec* rec; uint8_t* flags; int* counts; double* poses;
+    double* out;                                       // T_cw[16] of the winner, then ints {C, best hypothesis, best count, M, gate}
+    PoseArgs A;                                        // the lane's camera, level table and chi2 bound; the refinement's own arguments
+    double* probPoints; uint8_t* probFlags; size_t flagStride;      // the refinement problem (writable views of A.points / A.inFrame ..)
+    int w, h, nLev; double logScale;                   // the in-frame test under the refined pose
+    uint8_t* inF;                                      // [nP] (null: not wanted)
+    double* summary;                                   // the lane's results in its slice of the download block (RELOC_SUM_*)
+};
+// summary slice: doubles [0, 16) T_cw (refined when the gate was open, else the winning hypothesis), [16, 19) the LM's initial error,
+// final error, lambda; ints from double 20: C, best hypothesis, best count, M, gate, inliers, stereo inliers, iterations, inner, success
+constexpr int RELOC_SUM_DOUBLES = 32, RELOC_SUM_INTS = 20;
+
 // whitened residual (and Jacobian rows wrt [omega, v]) of one factor at T (world <- camera)
 __device__ __forceinline__ int pose_factor_eval(const double* f, const DPose& T, const PoseArgs& A,
                                                 double* r, double (*J)[6]) {
@@ -388,6 +409,24 @@ __device__ __forceinline__ void pose_find_outliers(const PoseArgs& A, int M, con
     if (A.monoOnly) nSt = nIn;           // findOutliersMono returns the inlier count in both slots (:651-683)
     if (nSt) atomicAdd(&sCnt[1], nSt);
     __syncthreads();
+}
+
+// worldToFrame for one camera (src/FeatureTracker.cpp:685-741, src/Map.cpp:13-23): (x, y, z) is the point in THAT camera's frame.
+// Visible: pixel and predicted scale level are written.  msd: the point's MapPoint::maxScaleDist (read only for a visible point).
+__device__ __forceinline__ bool world_to_frame_cam(double x, double y, double z, double fx, double fy, double cx, double cy, int w, int h,
+                                                   const float* msd, double logScale, int nLev, float& uo, float& vo, int& lvl) {
+    if (z <= 0.0) return false;
+    const double invZ = 1.0 / z;
+    const double u = fx * x * invZ + cx, v = fy * y * invZ + cy;
+    if (u < 0 || v < 0 || u >= w || v >= h) return false;
+    const float dist = (float)sqrt(x * x + y * y + z * z);
+    const float dif = *msd / dist;
+    const double s = log((double)dif) / logScale;
+    int sc = (int)s;
+    sc += (sc < s);
+    if (sc < 0) sc = 0; else if (sc >= nLev) sc = nLev - 1;
+    uo = (float)u; vo = (float)v; lvl = sc;
+    return true;
 }
 
 }  // namespace vslam

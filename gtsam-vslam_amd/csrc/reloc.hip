@@ -9,6 +9,10 @@
 //   k_reloc_ransac  one wave per hypothesis: three sampled correspondences -> rigid pose (fp64), scored over all records
 //   k_reloc_best    one wave: the winning hypothesis and its inlier flags
 // The winner's inliers are refined by the existing motion-only LM (vslam_matcher::estimate_pose).
+// Several lanes in one call (vslam_relocalize_batch, vslam_batch_relocalize): the k_*_b forms of the four kernels - the same bodies,
+// the lane as a grid dimension, arguments from a RelocLane table - then
+//   k_reloc_problem_b  the refinement problem built on the device (no wait before step D), refined by k_pose_lm_b behind a gate
+//   k_reloc_inframe_b  the lane's results into the download block; the left-image test of the map under the refined pose
 #include "pose_dev.hpp"
 #include "track_dev.hpp"
 
@@ -32,9 +36,11 @@ __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, cons
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-__global__ __launch_bounds__(256) void k_reloc_match(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
-                                                     int maxHamming, int ratioPct, int* __restrict__ dOut,
-                                                     unsigned long long* __restrict__ keyWin) {
+// The bodies below are shared by the one-session kernels (arguments by value) and the lane-table forms (k_*_b: the lane is a grid
+// dimension, arguments from a RelocLane entry): one copy of every rule.
+__device__ __forceinline__ void reloc_match_body(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
+                                                 int maxHamming, int ratioPct, int* __restrict__ dOut,
+                                                 unsigned long long* __restrict__ keyWin) {
     __shared__ uint4 tile[RELOC_TILE * 2];
     const int p = blockIdx.x * 256 + threadIdx.x;
     uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
@@ -60,12 +66,24 @@ __global__ __launch_bounds__(256) void k_reloc_match(int nP, const uint4* __rest
         atomicMin(&keyWin[i1], ((unsigned long long)d1 << 32) | (unsigned)p);
 }
 
-__global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned long long* __restrict__ keyWin,
-                                                      const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
-                                                      const float* __restrict__ depth, const int* __restrict__ rightIdxs,
-                                                      const double* __restrict__ pts, double fx, double fy, double cx, double cy,
-                                                      RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
-                                                      int* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_reloc_match(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
+                                                     int maxHamming, int ratioPct, int* __restrict__ dOut,
+                                                     unsigned long long* __restrict__ keyWin) {
+    reloc_match_body(nP, descP, nL, descL, maxHamming, ratioPct, dOut, keyWin);
+}
+// grid (ceil(max nP / 256), lanes).  A workgroup past its lane's points leaves as a whole, before the body's first barrier.
+__global__ __launch_bounds__(256) void k_reloc_match_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.y);
+    if ((int)(blockIdx.x * 256) >= L.nP) return;
+    reloc_match_body(L.nP, L.descP, L.nL, L.descL, L.maxHamming, L.ratioPct, L.dOut, L.keyWin);
+}
+
+__device__ __forceinline__ void reloc_pairs_body(int nL, const unsigned long long* __restrict__ keyWin,
+                                                 const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
+                                                 const float* __restrict__ depth, const int* __restrict__ rightIdxs,
+                                                 const double* __restrict__ pts, double fx, double fy, double cx, double cy,
+                                                 RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
+                                                 int* __restrict__ out) {
     __shared__ int wsum[16];
     int run = 0;
     for (int base = 0; base < nL; base += 1024) {
@@ -97,6 +115,21 @@ __global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned lon
         run += tot;
     }
     if (threadIdx.x == 0) out[0] = run;
+}
+
+__global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned long long* __restrict__ keyWin,
+                                                      const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
+                                                      const float* __restrict__ depth, const int* __restrict__ rightIdxs,
+                                                      const double* __restrict__ pts, double fx, double fy, double cx, double cy,
+                                                      RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
+                                                      int* __restrict__ out) {
+    reloc_pairs_body(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
+}
+// one workgroup per lane
+__global__ __launch_bounds__(1024) void k_reloc_pairs_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    reloc_pairs_body(L.nL, L.keyWin, L.kpsL, L.kpsR, L.depth, L.rightIdxs, L.pts, L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.rec, L.pairs, L.keyWinner,
+                     (int*)(L.out + 16));
 }
 
 __device__ __forceinline__ unsigned reloc_mix(unsigned s, unsigned h, unsigned j) {
@@ -166,8 +199,8 @@ __device__ __forceinline__ bool reloc_inlier(const RelocRec& r, const DPose& T, 
     return !((eu * eu + ev * ev + eur * eur) * (double)lvl[r.octave] > A.thres);
 }
 
-__global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
-                                                     unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
+__device__ __forceinline__ void reloc_ransac_body(const PoseArgs& A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
+                                                  unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
     __shared__ float sLvl[MAX_LEVELS];
     pose_stage_levels(A, sLvl);
     const int h = blockIdx.x, lane = threadIdx.x;
@@ -190,8 +223,18 @@ __global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec*
     }
 }
 
-__global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
-                                                   const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
+__global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
+                                                     unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
+    reloc_ransac_body(A, rec, nRec, seed, counts, poses);
+}
+// grid (hypotheses, lanes)
+__global__ __launch_bounds__(64) void k_reloc_ransac_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.y);
+    reloc_ransac_body(L.A, L.rec, (const int*)(L.out + 16), L.seed, L.counts, L.poses);
+}
+
+__device__ __forceinline__ void reloc_best_body(const PoseArgs& A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
+                                                const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
     __shared__ float sLvl[MAX_LEVELS];
     pose_stage_levels(A, sLvl);
     const int lane = threadIdx.x;
@@ -222,11 +265,84 @@ __global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* _
     }
 }
 
+__global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
+                                                   const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
+    reloc_best_body(A, rec, nHyp, counts, poses, out, flags);
+}
+// one wave per lane
+__global__ __launch_bounds__(64) void k_reloc_best_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    reloc_best_body(L.A, L.rec, L.nHyp, L.counts, L.poses, L.out, L.flags);
+}
+
+// The refinement problem of a lane, built where the one-session call builds it on the host: the winner's inlier correspondences, in
+// correspondence order, into the lane's matcher's pose buffers - points = X_w, matches = (i, rightIdxs[i]), both in-frame flags 1,
+// both outlier flags 0, poseIO = the winning hypothesis - and the two words the pose kernel reads on the device: the problem size
+// (PoseArgs::Mdev) and the gate (0: fewer than three correspondences or no inlier, the lane is not refined).  One workgroup per lane.
+__global__ __launch_bounds__(1024) void k_reloc_problem_b(const RelocLane* __restrict__ lanes) {
+    __shared__ int wsum[16];
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    int* outI = (int*)(L.out + 16);
+    const int C = outI[0];
+    const bool go = !(C < 3 || outI[2] <= 0);
+    int run = 0;
+    if (go) {
+        const size_t fs = L.flagStride;
+        for (int base = 0; base < C; base += 1024) {
+            const int c = base + threadIdx.x;
+            const bool keep = c < C && L.flags[c];
+            int tot;
+            const int pos = run + block_excl_scan_1024(keep, wsum, tot);
+            if (keep) {
+                const RelocRec& r = L.rec[c];
+                L.probPoints[3 * (size_t)pos] = r.Xw[0]; L.probPoints[3 * (size_t)pos + 1] = r.Xw[1]; L.probPoints[3 * (size_t)pos + 2] = r.Xw[2];
+                L.A.matches[2 * pos] = r.i; L.A.matches[2 * pos + 1] = L.rightIdxs[r.i];
+                L.probFlags[pos] = 1; L.probFlags[fs + pos] = 1; L.probFlags[2 * fs + pos] = 0; L.probFlags[3 * fs + pos] = 0;
+            }
+            run += tot;
+        }
+    }
+    if (threadIdx.x < 16 && go) L.A.poseIO[threadIdx.x] = L.out[threadIdx.x];
+    if (threadIdx.x == 0) { outI[3] = run; outI[4] = go ? 1 : 0; }
+}
+
+// Grid (ceil(max nP / 256), lanes).  The lane's results go to its summary slice (workgroup 0); for a lane whose refined inlier count
+// reaches min_inliers, the left-camera worldToFrame test of every uploaded map point under the refined pose: one byte per point.
+__global__ __launch_bounds__(256) void k_reloc_inframe_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.y);
+    const int* outI = (const int*)(L.out + 16);
+    const int gate = outI[4];
+    const int nIn = gate ? L.A.out[0] : 0;
+    const bool success = gate && nIn >= L.minInliers;
+    if (blockIdx.x == 0) {
+        const int t = threadIdx.x;
+        if (t < 16) L.summary[t] = gate ? L.A.poseIO[t] : L.out[t];
+        else if (t < 19) L.summary[t] = gate ? L.A.poseIO[t] : 0.0;
+        else if (t == 19) {
+            int* sI = (int*)(L.summary + RELOC_SUM_INTS);
+            sI[0] = outI[0]; sI[1] = outI[1]; sI[2] = outI[2]; sI[3] = outI[3]; sI[4] = gate;
+            sI[5] = nIn; sI[6] = gate ? L.A.out[1] : 0; sI[7] = gate ? L.A.out[2] : 0; sI[8] = gate ? L.A.out[3] : 0; sI[9] = success ? 1 : 0;
+        }
+    }
+    if (!success || !L.inF) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= L.nP) return;
+    DPose T;
+    pose_from_rm16(L.A.poseIO, T);
+    const double p[3] = {L.pts[3 * (size_t)i], L.pts[3 * (size_t)i + 1], L.pts[3 * (size_t)i + 2]};
+    double pc[3];
+    mat3_vec(T.R, p, pc);
+#pragma unroll
+    for (int k = 0; k < 3; k++) pc[k] += T.t[k];
+    float uo, vo; int lvl;
+    L.inF[i] = world_to_frame_cam(pc[0], pc[1], pc[2], L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.w, L.h, L.msd + i, L.logScale, L.nLev, uo, vo, lvl) ? 1 : 0;
+}
+
 }  // namespace vslam
 
 using namespace vslam;
 
-vslam_status vslam_matcher::ensure_reloc_cap(int n) {
+vslam_status vslam_matcher::ensure_reloc_cap(int n, bool uploads) {
     if (!d_rlKeyWin) {
         VS_HIP(poison_malloc(&d_rlKeyWin, (size_t)RELOC_MAX_KEYS * sizeof(unsigned long long)));
         VS_HIP(poison_malloc(&d_rlKeyWinner, (size_t)RELOC_MAX_KEYS * sizeof(int)));
@@ -236,24 +352,27 @@ vslam_status vslam_matcher::ensure_reloc_cap(int n) {
         VS_HIP(poison_malloc(&d_rlPoses, (size_t)RELOC_MAX_HYP * 12 * sizeof(double)));
         VS_HIP(poison_malloc(&d_rlOut, 20 * sizeof(double)));
     }
-    if (n <= rlCap) return VSLAM_OK;
-    hipFree(d_rlPts); hipFree(d_rlDesc); hipFree(d_rlD); hipFree(d_rlPairs);
-    d_rlPts = nullptr; d_rlDesc = nullptr; d_rlD = nullptr; d_rlPairs = nullptr; rlCap = 0;
     const int cap2 = vslam::align_up(std::max(n, 1), 1024);
+    if (n > rlDCap) {
+        hipFree(d_rlD);
+        d_rlD = nullptr; rlDCap = 0;
+        VS_HIP(poison_malloc(&d_rlD, (size_t)cap2 * 3 * sizeof(int)));
+        rlDCap = cap2;
+    }
+    if (!uploads || n <= rlCap) return VSLAM_OK;     // (the batched call keeps map points and pairs in its own blocks)
+    hipFree(d_rlPts); hipFree(d_rlDesc); hipFree(d_rlPairs);
+    d_rlPts = nullptr; d_rlDesc = nullptr; d_rlPairs = nullptr; rlCap = 0;
     VS_HIP(poison_malloc(&d_rlPts, (size_t)cap2 * 3 * sizeof(double)));
     VS_HIP(poison_malloc(&d_rlDesc, (size_t)cap2 * 32));
-    VS_HIP(poison_malloc(&d_rlD, (size_t)cap2 * 3 * sizeof(int)));
     VS_HIP(poison_malloc(&d_rlPairs, (size_t)cap2 * sizeof(int)));
     rlCap = cap2;
     return VSLAM_OK;
 }
 
-vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
-                                       int32_t* pairsOut, vslam_reloc_report* rep) {
-    if (n < 0 || (n > 0 && (!xyz || !desc)) || !T_cw_out || !rep) { set_error("relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
-    if (mono) { set_error("relocalize on a mono matcher"); return VSLAM_ERR_INVALID; }
-    vslam_reloc_params P = prm ? *prm : vslam_reloc_params{};
-    if (!P.max_hamming) P.max_hamming = 50;                 // a zero field takes its default
+// a zero field takes its default; the ranges of vslam_hip.h
+vslam_status vslam::reloc_resolve_params(const vslam_reloc_params* prm, vslam_reloc_params& P) {
+    P = prm ? *prm : vslam_reloc_params{};
+    if (!P.max_hamming) P.max_hamming = 50;
     if (!P.ratio_pct) P.ratio_pct = 80;
     if (!P.n_hypotheses) P.n_hypotheses = 256;
     if (!P.seed) P.seed = 0x52454C4Fu;
@@ -263,6 +382,15 @@ vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, i
         set_error("relocalize: parameters out of range (max_hamming 0..256, ratio_pct 0..100, n_hypotheses 1..%d, min_inliers >= 0)", RELOC_MAX_HYP);
         return VSLAM_ERR_INVALID;
     }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
+                                       int32_t* pairsOut, vslam_reloc_report* rep) {
+    if (n < 0 || (n > 0 && (!xyz || !desc)) || !T_cw_out || !rep) { set_error("relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
+    if (mono) { set_error("relocalize on a mono matcher"); return VSLAM_ERR_INVALID; }
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(prm, P));
     if (!stereoDone) { set_error("relocalize needs a completed stereo match"); return VSLAM_ERR_INVALID; }
     if (n > RELOC_MAX_POINTS) { set_error("relocalize: %d map points exceed the limit (%d)", n, RELOC_MAX_POINTS); return VSLAM_ERR_CAPACITY; }
     VS_HIP(hipSetDevice(device));
@@ -359,7 +487,213 @@ vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t
     return VSLAM_OK;
 }
 
+// ---- the batched call ---------------------------------------------------------------------------------------------------------------
+namespace vslam { void launch_pose_batch(hipStream_t s, const PoseLane* dLanes, int B); }
+
+namespace {
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+}
+
+vslam_status vslam::reloc_batch_check(const RelocBatchLane* lanes, int B, int device) {
+    for (int b = 0; b < B; b++) {
+        const vslam_matcher* m = lanes[b].m;
+        if (!m) continue;
+        if (m->mono) { set_error("relocalize_batch: lane %d is a mono matcher", b); return VSLAM_ERR_INVALID; }
+        if (m->device != device) { set_error("relocalize_batch: lane %d is on device %d, the first lane on %d", b, m->device, device); return VSLAM_ERR_INVALID; }
+        if (!m->stereoDone) { set_error("relocalize_batch: lane %d needs a completed stereo match", b); return VSLAM_ERR_INVALID; }
+        if (lanes[b].n < 0) { set_error("relocalize_batch: lane %d: invalid arguments", b); return VSLAM_ERR_INVALID; }
+        for (int a = 0; a < b; a++)
+            if (lanes[a].m == m) { set_error("relocalize_batch: lanes %d and %d are the same matcher", a, b); return VSLAM_ERR_INVALID; }
+    }
+    for (int b = 0; b < B; b++)
+        if (lanes[b].m && lanes[b].n > RELOC_MAX_POINTS) {
+            set_error("relocalize_batch: lane %d: %d map points exceed the limit (%d)", b, lanes[b].n, RELOC_MAX_POINTS);
+            return VSLAM_ERR_CAPACITY;
+        }
+    return VSLAM_OK;
+}
+
+void vslam::reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan) {
+    plan = RelocBatchPlan{};
+    size_t up = up256((size_t)B * sizeof(RelocLane));
+    plan.oPose = up;
+    up = up256(up + (size_t)B * sizeof(PoseLane));
+    size_t dn = 0;
+    for (int b = 0; b < B; b++) {
+        RelocBatchLane& q = lanes[b];
+        if (!q.m) continue;
+        plan.nOn++;
+        plan.maxN = std::max(plan.maxN, q.n);
+        q.oXyz = up; up += up256((size_t)q.n * 24);
+        q.oDesc = up; up += up256((size_t)q.n * 32);
+        q.oMsd = up; if (q.wantInFrame) up += up256((size_t)q.n * 4);
+        q.oSum = dn; dn += up256(RELOC_SUM_DOUBLES * sizeof(double));
+        q.oPairs = dn; dn += up256((size_t)q.n * 4);
+        q.oInF = dn; if (q.wantInFrame) dn += up256((size_t)q.n);
+    }
+    plan.upCopyBytes = up;
+    for (int b = 0; b < B; b++) if (lanes[b].m) { lanes[b].oKeyWin = up; up += up256((size_t)RELOC_MAX_KEYS * sizeof(unsigned long long)); }
+    plan.upBytes = up; plan.dnBytes = dn;
+}
+
+vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
+                                    const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps) {
+    if (!plan.nOn) return VSLAM_OK;
+    const int H = P.n_hypotheses, nOn = plan.nOn;
+    // ---- the frames' keys: this stream after the extractors' last run; limits; capacities (all before the first launch) ----------
+    std::vector<vslam_extractor*> seen;
+    for (int b = 0; b < B; b++) {
+        vslam_matcher* m = lanes[b].m;
+        if (!m) continue;
+        for (vslam_extractor* fe : {m->feL, m->feR}) {
+            if (!fe || std::find(seen.begin(), seen.end(), fe) != seen.end()) continue;
+            seen.push_back(fe);
+            if (fe->evDone) VS_HIP(hipStreamWaitEvent(stream, fe->evDone, 0));
+        }
+        VS_CHECK(m->refresh_keys(false));
+        lanes[b].nL = m->nKeys[0];
+        if (lanes[b].nL > RELOC_MAX_KEYS) {
+            set_error("relocalize_batch: lane %d: %d left keypoints exceed the limit (%d)", b, lanes[b].nL, RELOC_MAX_KEYS);
+            return VSLAM_ERR_CAPACITY;
+        }
+    }
+    for (int b = 0; b < B; b++) {
+        vslam_matcher* m = lanes[b].m;
+        if (!m) continue;
+        VS_CHECK(m->ensure_reloc_cap(lanes[b].n, false));
+        VS_CHECK(m->ensure_pose_cap(std::max(lanes[b].nL, 1)));      // the refinement: at most one factor per left key
+        VS_CHECK(m->ensure_proj_cap(std::max(lanes[b].nL, 1)));
+    }
+    // ---- lane tables (active lanes only: entry k of both tables is the k-th active lane) -----------------------------------------
+    RelocLane* hT = (RelocLane*)blk.h_up;
+    PoseLane* hP = (PoseLane*)(blk.h_up + plan.oPose);
+    const RelocLane* dT = (const RelocLane*)blk.d_up;
+    const PoseLane* dP = (const PoseLane*)(blk.d_up + plan.oPose);
+    int k = 0;
+    for (int b = 0; b < B; b++) {
+        const RelocBatchLane& q = lanes[b];
+        vslam_matcher* m = q.m;
+        if (!m) continue;
+        RelocLane& L = hT[k];
+        L = RelocLane{};
+        L.nP = q.n; L.nL = q.nL;
+        L.descP = (const uint4*)(blk.d_up + q.oDesc); L.descL = (const uint4*)m->d_desc[0];
+        L.pts = (const double*)(blk.d_up + q.oXyz); L.msd = q.wantInFrame ? (const float*)(blk.d_up + q.oMsd) : nullptr;
+        L.maxHamming = P.max_hamming; L.ratioPct = P.ratio_pct; L.nHyp = H; L.minInliers = P.min_inliers; L.seed = P.seed;
+        L.dOut = m->d_rlD; L.keyWin = (unsigned long long*)(blk.d_up + q.oKeyWin); L.keyWinner = m->d_rlKeyWinner;
+        L.pairs = (int*)(blk.d_dn + q.oPairs);
+        L.kpsL = m->d_kps[0]; L.kpsR = m->d_kps[1]; L.depth = m->d_depth; L.rightIdxs = m->d_rightIdxs;
+        L.rec = (RelocRec*)m->d_rlRec; L.flags = m->d_rlFlags; L.counts = m->d_rlCounts; L.poses = m->d_rlPoses; L.out = m->d_rlOut;
+        int* outI = (int*)(m->d_rlOut + 16);
+        m->pose_lane(L.A, std::max(q.nL, 1), outI + 3, outI + 4, 1, 0, 0);      // problem size and gate: written by k_reloc_problem_b
+        L.probPoints = m->d_points; L.probFlags = m->d_flags; L.flagStride = (size_t)m->poseCap;
+        L.w = m->rig.width; L.h = m->rig.height; L.nLev = m->feL->nLevels; L.logScale = logScale;
+        L.inF = q.wantInFrame ? blk.d_dn + q.oInF : nullptr;
+        L.summary = (double*)(blk.d_dn + q.oSum);
+        hP[k] = PoseLane{};
+        hP[k].A = L.A;
+        m->rlLast[0] = q.n; m->rlLast[1] = q.nL; m->rlLast[2] = H; m->rlLast[3] = 0;
+        k++;
+    }
+    // ---- one upload, the stages once for all lanes, one download, one wait ---------------------------------------------------------
+    VS_HIP(hipMemcpyAsync(blk.d_up, blk.h_up, plan.upCopyBytes, hipMemcpyHostToDevice, stream));
+    VS_HIP(hipMemsetAsync(blk.d_up + plan.upCopyBytes, 0xFF, plan.upBytes - plan.upCopyBytes, stream));      // key winners: none
+    VS_HIP(hipMemsetAsync(blk.d_dn, 0xFF, plan.dnBytes, stream));                                              // pairs: -1
+    const int gx = (plan.maxN + 255) / 256;
+    StageTimer off; off.enabled = false;
+    StageTimer& T = tm ? *tm : off;
+    int t = T.begin("reloc_match");
+    if (gx) hipLaunchKernelGGL(k_reloc_match_b, dim3(gx, nOn), dim3(256), 0, stream, dT);
+    T.end(t);
+    t = T.begin("reloc_pairs");
+    hipLaunchKernelGGL(k_reloc_pairs_b, dim3(nOn), dim3(1024), 0, stream, dT);
+    T.end(t);
+    t = T.begin("reloc_ransac");
+    hipLaunchKernelGGL(k_reloc_ransac_b, dim3(H, nOn), dim3(64), 0, stream, dT);
+    hipLaunchKernelGGL(k_reloc_best_b, dim3(nOn), dim3(64), 0, stream, dT);
+    T.end(t);
+    t = T.begin("reloc_refine");
+    hipLaunchKernelGGL(k_reloc_problem_b, dim3(nOn), dim3(1024), 0, stream, dT);
+    launch_pose_batch(stream, dP, nOn);
+    T.end(t);
+    t = T.begin("reloc_inframe");
+    hipLaunchKernelGGL(k_reloc_inframe_b, dim3(std::max(gx, 1), nOn), dim3(256), 0, stream, dT);
+    T.end(t);
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipMemcpyAsync(blk.h_dn, blk.d_dn, plan.dnBytes, hipMemcpyDeviceToHost, stream));
+    VS_HIP(hipStreamSynchronize(stream));
+    for (int b = 0; b < B; b++) {
+        const RelocBatchLane& q = lanes[b];
+        if (!q.m) continue;
+        const double* s = (const double*)(blk.h_dn + q.oSum);
+        const int* sI = (const int*)(s + RELOC_SUM_INTS);
+        vslam_reloc_report& r = reps[b];
+        r = vslam_reloc_report{};
+        r.n_points = q.n; r.n_pairs = sI[0]; r.best_hypothesis = sI[1]; r.best_count = sI[2];
+        q.m->rlLast[3] = sI[0];
+        if (!sI[4]) continue;                               // fewer than three correspondences or no inlier: not refined, success = 0
+        r.n_inliers = sI[5]; r.n_stereo = sI[6];
+        r.lm.iterations = sI[7]; r.lm.inner_iterations = sI[8]; r.lm.initial_error = s[16]; r.lm.final_error = s[17]; r.lm.lambda = s[18];
+        r.success = sI[9];
+        if (r.success) memcpy(T_cw_out + 16 * (size_t)b, s, 16 * sizeof(double));
+    }
+    return VSLAM_OK;
+}
+
+static vslam_status reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dnBytes) {
+    const size_t need[2] = {std::max<size_t>(upBytes, 256), std::max<size_t>(dnBytes, 256)};
+    for (int k = 0; k < 2; k++) {
+        if (need[k] <= m->rlBlkCap[k]) continue;
+        VS_HIP(hipStreamSynchronize(m->stream));
+        if (m->rlBlk[2 * k]) hipHostFree(m->rlBlk[2 * k]);
+        hipFree(m->rlBlk[2 * k + 1]);
+        m->rlBlk[2 * k] = m->rlBlk[2 * k + 1] = nullptr; m->rlBlkCap[k] = 0;
+        const size_t cap = need[k] + need[k] / 2;
+        VS_HIP(hipHostMalloc((void**)&m->rlBlk[2 * k], cap, hipHostMallocDefault));
+        VS_HIP(hipMalloc((void**)&m->rlBlk[2 * k + 1], cap));
+        m->rlBlkCap[k] = cap;
+    }
+    return VSLAM_OK;
+}
+
 extern "C" {
+
+vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lanes, const double* const* points_xyz, const uint8_t* const* desc,
+                                    const int32_t* n_points, const vslam_reloc_params* params, double* T_cw_out, int32_t* const* pairs_out,
+                                    vslam_reloc_report* reports) {
+    if (!matchers || lanes <= 0 || !n_points || !T_cw_out || !reports) { set_error("relocalize_batch: invalid arguments"); return VSLAM_ERR_INVALID; }
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(params, P));
+    std::vector<RelocBatchLane> q((size_t)lanes);
+    vslam_matcher* first = nullptr;
+    for (int b = 0; b < lanes; b++) {
+        if (!matchers[b]) continue;
+        q[b].m = matchers[b]; q[b].n = n_points[b];
+        if (!first) first = matchers[b];
+        if (n_points[b] > 0 && (!points_xyz || !desc || !points_xyz[b] || !desc[b])) {
+            set_error("relocalize_batch: lane %d: invalid arguments", b);
+            return VSLAM_ERR_INVALID;
+        }
+    }
+    if (!first) return VSLAM_OK;
+    VS_CHECK(reloc_batch_check(q.data(), lanes, first->device));
+    VS_HIP(hipSetDevice(first->device));
+    for (int b = 0; b < lanes; b++)                         // work of the other matchers' own streams (key uploads, stereo) ends first
+        if (q[b].m && q[b].m->stream != first->stream) VS_HIP(hipStreamSynchronize(q[b].m->stream));
+    RelocBatchPlan plan;
+    reloc_batch_plan(q.data(), lanes, plan);
+    VS_CHECK(reloc_own_blocks(first, plan.upBytes, plan.dnBytes));
+    const RelocBlocks blk{first->rlBlk[0], first->rlBlk[1], first->rlBlk[2], first->rlBlk[3]};
+    for (int b = 0; b < lanes; b++) {
+        if (!q[b].m || q[b].n <= 0) continue;
+        memcpy(blk.h_up + q[b].oXyz, points_xyz[b], (size_t)q[b].n * 24);
+        memcpy(blk.h_up + q[b].oDesc, desc[b], (size_t)q[b].n * 32);
+    }
+    VS_CHECK(reloc_batch_run(q.data(), lanes, plan, blk, first->stream, P, 1.0, &first->timer, T_cw_out, reports));
+    for (int b = 0; b < lanes; b++)
+        if (q[b].m && q[b].n > 0 && pairs_out && pairs_out[b]) memcpy(pairs_out[b], blk.h_dn + q[b].oPairs, (size_t)q[b].n * sizeof(int));
+    return VSLAM_OK;
+}
 
 vslam_status vslam_relocalize(vslam_matcher* m, const double* points_xyz, const uint8_t* desc, int32_t n_points,
                               const vslam_reloc_params* params, double* T_cw_out, int32_t* pairs_out, vslam_reloc_report* report) {

@@ -753,30 +753,41 @@ vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int st
     else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
     VS_CHECK(vslam_extractor_run(fe));
     VS_CHECK(fm->stereo_match());
-    // every map point that is not an outlier, in creation order; the most recent 65536 if there are more
-    std::vector<int> ids;
-    std::vector<double> xyz; std::vector<uint8_t> desc; std::vector<float> msd;
-    {
-        std::lock_guard<std::mutex> lk(mapMutex);
-        for (int m = 0; m < (int)mapPoints.size(); m++) if (!mpOutlier[m]) ids.push_back(m);
-        if (ids.size() > 65536) ids.erase(ids.begin(), ids.end() - 65536);
-        const size_t n = ids.size();
-        xyz.resize(3 * n); desc.resize(32 * n); msd.resize(n);
-        for (size_t j = 0; j < n; j++) {
-            const SysMP& mp = mapPoints[ids[j]];
-            xyz[3 * j] = mp.wp[0]; xyz[3 * j + 1] = mp.wp[1]; xyz[3 * j + 2] = mp.wp[2];
-            memcpy(desc.data() + 32 * j, mp.desc, 32);
-            msd[j] = mp.maxScaleDist;
-        }
-    }
+    const size_t n = (size_t)reloc_candidates();
+    std::vector<double> xyz(3 * n); std::vector<uint8_t> desc(32 * n); std::vector<float> msd(n);
+    reloc_fill_upload(xyz.data(), desc.data(), msd.data());
     double T_cw[16];
-    VS_CHECK(fm->relocalize(xyz.data(), desc.data(), (int)ids.size(), prm, T_cw, nullptr, rep));
+    VS_CHECK(fm->relocalize(xyz.data(), desc.data(), (int)n, prm, T_cw, nullptr, rep));
     if (!rep->success) { memcpy(T_wc_out, camPose.data(), sizeof(double) * 16); return VSLAM_OK; }
     // the map points the new pose places inside the left image
-    const size_t n = ids.size();
     std::vector<float> pl(2 * n), pr(2 * n); std::vector<int> ll(n), lr(n); std::vector<uint8_t> inF(n), inFR(n);
     VS_CHECK(vslam_world_to_frame(fm, T_cw, (int)n, xyz.data(), msd.data(), (float)std::log((double)cfg.fe.scale), pl.data(), pr.data(),
                                   ll.data(), lr.data(), inF.data(), inFR.data()));
+    reloc_commit(T_cw, inF.data(), T_wc_out);
+    return VSLAM_OK;
+}
+
+// every map point that is not an outlier, in creation order; the most recent 65536 if there are more
+int vslam_system::reloc_candidates() {
+    std::lock_guard<std::mutex> lk(mapMutex);
+    rlIds.clear();
+    for (int m = 0; m < (int)mapPoints.size(); m++) if (!mpOutlier[m]) rlIds.push_back(m);
+    if (rlIds.size() > 65536) rlIds.erase(rlIds.begin(), rlIds.end() - 65536);
+    return (int)rlIds.size();
+}
+
+void vslam_system::reloc_fill_upload(double* xyz, uint8_t* desc, float* msd) {
+    std::lock_guard<std::mutex> lk(mapMutex);
+    for (size_t j = 0; j < rlIds.size(); j++) {
+        const SysMP& mp = mapPoints[rlIds[j]];
+        xyz[3 * j] = mp.wp[0]; xyz[3 * j + 1] = mp.wp[1]; xyz[3 * j + 2] = mp.wp[2];
+        memcpy(desc + 32 * j, mp.desc, 32);
+        msd[j] = mp.maxScaleDist;
+    }
+}
+
+// a successful relocalisation: the pose state of a frame tracked with zero predicted motion; inF: per candidate, inside the left image
+void vslam_system::reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out) {
     const M4 poseEst = m4_rigid_inv(m4_from(T_cw));
     std::lock_guard<std::mutex> lk(mapMutex);
     allFrames.push_back({false, -1, latestKF, m4_mul(keyFrames[latestKF].poseInv, poseEst)});      // addFrame
@@ -785,13 +796,12 @@ vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int st
     predNPoseRef = m4_identity();
     predNPose = poseEst; predNPoseInv = camPoseInv;
     active.clear();
-    for (size_t j = 0; j < n; j++) {
-        mpInFrame[ids[j]] = inF[j];
-        if (inF[j]) active.push_back(ids[j]);
+    for (size_t j = 0; j < rlIds.size(); j++) {
+        mpInFrame[rlIds[j]] = inF[j];
+        if (inF[j]) active.push_back(rlIds[j]);
     }
     lastMatches.clear(); lastOutliers.clear();
     memcpy(T_wc_out, camPose.data(), sizeof(double) * 16);
-    return VSLAM_OK;
 }
 
 // ---- the local-mapping pass on its schedule ---------------------------------------------------------------------------------

@@ -266,6 +266,11 @@ struct vslam_system {
     // relocalisation from the session's own map, without a pose prior (no reference counterpart; vslam_hip.h)
     vslam_status relocalize(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_reloc_params* prm,
                             double* T_wc_out, vslam_reloc_report* rep);
+    // its host steps, shared with vslam_batch_relocalize: the candidate list (returns its size), the upload arrays, the commit of a success
+    std::vector<int> rlIds;
+    int reloc_candidates();
+    void reloc_fill_upload(double* xyz, uint8_t* desc, float* msd);
+    void reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

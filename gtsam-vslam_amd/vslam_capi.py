@@ -274,13 +274,7 @@ class Matcher:
     def relocalize_debug(self):
         """(d1, i1, d2) per map point, winning map point per left key, count per hypothesis and the winner's inlier flag
         per correspondence of the last relocalize call (test tap)"""
-        sz = np.zeros(4, np.int32)
-        _chk(self.L.vslam_relocalize_debug(self.h, None, 0, None, 0, None, 0, None, 0, _p(sz)))
-        n, nL, H, Cn = (int(v) for v in sz)
-        d3 = np.zeros((max(n, 1), 3), np.int32); kw = np.zeros(max(nL, 1), np.int32)
-        hc = np.zeros(max(H, 1), np.int32); fl = np.zeros(max(Cn, 1), np.uint8)
-        _chk(self.L.vslam_relocalize_debug(self.h, _p(d3), n, _p(kw), nL, _p(hc), H, _p(fl), Cn, _p(sz)))
-        return dict(d=d3[:n], key_winner=kw[:nL], counts=hc[:H], flags=fl[:Cn])
+        return _reloc_debug(lambda *a: self.L.vslam_relocalize_debug(self.h, *a))
 
 
 MPV_DTYPE = np.dtype([("desc", "u1", 32), ("predLx", "<f4"), ("predLy", "<f4"), ("predRx", "<f4"),
@@ -309,6 +303,44 @@ def _reloc_report_dict(rep):
     d["lm"] = dict(iterations=rep.lm.iterations, inner=rep.lm.inner_iterations, initialError=rep.lm.initial_error,
                    finalError=rep.lm.final_error, lam=rep.lm.lam)
     return d
+
+
+def _reloc_debug(call):
+    """the arrays of a relocalize_debug tap; call(d3, cap, kw, cap, hc, cap, fl, cap, sizes4) is the bound C function"""
+    sz = np.zeros(4, np.int32)
+    _chk(call(None, 0, None, 0, None, 0, None, 0, _p(sz)))
+    n, nL, H, Cn = (int(v) for v in sz)
+    d3 = np.zeros((max(n, 1), 3), np.int32); kw = np.zeros(max(nL, 1), np.int32)
+    hc = np.zeros(max(H, 1), np.int32); fl = np.zeros(max(Cn, 1), np.uint8)
+    _chk(call(_p(d3), n, _p(kw), nL, _p(hc), H, _p(fl), Cn, _p(sz)))
+    return dict(d=d3[:n], key_winner=kw[:nL], counts=hc[:H], flags=fl[:Cn])
+
+
+def relocalize_batch(matchers, points, descs, T_out=None, **params):
+    """vslam_relocalize_batch: matchers / points / descs per lane (a None matcher: the lane is idle).  Returns (T [lanes, 4, 4],
+    reports, pairs): a lane's T row is written only on its success (T_out: the array to write into, e.g. pre-filled), its
+    report and pairs are None for an idle lane."""
+    B = len(matchers)
+    L = lib()
+    mh = (C.c_void_p * B)(); pp = (C.c_void_p * B)(); dp = (C.c_void_p * B)(); qp = (C.c_void_p * B)()
+    n = np.zeros(B, np.int32)
+    keep, pairs = [], [None] * B
+    for b, m in enumerate(matchers):
+        if m is None:
+            continue
+        x = np.ascontiguousarray(points[b], np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(descs[b], np.uint8).reshape(-1, 32)
+        assert len(x) == len(d)
+        pairs[b] = np.full(max(len(x), 1), -1, np.int32)
+        keep += [x, d]
+        mh[b], pp[b], dp[b], qp[b], n[b] = m.h.value, x.ctypes.data, d.ctypes.data, pairs[b].ctypes.data, len(x)
+    prm = RelocParams(**{k: int(v) for k, v in params.items()})
+    T = np.zeros((B, 4, 4)) if T_out is None else T_out
+    assert T.dtype == np.float64 and T.shape == (B, 4, 4) and T.flags.c_contiguous
+    reps = (RelocReport * B)()
+    _chk(L.vslam_relocalize_batch(mh, B, pp, dp, _p(n), C.byref(prm), _p(T), qp, reps))
+    return (T, [_reloc_report_dict(reps[b]) if matchers[b] is not None else None for b in range(B)],
+            [pairs[b][:n[b]] if matchers[b] is not None else None for b in range(B)])
 
 
 def match_projection(matcher, mps, rad, matchedL, matchedR, matches):
@@ -1536,6 +1568,27 @@ class Batch:
         else:
             _chk(self.L.vslam_batch_track_stereo_prefetch_color(self.h_b, lp, rp, int(st), int(ch), *args))
         return T, [_report_dict(reps[b]) for b in range(B)]
+
+    def relocalize(self, lefts, rights, frame_numbers, mask=None, on_device=False, stride=None, **params):
+        """vslam_batch_relocalize with gray frames: (T_wc [lanes, 4, 4], reports).  A masked lane's T row is the recovered
+        pose, or its unchanged camera pose on failure; the rows and reports (None) of lanes outside the mask are not written."""
+        B = self.lanes
+        T = np.zeros((B, 4, 4))
+        reps = (RelocReport * B)()
+        keep = []
+        lp, rp, st, ch = self._images(lefts, rights, mask, on_device, stride, 1, keep)
+        if ch != 1:
+            raise ValueError("relocalize takes gray frames")
+        fr = np.ascontiguousarray(frame_numbers, np.int32)
+        mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
+        prm = RelocParams(**{k: int(v) for k, v in params.items()})
+        _chk(self.L.vslam_batch_relocalize(self.h_b, lp, rp, int(st), int(on_device), _p(fr), _p(mk) if mk is not None else None,
+                                           C.byref(prm), _p(T), reps))
+        return T, [_reloc_report_dict(reps[b]) if mask is None or mask[b] else None for b in range(B)]
+
+    def relocalize_debug(self, lane):
+        """Matcher.relocalize_debug of lane `lane`: its part of the last relocalize call (test tap)"""
+        return _reloc_debug(lambda *a: self.L.vslam_batch_relocalize_debug(self.h_b, int(lane), *a))
 
     def _buckets(self, imu_buckets, keep):
         B = self.lanes

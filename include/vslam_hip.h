@@ -381,6 +381,23 @@ vslam_status vslam_relocalize(vslam_matcher* m, const double* points_xyz, const 
 vslam_status vslam_relocalize_debug(vslam_matcher* m, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner, int32_t cap_keys,
                                     int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags, int32_t cap_pairs,
                                     int32_t* sizes4);
+/* vslam_relocalize for several matchers ("lanes") in one call: one launch per stage for all of them (k_reloc_match_b,
+ * k_reloc_pairs_b, k_reloc_ransac_b, k_reloc_best_b with the lane as a grid dimension and a per-lane argument table), one
+ * upload, one download, one wait.  A lane's result IS what vslam_relocalize returns for that matcher, points and parameters,
+ * including step D's side effect on its stereo match: the kernels share their bodies with the one-session kernels.  Step D's
+ * problem is built on the device (k_reloc_problem_b: the winner's inliers compacted in correspondence order into the lane's
+ * pose buffers, with the problem size and a gate word the pose kernel reads there), so that no wait separates steps C and D;
+ * a lane with fewer than three correspondences or no inlier is not refined.
+ * matchers[b] = NULL: lane b is idle (its report, pairs and T_cw_out row are not written).  Every other matcher must be a
+ * different stereo matcher with a completed stereo match, all on one device, else VSLAM_ERR_INVALID; per lane the limits of
+ * vslam_relocalize (VSLAM_ERR_CAPACITY); after any error nothing has been launched.  params: one set for all lanes.
+ * T_cw_out [lanes][16]: a lane's row is written only on its success.  pairs_out and its entries may be NULL.
+ * Streams: matchers that do not share the first active matcher's stream are synchronised first (hipStreamSynchronize on
+ * their own streams); all work then runs on the first active matcher's stream, and the call returns after it has finished.
+ * vslam_relocalize_debug on a lane's matcher returns that lane's part of the last batched call. */
+vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lanes, const double* const* points_xyz,
+                                    const uint8_t* const* desc, const int32_t* n_points, const vslam_reloc_params* params,
+                                    double* T_cw_out, int32_t* const* pairs_out, vslam_reloc_report* reports);
 
 /* ---------------------------------------------------------------------------
  * Local bundle adjustment — replaces the numerical core of LocalMapper::localBA
@@ -975,6 +992,30 @@ vslam_status vslam_batch_track_stereo_prefetch_raw(vslam_batch* batch, const uin
  * the lane's matcher buffers, and the old session's key slabs (HBM) go to a free list of the batch, from which the
  * sessions of all lanes take before new memory is allocated; vslam_batch_destroy frees it. */
 vslam_status vslam_batch_restart_lane(vslam_batch* batch, int32_t lane, const vslam_system_config* config);
+/* Relocalisation of the lanes in lane_mask (NULL = all) from their own maps, in lockstep: for every such lane exactly what
+ * vslam_system_relocalize does for that session - mapping results due at frame_numbers[lane] land as in a tracked step, one
+ * extraction enqueue and one stereo launch set for all of them, the lane's non-outlier map points (creation order, the most
+ * recent 65536) gathered straight into the batch's pinned upload block, then the stages of vslam_relocalize_batch and
+ * k_reloc_inframe_b (the left-image test of every uploaded map point under the refined pose, for lanes that succeeded), one
+ * wait, one download.  Success and failure are committed per lane as vslam_system_relocalize commits them: on failure
+ * (reports[lane].success = 0) nothing in that session changes and its T_wc_out row is the unchanged camera pose.
+ * Gray, rectified frames; stereo lanes without IMU.  Lanes outside the mask are not touched: session, matcher state,
+ * mapping jobs in flight, T_wc_out row and report stay as they are.  VSLAM_ERR_INVALID, with a message that names the lane
+ * and nothing changed: an IMU batch, a masked lane without a map (also a restarted lane whose frame 0 has not been tracked),
+ * NULL images for a masked lane.  A pending prefetch is waited for and discarded (as vslam_batch_restart_lane does): the
+ * next step extracts its frames itself.  With timing on, the stages show in vslam_batch_timings as reloc_match,
+ * reloc_pairs, reloc_ransac, reloc_refine, reloc_inframe.  No device memory is allocated or freed in a steady-state call
+ * (a lane's relocalisation buffers are allocated at its first use; the blocks grow as a step's do).
+ * Intended use: the lanes that tracked go through vslam_batch_track_stereo with the lost lanes masked out, the lost lanes
+ * through this call with the same frame numbers. */
+vslam_status vslam_batch_relocalize(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                    int32_t on_device, const int32_t* frame_numbers, const uint8_t* lane_mask,
+                                    const vslam_reloc_params* params, double* T_wc_out /* [lanes][16] */,
+                                    vslam_reloc_report* reports /* [lanes] */);
+/* vslam_relocalize_debug on lane `lane`'s matcher: its part of the last vslam_batch_relocalize call (test tap) */
+vslam_status vslam_batch_relocalize_debug(vslam_batch* batch, int32_t lane, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner,
+                                          int32_t cap_keys, int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags,
+                                          int32_t cap_pairs, int32_t* sizes4);
 /* key slabs the batch has allocated in total (bytes), and how many of them sessions hold / the free list holds; any
  * pointer may be NULL */
 vslam_status vslam_batch_memory(vslam_batch* batch, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free);

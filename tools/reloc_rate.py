@@ -8,7 +8,13 @@ Reported: the wall-clock time of a call (host clock around the call, which ends 
 per kernel group from the matcher's HIP events (summed over a repetition's calls, divided by their number).  Five warm-up
 calls, then `reps` repetitions of `calls` calls each; median and range over the repetitions.  Beside it, as context only, the
 time of the numpy restatement (tests/reloc_ref.py, steps A - C and the CPU pose solve) on one core for the same input.
-usage: python tools/reloc_rate.py [out.json] [calls] [reps]"""
+usage: python tools/reloc_rate.py [out.json] [calls] [reps]
+
+--lanes: the batched call.  For L = 1, 4 and 16 lanes (L matchers on images 2b / 2b + 1 of one extractor, each with a frame and a
+map of the shape above from its own seed) the wall-clock time of ONE vslam_relocalize_batch call against L sequential
+vslam_relocalize calls on the same matchers, same build, same process.  Five warm-up calls of each form, then `reps` repetitions
+that alternate the two forms (`calls` calls each); host clock around calls that end in a device synchronise.
+usage: python tools/reloc_rate.py --lanes [out.json] [calls] [reps]"""
 import json, os, sys, time
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +59,58 @@ def build(seed=1):
                 points=points, desc=desc)
 
 
+def main_lanes(argv):
+    out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "reloc_batch_rate.json")
+    calls = int(argv[1]) if len(argv) > 1 else 30
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    if vc.device_count() < 1:
+        raise RuntimeError("reloc_rate needs a GPU: a time taken anywhere else says nothing about the stage")
+    LMAX = 16
+    ge = vc.Extractor(RIG["w"], RIG["h"], 1500, batch=2 * LMAX)
+    ms, gs = [], []
+    for b in range(LMAX):
+        g = build(seed=1 + b)
+        m = vc.Matcher(RIG, ge, 2 * b, ge, 2 * b + 1)
+        m.stereo_finalize_arrays(g["best"], g["depth"], g["sad"], N_KEYS)
+        m.set_keys(0, g["kL"], g["dL"]); m.set_keys(1, g["kR"], g["dR"])
+        m.set_timing(False)
+        ms.append(m); gs.append(g)
+    pts = [g["points"] for g in gs]; dsc = [g["desc"] for g in gs]
+    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, calls_per_repetition=calls, repetitions=reps, lanes={})
+    for L in (1, 4, 16):
+        def batched():
+            return vc.relocalize_batch(ms[:L], pts[:L], dsc[:L])
+
+        def sequential():
+            return [ms[b].relocalize(pts[b], dsc[b], pairs=True) for b in range(L)]
+
+        for _ in range(5):
+            Tb, repb, _ = batched()
+            seq = sequential()
+        same = all(repb[b][k] == seq[b][1][k] for b in range(L) for k in ("success", "n_pairs", "best_hypothesis", "best_count", "n_inliers", "n_stereo")) and \
+            all(seq[b][0] is not None and float(np.abs(seq[b][0] - Tb[b]).max()) < 1e-12 for b in range(L))
+        wb, ws = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                batched()
+            wb.append((time.perf_counter() - t0) / calls * 1e3)
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                sequential()
+            ws.append((time.perf_counter() - t0) / calls * 1e3)
+        stat = lambda v: dict(median=float(np.median(v)), min=min(v), max=max(v))
+        res["lanes"][str(L)] = dict(batched_call_ms=stat(wb), sequential_calls_ms=stat(ws), batched_over_sequential=float(np.median(wb) / np.median(ws)),
+                                    batched_ms_per_lane=float(np.median(wb)) / L, lanes_equal_the_single_calls=bool(same),
+                                    inliers=[repb[b]["n_inliers"] for b in range(L)])
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--lanes":
+        return main_lanes(sys.argv[2:])
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reloc_rate.json")
     calls = int(sys.argv[2]) if len(sys.argv) > 2 else 50
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
