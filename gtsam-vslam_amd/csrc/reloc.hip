@@ -9,6 +9,9 @@
 //   k_reloc_ransac  one wave per hypothesis: three sampled correspondences -> rigid pose (fp64), scored over all records
 //   k_reloc_best    one wave: the winning hypothesis and its inlier flags
 // The winner's inliers are refined by the existing motion-only LM (vslam_matcher::estimate_pose).
+// vslam_reloc_params::mode = 1 (hypotheses from 2D-3D correspondences, restated by tests/reloc_p3p_ref.py): the same bodies with
+// MODE = 1 behind k_reloc_pairs_p3p (every winning pair, the key's unit bearing in the X_c slot), k_reloc_ransac_p3p (a P3P solver
+// in fp64: up to four poses per hypothesis, all scored in one pass over the records) and k_reloc_best_p3p; k_reloc_match is shared.
 // Several lanes in one call (vslam_relocalize_batch, vslam_batch_relocalize): the k_*_b forms of the four kernels - the same bodies,
 // the lane as a grid dimension, arguments from a RelocLane table - then
 //   k_reloc_problem_b  the refinement problem built on the device (no wait before step D), refined by k_pose_lm_b behind a gate
@@ -25,10 +28,11 @@ constexpr int RELOC_MAX_HYP = 1024;
 constexpr int RELOC_DRAWS = 16;               // sample indices tried per hypothesis
 
 struct RelocRec {            // one correspondence: map point p <-> left key i
-    double Xw[3], Xc[3];     // world position of p; key i back-projected with its depth (camera frame)
-    float kx, ky, kxr;       // left keypoint, x of the matched right keypoint
-    int octave, p, i;
+    double Xw[3], Xc[3];     // world position of p; key i back-projected with its depth (camera frame).  Mode 1: Xc = the key's unit bearing
+    float kx, ky, kxr;       // left keypoint, x of the matched right keypoint (mode 1: 0 without the stereo flag)
+    int octave, p, i;        // mode 1: octave + RELOC_STEREO_BIT with the stereo flag (estimatedDepth > 0 && rightIdxs >= 0)
 };
+constexpr int RELOC_STEREO_BIT = 256;
 static_assert(sizeof(RelocRec) == 72, "records are downloaded as plain bytes");
 
 __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
@@ -78,6 +82,7 @@ __global__ __launch_bounds__(256) void k_reloc_match_b(const RelocLane* __restri
     reloc_match_body(L.nP, L.descP, L.nL, L.descL, L.maxHamming, L.ratioPct, L.dOut, L.keyWin);
 }
 
+template <int MODE>
 __device__ __forceinline__ void reloc_pairs_body(int nL, const unsigned long long* __restrict__ keyWin,
                                                  const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
                                                  const float* __restrict__ depth, const int* __restrict__ rightIdxs,
@@ -96,19 +101,28 @@ __device__ __forceinline__ void reloc_pairs_body(int nL, const unsigned long lon
             keyWinner[i] = p;
             z = depth[i]; ri = rightIdxs[i];
         }
-        const bool keep = p >= 0 && z > 0 && ri >= 0;       // a winner on a key without depth is dropped; the key stays lost to the loser
+        const bool stereo = z > 0 && ri >= 0;
+        const bool keep = p >= 0 && (MODE == 1 || stereo);  // mode 0: a winner on a key without depth is dropped; the key stays lost to the loser
         int tot;
         const int pos = run + block_excl_scan_1024(keep, wsum, tot);
         if (keep) {
             const vslam_keypoint k = kpsL[i];
             RelocRec r;
             r.Xw[0] = pts[3 * (size_t)p]; r.Xw[1] = pts[3 * (size_t)p + 1]; r.Xw[2] = pts[3 * (size_t)p + 2];
-            const double zp = (double)z;                    // back-projection exactly as k_init_map
-            r.Xc[0] = ((double)k.x - cx) * zp / fx;
-            r.Xc[1] = ((double)k.y - cy) * zp / fy;
-            r.Xc[2] = zp;
-            r.kx = k.x; r.ky = k.y; r.kxr = kpsR[ri].x;
-            r.octave = k.octave; r.p = p; r.i = i;
+            if constexpr (MODE == 0) {
+                const double zp = (double)z;                // back-projection exactly as k_init_map
+                r.Xc[0] = ((double)k.x - cx) * zp / fx;
+                r.Xc[1] = ((double)k.y - cy) * zp / fy;
+                r.Xc[2] = zp;
+                r.kx = k.x; r.ky = k.y; r.kxr = kpsR[ri].x;
+                r.octave = k.octave; r.p = p; r.i = i;
+            } else {                                        // the unit bearing of the key: ((kx - cx) / fx, (ky - cy) / fy, 1) / its norm
+                const double bx = ((double)k.x - cx) / fx, by = ((double)k.y - cy) / fy;
+                const double nb = sqrt((bx * bx + by * by) + 1.0);
+                r.Xc[0] = bx / nb; r.Xc[1] = by / nb; r.Xc[2] = 1.0 / nb;
+                r.kx = k.x; r.ky = k.y; r.kxr = stereo ? kpsR[ri].x : 0.f;
+                r.octave = k.octave + (stereo ? RELOC_STEREO_BIT : 0); r.p = p; r.i = i;
+            }
             rec[pos] = r;
             pairs[p] = i;
         }
@@ -123,13 +137,26 @@ __global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned lon
                                                       const double* __restrict__ pts, double fx, double fy, double cx, double cy,
                                                       RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
                                                       int* __restrict__ out) {
-    reloc_pairs_body(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
+    reloc_pairs_body<0>(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
+}
+__global__ __launch_bounds__(1024) void k_reloc_pairs_p3p(int nL, const unsigned long long* __restrict__ keyWin,
+                                                          const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
+                                                          const float* __restrict__ depth, const int* __restrict__ rightIdxs,
+                                                          const double* __restrict__ pts, double fx, double fy, double cx, double cy,
+                                                          RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
+                                                          int* __restrict__ out) {
+    reloc_pairs_body<1>(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
 }
 // one workgroup per lane
 __global__ __launch_bounds__(1024) void k_reloc_pairs_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.x);
-    reloc_pairs_body(L.nL, L.keyWin, L.kpsL, L.kpsR, L.depth, L.rightIdxs, L.pts, L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.rec, L.pairs, L.keyWinner,
-                     (int*)(L.out + 16));
+    reloc_pairs_body<0>(L.nL, L.keyWin, L.kpsL, L.kpsR, L.depth, L.rightIdxs, L.pts, L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.rec, L.pairs, L.keyWinner,
+                        (int*)(L.out + 16));
+}
+__global__ __launch_bounds__(1024) void k_reloc_pairs_p3p_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    reloc_pairs_body<1>(L.nL, L.keyWin, L.kpsL, L.kpsR, L.depth, L.rightIdxs, L.pts, L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.rec, L.pairs, L.keyWinner,
+                        (int*)(L.out + 16));
 }
 
 __device__ __forceinline__ unsigned reloc_mix(unsigned s, unsigned h, unsigned j) {
@@ -199,6 +226,222 @@ __device__ __forceinline__ bool reloc_inlier(const RelocRec& r, const DPose& T, 
     return !((eu * eu + ev * ev + eur * eur) * (double)lvl[r.octave] > A.thres);
 }
 
+// ---- mode 1: poses from three (world point, unit bearing) pairs -------------------------------------------------------------------
+// The solver of tests/reloc_p3p_ref.py, operation for operation (fp64 + - * / and sqrt, every sum and product associated as there;
+// the library is built with -ffp-contract=off): the depths l along the bearings obey l^T M12 l = a12, l^T M13 l = a13,
+// l^T M23 l = a23; D1 = a23 M12 - a12 M23 and D2 = a23 M13 - a13 M23 are homogeneous, a real root g of det(D1 + g D2) makes
+// D0 = D1 + g D2 a pair of planes, each plane and the other conic of the pencil give a quadratic in l3 / l2.  Everything is
+// wave-uniform; nothing is indexed dynamically (slots and selections are written out).
+constexpr int P3P_CUBIC_STEPS = 16, P3P_REFINE_STEPS = 3;
+
+// the sampling rule of reloc_hypothesis (that function keeps its own copy: its code object is held to the one before mode 1 existed)
+__device__ __forceinline__ bool reloc_sample(int C, unsigned seed, int h, int* idx) {
+    if (C < 3) return false;
+    idx[0] = idx[1] = idx[2] = -1;
+    int got = 0;
+#pragma unroll
+    for (int j = 0; j < RELOC_DRAWS; j++) {
+        const int v = (int)(((unsigned long long)reloc_mix(seed, (unsigned)h, (unsigned)j) * (unsigned long long)C) >> 32);
+        const bool fresh = got < 3 && v != idx[0] && v != idx[1];
+        if (fresh) {
+            if (got == 0) idx[0] = v; else if (got == 1) idx[1] = v; else idx[2] = v;
+            got++;
+        }
+    }
+    return got == 3;
+}
+
+struct Sym3 { double m00, m01, m02, m11, m12, m22; };
+
+__device__ __forceinline__ Sym3 sym3_adj(const Sym3& a) {
+    Sym3 r;
+    r.m00 = a.m11 * a.m22 - a.m12 * a.m12; r.m01 = a.m02 * a.m12 - a.m01 * a.m22; r.m02 = a.m01 * a.m12 - a.m02 * a.m11;
+    r.m11 = a.m00 * a.m22 - a.m02 * a.m02; r.m12 = a.m01 * a.m02 - a.m00 * a.m12; r.m22 = a.m00 * a.m11 - a.m01 * a.m01;
+    return r;
+}
+__device__ __forceinline__ double sym3_tr(const Sym3& a, const Sym3& b) {      // trace(a b)
+    return ((a.m00 * b.m00 + a.m11 * b.m11) + a.m22 * b.m22) + 2.0 * ((a.m01 * b.m01 + a.m02 * b.m02) + a.m12 * b.m12);
+}
+__device__ __forceinline__ double sq3(double x, double y, double z) { return (x * x + y * y) + z * z; }
+__device__ __forceinline__ int first_max3(double a, double b, double c) {
+    int k = 0; double m = a;
+    if (b > m) { k = 1; m = b; }
+    if (c > m) k = 2;
+    return k;
+}
+__device__ __forceinline__ double sel3(int k, double a, double b, double c) { return k == 0 ? a : k == 1 ? b : c; }
+
+// a real root of x^3 + b x^2 + c x + d: a start outside the stationary points, then a fixed number of Newton steps
+__device__ __forceinline__ double p3p_cubic_root(double b, double c, double d) {
+    const double bb = b * b, tc = 3.0 * c;
+    double r;
+    if (bb >= tc) {
+        const double v = sqrt(bb - tc);
+        const double t1 = (-b - v) / 3.0;
+        double k = ((t1 + b) * t1 + c) * t1 + d;
+        if (k > 0) r = t1 - sqrt(-k / (3.0 * t1 + b));
+        else {
+            const double t2 = (-b + v) / 3.0;
+            k = ((t2 + b) * t2 + c) * t2 + d;
+            r = t2 + sqrt(-k / (3.0 * t2 + b));
+        }
+    } else {
+        r = -b / 3.0;
+        const double s = (3.0 * r + 2.0 * b) * r + c;
+        if ((s < 0 ? -s : s) < 1e-4) r = r + 1.0;
+    }
+#pragma unroll 1
+    for (int it = 0; it < P3P_CUBIC_STEPS; it++) {
+        const double fx = ((r + b) * r + c) * r + d;
+        const double fp = (3.0 * r + 2.0 * b) * r + c;
+        r = r - fx / fp;
+    }
+    return r;
+}
+
+struct P3PCoef { double a12, a13, a23, c12, c13, c23; };
+
+// one root tau = l3 / l2 on the plane l1 = w0 l2 + w1 l3: the depths, polished on the three original equations; false = void
+__device__ __forceinline__ bool p3p_depths(const P3PCoef& q, double w0, double w1, double tau, double& l1, double& l2, double& l3) {
+    const double den = tau * (tau - 2.0 * q.c23) + 1.0;
+    l2 = sqrt(q.a23 / den);
+    l3 = tau * l2;
+    l1 = w0 * l2 + w1 * l3;
+    if (!(tau > 0 && l1 > 0)) return false;
+#pragma unroll 1
+    for (int it = 0; it < P3P_REFINE_STEPS; it++) {
+        const double h1 = 0.5 * (((l1 * l1 + l2 * l2) - ((2.0 * q.c12) * l1) * l2) - q.a12);
+        const double h2 = 0.5 * (((l1 * l1 + l3 * l3) - ((2.0 * q.c13) * l1) * l3) - q.a13);
+        const double h3 = 0.5 * (((l2 * l2 + l3 * l3) - ((2.0 * q.c23) * l2) * l3) - q.a23);
+        const double j11 = l1 - q.c12 * l2, j12 = l2 - q.c12 * l1;
+        const double j21 = l1 - q.c13 * l3, j23 = l3 - q.c13 * l1;
+        const double j32 = l2 - q.c23 * l3, j33 = l3 - q.c23 * l2;
+        const double det = -((j11 * j23) * j32) - (j12 * j21) * j33;
+        const double u = h2 * j33 - j23 * h3;
+        const double d1 = (-(h1 * (j23 * j32)) - j12 * u) / det;
+        const double d2 = (j11 * u - h1 * (j21 * j33)) / det;
+        const double d3 = ((h1 * (j21 * j32) - j11 * (h2 * j32)) - j12 * (j21 * h3)) / det;
+        l1 = l1 - d1; l2 = l2 - d2; l3 = l3 - d3;
+    }
+    const double inf = __builtin_huge_val();
+    return l1 > 0 && l1 < inf && l2 > 0 && l2 < inf && l3 > 0 && l3 < inf;
+}
+
+// the pose between the world triple's frame (e1, e2, e3) and the frame of the camera points l_k y_k; false = void
+__device__ __forceinline__ bool p3p_pose(const double* X0, const double* y0, const double* y1, const double* y2, const double* e1, const double* e2,
+                                         const double* e3, double l1, double l2, double l3, DPose& T) {
+    const double Y0[3] = {l1 * y0[0], l1 * y0[1], l1 * y0[2]}, Y1[3] = {l2 * y1[0], l2 * y1[1], l2 * y1[2]}, Y2[3] = {l3 * y2[0], l3 * y2[1], l3 * y2[2]};
+    double f1[3], f2[3], f3[3];
+    if (!reloc_frame(Y0, Y1, Y2, f1, f2, f3)) return false;
+    const double inf = __builtin_huge_val();
+    bool fin = true;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double v = f1[r] * e1[c] + f2[r] * e2[c] + f3[r] * e3[c];
+            T.R[3 * r + c] = v;
+            fin = fin && v > -inf && v < inf;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const double v = Y0[r] - (T.R[3 * r] * X0[0] + T.R[3 * r + 1] * X0[1] + T.R[3 * r + 2] * X0[2]);
+        T.t[r] = v;
+        fin = fin && v > -inf && v < inf;
+    }
+    return fin;
+}
+
+// the two solution slots of one plane (normal n): smaller tau first
+__device__ __forceinline__ void p3p_plane(const P3PCoef& q, const Sym3& E, double n0, double n1, double n2, const double* X0, const double* y0,
+                                          const double* y1, const double* y2, const double* e1, const double* e2, const double* e3,
+                                          DPose& Ta, bool& oka, DPose& Tb, bool& okb) {
+    oka = okb = false;
+    const double w0 = -(n1 / n0), w1 = -(n2 / n0);
+    const double qa = ((E.m00 * w1) * w1 + (2.0 * E.m02) * w1) + E.m22;
+    const double hb = ((E.m00 * w0) * w1 + E.m01 * w1) + (E.m02 * w0 + E.m12);
+    const double qc = ((E.m00 * w0) * w0 + (2.0 * E.m01) * w0) + E.m11;
+    const double disc = hb * hb - qa * qc;
+    if (!(disc >= 0)) return;
+    const double sq = sqrt(disc);
+    double l1, l2, l3;
+    if (p3p_depths(q, w0, w1, (-hb - sq) / qa, l1, l2, l3)) oka = p3p_pose(X0, y0, y1, y2, e1, e2, e3, l1, l2, l3, Ta);
+    if (p3p_depths(q, w0, w1, (-hb + sq) / qa, l1, l2, l3)) okb = p3p_pose(X0, y0, y1, y2, e1, e2, e3, l1, l2, l3, Tb);
+}
+
+// hypothesis h in mode 1: up to four camera <- world poses in slots 0 .. 3 (ok[s] false = void)
+__device__ __forceinline__ void reloc_hypothesis_p3p(const RelocRec* __restrict__ rec, int C, unsigned seed, int h, DPose& T0, DPose& T1, DPose& T2,
+                                                     DPose& T3, bool& ok0, bool& ok1, bool& ok2, bool& ok3) {
+    ok0 = ok1 = ok2 = ok3 = false;
+    int idx[3];
+    if (!reloc_sample(C, seed, h, idx)) return;
+    const RelocRec &r0 = rec[idx[0]], &r1 = rec[idx[1]], &r2 = rec[idx[2]];
+    const double X0[3] = {r0.Xw[0], r0.Xw[1], r0.Xw[2]}, X1[3] = {r1.Xw[0], r1.Xw[1], r1.Xw[2]}, X2[3] = {r2.Xw[0], r2.Xw[1], r2.Xw[2]};
+    const double y0[3] = {r0.Xc[0], r0.Xc[1], r0.Xc[2]}, y1[3] = {r1.Xc[0], r1.Xc[1], r1.Xc[2]}, y2[3] = {r2.Xc[0], r2.Xc[1], r2.Xc[2]};
+    double e1[3], e2[3], e3[3];
+    if (!reloc_frame(X0, X1, X2, e1, e2, e3)) return;                       // coincident or collinear world points
+    // coincident bearings
+    if (sq3(y0[1] * y1[2] - y0[2] * y1[1], y0[2] * y1[0] - y0[0] * y1[2], y0[0] * y1[1] - y0[1] * y1[0]) < 1e-12) return;
+    if (sq3(y0[1] * y2[2] - y0[2] * y2[1], y0[2] * y2[0] - y0[0] * y2[2], y0[0] * y2[1] - y0[1] * y2[0]) < 1e-12) return;
+    if (sq3(y1[1] * y2[2] - y1[2] * y2[1], y1[2] * y2[0] - y1[0] * y2[2], y1[0] * y2[1] - y1[1] * y2[0]) < 1e-12) return;
+    P3PCoef q;
+    q.a12 = sq3(X0[0] - X1[0], X0[1] - X1[1], X0[2] - X1[2]);
+    q.a13 = sq3(X0[0] - X2[0], X0[1] - X2[1], X0[2] - X2[2]);
+    q.a23 = sq3(X1[0] - X2[0], X1[1] - X2[1], X1[2] - X2[2]);
+    q.c12 = (y0[0] * y1[0] + y0[1] * y1[1]) + y0[2] * y1[2];
+    q.c13 = (y0[0] * y2[0] + y0[1] * y2[1]) + y0[2] * y2[2];
+    q.c23 = (y1[0] * y2[0] + y1[1] * y2[1]) + y1[2] * y2[2];
+    Sym3 D1, D2;
+    D1.m00 = q.a23; D1.m01 = -(q.a23 * q.c12); D1.m02 = 0.0; D1.m11 = q.a23 - q.a12; D1.m12 = q.a12 * q.c23; D1.m22 = -q.a12;
+    D2.m00 = q.a23; D2.m01 = 0.0; D2.m02 = -(q.a23 * q.c13); D2.m11 = -q.a13; D2.m12 = q.a13 * q.c23; D2.m22 = q.a23 - q.a13;
+    const Sym3 A1 = sym3_adj(D1), A2 = sym3_adj(D2);
+    const double k0 = (D1.m00 * A1.m00 + D1.m01 * A1.m01) + D1.m02 * A1.m02;
+    const double k3 = (D2.m00 * A2.m00 + D2.m01 * A2.m01) + D2.m02 * A2.m02;
+    const double k1 = sym3_tr(A1, D2), k2 = sym3_tr(A2, D1);
+    const double g = p3p_cubic_root(k2 / k3, k1 / k3, k0 / k3);
+    Sym3 D0;
+    D0.m00 = D1.m00 + g * D2.m00; D0.m01 = D1.m01 + g * D2.m01; D0.m02 = D1.m02 + g * D2.m02;
+    D0.m11 = D1.m11 + g * D2.m11; D0.m12 = D1.m12 + g * D2.m12; D0.m22 = D1.m22 + g * D2.m22;
+    const Sym3 B = sym3_adj(D0);
+    // adj(D0) = -p p^T: the column of the most negative diagonal entry
+    const int k = first_max3(-B.m00, -B.m11, -B.m22);
+    const double bm = sel3(k, B.m00, B.m11, B.m22);
+    if (!(bm < 0)) return;
+    const double s = sqrt(-bm);
+    const double p0 = sel3(k, B.m00, B.m01, B.m02) / s, p1 = sel3(k, B.m01, B.m11, B.m12) / s, p2 = sel3(k, B.m02, B.m12, B.m22) / s;
+    // N = D0 + [p]x has rank one: its rows are multiples of one plane's normal, its columns of the other's
+    const double N00 = D0.m00, N01 = D0.m01 - p2, N02 = D0.m02 + p1;
+    const double N10 = D0.m01 + p2, N11 = D0.m11, N12 = D0.m12 - p0;
+    const double N20 = D0.m02 - p1, N21 = D0.m12 + p0, N22 = D0.m22;
+    const int kr = first_max3(sq3(N00, N01, N02), sq3(N10, N11, N12), sq3(N20, N21, N22));
+    const int kc = first_max3(sq3(N00, N10, N20), sq3(N01, N11, N21), sq3(N02, N12, N22));
+    const double ag = g < 0 ? -g : g;
+    const bool useD2 = ag <= 1.0;                                           // the conic of the pencil farther from D0
+    Sym3 E;
+    E.m00 = useD2 ? D2.m00 : D1.m00; E.m01 = useD2 ? D2.m01 : D1.m01; E.m02 = useD2 ? D2.m02 : D1.m02;
+    E.m11 = useD2 ? D2.m11 : D1.m11; E.m12 = useD2 ? D2.m12 : D1.m12; E.m22 = useD2 ? D2.m22 : D1.m22;
+    p3p_plane(q, E, sel3(kr, N00, N10, N20), sel3(kr, N01, N11, N21), sel3(kr, N02, N12, N22), X0, y0, y1, y2, e1, e2, e3, T0, ok0, T1, ok1);
+    p3p_plane(q, E, sel3(kc, N00, N01, N02), sel3(kc, N10, N11, N12), sel3(kc, N20, N21, N22), X0, y0, y1, y2, e1, e2, e3, T2, ok2, T3, ok3);
+}
+
+// mode-1 chi2 test of one correspondence under T: left u, left v and, with the stereo flag, right u - against the same bound
+__device__ __forceinline__ bool reloc_inlier_p3p(const double* Xw, float kx, float ky, float kxr, bool stereo, double w, const DPose& T,
+                                                 const PoseArgs& A) {
+    double pc[3];
+    mat3_vec(T.R, Xw, pc);
+#pragma unroll
+    for (int k = 0; k < 3; k++) pc[k] += T.t[k];
+    if (!(pc[2] > 0)) return false;
+    const double pr[3] = {pc[0] - A.b, pc[1], pc[2]};
+    double eu, ev, eur, evr;
+    reproj_residual(pc, kx, ky, A, eu, ev);
+    reproj_residual(pr, kxr, ky, A, eur, evr);
+    const double val = stereo ? (eu * eu + ev * ev + eur * eur) * w : (eu * eu + ev * ev) * w;
+    return !(val > A.thres);
+}
+
+template <int MODE>
 __device__ __forceinline__ void reloc_ransac_body(const PoseArgs& A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
                                                   unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
     __shared__ float sLvl[MAX_LEVELS];
@@ -207,13 +450,51 @@ __device__ __forceinline__ void reloc_ransac_body(const PoseArgs& A, const Reloc
     const int C = *nRec;
     DPose T;
     int count = 0;
-    const bool valid = reloc_hypothesis(rec, C, seed, h, T);      // (the same value in every lane)
-    if (valid) {
-        for (int base = 0; base < C; base += 64) {
-            const int c = base + lane;
-            const bool in = c < C && reloc_inlier(rec[c], T, A, sLvl);
-            count += __popcll(__ballot(in));
+    bool valid;
+    if constexpr (MODE == 0) {
+        valid = reloc_hypothesis(rec, C, seed, h, T);             // (the same value in every lane)
+        if (valid) {
+            for (int base = 0; base < C; base += 64) {
+                const int c = base + lane;
+                const bool in = c < C && reloc_inlier(rec[c], T, A, sLvl);
+                count += __popcll(__ballot(in));
+            }
         }
+    } else {
+        // up to four poses, scored in ONE pass: a lane loads its record once and tests it against every valid slot
+        DPose T1, T2, T3;
+        bool ok0, ok1, ok2, ok3;
+        reloc_hypothesis_p3p(rec, C, seed, h, T, T1, T2, T3, ok0, ok1, ok2, ok3);
+        valid = ok0 || ok1 || ok2 || ok3;
+        int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+        if (valid) {
+            for (int base = 0; base < C; base += 64) {
+                const int c = base + lane;
+                const bool live = c < C;
+                const RelocRec& r = rec[live ? c : 0];
+                const double Xw[3] = {r.Xw[0], r.Xw[1], r.Xw[2]};
+                const float kx = r.kx, ky = r.ky, kxr = r.kxr;
+                const int oct = r.octave;
+                const bool stereo = (oct & RELOC_STEREO_BIT) != 0;
+                const double w = (double)sLvl[oct & (RELOC_STEREO_BIT - 1)];
+                if (ok0) n0 += __popcll(__ballot(live && reloc_inlier_p3p(Xw, kx, ky, kxr, stereo, w, T, A)));
+                if (ok1) n1 += __popcll(__ballot(live && reloc_inlier_p3p(Xw, kx, ky, kxr, stereo, w, T1, A)));
+                if (ok2) n2 += __popcll(__ballot(live && reloc_inlier_p3p(Xw, kx, ky, kxr, stereo, w, T2, A)));
+                if (ok3) n3 += __popcll(__ballot(live && reloc_inlier_p3p(Xw, kx, ky, kxr, stereo, w, T3, A)));
+            }
+        }
+        // the largest count over the valid slots, the lowest slot on a tie; its pose is the hypothesis's
+        int bs = -1;
+        count = -1;
+        if (ok0 && n0 > count) { count = n0; bs = 0; }
+        if (ok1 && n1 > count) { count = n1; bs = 1; }
+        if (ok2 && n2 > count) { count = n2; bs = 2; }
+        if (ok3 && n3 > count) { count = n3; bs = 3; }
+        if (bs < 0) count = 0;
+#pragma unroll
+        for (int k = 0; k < 9; k++) T.R[k] = bs == 1 ? T1.R[k] : bs == 2 ? T2.R[k] : bs == 3 ? T3.R[k] : T.R[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) T.t[k] = bs == 1 ? T1.t[k] : bs == 2 ? T2.t[k] : bs == 3 ? T3.t[k] : T.t[k];
     }
     if (lane == 0) {
         counts[h] = count;
@@ -225,14 +506,23 @@ __device__ __forceinline__ void reloc_ransac_body(const PoseArgs& A, const Reloc
 
 __global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
                                                      unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
-    reloc_ransac_body(A, rec, nRec, seed, counts, poses);
+    reloc_ransac_body<0>(A, rec, nRec, seed, counts, poses);
+}
+__global__ __launch_bounds__(64) void k_reloc_ransac_p3p(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
+                                                         unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
+    reloc_ransac_body<1>(A, rec, nRec, seed, counts, poses);
 }
 // grid (hypotheses, lanes)
 __global__ __launch_bounds__(64) void k_reloc_ransac_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.y);
-    reloc_ransac_body(L.A, L.rec, (const int*)(L.out + 16), L.seed, L.counts, L.poses);
+    reloc_ransac_body<0>(L.A, L.rec, (const int*)(L.out + 16), L.seed, L.counts, L.poses);
+}
+__global__ __launch_bounds__(64) void k_reloc_ransac_p3p_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.y);
+    reloc_ransac_body<1>(L.A, L.rec, (const int*)(L.out + 16), L.seed, L.counts, L.poses);
 }
 
+template <int MODE>
 __device__ __forceinline__ void reloc_best_body(const PoseArgs& A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
                                                 const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
     __shared__ float sLvl[MAX_LEVELS];
@@ -258,7 +548,14 @@ __device__ __forceinline__ void reloc_best_body(const PoseArgs& A, const RelocRe
     for (int k = 0; k < 9; k++) T.R[k] = o[k];
 #pragma unroll
     for (int k = 0; k < 3; k++) T.t[k] = o[9 + k];
-    for (int c = lane; c < C; c += 64) flags[c] = bc > 0 && reloc_inlier(rec[c], T, A, sLvl) ? 1 : 0;
+    for (int c = lane; c < C; c += 64) {
+        if constexpr (MODE == 0) flags[c] = bc > 0 && reloc_inlier(rec[c], T, A, sLvl) ? 1 : 0;
+        else {
+            const RelocRec& r = rec[c];
+            const int oct = r.octave;
+            flags[c] = bc > 0 && reloc_inlier_p3p(r.Xw, r.kx, r.ky, r.kxr, (oct & RELOC_STEREO_BIT) != 0, (double)sLvl[oct & (RELOC_STEREO_BIT - 1)], T, A) ? 1 : 0;
+        }
+    }
     if (lane == 0) {
         pose_to_rm16(T, out);
         outI[1] = bh; outI[2] = bc;
@@ -267,12 +564,20 @@ __device__ __forceinline__ void reloc_best_body(const PoseArgs& A, const RelocRe
 
 __global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
                                                    const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
-    reloc_best_body(A, rec, nHyp, counts, poses, out, flags);
+    reloc_best_body<0>(A, rec, nHyp, counts, poses, out, flags);
+}
+__global__ __launch_bounds__(64) void k_reloc_best_p3p(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
+                                                       const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
+    reloc_best_body<1>(A, rec, nHyp, counts, poses, out, flags);
 }
 // one wave per lane
 __global__ __launch_bounds__(64) void k_reloc_best_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.x);
-    reloc_best_body(L.A, L.rec, L.nHyp, L.counts, L.poses, L.out, L.flags);
+    reloc_best_body<0>(L.A, L.rec, L.nHyp, L.counts, L.poses, L.out, L.flags);
+}
+__global__ __launch_bounds__(64) void k_reloc_best_p3p_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    reloc_best_body<1>(L.A, L.rec, L.nHyp, L.counts, L.poses, L.out, L.flags);
 }
 
 // The refinement problem of a lane, built where the one-session call builds it on the host: the winner's inlier correspondences, in
@@ -382,6 +687,10 @@ vslam_status vslam::reloc_resolve_params(const vslam_reloc_params* prm, vslam_re
         set_error("relocalize: parameters out of range (max_hamming 0..256, ratio_pct 0..100, n_hypotheses 1..%d, min_inliers >= 0)", RELOC_MAX_HYP);
         return VSLAM_ERR_INVALID;
     }
+    if (P.mode != 0 && P.mode != 1) {
+        set_error("relocalize: mode %d (0: hypotheses from stereo-triangulated keys, 1: from 2D-3D correspondences)", P.mode);
+        return VSLAM_ERR_INVALID;
+    }
     return VSLAM_OK;
 }
 
@@ -420,12 +729,14 @@ vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, i
                                   P.max_hamming, P.ratio_pct, d_rlD, d_rlKeyWin);
         timer.end(t);
         t = timer.begin("reloc_pairs");
-        hipLaunchKernelGGL(k_reloc_pairs, dim3(1), dim3(1024), 0, stream, nL, d_rlKeyWin, d_kps[0], d_kps[1], d_depth, d_rightIdxs, d_rlPts,
-                           rig.fx, rig.fy, rig.cx, rig.cy, (RelocRec*)d_rlRec, d_rlPairs, d_rlKeyWinner, outI);
+        hipLaunchKernelGGL(P.mode ? k_reloc_pairs_p3p : k_reloc_pairs, dim3(1), dim3(1024), 0, stream, nL, d_rlKeyWin, d_kps[0], d_kps[1], d_depth,
+                           d_rightIdxs, d_rlPts, rig.fx, rig.fy, rig.cx, rig.cy, (RelocRec*)d_rlRec, d_rlPairs, d_rlKeyWinner, outI);
         timer.end(t);
         t = timer.begin("reloc_ransac");
-        hipLaunchKernelGGL(k_reloc_ransac, dim3(H), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, outI, P.seed, d_rlCounts, d_rlPoses);
-        hipLaunchKernelGGL(k_reloc_best, dim3(1), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, H, d_rlCounts, d_rlPoses, d_rlOut, d_rlFlags);
+        hipLaunchKernelGGL(P.mode ? k_reloc_ransac_p3p : k_reloc_ransac, dim3(H), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, outI, P.seed,
+                           d_rlCounts, d_rlPoses);
+        hipLaunchKernelGGL(P.mode ? k_reloc_best_p3p : k_reloc_best, dim3(1), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, H, d_rlCounts,
+                           d_rlPoses, d_rlOut, d_rlFlags);
         timer.end(t);
         VS_HIP(hipGetLastError());
         // one download block: out (T_cw, ints) | records | rightIdxs | flags
@@ -606,11 +917,11 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
     if (gx) hipLaunchKernelGGL(k_reloc_match_b, dim3(gx, nOn), dim3(256), 0, stream, dT);
     T.end(t);
     t = T.begin("reloc_pairs");
-    hipLaunchKernelGGL(k_reloc_pairs_b, dim3(nOn), dim3(1024), 0, stream, dT);
+    hipLaunchKernelGGL(P.mode ? k_reloc_pairs_p3p_b : k_reloc_pairs_b, dim3(nOn), dim3(1024), 0, stream, dT);
     T.end(t);
     t = T.begin("reloc_ransac");
-    hipLaunchKernelGGL(k_reloc_ransac_b, dim3(H, nOn), dim3(64), 0, stream, dT);
-    hipLaunchKernelGGL(k_reloc_best_b, dim3(nOn), dim3(64), 0, stream, dT);
+    hipLaunchKernelGGL(P.mode ? k_reloc_ransac_p3p_b : k_reloc_ransac_b, dim3(H, nOn), dim3(64), 0, stream, dT);
+    hipLaunchKernelGGL(P.mode ? k_reloc_best_p3p_b : k_reloc_best_b, dim3(nOn), dim3(64), 0, stream, dT);
     T.end(t);
     t = T.begin("reloc_refine");
     hipLaunchKernelGGL(k_reloc_problem_b, dim3(nOn), dim3(1024), 0, stream, dT);

@@ -258,7 +258,7 @@ class Matcher:
 
     def relocalize(self, points, desc, pairs=True, **params):
         """vslam_relocalize on the matcher's current frame: (T_cw or None, report dict, pairs or None).  params: the
-        fields of RelocParams (max_hamming, ratio_pct, n_hypotheses, seed, min_inliers; 0 / absent = default)."""
+        fields of RelocParams (max_hamming, ratio_pct, n_hypotheses, seed, min_inliers, mode; 0 / absent = default)."""
         points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         assert len(desc) == len(points)
@@ -290,7 +290,7 @@ class LmReport(C.Structure):
 
 class RelocParams(C.Structure):
     _fields_ = [("max_hamming", C.c_int32), ("ratio_pct", C.c_int32), ("n_hypotheses", C.c_int32), ("seed", C.c_uint32),
-                ("min_inliers", C.c_int32)]
+                ("min_inliers", C.c_int32), ("mode", C.c_int32)]
 
 
 class RelocReport(C.Structure):

@@ -352,6 +352,21 @@ vslam_status vslam_world_to_frame(vslam_matcher* m, const double* T_cw, int32_t 
  *      passes the chi2 bound 7.815.  The winner is the largest (count << 32 | 0xFFFFFFFF - h).
  *   D  the winner's inliers, in correspondence order, refined by vslam_estimate_pose from the hypothesis;
  *      success = n_inliers >= min_inliers.  T_cw_out is written only on success.
+ * params->mode = 1 builds the hypotheses from 2D-3D correspondences instead (no stereo depth is read before step D;
+ * DESIGN.md section 6 item 22, restated by tests/reloc_p3p_ref.py).  Step A is unchanged; then
+ *   B' k_reloc_pairs_p3p: EVERY winning pair, in ascending key index, as correspondences {X_w, y (the key's unit bearing:
+ *      ((kx - cx) / fx, (ky - cy) / fy, 1) divided by its norm, fp64), kx, ky, kxr, octave, p, i, stereo}; stereo =
+ *      estimatedDepth > 0 && rightIdxs >= 0, kxr is the matched right key's x with the flag and 0 without.  n_pairs = C.
+ *   C' k_reloc_ransac_p3p / k_reloc_best_p3p: the sampling of step C; the three (X_w, y) pairs go through a P3P solver (fp64
+ *      + - * / and sqrt in a fixed order: a degenerate conic of the pencil of the three distance equations, its real root by
+ *      16 Newton steps, two quadratics, 3 Gauss-Newton steps on the depths) that fills up to four solution slots with
+ *      camera <- world poses.  A slot is void for collinear world points or coincident bearings (|.|^2 < 1e-12), a
+ *      non-finite value or a depth <= 0.  A correspondence counts for a slot iff z > 0 and its residual - (left u, left v,
+ *      right u) with the stereo flag, (left u, left v) without, weighted by the octave's InvSigmaFactor - passes the same
+ *      bound 7.815.  A hypothesis's count is the largest over its slots (the lowest slot on a tie) and its pose that slot's;
+ *      the winner is chosen as in step C.
+ *   D  as above; a correspondence without a right match enters with matches = (i, -1): a left-only factor.
+ * Any other mode: VSLAM_ERR_INVALID, nothing launched.  The mode belongs to the call (one params set per batched call).
  * Everything is enqueued on the matcher's stream; the call waits once before the refinement and once at its end.
  * n_points <= 65536 and at most 7680 left keys, else VSLAM_ERR_CAPACITY; no completed stereo match, n_hypotheses above
  * 1024 or a negative parameter: VSLAM_ERR_INVALID.  Like vslam_estimate_pose, step D may clear the stereo match of a
@@ -363,6 +378,7 @@ typedef struct vslam_reloc_params {   /* a zero field takes the default in brack
     int32_t n_hypotheses;    /* [256] at most 1024 */
     uint32_t seed;           /* [0x52454C4F] */
     int32_t min_inliers;     /* [50]  the fleet's "lost" limit */
+    int32_t mode;            /* [0]   0: hypotheses from stereo-triangulated keys (steps B, C); 1: from 2D-3D correspondences (B', C') */
 } vslam_reloc_params;
 
 typedef struct vslam_reloc_report {

@@ -14,7 +14,13 @@ usage: python tools/reloc_rate.py [out.json] [calls] [reps]
 map of the shape above from its own seed) the wall-clock time of ONE vslam_relocalize_batch call against L sequential
 vslam_relocalize calls on the same matchers, same build, same process.  Five warm-up calls of each form, then `reps` repetitions
 that alternate the two forms (`calls` calls each); host clock around calls that end in a device synchronise.
-usage: python tools/reloc_rate.py --lanes [out.json] [calls] [reps]"""
+usage: python tools/reloc_rate.py --lanes [out.json] [calls] [reps]
+
+--mode 0 | 1 (with either form above): vslam_reloc_params::mode of every call (default 0).
+--mode both: the two hypothesis modes against each other on the same resident frame and map, same build, same process - five warm-up
+calls of each, then `reps` repetitions that alternate mode 0 and mode 1 (`calls` calls each): wall-clock time per call and device
+time per kernel group of each mode; then the 16-lane vslam_relocalize_batch call of each mode, alternated in the same way.
+usage: python tools/reloc_rate.py --mode both [out.json] [calls] [reps]"""
 import json, os, sys, time
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +32,7 @@ import vslam_capi as vc
 
 N_KEYS, N_POINTS, N_TRUE = 1500, 20000, 1200
 RIG = synth.RIGS["euroc"]
+MODE = 0            # --mode
 
 
 def flip(desc, k, rng):
@@ -76,13 +83,13 @@ def main_lanes(argv):
         m.set_timing(False)
         ms.append(m); gs.append(g)
     pts = [g["points"] for g in gs]; dsc = [g["desc"] for g in gs]
-    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, calls_per_repetition=calls, repetitions=reps, lanes={})
+    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, mode=MODE, calls_per_repetition=calls, repetitions=reps, lanes={})
     for L in (1, 4, 16):
         def batched():
-            return vc.relocalize_batch(ms[:L], pts[:L], dsc[:L])
+            return vc.relocalize_batch(ms[:L], pts[:L], dsc[:L], mode=MODE)
 
         def sequential():
-            return [ms[b].relocalize(pts[b], dsc[b], pairs=True) for b in range(L)]
+            return [ms[b].relocalize(pts[b], dsc[b], pairs=True, mode=MODE) for b in range(L)]
 
         for _ in range(5):
             Tb, repb, _ = batched()
@@ -108,7 +115,82 @@ def main_lanes(argv):
     print(json.dumps(res))
 
 
+def main_modes(argv):
+    out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "reloc_p3p_rate.json")
+    calls = int(argv[1]) if len(argv) > 1 else 50
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    if vc.device_count() < 1:
+        raise RuntimeError("reloc_rate needs a GPU: a time taken anywhere else says nothing about the stage")
+    stat = lambda v: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+    LMAX = 16
+    ge = vc.Extractor(RIG["w"], RIG["h"], 1500, batch=2 * LMAX)
+    ms, gs = [], []
+    for b in range(LMAX):
+        g = build(seed=1 + b)
+        m = vc.Matcher(RIG, ge, 2 * b, ge, 2 * b + 1)
+        m.stereo_finalize_arrays(g["best"], g["depth"], g["sad"], N_KEYS)
+        m.set_keys(0, g["kL"], g["dL"]); m.set_keys(1, g["kR"], g["dR"])
+        ms.append(m); gs.append(g)
+    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, calls_per_repetition=calls, repetitions=reps, single_call={}, batched_16_lanes={})
+    # ---- one call on one matcher, timing on: wall clock and kernel groups, the modes alternated
+    m, g = ms[0], gs[0]
+    st = m.stereo_fetch(N_KEYS, N_KEYS)
+    last = {}
+    for _ in range(5):
+        for mode in (0, 1):
+            last[mode] = m.relocalize(g["points"], g["desc"], pairs=False, mode=mode)
+    m.timings()
+    wall, groups = {0: [], 1: []}, {0: [], 1: []}
+    for _ in range(reps):
+        for mode in (0, 1):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                m.relocalize(g["points"], g["desc"], pairs=False, mode=mode)
+            wall[mode].append((time.perf_counter() - t0) / calls * 1e3)
+            groups[mode].append({k: v / calls for k, v in m.timings().items()})
+    import pyoracle, reloc_p3p_ref as pp
+    ref = pp.relocalize(pyoracle, RIG, pyoracle.Extractor(1500).InvSigmaFactor, g["points"], g["desc"], g["kL"], g["dL"], g["kR"], st, mode=1)
+    T1, rep1, _ = last[1]
+    for mode in (0, 1):
+        rep = last[mode][1]
+        res["single_call"]["mode_%d" % mode] = dict(
+            report={k: rep[k] for k in ("success", "n_pairs", "best_count", "n_inliers", "n_stereo")}, wall_ms_per_call=stat(wall[mode]),
+            device_ms_per_call={k: stat([gr.get(k, 0.0) for gr in groups[mode]]) for k in sorted(groups[mode][0])})
+    res["single_call"]["mode_1"]["same_result_as_restatement"] = bool(
+        ref["n_pairs"] == rep1["n_pairs"] and ref["best_count"] == rep1["best_count"] and ref["n_inliers"] == rep1["n_inliers"] and
+        ref["T_cw"] is not None and T1 is not None and float(np.abs(ref["T_cw"] - T1).max()) < 1e-7)
+    # ---- the 16-lane batched call, timing off
+    for m in ms:
+        m.set_timing(False)
+    pts = [g["points"] for g in gs]; dsc = [g["desc"] for g in gs]
+    reps_b = {}
+    for _ in range(5):
+        for mode in (0, 1):
+            reps_b[mode] = vc.relocalize_batch(ms, pts, dsc, mode=mode)[1]
+    wb = {0: [], 1: []}
+    for _ in range(reps):
+        for mode in (0, 1):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                vc.relocalize_batch(ms, pts, dsc, mode=mode)
+            wb[mode].append((time.perf_counter() - t0) / calls * 1e3)
+    for mode in (0, 1):
+        res["batched_16_lanes"]["mode_%d" % mode] = dict(batched_call_ms=stat(wb[mode]), batched_ms_per_lane=float(np.median(wb[mode])) / LMAX,
+                                                         inliers=[r["n_inliers"] for r in reps_b[mode]], pairs=[r["n_pairs"] for r in reps_b[mode]])
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
+    global MODE
+    if "--mode" in sys.argv:
+        k = sys.argv.index("--mode")
+        mode = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+        if mode == "both":
+            return main_modes(sys.argv[1:])
+        MODE = int(mode)
     if len(sys.argv) > 1 and sys.argv[1] == "--lanes":
         return main_lanes(sys.argv[2:])
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reloc_rate.json")
@@ -123,16 +205,16 @@ def main():
     m.set_keys(0, g["kL"], g["dL"]); m.set_keys(1, g["kR"], g["dR"])
     st = m.stereo_fetch(N_KEYS, N_KEYS)
     for _ in range(5):
-        T, rep, _ = m.relocalize(g["points"], g["desc"], pairs=False)
+        T, rep, _ = m.relocalize(g["points"], g["desc"], pairs=False, mode=MODE)
     m.timings()
     wall, groups = [], []
     for _ in range(reps):
         t0 = time.perf_counter()
         for _ in range(calls):
-            m.relocalize(g["points"], g["desc"], pairs=False)
+            m.relocalize(g["points"], g["desc"], pairs=False, mode=MODE)
         wall.append((time.perf_counter() - t0) / calls * 1e3)
         groups.append({k: v / calls for k, v in m.timings().items()})
-    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, calls_per_repetition=calls, repetitions=reps,
+    res = dict(keys=N_KEYS, map_points=N_POINTS, hypotheses=256, mode=MODE, calls_per_repetition=calls, repetitions=reps,
                report={k: rep[k] for k in ("success", "n_pairs", "best_count", "n_inliers", "n_stereo")},
                hamming_tests_per_call=N_KEYS * N_POINTS,
                wall_ms_per_call=dict(median=float(np.median(wall)), min=min(wall), max=max(wall)),
@@ -142,12 +224,12 @@ def main():
     if mt > 0:
         res["hamming_tests_per_second_in_k_reloc_match"] = N_KEYS * N_POINTS / (mt * 1e-3)
     # context: the numpy restatement on one core (best of three)
-    import pyoracle, reloc_ref as rr
+    import pyoracle, reloc_ref as rr, reloc_p3p_ref as pp
     inv_sigma = pyoracle.Extractor(1500).InvSigmaFactor
     cpu = []
     for _ in range(3):
         t0 = time.perf_counter()
-        ref = rr.relocalize(pyoracle, RIG, inv_sigma, g["points"], g["desc"], g["kL"], g["dL"], g["kR"], st)
+        ref = (pp if MODE else rr).relocalize(pyoracle, RIG, inv_sigma, g["points"], g["desc"], g["kL"], g["dL"], g["kR"], st, **(dict(mode=1) if MODE else {}))
         cpu.append((time.perf_counter() - t0) * 1e3)
     res["numpy_restatement_one_core_ms"] = dict(best=min(cpu), all=cpu)
     res["same_result_as_restatement"] = bool(ref["n_pairs"] == rep["n_pairs"] and ref["best_count"] == rep["best_count"] and
