@@ -184,9 +184,11 @@ struct vslam_batch {
     vslam_status ensure_dn(size_t bytes);
     vslam_status serve_requests();
     vslam_status first_error();
-    vslam_status host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates);
+    vslam_status host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates, bool needImu = true);
+    // imuCall: vslam_batch_relocalize_imu (imu: the phase-2 lanes' buckets, ireps: [B]); else vslam_batch_relocalize (both null)
     vslam_status relocalize(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames, const uint8_t* mask,
-                            const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps);
+                            const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps, bool imuCall = false,
+                            const vslam_imu_bucket* imu = nullptr, vslam_reloc_imu_report* ireps = nullptr);
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
     vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
@@ -506,7 +508,7 @@ vslam_status vslam_batch::first_error() {
 // The host begin phase of the lanes that are on in ls[]: mapping results due at the lanes' frame numbers land (frame_begin_a, the
 // group's request service, frame_begin_b1, the merged changePosesLCA pass, frame_begin_b2).  candidates: the tracker's candidate
 // lists as well (a tracked step; a relocalisation gathers its own).
-vslam_status vslam_batch::host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates) {
+vslam_status vslam_batch::host_begin(const int* frames, const vslam_imu_bucket* imu, bool candidates, bool needImu) {
     using clk = std::chrono::steady_clock;
     auto sub = [&](int k, clk::time_point& ts) { const auto t1 = clk::now(); subSum[k] += std::chrono::duration<double>(t1 - ts).count(); ts = t1; };
 
@@ -517,7 +519,7 @@ vslam_status vslam_batch::host_begin(const int* frames, const vslam_imu_bucket* 
         hipSetDevice(device);
         vslam_system* s = sys[b];
         s->deferDevice = true;
-        const vslam_status bs = s->frame_begin_a(s->ctx, frames[b], imu ? &imu[b] : nullptr);
+        const vslam_status bs = s->frame_begin_a(s->ctx, frames[b], imu ? &imu[b] : nullptr, needImu);
         s->deferDevice = false;
         LANE_TRY(bs);
     });
@@ -597,6 +599,7 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
         if (!q.on) continue;
         if (!L[b] || !R[b]) { set_error("vslam_batch: lane %d has no images", b); return VSLAM_ERR_INVALID; }
         q.first = frames[b] == 0;
+        if (sys[b]->relocPending) { set_error("vslam_batch: lane %d: %s", b, kRelocPendingMsg); return VSLAM_ERR_INVALID; }
         if (needFirst[b] && !q.first) { set_error("vslam_batch: lane %d was restarted, its next frame must carry frame number 0 (got %d)", b, frames[b]); return VSLAM_ERR_INVALID; }
         nOn++;
     }
@@ -876,16 +879,20 @@ vslam_status vslam_batch::step(const uint8_t* const* L, const uint8_t* const* R,
 // enqueue, one stereo launch set and one launch per relocalisation stage for all of them (reloc.hip: reloc_batch_run), the map points
 // gathered straight into the group's upload block.  One wait for the extraction's counts (as a step has), one at the end.
 vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames,
-                                     const uint8_t* mask, const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps) {
-    if (!L || !R || !frames || !T_wc_out || !reps) { set_error("vslam_batch_relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
+                                     const uint8_t* mask, const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps, bool imuCall,
+                                     const vslam_imu_bucket* imu, vslam_reloc_imu_report* ireps) {
+    const char* const fn = imuCall ? "vslam_batch_relocalize_imu" : "vslam_batch_relocalize";
+    if (!L || !R || !frames || !T_wc_out || !reps || (imuCall && !ireps)) { set_error("%s: invalid arguments", fn); return VSLAM_ERR_INVALID; }
     // ---- refusals: nothing has changed when one of these returns ----------------------------------------------------------------
     int nOn = 0;
     for (int b = 0; b < B; b++) {
         if (mask && !mask[b]) continue;
         nOn++;
-        if (useImu) { set_error("vslam_batch_relocalize: lane %d: an IMU batch cannot relocalise yet (its velocity would need re-initialising)", b); return VSLAM_ERR_INVALID; }
-        if (!L[b] || !R[b]) { set_error("vslam_batch_relocalize: lane %d has no images", b); return VSLAM_ERR_INVALID; }
-        if (needFirst[b] || sys[b]->keyFrames.empty()) { set_error("vslam_batch_relocalize: lane %d has no map (track its frame 0 first)", b); return VSLAM_ERR_INVALID; }
+        if (useImu && !imuCall) { set_error("vslam_batch_relocalize: lane %d: an IMU batch cannot relocalise yet (its velocity would need re-initialising)", b); return VSLAM_ERR_INVALID; }
+        if (!useImu && imuCall) { set_error("vslam_batch_relocalize_imu: lane %d: a batch without IMU relocalises through vslam_batch_relocalize", b); return VSLAM_ERR_INVALID; }
+        if (!L[b] || !R[b]) { set_error("%s: lane %d has no images", fn, b); return VSLAM_ERR_INVALID; }
+        if (needFirst[b] || sys[b]->keyFrames.empty()) { set_error("%s: lane %d has no map (track its frame 0 first)", fn, b); return VSLAM_ERR_INVALID; }
+        if (imuCall) VS_CHECK(sys[b]->reloc_imu_check(imu ? &imu[b] : nullptr, fn, b));      // (a lane between its two poses needs its bucket)
     }
     vslam_reloc_params P;
     VS_CHECK(reloc_resolve_params(prm, P));
@@ -894,7 +901,7 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
     vslam::thread_pool_wants_priority() = true;
     for (int b = 0; b < B; b++) { ls[b] = LaneStep{}; ls[b].on = !mask || mask[b]; }
     // ---- host: mapping results due at these frame numbers land as in a tracked step ------------------------------------------------
-    VS_CHECK(host_begin(frames, nullptr, false));
+    VS_CHECK(host_begin(frames, nullptr, false, false));
     // ---- device: the frames' extraction; a prefetched one (for a tracked step's images) finishes first and is discarded ---------
     prefetched.clear();
     if (fe->countsPending) VS_CHECK(fe->wait_counts());
@@ -907,6 +914,10 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
         hipSetDevice(device);
         if (sys[b]->pass.collectDue) LANE_TRY(sys[b]->frame_mid());
         rl[b].m = sys[b]->fm; rl[b].n = sys[b]->reloc_candidates(); rl[b].wantInFrame = true;
+        if (imuCall && sys[b]->relocPending) {               // second pose: the bucket since the first, x0 = the camera pose, b0 = biasGood
+            sys[b]->reloc_imu_input(sys[b]->ctx, &imu[b]);
+            rl[b].imu = &sys[b]->ctx.in;
+        }
     });
     kick();
     VS_CHECK(first_error());
@@ -937,13 +948,16 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
     // ---- device: every relocalisation stage once for all lanes; one wait ----------------------------------------------------------
     std::vector<double> Tcw((size_t)B * 16, 0.0);
     const RelocBlocks blk{h_up, d_up, h_dn, d_dn};
-    VS_CHECK(reloc_batch_run(rl.data(), B, plan, blk, stream, P, (double)(float)std::log((double)shared.fe.scale), &timer, Tcw.data(), reps));
+    if (imuCall) for (int b = 0; b < B; b++) if (ls[b].on) ireps[b] = vslam_reloc_imu_report{};
+    VS_CHECK(reloc_batch_run_imu(rl.data(), B, plan, blk, stream, P, (double)(float)std::log((double)shared.fe.scale), &timer, Tcw.data(), reps,
+                                 imuCall ? ireps : nullptr));
     // ---- host: commit per lane (a failure changes nothing in its session) ----------------------------------------------------------
     pool.run(B, [&](int b) {
         if (!ls[b].on) return;
         vslam_system* s = sys[b];
         double* out = T_wc_out + 16 * (size_t)b;
-        if (reps[b].success) s->reloc_commit(Tcw.data() + 16 * (size_t)b, h_dn + rl[b].oInF, out);
+        if (imuCall) s->reloc_imu_finish(reps[b], ireps[b], Tcw.data() + 16 * (size_t)b, h_dn + rl[b].oInF, out);
+        else if (reps[b].success) s->reloc_commit(Tcw.data() + 16 * (size_t)b, h_dn + rl[b].oInF, out);
         else memcpy(out, s->camPose.data(), sizeof(double) * 16);
     });
     return VSLAM_OK;
@@ -1010,6 +1024,14 @@ vslam_status vslam_batch_relocalize(vslam_batch* b, const uint8_t* const* left, 
                                     vslam_reloc_report* reports) {
     if (!b) return VSLAM_ERR_INVALID;
     return b->relocalize(left, right, stride, on_device != 0, frame_numbers, lane_mask, params, T_wc_out, reports);
+}
+
+vslam_status vslam_batch_relocalize_imu(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride, int32_t on_device,
+                                        const int32_t* frame_numbers, const vslam_imu_bucket* imu, const uint8_t* lane_mask,
+                                        const vslam_reloc_params* params, double* T_wc_out, vslam_reloc_report* reports,
+                                        vslam_reloc_imu_report* imu_reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->relocalize(left, right, stride, on_device != 0, frame_numbers, lane_mask, params, T_wc_out, reports, true, imu, imu_reports);
 }
 
 vslam_status vslam_batch_relocalize_debug(vslam_batch* b, int32_t lane, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner,

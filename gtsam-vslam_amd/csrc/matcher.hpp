@@ -267,8 +267,13 @@ struct RelocBatchLane {
     bool wantInFrame = false;        // the in-frame bytes under the refined pose (needs maxScaleDist in the upload block)
     size_t oXyz = 0, oDesc = 0, oMsd = 0, oKeyWin = 0, oSum = 0, oPairs = 0, oInF = 0;      // byte offsets (reloc_batch_plan)
     int nL = 0;                      // left keys (reloc_batch_run)
+    // phase 2 of an IMU relocalisation: the bucket between the two poses with T_wc_prev = the first pose and bias_prev = biasGood
+    // (velocity_prev is not read: the prediction starts at rest); null: no velocity is re-initialised for this lane
+    const vslam_imu_input* imu = nullptr;
+    size_t oImu = 0;                 // its staged samples (7 n + 6 doubles) in the upload block
 };
-struct RelocBatchPlan { size_t oPose = 0, upCopyBytes = 0, upBytes = 0, dnBytes = 0; int maxN = 0, nOn = 0; };
+// (oImuTab: the pre-integration's lane table, present only when a lane carries a bucket - the layout is otherwise the one before it existed)
+struct RelocBatchPlan { size_t oPose = 0, oImuTab = 0, upCopyBytes = 0, upBytes = 0, dnBytes = 0; int maxN = 0, nOn = 0, nImu = 0; };
 struct RelocBlocks { uint8_t* h_up; uint8_t* d_up; uint8_t* h_dn; uint8_t* d_dn; };
 vslam_status reloc_resolve_params(const vslam_reloc_params* prm, vslam_reloc_params& P);
 // per-lane argument checks of the batched call (limits and status rules of vslam_relocalize); nothing is changed
@@ -278,4 +283,13 @@ void reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan);
 // download and ONE wait on `stream`; reports and T_cw_out ([B][16], written per lane only on success) are filled per active lane.
 vslam_status reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
                              const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps);
+// The same with the velocity rule for the lanes that carry a bucket (RelocBatchLane::imu): their buckets staged into the upload block and
+// pre-integrated by ONE k_imu_preintegrate_b launch ahead of the stages, k_reloc_velocity_b after them.  imuReps [B]: phase (2 on
+// success, else 0), dt, velocity_prev, velocity, rot_residual of those lanes (bias is the caller's).  A bucket whose covariance has no
+// Cholesky factor: VSLAM_ERR_INVALID naming the lane, after the wait - the caller commits nothing.
+vslam_status reloc_batch_run_imu(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
+                                 const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
+                                 vslam_reloc_imu_report* imuReps);
+// pinned + device blocks of a matcher's own (vslam_relocalize_batch with this matcher first; a session's relocalize_imu): grown on demand
+vslam_status reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dnBytes);
 }  // namespace vslam

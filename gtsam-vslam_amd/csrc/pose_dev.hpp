@@ -55,10 +55,15 @@ struct RelocLane {
     int w, h, nLev; double logScale;                   // the in-frame test under the refined pose
     uint8_t* inF;                                      // [nP] (null: not wanted)
     double* summary;                                   // the lane's results in its slice of the download block (RELOC_SUM_*)
+    // phase 2 of an IMU relocalisation (k_reloc_velocity_b; all null otherwise): the lane's pre-integrated bucket (DPim: deltaTij first),
+    // the state predicted from (T_prev, v = 0, biasGood) (DNav: R[9], t[3], v[3]) and the pre-integration's status word
+    const double* velPim; const double* velPred; const double* velStatus;
 };
 // summary slice: doubles [0, 16) T_cw (refined when the gate was open, else the winning hypothesis), [16, 19) the LM's initial error,
-// final error, lambda; ints from double 20: C, best hypothesis, best count, M, gate, inliers, stereo inliers, iterations, inner, success
-constexpr int RELOC_SUM_DOUBLES = 32, RELOC_SUM_INTS = 20;
+// final error, lambda; ints from double 20: C, best hypothesis, best count, M, gate, inliers, stereo inliers, iterations, inner, success,
+// then (k_reloc_velocity_b, phase-2 lanes only) int 10: 1 when the bucket's covariance had no Cholesky factor; doubles [32, 40): dt,
+// velocity_prev[3], velocity[3], rot_residual (written on success only)
+constexpr int RELOC_SUM_DOUBLES = 40, RELOC_SUM_INTS = 20, RELOC_SUM_VEL = 32;
 
 // whitened residual (and Jacobian rows wrt [omega, v]) of one factor at T (world <- camera)
 __device__ __forceinline__ int pose_factor_eval(const double* f, const DPose& T, const PoseArgs& A,

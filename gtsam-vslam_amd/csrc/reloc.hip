@@ -16,8 +16,14 @@
 // the lane as a grid dimension, arguments from a RelocLane table - then
 //   k_reloc_problem_b  the refinement problem built on the device (no wait before step D), refined by k_pose_lm_b behind a gate
 //   k_reloc_inframe_b  the lane's results into the download block; the left-image test of the map under the refined pose
+// Stereo + IMU sessions (vslam_system_relocalize_imu, vslam_batch_relocalize_imu; restated by tests/reloc_imu_ref.py): the second of two
+// relocalised poses re-initialises the velocity - the bucket between the poses through k_imu_preintegrate_b (pose_imu.hip) ahead of the
+// stages, then
+//   k_reloc_velocity_b  one wave per lane: the start velocity for which the IMU prediction lands on the new pose (k_reloc_velocity: the
+//                       same body with its arguments by value, for the rule's test tap)
 #include "pose_dev.hpp"
 #include "track_dev.hpp"
+#include "imu_dev.hpp"
 
 namespace vslam {
 
@@ -643,6 +649,53 @@ __global__ __launch_bounds__(256) void k_reloc_inframe_b(const RelocLane* __rest
     L.inF[i] = world_to_frame_cam(pc[0], pc[1], pc[2], L.A.fx, L.A.fy, L.A.cx, L.A.cy, L.w, L.h, L.msd + i, L.logScale, L.nLev, uo, vo, lvl) ? 1 : 0;
 }
 
+// Phase 2 of an IMU relocalisation (restated by tests/reloc_imu_ref.py): the velocity from two relocalised
+// poses.  Tcw: the refined camera <- world pose (row-major 4x4); pim / pred: the bucket between the poses, pre-integrated with biasGood
+// and predicted from (T_prev, v = 0, biasGood) by k_imu_preintegrate_b.  One wave; every value is formed by one lane in a written order:
+//   T_new = (R^T, -R^T t):   t_new[i] = -((R[0][i] t[0] + R[1][i] t[1]) + R[2][i] t[2])
+//   lane i < 3:   velocity_prev[i] = (t_new[i] - pred.t[i]) / dt,   velocity[i] = pred.v[i] + velocity_prev[i]
+//   lane 3:       rot_residual = sqrt of the sum, in row-major order, of (pred.R[r][c] - R[c][r])^2
+// out[8]: dt, velocity_prev, velocity, rot_residual.
+__device__ __forceinline__ void reloc_velocity_body(const double* __restrict__ Tcw, const double* __restrict__ pim, const double* __restrict__ pred,
+                                                    double* __restrict__ out) {
+    const int i = threadIdx.x;
+    const double dt = pim[0];
+    if (i < 3) {
+        const double tn = -((Tcw[i] * Tcw[3] + Tcw[4 + i] * Tcw[7]) + Tcw[8 + i] * Tcw[11]);
+        const double vp = (tn - pred[9 + i]) / dt;
+        out[1 + i] = vp;
+        out[4 + i] = pred[12 + i] + vp;
+    } else if (i == 3) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double d = pred[3 * r + c] - Tcw[4 * c + r];
+                s = s + d * d;
+            }
+        out[7] = sqrt(s);
+        out[0] = dt;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_reloc_velocity(const double* __restrict__ Tcw, const double* __restrict__ pim, const double* __restrict__ pred,
+                                                       double* __restrict__ out) {
+    reloc_velocity_body(Tcw, pim, pred, out);
+}
+// One wave per lane, after k_reloc_inframe_b.  A lane without a pre-integrated bucket (phase 1) leaves at once; the pre-integration's
+// status goes to the summary whatever the relocalisation gave; the rule runs behind the success word k_reloc_inframe_b tests.
+__global__ __launch_bounds__(64) void k_reloc_velocity_b(const RelocLane* __restrict__ lanes) {
+    const RelocLane& L = *lane_entry(lanes, blockIdx.x);
+    if (!L.velPim) return;
+    if (threadIdx.x == 0) ((int*)(L.summary + RELOC_SUM_INTS))[10] = *L.velStatus != 0.0 ? 1 : 0;
+    const int* outI = (const int*)(L.out + 16);
+    const int gate = outI[4];
+    const int nIn = gate ? L.A.out[0] : 0;
+    if (!(gate && nIn >= L.minInliers)) return;
+    reloc_velocity_body(L.A.poseIO, L.velPim, L.velPred, L.summary + RELOC_SUM_VEL);
+}
+
 }  // namespace vslam
 
 using namespace vslam;
@@ -799,7 +852,10 @@ vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t
 }
 
 // ---- the batched call ---------------------------------------------------------------------------------------------------------------
-namespace vslam { void launch_pose_batch(hipStream_t s, const PoseLane* dLanes, int B); }
+namespace vslam {
+void launch_pose_batch(hipStream_t s, const PoseLane* dLanes, int B);
+void launch_imu_batch(hipStream_t s, const ImuLane* dLanes, int B);
+}
 
 namespace {
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -829,12 +885,15 @@ void vslam::reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan)
     size_t up = up256((size_t)B * sizeof(RelocLane));
     plan.oPose = up;
     up = up256(up + (size_t)B * sizeof(PoseLane));
+    for (int b = 0; b < B; b++) if (lanes[b].m && lanes[b].imu) plan.nImu++;
+    if (plan.nImu) { plan.oImuTab = up; up = up256(up + (size_t)B * sizeof(ImuLane)); }
     size_t dn = 0;
     for (int b = 0; b < B; b++) {
         RelocBatchLane& q = lanes[b];
         if (!q.m) continue;
         plan.nOn++;
         plan.maxN = std::max(plan.maxN, q.n);
+        if (q.imu) { q.oImu = up; up += up256((size_t)(7 * std::max(q.imu->n_samples, 0) + 6) * sizeof(double)); }
         q.oXyz = up; up += up256((size_t)q.n * 24);
         q.oDesc = up; up += up256((size_t)q.n * 32);
         q.oMsd = up; if (q.wantInFrame) up += up256((size_t)q.n * 4);
@@ -849,7 +908,14 @@ void vslam::reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan)
 
 vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
                                     const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps) {
+    return reloc_batch_run_imu(lanes, B, plan, blk, stream, P, logScale, tm, T_cw_out, reps, nullptr);
+}
+
+vslam_status vslam::reloc_batch_run_imu(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
+                                        const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
+                                        vslam_reloc_imu_report* imuReps) {
     if (!plan.nOn) return VSLAM_OK;
+    if (plan.nImu && !imuReps) { set_error("relocalize_batch: a lane carries an IMU bucket but no report array was given"); return VSLAM_ERR_INVALID; }
     const int H = P.n_hypotheses, nOn = plan.nOn;
     // ---- the frames' keys: this stream after the extractors' last run; limits; capacities (all before the first launch) ----------
     std::vector<vslam_extractor*> seen;
@@ -880,6 +946,8 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
     PoseLane* hP = (PoseLane*)(blk.h_up + plan.oPose);
     const RelocLane* dT = (const RelocLane*)blk.d_up;
     const PoseLane* dP = (const PoseLane*)(blk.d_up + plan.oPose);
+    ImuLane* hI = (ImuLane*)(blk.h_up + plan.oImuTab);      // (read only when a lane carries a bucket)
+    const ImuLane* dI = (const ImuLane*)(blk.d_up + plan.oImuTab);
     int k = 0;
     for (int b = 0; b < B; b++) {
         const RelocBatchLane& q = lanes[b];
@@ -903,6 +971,22 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
         L.summary = (double*)(blk.d_dn + q.oSum);
         hP[k] = PoseLane{};
         hP[k].A = L.A;
+        if (plan.nImu) {
+            // the pre-integration's entry of this lane: idle (n = 0) without a bucket; with one, staged as a tracked IMU step stages it
+            // (dt rule, dt0 = 1 / hz, integration bias = bias_prev) and predicted from (T_wc_prev, v = 0).  Its outputs live in the
+            // matcher's IMU scratch; the status word in the spare slot behind the prediction.
+            ImuLane& I = hI[k];
+            I = ImuLane{};
+            if (q.imu) {
+                VS_CHECK(m->imu_stage(q.imu, 0.0, (double*)(blk.h_up + q.oImu), (double*)(blk.d_up + q.oImu), I));
+                for (int c = 0; c < 3; c++) I.si.v[c] = 0.0;
+                I.takeFrom = nullptr;
+                I.status = m->imuPred + sizeof(DNav) / sizeof(double);
+                L.velPim = (const double*)I.pim; L.velPred = (const double*)I.pred; L.velStatus = I.status;
+                // (the staged views point into the caller's upload block: nothing may run on them after this call)
+                m->imuSamplesDev = nullptr; m->imuBiasDev = nullptr; m->imuN = 0;
+            }
+        }
         m->rlLast[0] = q.n; m->rlLast[1] = q.nL; m->rlLast[2] = H; m->rlLast[3] = 0;
         k++;
     }
@@ -913,7 +997,13 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
     const int gx = (plan.maxN + 255) / 256;
     StageTimer off; off.enabled = false;
     StageTimer& T = tm ? *tm : off;
-    int t = T.begin("reloc_match");
+    int t;
+    if (plan.nImu) {                                // the phase-2 lanes' buckets: independent of the stages below, ahead of them
+        t = T.begin("reloc_preintegrate");
+        launch_imu_batch(stream, dI, nOn);
+        T.end(t);
+    }
+    t = T.begin("reloc_match");
     if (gx) hipLaunchKernelGGL(k_reloc_match_b, dim3(gx, nOn), dim3(256), 0, stream, dT);
     T.end(t);
     t = T.begin("reloc_pairs");
@@ -930,9 +1020,15 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
     t = T.begin("reloc_inframe");
     hipLaunchKernelGGL(k_reloc_inframe_b, dim3(std::max(gx, 1), nOn), dim3(256), 0, stream, dT);
     T.end(t);
+    if (plan.nImu) {
+        t = T.begin("reloc_velocity");
+        hipLaunchKernelGGL(k_reloc_velocity_b, dim3(nOn), dim3(64), 0, stream, dT);
+        T.end(t);
+    }
     VS_HIP(hipGetLastError());
     VS_HIP(hipMemcpyAsync(blk.h_dn, blk.d_dn, plan.dnBytes, hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
+    int noFactor = -1;
     for (int b = 0; b < B; b++) {
         const RelocBatchLane& q = lanes[b];
         if (!q.m) continue;
@@ -942,16 +1038,30 @@ vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBat
         r = vslam_reloc_report{};
         r.n_points = q.n; r.n_pairs = sI[0]; r.best_hypothesis = sI[1]; r.best_count = sI[2];
         q.m->rlLast[3] = sI[0];
+        if (q.imu) {
+            imuReps[b] = vslam_reloc_imu_report{};
+            if (sI[10] && noFactor < 0) noFactor = b;
+        }
         if (!sI[4]) continue;                               // fewer than three correspondences or no inlier: not refined, success = 0
         r.n_inliers = sI[5]; r.n_stereo = sI[6];
         r.lm.iterations = sI[7]; r.lm.inner_iterations = sI[8]; r.lm.initial_error = s[16]; r.lm.final_error = s[17]; r.lm.lambda = s[18];
         r.success = sI[9];
         if (r.success) memcpy(T_cw_out + 16 * (size_t)b, s, 16 * sizeof(double));
+        if (q.imu && r.success) {
+            vslam_reloc_imu_report& v = imuReps[b];
+            const double* o = s + RELOC_SUM_VEL;
+            v.phase = 2; v.dt = o[0]; v.rot_residual = o[7];
+            for (int c = 0; c < 3; c++) { v.velocity_prev[c] = o[1 + c]; v.velocity[c] = o[4 + c]; }
+        }
+    }
+    if (noFactor >= 0) {
+        set_error("relocalize: lane %d: IMU pre-integration: the 15x15 covariance has no Cholesky factor (no information matrix, no IMU factor)", noFactor);
+        return VSLAM_ERR_INVALID;
     }
     return VSLAM_OK;
 }
 
-static vslam_status reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dnBytes) {
+vslam_status vslam::reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dnBytes) {
     const size_t need[2] = {std::max<size_t>(upBytes, 256), std::max<size_t>(dnBytes, 256)};
     for (int k = 0; k < 2; k++) {
         if (need[k] <= m->rlBlkCap[k]) continue;
@@ -967,7 +1077,86 @@ static vslam_status reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dn
     return VSLAM_OK;
 }
 
+// Test taps of the velocity rule: B buckets through ONE k_imu_preintegrate_b launch, then k_reloc_velocity (laneForm false: B = 1, the
+// arguments by value) or ONE k_reloc_velocity_b launch over a RelocLane table whose entries hold what the kernel reads - the pose where
+// step D leaves it, an open gate, the pre-integration's outputs.  Everything lives in one temporary block; the rows of `out` are uploaded
+// first, so an idle lane's row comes back as the caller filled it.
+static vslam_status reinit_velocity_tap(vslam_matcher* m, int B, const vslam_imu_input* imus, const double* Tcw, double* out, bool laneForm) {
+    if (!m || B <= 0 || !imus || !Tcw || !out || (!laneForm && B != 1)) { set_error("IMU velocity tap: invalid arguments"); return VSLAM_ERR_INVALID; }
+    for (int b = 0; b < B; b++)
+        if (imus[b].n_samples < 0 || (!laneForm && imus[b].n_samples == 0)) { set_error("IMU velocity tap: lane %d: bucket length %d", b, imus[b].n_samples); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(m->device));
+    constexpr size_t PD = sizeof(DPim) / sizeof(double), ND = sizeof(DNav) / sizeof(double);
+    // per lane (doubles): poseIO 32 | out 20 | pose-kernel ints 2 | summary | DPim | Lam 225 | DNav | status 1 | samples 7 n + 6
+    constexpr size_t O_OUT = 32, O_INTS = 52, O_SUM = 54, O_PIM = O_SUM + RELOC_SUM_DOUBLES, O_LAM = O_PIM + PD, O_PRED = O_LAM + 225, O_ST = O_PRED + ND,
+                     O_SMP = O_ST + 1;
+    std::vector<size_t> off(B + 1, 0);
+    for (int b = 0; b < B; b++) off[b + 1] = off[b] + O_SMP + 7 * (size_t)imus[b].n_samples + 6;
+    std::vector<double> h(off[B], 0.0);
+    std::vector<RelocLane> rl((size_t)B);
+    std::vector<ImuLane> il((size_t)B);
+    double* d = nullptr; RelocLane* dR = nullptr; ImuLane* dI = nullptr;
+    auto run = [&]() -> vslam_status {
+        VS_HIP(hipMalloc(&d, off[B] * sizeof(double)));
+        VS_HIP(hipMalloc(&dR, (size_t)B * sizeof(RelocLane)));
+        VS_HIP(hipMalloc(&dI, (size_t)B * sizeof(ImuLane)));
+        for (int b = 0; b < B; b++) {
+            double* hb = h.data() + off[b];
+            double* db = d + off[b];
+            memcpy(hb, Tcw + 16 * (size_t)b, 16 * sizeof(double));
+            ((int*)(hb + O_OUT + 16))[4] = 1;                                   // the gate: open; inliers 0 >= min_inliers 0
+            memcpy(hb + O_SUM + RELOC_SUM_VEL, out + 8 * (size_t)b, 8 * sizeof(double));
+            RelocLane& L = rl[b];
+            L = RelocLane{};
+            ImuLane& I = il[b];
+            I = ImuLane{};
+            L.out = db + O_OUT; L.A.poseIO = db; L.A.out = (int*)(db + O_INTS); L.minInliers = 0; L.summary = db + O_SUM;
+            if (imus[b].n_samples == 0) continue;                               // idle lane: both kernels leave at their first test
+            VS_CHECK(m->imu_stage(&imus[b], 0.0, hb + O_SMP, db + O_SMP, I));
+            for (int c = 0; c < 3; c++) I.si.v[c] = 0.0;
+            I.takeFrom = nullptr;
+            I.pim = (DPim*)(db + O_PIM); I.Lam = db + O_LAM; I.pred = (DNav*)(db + O_PRED); I.status = db + O_ST;
+            L.velPim = db + O_PIM; L.velPred = db + O_PRED; L.velStatus = db + O_ST;
+        }
+        hipStream_t st = m->stream;
+        VS_HIP(hipMemcpyAsync(d, h.data(), off[B] * sizeof(double), hipMemcpyHostToDevice, st));
+        VS_HIP(hipMemcpyAsync(dR, rl.data(), (size_t)B * sizeof(RelocLane), hipMemcpyHostToDevice, st));
+        VS_HIP(hipMemcpyAsync(dI, il.data(), (size_t)B * sizeof(ImuLane), hipMemcpyHostToDevice, st));
+        launch_imu_batch(st, dI, B);
+        if (laneForm) hipLaunchKernelGGL(k_reloc_velocity_b, dim3(B), dim3(64), 0, st, (const RelocLane*)dR);
+        else hipLaunchKernelGGL(k_reloc_velocity, dim3(1), dim3(64), 0, st, (const double*)d, (const double*)(d + O_PIM), (const double*)(d + O_PRED),
+                                d + O_SUM + RELOC_SUM_VEL);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(h.data(), d, off[B] * sizeof(double), hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        return VSLAM_OK;
+    };
+    const vslam_status rs = run();
+    hipFree(d); hipFree(dR); hipFree(dI);
+    m->imuSamplesDev = nullptr; m->imuBiasDev = nullptr; m->imuN = 0;      // (the staged views pointed into the temporary block)
+    if (rs != VSLAM_OK) return rs;
+    int bad = -1;
+    for (int b = 0; b < B; b++) {
+        const double* hb = h.data() + off[b];
+        memcpy(out + 8 * (size_t)b, hb + O_SUM + RELOC_SUM_VEL, 8 * sizeof(double));
+        if (imus[b].n_samples > 0 && hb[O_ST] != 0.0 && bad < 0) bad = b;
+    }
+    if (bad >= 0) {
+        set_error("IMU velocity tap lane %d: the 15x15 covariance has no Cholesky factor (no information matrix)", bad);
+        return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
 extern "C" {
+
+vslam_status vslam_imu_reinit_velocity(vslam_matcher* m, const vslam_imu_input* imu, const double* T_cw_new, double* out) {
+    return reinit_velocity_tap(m, 1, imu, T_cw_new, out, false);
+}
+
+vslam_status vslam_imu_reinit_velocity_batch(vslam_matcher* m, int32_t n_lanes, const vslam_imu_input* imus, const double* T_cw_new, double* out) {
+    return reinit_velocity_tap(m, n_lanes, imus, T_cw_new, out, true);
+}
 
 vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lanes, const double* const* points_xyz, const uint8_t* const* desc,
                                     const int32_t* n_points, const vslam_reloc_params* params, double* T_cw_out, int32_t* const* pairs_out,

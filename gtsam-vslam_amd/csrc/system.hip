@@ -467,8 +467,8 @@ vslam_status vslam_system::change_poses_lca(int endIdx) {
 //   frame_candidates / frame_fill_upload   activeMapPoints -> the tracker's upload arrays
 //   frame_imu_input the frame's IMU problem
 //   frame_post      everything after the device: bookkeeping, keyframe rule, insertKeyFrame, updatePoses, local mapping
-vslam_status vslam_system::frame_begin_a(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu) {
-    if (cfg.use_imu && frame > 0 && (!imu || imu->n <= 0)) { set_error("vslam_system: IMU mode needs the frame's IMU bucket"); return VSLAM_ERR_INVALID; }
+vslam_status vslam_system::frame_begin_a(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu, bool needImu) {
+    if (needImu && cfg.use_imu && frame > 0 && (!imu || imu->n <= 0)) { set_error("vslam_system: IMU mode needs the frame's IMU bucket"); return VSLAM_ERR_INVALID; }
     c.frame = frame; c.imu = imu;
     c.out = vslam_frame_report{};
     c.out.frame = frame;
@@ -504,8 +504,8 @@ vslam_status vslam_system::frame_begin_b2(SysFrameCtx&) {
     return VSLAM_OK;
 }
 
-vslam_status vslam_system::frame_begin(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu) {
-    VS_CHECK(frame_begin_a(c, frame, imu));
+vslam_status vslam_system::frame_begin(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu, bool needImu) {
+    VS_CHECK(frame_begin_a(c, frame, imu, needImu));
     VS_CHECK(run_deferred());
     return frame_begin_b(c);
 }
@@ -619,6 +619,7 @@ vslam_status vslam_system::frame_post_a(SysFrameCtx& c, const SysTrackState& st)
         if (cfg.use_imu) {
             for (int k = 0; k < 3; k++) velocity[k] = c.imuOut.velocity[k];       // mVelocity = mNewVelocity (:1277)
             for (int k = 0; k < 6; k++) bias[k] = c.imuOut.bias[k];               // initialBias as the frame's last solve left it
+            if (tr.n_inliers >= 50) for (int k = 0; k < 6; k++) biasGood[k] = bias[k];      // (the retry loop's "lost" limit; read only by relocalize_imu)
         }
         lastMatches = matches; lastOutliers = outl;
         out.n_keyframes = (int)keyFrames.size(); out.n_map_points = (int)mapPoints.size(); out.n_active_after = (int)active.size();
@@ -680,10 +681,14 @@ vslam_status vslam_system::raw_args(int stride, int channels, const char* fn) co
     return VSLAM_OK;
 }
 
+const char* const vslam_sys::kRelocPendingMsg = "vslam_system: the session's velocity is not re-initialised yet (one relocalised pose is committed): "
+                                              "relocalise once more (vslam_system_relocalize_imu / vslam_batch_relocalize_imu) before tracking";
+
 vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride, int channels, bool onDevice, int frame,
                                  const vslam_imu_bucket* imu, double* T_wc_out, vslam_frame_report* rep, bool raw) {
     if (!L || !R || !T_wc_out) return VSLAM_ERR_INVALID;
     if (monoMode) { set_error("vslam_system: a mono session takes vslam_system_track_mono_imu"); return VSLAM_ERR_INVALID; }
+    if (relocPending) { set_error("%s", kRelocPendingMsg); return VSLAM_ERR_INVALID; }
     if (raw) VS_CHECK(raw_args(stride, channels, "vslam_system_track_stereo_raw"));
     SysFrameCtx& c = ctx;
     VS_CHECK(frame_begin(c, frame, imu));
@@ -767,6 +772,86 @@ vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int st
     return VSLAM_OK;
 }
 
+// ---- relocalisation of a stereo + IMU session: the velocity from two relocalised poses -------------
+// the refusals of a call on this session; nothing has changed when one returns (lane < 0: a single session)
+vslam_status vslam_system::reloc_imu_check(const vslam_imu_bucket* imu, const char* fn, int lane) const {
+    char who[32] = "";
+    if (lane >= 0) snprintf(who, sizeof(who), "lane %d: ", lane);
+    if (monoMode) { set_error("%s: %sa mono session cannot relocalise (stereo depth is needed)", fn, who); return VSLAM_ERR_INVALID; }
+    if (!cfg.use_imu) { set_error("%s: %sa session without IMU relocalises through vslam_system_relocalize / vslam_batch_relocalize", fn, who); return VSLAM_ERR_INVALID; }
+    if (keyFrames.empty()) { set_error("%s: %sthe session has no map (track frame 0 first)", fn, who); return VSLAM_ERR_INVALID; }
+    if (relocPending && (!imu || imu->n < 1 || !imu->acceleration || !imu->angular_velocity || !imu->timestamps_ns)) {
+        set_error("%s: %sthe second relocalisation needs the IMU bucket since the first (n >= 1)", fn, who);
+        return VSLAM_ERR_INVALID;
+    }
+    if (relocPending && cfg.imu_hz <= 0) { set_error("%s: %simu_hz must be positive", fn, who); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
+// the IMU problem of a phase-2 lane: frame_imu_input with b0 = biasGood (v0 is not read: the prediction starts at rest)
+void vslam_system::reloc_imu_input(SysFrameCtx& c, const vslam_imu_bucket* imu) {
+    c.imu = imu;
+    frame_imu_input(c);
+    for (int k = 0; k < 3; k++) c.in.velocity_prev[k] = 0.0;
+    for (int k = 0; k < 6; k++) c.in.bias_prev[k] = biasGood[k];
+}
+
+// the outcome of a call on this session.  irep: a phase-2 lane's values from the device (reloc_batch_run_imu), else zero.
+void vslam_system::reloc_imu_finish(const vslam_reloc_report& rep, vslam_reloc_imu_report& irep, const double* T_cw, const uint8_t* inF,
+                                    double* T_wc_out) {
+    const bool second = relocPending;
+    if (!rep.success) {                                     // the flag drops, nothing else changes: a later success is a first pose again
+        relocPending = false;
+        irep = vslam_reloc_imu_report{};
+        memcpy(T_wc_out, camPose.data(), sizeof(double) * 16);
+        return;
+    }
+    if (!second) {
+        reloc_commit(T_cw, inF, T_wc_out, 1);
+        relocPending = true;
+        irep = vslam_reloc_imu_report{};
+        irep.phase = 1;
+        return;
+    }
+    reloc_commit(T_cw, inF, T_wc_out, 2);
+    for (int k = 0; k < 3; k++) velocity[k] = irep.velocity[k];
+    for (int k = 0; k < 6; k++) { bias[k] = biasGood[k]; irep.bias[k] = biasGood[k]; }
+    relocPending = false;
+    irep.phase = 2;
+}
+
+// One lane through the batched stages (reloc.hip: reloc_batch_run_imu), on the matcher's own blocks and stream: a lane of
+// vslam_batch_relocalize_imu gives this call's result by construction.
+vslam_status vslam_system::relocalize_imu(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
+                                          const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* rep, vslam_reloc_imu_report* irep) {
+    if (!L || !R || !T_wc_out || !rep || !irep) { set_error("vslam_system_relocalize_imu: invalid arguments"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(reloc_imu_check(imu, "vslam_system_relocalize_imu", -1));
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(prm, P));
+    const bool second = relocPending;
+    SysFrameCtx& c = ctx;
+    VS_CHECK(frame_begin(c, frame, second ? imu : nullptr, false));      // (the first pose needs no bucket; the second's was checked above)
+    VS_CHECK(frame_mid());
+    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
+    else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
+    VS_CHECK(vslam_extractor_run(fe));
+    VS_CHECK(fm->stereo_match());
+    if (second) reloc_imu_input(c, imu);
+    RelocBatchLane q;
+    q.m = fm; q.n = reloc_candidates(); q.wantInFrame = true; q.imu = second ? &c.in : nullptr;
+    RelocBatchPlan plan;
+    reloc_batch_plan(&q, 1, plan);
+    VS_CHECK(reloc_own_blocks(fm, plan.upBytes, plan.dnBytes));
+    const RelocBlocks blk{fm->rlBlk[0], fm->rlBlk[1], fm->rlBlk[2], fm->rlBlk[3]};
+    reloc_fill_upload((double*)(blk.h_up + q.oXyz), blk.h_up + q.oDesc, (float*)(blk.h_up + q.oMsd));
+    VS_CHECK(reloc_batch_check(&q, 1, cfg.device));
+    double T_cw[16] = {0};
+    *irep = vslam_reloc_imu_report{};
+    VS_CHECK(reloc_batch_run_imu(&q, 1, plan, blk, fm->stream, P, (double)(float)std::log((double)cfg.fe.scale), &fm->timer, T_cw, rep, irep));
+    reloc_imu_finish(*rep, *irep, T_cw, blk.h_dn + q.oInF, T_wc_out);
+    return VSLAM_OK;
+}
+
 // every map point that is not an outlier, in creation order; the most recent 65536 if there are more
 int vslam_system::reloc_candidates() {
     std::lock_guard<std::mutex> lk(mapMutex);
@@ -787,14 +872,22 @@ void vslam_system::reloc_fill_upload(double* xyz, uint8_t* desc, float* msd) {
 }
 
 // a successful relocalisation: the pose state of a frame tracked with zero predicted motion; inF: per candidate, inside the left image
-void vslam_system::reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out) {
+// (phase 2 of an IMU session: the second of two relocalised poses - the predicted motion of updatePoses, :1699-1708)
+void vslam_system::reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out, int phase) {
     const M4 poseEst = m4_rigid_inv(m4_from(T_cw));
     std::lock_guard<std::mutex> lk(mapMutex);
     allFrames.push_back({false, -1, latestKF, m4_mul(keyFrames[latestKF].poseInv, poseEst)});      // addFrame
+    const M4 prevWPoseInv = camPoseInv;
     camRefPose = m4_mul(lastKFPoseInv, poseEst);
     camPose = poseEst; camPoseInv = m4_affine_inv(poseEst);
-    predNPoseRef = m4_identity();
-    predNPose = poseEst; predNPoseInv = camPoseInv;
+    if (phase == 2) {
+        predNPoseRef = m4_mul(prevWPoseInv, poseEst);
+        predNPose = m4_mul(poseEst, predNPoseRef);
+        predNPoseInv = m4_affine_inv(predNPose);
+    } else {
+        predNPoseRef = m4_identity();
+        predNPose = poseEst; predNPoseInv = camPoseInv;
+    }
     active.clear();
     for (size_t j = 0; j < rlIds.size(); j++) {
         mpInFrame[rlIds[j]] = inF[j];
@@ -1326,6 +1419,23 @@ vslam_status vslam_system_relocalize(vslam_system* s, const uint8_t* left, const
                                      int32_t frame_number, const vslam_reloc_params* params, double* T_wc_out, vslam_reloc_report* report) {
     if (!s) return VSLAM_ERR_INVALID;
     return s->relocalize(left, right, stride, on_device != 0, frame_number, params, T_wc_out, report);
+}
+
+vslam_status vslam_system_relocalize_imu(vslam_system* s, const uint8_t* left, const uint8_t* right, int32_t stride, int32_t on_device,
+                                         int32_t frame_number, const vslam_imu_bucket* imu, const vslam_reloc_params* params, double* T_wc_out,
+                                         vslam_reloc_report* report, vslam_reloc_imu_report* imu_report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->relocalize_imu(left, right, stride, on_device != 0, frame_number, imu, params, T_wc_out, report, imu_report);
+}
+
+vslam_status vslam_system_imu_state(vslam_system* s, double* velocity3, double* bias6, double* bias_good6, int32_t* pending) {
+    if (!s) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    if (velocity3) for (int k = 0; k < 3; k++) velocity3[k] = s->velocity[k];
+    if (bias6) for (int k = 0; k < 6; k++) bias6[k] = s->bias[k];
+    if (bias_good6) for (int k = 0; k < 6; k++) bias_good6[k] = s->biasGood[k];
+    if (pending) *pending = s->relocPending ? 1 : 0;
+    return VSLAM_OK;
 }
 
 vslam_status vslam_system_wait_mapping(vslam_system* s) {

@@ -119,6 +119,7 @@ struct SysProfScope {
     ~SysProfScope() { ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); n++; }
 };
 
+extern const char* const kRelocPendingMsg;      // the refusal of a tracked frame between the two poses of an IMU relocalisation
 struct SysFrame { bool isKF; int kf; int prevKF; M4 refPose; };   // allFramesPoses entry (trajectory output)
 
 // One local-mapping pass (LocalMapper::beginLocalMapping's loop body, src/OptimizationBA.cpp:960-975) in flight.  The map is
@@ -240,8 +241,9 @@ struct vslam_system {
                       vslam_matcher* adoptFm = nullptr);
     vslam_status wait_idle();          // waits for the mapping job in flight (if any); its result stays unread
     void release();
-    vslam_status frame_begin(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu);      // = _a, the deferred device calls, _b
-    vslam_status frame_begin_a(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu);
+    // needImu = false: a relocalisation (an IMU session's call may come without a bucket)
+    vslam_status frame_begin(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu, bool needImu = true);      // = _a, the deferred device calls, _b
+    vslam_status frame_begin_a(SysFrameCtx& c, int frame, const vslam_imu_bucket* imu, bool needImu = true);
     vslam_status frame_begin_b(SysFrameCtx& c);
     vslam_status frame_mid_locked();
     vslam_status frame_mid();          // host work that only has to precede frame_post: the local BA's window collection + hand-over (a
@@ -270,7 +272,18 @@ struct vslam_system {
     std::vector<int> rlIds;
     int reloc_candidates();
     void reloc_fill_upload(double* xyz, uint8_t* desc, float* msd);
-    void reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out);
+    // phase 0 / 1: identity predicted motion (a non-IMU session; the first pose of an IMU session), 2: the predicted motion of updatePoses
+    void reloc_commit(const double* T_cw, const uint8_t* inF, double* T_wc_out, int phase = 0);
+    // stereo + IMU sessions: the velocity comes from two relocalised poses and the bucket between them
+    bool relocPending = false;         // the first pose is committed, the velocity is not: only relocalize_imu is accepted
+    double biasGood[6] = {0, 0, 0, 0, 0, 0};      // bias at the end of the last tracked frame with >= 50 inliers
+    vslam_status relocalize_imu(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
+                                const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* rep, vslam_reloc_imu_report* irep);
+    // its host steps, shared with vslam_batch_relocalize_imu: the refusals (fn / lane name the caller in the message), the phase-2 lane's
+    // IMU problem (c.in: x0 = the camera pose, b0 = biasGood), the commit of the call's outcome
+    vslam_status reloc_imu_check(const vslam_imu_bucket* imu, const char* fn, int lane) const;
+    void reloc_imu_input(SysFrameCtx& c, const vslam_imu_bucket* imu);
+    void reloc_imu_finish(const vslam_reloc_report& rep, vslam_reloc_imu_report& irep, const double* T_cw, const uint8_t* inF, double* T_wc_out);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

@@ -305,6 +305,16 @@ def _reloc_report_dict(rep):
     return d
 
 
+class RelocImuReport(C.Structure):
+    _fields_ = [("phase", C.c_int32), ("dt", C.c_double), ("velocity_prev", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("bias", C.c_double * 6), ("rot_residual", C.c_double)]
+
+
+def _reloc_imu_report_dict(rep):
+    return dict(phase=rep.phase, dt=rep.dt, velocity_prev=np.array(list(rep.velocity_prev)), velocity=np.array(list(rep.velocity)),
+                bias=np.array(list(rep.bias)), rot_residual=rep.rot_residual)
+
+
 def _reloc_debug(call):
     """the arrays of a relocalize_debug tap; call(d3, cap, kw, cap, hc, cap, fl, cap, sizes4) is the bound C function"""
     sz = np.zeros(4, np.int32)
@@ -815,6 +825,34 @@ def imu_preintegrate_batch(matcher, buckets, solve_io=None, fill=np.nan):
     return pim, lam.reshape(B, 15, 15), pred
 
 
+def imu_reinit_velocity(matcher, gravity, noise, T_body_sensor, T_wc_prev, bias_good, acc, gyro, timestamps_ns, hz, T_cw_new):
+    """Test tap: the velocity rule of an IMU relocalisation's second pose (k_imu_preintegrate_b + k_reloc_velocity) on one
+    bucket; returns dict(dt, velocity_prev, velocity, rot_residual)."""
+    imu = _imu_input(gravity, noise, T_body_sensor, T_wc_prev, np.zeros(3), bias_good, acc, gyro, timestamps_ns, hz)
+    T = np.ascontiguousarray(T_cw_new, np.float64).reshape(16)
+    out = np.zeros(8)
+    _chk(matcher.L.vslam_imu_reinit_velocity(matcher.h, C.byref(imu), _p(T), _p(out)))
+    return dict(dt=out[0], velocity_prev=out[1:4].copy(), velocity=out[4:7].copy(), rot_residual=out[7])
+
+
+def imu_reinit_velocity_batch(matcher, lanes, fill=np.nan):
+    """Test tap: one launch of each kernel (k_imu_preintegrate_b, k_reloc_velocity_b) for several lanes.  lanes: per lane the
+    argument tuple of imu_reinit_velocity after `matcher` (an empty bucket = idle lane).  The rows start at `fill`; returns
+    out (B, 8): dt, velocity_prev[3], velocity[3], rot_residual."""
+    B = len(lanes)
+    imus = (ImuInput * B)()
+    keep = []
+    T = np.zeros((B, 16))
+    for b, args in enumerate(lanes):
+        one = _imu_input(args[0], args[1], args[2], args[3], np.zeros(3), *args[4:9])
+        keep.append(one)
+        imus[b] = one
+        T[b] = np.asarray(args[9], np.float64).reshape(16)
+    out = np.full((B, 8), fill)
+    _chk(matcher.L.vslam_imu_reinit_velocity_batch(matcher.h, B, imus, _p(T), _p(out)))
+    return out
+
+
 def tracker_set_map(matcher, xyz, desc, max_scale_dist, is_outlier=None):
     xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
     desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
@@ -1137,6 +1175,37 @@ class System:
         _chk(self.L.vslam_system_relocalize(self.h_sys, lp, rp, int(st), int(on_device), int(frame_number), C.byref(prm), _p(T),
                                             C.byref(rep)))
         return T, _reloc_report_dict(rep)
+
+    def relocalize_imu(self, left, right, frame_number, imu_bucket=None, on_device=False, stride=None, **params):
+        """vslam_system_relocalize_imu with gray frames: (T_wc, report dict, IMU report dict).  The first successful call commits
+        the pose (phase 1); the next one takes the bucket since it and re-initialises the velocity (phase 2)."""
+        T = np.zeros((4, 4))
+        rep = RelocReport(); irep = RelocImuReport()
+        prm = RelocParams(**{k: int(v) for k, v in params.items()})
+        b = None
+        keep = []
+        if imu_bucket is not None:
+            acc, gyr, ts = (np.ascontiguousarray(a, np.float64) for a in imu_bucket)
+            keep = [acc, gyr, ts]
+            b = ImuBucket(len(ts), _p(acc), _p(gyr), _p(ts))
+        if on_device:
+            lp, rp, st = C.c_void_p(left), C.c_void_p(right), stride or self.w
+        else:
+            left, ch, st = _image(left, self.h, self.w)
+            right, chr_, _ = _image(right, self.h, self.w)
+            if ch != 1 or chr_ != 1:
+                raise ValueError("relocalize takes gray frames")
+            keep += [left, right]
+            lp, rp = _p(left), _p(right)
+        _chk(self.L.vslam_system_relocalize_imu(self.h_sys, lp, rp, int(st), int(on_device), int(frame_number),
+                                                C.byref(b) if b is not None else None, C.byref(prm), _p(T), C.byref(rep), C.byref(irep)))
+        return T, _reloc_report_dict(rep), _reloc_imu_report_dict(irep)
+
+    def imu_state(self):
+        """test tap: dict(velocity, bias, bias_good, pending) of the session"""
+        v = np.zeros(3); b = np.zeros(6); g = np.zeros(6); p = C.c_int32()
+        _chk(self.L.vslam_system_imu_state(self.h_sys, _p(v), _p(b), _p(g), C.byref(p)))
+        return dict(velocity=v, bias=b, bias_good=g, pending=p.value)
 
     def wait_mapping(self):
         _chk(self.L.vslam_system_wait_mapping(self.h_sys))
@@ -1585,6 +1654,26 @@ class Batch:
         _chk(self.L.vslam_batch_relocalize(self.h_b, lp, rp, int(st), int(on_device), _p(fr), _p(mk) if mk is not None else None,
                                            C.byref(prm), _p(T), reps))
         return T, [_reloc_report_dict(reps[b]) if mask is None or mask[b] else None for b in range(B)]
+
+    def relocalize_imu(self, lefts, rights, frame_numbers, imu_buckets=None, mask=None, on_device=False, stride=None, **params):
+        """vslam_batch_relocalize_imu with gray frames: (T_wc [lanes, 4, 4], reports, IMU reports).  imu_buckets: per-lane
+        (acc, gyro, ts) for the lanes whose velocity is pending, None entries elsewhere (or None if no lane is)."""
+        B = self.lanes
+        T = np.zeros((B, 4, 4))
+        reps = (RelocReport * B)(); ireps = (RelocImuReport * B)()
+        keep = []
+        lp, rp, st, ch = self._images(lefts, rights, mask, on_device, stride, 1, keep)
+        if ch != 1:
+            raise ValueError("relocalize takes gray frames")
+        bk = self._buckets(imu_buckets, keep)
+        fr = np.ascontiguousarray(frame_numbers, np.int32)
+        mk = np.ascontiguousarray(mask, np.uint8) if mask is not None else None
+        prm = RelocParams(**{k: int(v) for k, v in params.items()})
+        _chk(self.L.vslam_batch_relocalize_imu(self.h_b, lp, rp, int(st), int(on_device), _p(fr), bk, _p(mk) if mk is not None else None,
+                                               C.byref(prm), _p(T), reps, ireps))
+        on = [mask is None or bool(mask[b]) for b in range(B)]
+        return (T, [_reloc_report_dict(reps[b]) if on[b] else None for b in range(B)],
+                [_reloc_imu_report_dict(ireps[b]) if on[b] else None for b in range(B)])
 
     def relocalize_debug(self, lane):
         """Matcher.relocalize_debug of lane `lane`: its part of the last relocalize call (test tap)"""

@@ -868,11 +868,55 @@ vslam_status vslam_system_track_stereo_raw(vslam_system* sys, const uint8_t* lef
  * camRefPose = lastKFPoseInv * pose; the frame is recorded as addFrame records a non-keyframe frame; activeMapPoints
  * becomes, in creation order, every non-outlier map point that vslam_world_to_frame places inside the left image under the
  * new pose (MapPoint::inFrame follows); the last frame's match tables are cleared; no keyframe is inserted, and the next
- * vslam_system_track_stereo proceeds normally.  IMU sessions (their velocity would need re-initialising) and mono sessions:
- * VSLAM_ERR_INVALID with nothing changed. */
+ * vslam_system_track_stereo proceeds normally.  IMU sessions (their velocity would need re-initialising:
+ * vslam_system_relocalize_imu below is their call) and mono sessions: VSLAM_ERR_INVALID with nothing changed. */
 vslam_status vslam_system_relocalize(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
                                      int32_t on_device, int32_t frame_number, const vslam_reloc_params* params,
                                      double* T_wc_out, vslam_reloc_report* report);
+/* Relocalisation of a stereo + IMU session (use_imu = 1; gray frames): the pose as vslam_system_relocalize recovers it, and
+ * the velocity from TWO relocalised poses and the IMU bucket between them (restated by
+ * tests/reloc_imu_ref.py).  The session keeps two more pieces of state: a pending flag, and biasGood - the copy of the bias
+ * taken at the end of every tracked frame whose final n_inliers >= 50 (it starts as the bias starts).  Every call runs the
+ * front end and steps A-D of vslam_system_relocalize (mode 0 or 1); what a success commits depends on the flag:
+ *   phase 1 (flag clear): the commit of vslam_system_relocalize (identity predicted motion); velocity and bias stay
+ *     untouched; the flag is set.  imu is ignored and may be NULL.  imu_report->phase = 1.
+ *   phase 2 (flag set): imu = the bucket since the previous call (n >= 1).  With T_prev = the camera pose (phase 1's) and
+ *     T_new = the rigid inverse (R^T, -R^T t) of the refined T_cw: the bucket is pre-integrated as a pose solve stages it
+ *     (dt rule of vslam_imu_predict, dt0 = 1 / hz) with the integration bias biasGood, and predicted from (T_prev, v = 0,
+ *     biasGood): pred.R, pred.t, pred.v, dt = deltaTij (the pre-integration's own sum of sample periods).  Then, in fp64,
+ *       velocity_prev[i] = (t_new[i] - pred.t[i]) / dt        velocity[i] = pred.v[i] + velocity_prev[i]
+ *       rot_residual = sqrt(sum_ij (pred.R_ij - R_new_ij)^2)   (row-major order; reported, nothing is gated on it)
+ *     - the prediction is affine in the start velocity, so velocity_prev is the v0 whose prediction lands on t_new and
+ *     velocity the v1 it implies.  The pose is committed as in phase 1 but with the predicted motion of updatePoses
+ *     (predNPoseRef = camPoseInv_prev * pose, predNPose = pose * predNPoseRef); the session's velocity = velocity, bias =
+ *     biasGood; the flag is cleared.  imu_report->phase = 2 and its other fields are filled (bias = biasGood).  The next
+ *     vslam_system_track_stereo is an ordinary IMU frame.
+ *   failure in either phase (report->success = 0, VSLAM_OK): the flag is cleared, nothing else changes, T_wc_out = the
+ *     unchanged camera pose, imu_report->phase = 0.  Phase 2 thus only ever follows a successful phase 1 by exactly one call.
+ * While the flag is set every vslam_system_track_stereo* form on the session (and a vslam_batch_track_stereo* step in which
+ * the lane is active) returns VSLAM_ERR_INVALID with nothing changed: relocalise once more.
+ * VSLAM_ERR_INVALID with nothing changed and nothing launched: a session without IMU or a mono session (use
+ * vslam_system_relocalize), no map, phase 2 with imu NULL or n < 1.  A phase-2 bucket whose 15x15 covariance has no
+ * Cholesky factor: VSLAM_ERR_INVALID (the condition of the IMU calls), the session is not changed. */
+typedef struct vslam_reloc_imu_report {
+    int32_t phase;            /* 0 failed, 1 pose committed / velocity pending, 2 velocity re-initialised */
+    double dt, velocity_prev[3], velocity[3], bias[6], rot_residual;   /* phase 2 only */
+} vslam_reloc_imu_report;
+vslam_status vslam_system_relocalize_imu(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
+                                         int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
+                                         const vslam_reloc_params* params, double* T_wc_out, vslam_reloc_report* report,
+                                         vslam_reloc_imu_report* imu_report);
+/* test tap: the IMU state of a session; any pointer may be NULL */
+vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
+/* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with
+ * the integration bias imu->bias_prev and predicted from (imu->T_wc_prev, v = 0: imu->velocity_prev is not read), then
+ * k_reloc_velocity applies the rule to the camera <- world pose T_cw_new[16].  out[8]: dt, velocity_prev[3], velocity[3],
+ * rot_residual.  Errors as vslam_imu_preintegrate.  Invalidates the matcher's staged IMU bucket. */
+vslam_status vslam_imu_reinit_velocity(vslam_matcher* m, const vslam_imu_input* imu, const double* T_cw_new, double* out);
+/* the same for n_lanes buckets with ONE launch of k_imu_preintegrate_b and ONE of k_reloc_velocity_b; T_cw_new [n_lanes][16],
+ * out [n_lanes][8].  A bucket with n_samples = 0 is an idle lane: its out row is left as the caller filled it. */
+vslam_status vslam_imu_reinit_velocity_batch(vslam_matcher* m, int32_t n_lanes, const vslam_imu_input* imus,
+                                             const double* T_cw_new, double* out);
 /* blocks until the device work of the pass in flight (local_mapping = 2) has finished; reports its failure, if any.
  * (Its results are still applied at the frames the schedule names.) */
 vslam_status vslam_system_wait_mapping(vslam_system* sys);
@@ -1015,7 +1059,7 @@ vslam_status vslam_batch_restart_lane(vslam_batch* batch, int32_t lane, const vs
  * k_reloc_inframe_b (the left-image test of every uploaded map point under the refined pose, for lanes that succeeded), one
  * wait, one download.  Success and failure are committed per lane as vslam_system_relocalize commits them: on failure
  * (reports[lane].success = 0) nothing in that session changes and its T_wc_out row is the unchanged camera pose.
- * Gray, rectified frames; stereo lanes without IMU.  Lanes outside the mask are not touched: session, matcher state,
+ * Gray, rectified frames; stereo lanes without IMU (an IMU batch: vslam_batch_relocalize_imu below).  Lanes outside the mask are not touched: session, matcher state,
  * mapping jobs in flight, T_wc_out row and report stay as they are.  VSLAM_ERR_INVALID, with a message that names the lane
  * and nothing changed: an IMU batch, a masked lane without a map (also a restarted lane whose frame 0 has not been tracked),
  * NULL images for a masked lane.  A pending prefetch is waited for and discarded (as vslam_batch_restart_lane does): the
@@ -1028,6 +1072,20 @@ vslam_status vslam_batch_relocalize(vslam_batch* batch, const uint8_t* const* le
                                     int32_t on_device, const int32_t* frame_numbers, const uint8_t* lane_mask,
                                     const vslam_reloc_params* params, double* T_wc_out /* [lanes][16] */,
                                     vslam_reloc_report* reports /* [lanes] */);
+/* The same call for a stereo + IMU batch: per masked lane what vslam_system_relocalize_imu does for that session, in the shape
+ * of vslam_batch_relocalize - one launch per stage for all lanes, one pinned upload (the phase-2 lanes' IMU samples travel in
+ * it), one wait, one download.  A call may hold lanes in both phases: the phase-2 lanes' buckets are pre-integrated by one
+ * k_imu_preintegrate_b launch ahead of the relocalisation stages (phase-1 lanes are idle entries), and k_reloc_velocity_b
+ * applies the velocity rule to the lanes whose refinement succeeded.  imu: [lanes] buckets, read for the masked lanes whose
+ * flag is set; NULL if no masked lane is in phase 2.  imu_reports: [lanes], written for the masked lanes.
+ * VSLAM_ERR_INVALID with a message that names the lane, nothing changed and nothing launched: a batch without IMU (use
+ * vslam_batch_relocalize), a masked lane without a map, NULL images for a masked lane, a masked phase-2 lane without a bucket
+ * or with n < 1.  A phase-2 bucket whose covariance has no Cholesky factor: VSLAM_ERR_INVALID naming the lane, no session is
+ * changed by the call. */
+vslam_status vslam_batch_relocalize_imu(vslam_batch* batch, const uint8_t* const* left, const uint8_t* const* right, int32_t stride,
+                                        int32_t on_device, const int32_t* frame_numbers, const vslam_imu_bucket* imu /* [lanes] or NULL */,
+                                        const uint8_t* lane_mask, const vslam_reloc_params* params, double* T_wc_out /* [lanes][16] */,
+                                        vslam_reloc_report* reports /* [lanes] */, vslam_reloc_imu_report* imu_reports /* [lanes] */);
 /* vslam_relocalize_debug on lane `lane`'s matcher: its part of the last vslam_batch_relocalize call (test tap) */
 vslam_status vslam_batch_relocalize_debug(vslam_batch* batch, int32_t lane, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner,
                                           int32_t cap_keys, int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags,

@@ -20,7 +20,16 @@ usage: python tools/reloc_rate.py --lanes [out.json] [calls] [reps]
 --mode both: the two hypothesis modes against each other on the same resident frame and map, same build, same process - five warm-up
 calls of each, then `reps` repetitions that alternate mode 0 and mode 1 (`calls` calls each): wall-clock time per call and device
 time per kernel group of each mode; then the 16-lane vslam_relocalize_batch call of each mode, alternated in the same way.
-usage: python tools/reloc_rate.py --mode both [out.json] [calls] [reps]"""
+usage: python tools/reloc_rate.py --mode both [out.json] [calls] [reps]
+
+--imu: the two phases of vslam_batch_relocalize_imu against each other.  The phases belong to sessions, so the frame and the map here
+are a session's own, not the crafted 1 500 x 20 000 shape above: L = 1 and 16 stereo + IMU lanes of a vslam_batch track the rendered
+EuRoC source frames 0, 2, 4, 6 (1 500 features; a map of ~2 000 points each), then every lane is relocalised on source frame 4 (first
+pose: the pose alone) and on source frame 6 with the bucket between them (second pose: + k_imu_preintegrate_b and k_reloc_velocity_b) -
+the two calls alternate by construction, same build, same process.  Five warm-up pairs, then `reps` repetitions of `pairs` pairs: wall
+clock per call of each phase (host clock around a call that ends in a device synchronise), timing off; then one repetition with the
+batch's stage timing on for the device time of every stage of each phase.
+usage: python tools/reloc_rate.py --imu [out.json] [pairs] [reps]"""
 import json, os, sys, time
 os.environ.setdefault("OMP_NUM_THREADS", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -182,6 +191,80 @@ def main_modes(argv):
     print(json.dumps(res))
 
 
+def main_imu(argv):
+    out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "reloc_imu_rate.json")
+    pairs = int(argv[1]) if len(argv) > 1 else 20
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    if vc.device_count() < 1:
+        raise RuntimeError("reloc_rate needs a GPU: a time taken anywhere else says nothing about the stage")
+    fps = RIG["fps"]
+    imu = dict(gravity=(0.0, 9.81, 0.0), noise=(1.6968e-4, 1.9393e-5, 2.0e-3, 3.0e-3), T_bs=synth.T_BC1, hz=200)
+    stat = lambda v: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+
+    def velocity(f):
+        h = 1e-4
+        return (synth.pose_at(f + h * fps, fps)[:3, 3] - synth.pose_at(f - h * fps, fps)[:3, 3]) / (2 * h)
+
+    def bucket(f0, f1):
+        S, dts, _ = synth.imu_samples(f0, f1, fps, noise_seed=0x1A00 + f1)
+        return (S[:, :3], S[:, 3:], np.arange(len(dts)) * 5e6)
+
+    src = [0, 2, 4, 6]
+    synth.prerender(src)
+    frames = [synth.stereo_frame(f) for f in src]
+    res = dict(features=1500, source_frames=src, mode=MODE, pairs_per_repetition=pairs, repetitions=reps, lanes={})
+    for L in (1, 16):
+        bt = vc.Batch(RIG, 1500, L, T0s=[synth.pose_at(0, fps)] * L, imu=imu, velocities=[velocity(0)] * L, local_mapping=1, host_threads=min(L, 8))
+        for n, f in enumerate(src):
+            bt.track([frames[n][0]] * L, [frames[n][1]] * L, [n] * L, imu_buckets=[bucket(src[n - 1], f)] * L if n else None)
+        fn = [len(src)]
+        bk = [bucket(4, 6)] * L
+
+        def pair(wall=None):
+            out = []
+            for ph, (k, b) in enumerate(((2, None), (3, bk))):
+                t0 = time.perf_counter()
+                T, rr_, ir = bt.relocalize_imu([frames[k][0]] * L, [frames[k][1]] * L, [fn[0]] * L, imu_buckets=b, mode=MODE)
+                if wall is not None:
+                    wall[ph].append((time.perf_counter() - t0) * 1e3)
+                fn[0] += 1
+                out.append((rr_, ir))
+            return out
+
+        for _ in range(5):
+            last = pair()
+        ok = all(last[0][1][b]["phase"] == 1 and last[1][1][b]["phase"] == 2 for b in range(L))
+        med = [[], []]
+        for _ in range(reps):
+            wall = [[], []]
+            for _ in range(pairs):
+                pair(wall)
+            for ph in range(2):
+                med[ph].append(float(np.mean(wall[ph])))
+        bt.set_timing(True)
+        pair()
+        bt.timings()
+        dev = [{}, {}]
+        for _ in range(pairs):
+            for ph, (k, b) in enumerate(((2, None), (3, bk))):
+                bt.relocalize_imu([frames[k][0]] * L, [frames[k][1]] * L, [fn[0]] * L, imu_buckets=b, mode=MODE)
+                fn[0] += 1
+                for name, ms in bt.timings()[0].items():
+                    if name.startswith("reloc_"):
+                        dev[ph].setdefault(name, []).append(ms)
+        bt.set_timing(False)
+        res["lanes"][str(L)] = dict(
+            phases_as_expected=bool(ok), map_points=last[1][0][0]["n_points"], pairs=last[1][0][0]["n_pairs"], inliers=last[1][0][0]["n_inliers"],
+            dt=last[1][1][0]["dt"], rot_residual=last[1][1][0]["rot_residual"],
+            first_pose_call_ms=stat(med[0]), second_pose_call_ms=stat(med[1]), second_minus_first_ms=float(np.median(med[1]) - np.median(med[0])),
+            device_ms_per_call_first_pose={k: stat(v) for k, v in sorted(dev[0].items())},
+            device_ms_per_call_second_pose={k: stat(v) for k, v in sorted(dev[1].items())})
+        bt.close()
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     global MODE
     if "--mode" in sys.argv:
@@ -191,6 +274,8 @@ def main():
         if mode == "both":
             return main_modes(sys.argv[1:])
         MODE = int(mode)
+    if len(sys.argv) > 1 and sys.argv[1] == "--imu":
+        return main_imu(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--lanes":
         return main_lanes(sys.argv[2:])
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "reloc_rate.json")
