@@ -1,0 +1,271 @@
+// Loop closing of a stereo session (no reference counterpart; vslam_hip.h): the relocalisation
+// stage asked on the part of the map the tracker has left behind, a pose graph over the keyframes solved by
+// vslam_pose_graph_optimize, and the commit that hands the old copy of the place back to the tracker.
+#include "system.hpp"
+#include <set>
+
+using namespace vslam;
+using namespace vslam_sys;
+
+namespace {
+bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P) {
+    P = prm ? *prm : vslam_loop_params{};
+    if (P.min_kf_gap < 0 || P.covis_min < 0 || !(P.loop_weight >= 0.0) || !std::isfinite(P.loop_weight)) return false;
+    if (P.min_kf_gap == 0) P.min_kf_gap = 20;
+    if (P.covis_min == 0) P.covis_min = 100;
+    if (P.loop_weight == 0.0) P.loop_weight = 10.0;
+    return true;
+}
+}  // namespace
+
+vslam_status vslam_system::loop_check(const char* fn) const {
+    if (monoMode) { set_error("%s: a mono session cannot close loops (stereo fixes the scale of the correction)", fn); return VSLAM_ERR_INVALID; }
+    if (cfg.use_imu) { set_error("%s: an IMU session cannot close loops yet (its velocity and gravity frame would have to follow)", fn); return VSLAM_ERR_INVALID; }
+    if (keyFrames.empty()) { set_error("%s: no tracked frame yet", fn); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
+// map points that are not outliers, not active, created at least minKfGap keyframes ago; creation order, the most recent 65536
+int vslam_system::loop_candidates(int minKfGap) {
+    std::lock_guard<std::mutex> lk(mapMutex);
+    rlIds.clear();
+    std::vector<uint8_t> isActive(mapPoints.size(), 0);
+    for (int a : active) isActive[a] = 1;
+    const long long newest = (long long)latestKF - minKfGap;
+    for (int m = 0; m < (int)mapPoints.size(); m++)
+        if (!mpOutlier[m] && !isActive[m] && mapPoints[m].kdx <= newest) rlIds.push_back(m);
+    if (rlIds.size() > 65536) rlIds.erase(rlIds.begin(), rlIds.end() - 65536);
+    return (int)rlIds.size();
+}
+
+vslam_status vslam_system::loop_apply(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep) {
+    VS_HIP(hipSetDevice(cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
+            VS_CHECK(change_poses_lca(endLBAIdx));
+            LBADone = false;
+        }
+        const int K = (int)keyFrames.size();
+        std::vector<double> poses((size_t)K * 16), fresh((size_t)K * 16);
+        std::vector<uint8_t> fixed(K, 0);
+        fixed[0] = fixed[kfLoop] = 1;
+        for (int k = 0; k < K; k++) memcpy(&poses[16 * (size_t)k], keyFrames[k].pose.data(), 16 * sizeof(double));
+        std::vector<vslam_pgo_edge> edges;
+        auto add = [&](int a, int b, const M4& Z, double w) {
+            vslam_pgo_edge e{};
+            e.i = a; e.j = b; e.w_rot = e.w_trans = w;
+            memcpy(e.Z, Z.data(), 16 * sizeof(double));
+            edges.push_back(e);
+        };
+        for (int k = 0; k < K; k++) {
+            const int p = keyFrames[k].prevKF;
+            if (p >= 0) add(p, k, m4_mul(keyFrames[p].poseInv, keyFrames[k].pose), 1.0);
+        }
+        rep->n_sequential = (int)edges.size();
+        std::set<std::pair<int, int>> seen;
+        for (int k = 0; k < K; k++)
+            for (const auto& c : keyFrames[k].sortedKFWeights) {
+                if (c.first < P.covis_min || c.second == k || c.second < 0 || c.second >= K) continue;
+                const int a = std::min(k, c.second), b = std::max(k, c.second);
+                if (!seen.insert({a, b}).second) continue;
+                add(a, b, m4_mul(keyFrames[a].poseInv, keyFrames[b].pose), 1.0);
+            }
+        rep->n_covisibility = (int)edges.size() - rep->n_sequential;
+        const M4 D = m4_mul(T_corr, camPoseInv);
+        add(kfLoop, latestKF, m4_mul(keyFrames[kfLoop].poseInv, m4_mul(D, keyFrames[latestKF].pose)), P.loop_weight);
+        rep->n_nodes = K; rep->n_edges = (int)edges.size();
+        VS_CHECK(vslam_pose_graph_optimize(poses.data(), fixed.data(), K, edges.data(), (int)edges.size(), &P.pgo, cfg.device, fresh.data(), &rep->pgo));
+        // ---- the commit ---------------------------------------------------------------------------------------------------------
+        const int nMp = (int)mapPoints.size();
+        std::vector<double> xyz((size_t)std::max(nMp, 1) * 3), moved((size_t)std::max(nMp, 1) * 3);
+        std::vector<int> ref(std::max(nMp, 1), -1);
+        int nMoved = 0;
+        for (int m = 0; m < nMp; m++) {
+            const SysMP& mp = mapPoints[m];
+            for (int c = 0; c < 3; c++) xyz[3 * (size_t)m + c] = mp.wp[c];
+            if (!mp.kfm.empty()) { ref[m] = mp.kfm[0].kf; nMoved++; }
+        }
+        VS_CHECK(vslam_pose_graph_move_points(xyz.data(), ref.data(), poses.data(), fresh.data(), nMp, K, cfg.device, moved.data()));
+        for (int m = 0; m < nMp; m++) for (int c = 0; c < 3; c++) mapPoints[m].wp[c] = moved[3 * (size_t)m + c];
+        for (int k = 0; k < K; k++) keyFrames[k].setPose(m4_from(&fresh[16 * (size_t)k]));
+        for (int k = 0; k < K; k++) {
+            const int p = keyFrames[k].prevKF;
+            if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
+        }
+        lca_finish(latestKF);
+        rep->points_moved = nMoved;
+    }
+    // the active set: reloc_commit's rule under the new camera pose
+    const size_t n = (size_t)reloc_candidates();
+    std::vector<double> xyz(3 * std::max<size_t>(n, 1)); std::vector<uint8_t> desc(32 * std::max<size_t>(n, 1)); std::vector<float> msd(std::max<size_t>(n, 1));
+    reloc_fill_upload(xyz.data(), desc.data(), msd.data());
+    std::vector<float> pl(2 * std::max<size_t>(n, 1)), pr(2 * std::max<size_t>(n, 1)); std::vector<int> ll(std::max<size_t>(n, 1)), lr(std::max<size_t>(n, 1));
+    std::vector<uint8_t> inF(std::max<size_t>(n, 1)), inFR(std::max<size_t>(n, 1));
+    if (n) VS_CHECK(vslam_world_to_frame(fm, camPoseInv.data(), (int)n, xyz.data(), msd.data(), (float)std::log((double)cfg.fe.scale), pl.data(), pr.data(),
+                                         ll.data(), lr.data(), inF.data(), inFR.data()));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        active.clear();
+        for (size_t j = 0; j < n; j++) {
+            mpInFrame[rlIds[j]] = inF[j];
+            if (inF[j]) active.push_back(rlIds[j]);
+        }
+        lastMatches.clear(); lastOutliers.clear();
+        rep->n_active_after = (int)active.size();
+    }
+    rep->corrected = 1;
+    return VSLAM_OK;
+}
+
+static void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep) {
+    const M4 D = m4_mul(T_corr, camPoseInv);
+    rep->drift_translation = std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
+    const double c = std::min(1.0, std::max(-1.0, (D[0] + D[5] + D[10] - 1.0) / 2.0));
+    rep->drift_rotation = std::acos(c);
+    memcpy(rep->T_wc_corrected, T_corr.data(), 16 * sizeof(double));
+}
+
+vslam_status vslam_system::correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep) {
+    if (!T_wc_corrected || !rep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check("vslam_system_correct_loop"));
+    vslam_loop_params P;
+    if (!resolve_loop_params(prm, P)) { set_error("vslam_system_correct_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
+    if (kfLoop < 0 || kfLoop >= (int)keyFrames.size() || kfLoop == latestKF) {
+        set_error("vslam_system_correct_loop: kf_loop %d (keyframes 0 .. %d, the latest excluded)", kfLoop, (int)keyFrames.size() - 1);
+        return VSLAM_ERR_INVALID;
+    }
+    for (int k = 0; k < 16; k++) if (!std::isfinite(T_wc_corrected[k])) { set_error("vslam_system_correct_loop: non-finite pose"); return VSLAM_ERR_INVALID; }
+    *rep = vslam_loop_report{};
+    rep->kf_loop = kfLoop;
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    rep->success = 1;
+    const M4 T_corr = m4_from(T_wc_corrected);
+    loop_drift(T_corr, camPoseInv, rep);
+    return loop_apply(kfLoop, T_corr, P, rep);
+}
+
+vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_report* rep) {
+    if (!rep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check("vslam_system_close_loop"));
+    vslam_loop_params P;
+    vslam_reloc_params RP;
+    if (!resolve_loop_params(prm, P)) { set_error("vslam_system_close_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(reloc_resolve_params(&P.reloc, RP));
+    if (!fm->stereoDone) { set_error("vslam_system_close_loop: the matcher holds no frame"); return VSLAM_ERR_INVALID; }
+    *rep = vslam_loop_report{};
+    rep->kf_loop = -1;
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    const size_t n = (size_t)loop_candidates(P.min_kf_gap);
+    rep->n_candidates = (int)n;
+    rep->reloc.n_points = (int)n;
+    if ((int)n < RP.min_inliers) return VSLAM_OK;
+    VS_HIP(hipSetDevice(cfg.device));
+    std::vector<double> xyz(3 * n); std::vector<uint8_t> desc(32 * n); std::vector<float> msd(n);
+    reloc_fill_upload(xyz.data(), desc.data(), msd.data());
+    std::vector<int> pairs(n, -1);
+    double T_cw[16];
+    {
+        // step D may clear stereo matches of the frame the matcher holds: saved here, restored below, so that nothing of the stage
+        // reaches the session
+        DevPool* pool = thread_pool(cfg.device);
+        if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+        const size_t c = (size_t)fm->cap;
+        PoolBuf<uint8_t> save(pool);
+        VS_HIP(save.alloc(c * 16));
+        uint8_t* s = save.p;
+        VS_HIP(hipMemcpyAsync(s, fm->d_rightIdxs, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(s + c * 4, fm->d_leftIdxs, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(s + c * 8, fm->d_depth, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(s + c * 12, fm->d_close, c, hipMemcpyDeviceToDevice, fm->stream));
+        const vslam_status st = fm->relocalize(xyz.data(), desc.data(), (int)n, &P.reloc, T_cw, pairs.data(), &rep->reloc);
+        VS_HIP(hipMemcpyAsync(fm->d_rightIdxs, s, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(fm->d_leftIdxs, s + c * 4, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(fm->d_depth, s + c * 8, c * 4, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipMemcpyAsync(fm->d_close, s + c * 12, c, hipMemcpyDeviceToDevice, fm->stream));
+        VS_HIP(hipStreamSynchronize(fm->stream));
+        VS_CHECK(st);
+    }
+    if (!rep->reloc.success) return VSLAM_OK;
+    // kf_loop: the keyframe (not the latest) that observes the most inliers of the winning hypothesis
+    {
+        const int C = fm->rlLast[3];
+        std::vector<uint8_t> flags(std::max(C, 1), 0);
+        VS_CHECK(fm->relocalize_debug(nullptr, 0, nullptr, 0, nullptr, 0, flags.data(), C, nullptr));
+        std::vector<std::pair<int, int>> byKey;                // (key, candidate): correspondences are in ascending key order
+        for (size_t p = 0; p < n; p++) if (pairs[p] >= 0) byKey.push_back({pairs[p], (int)p});
+        std::sort(byKey.begin(), byKey.end());
+        if ((int)byKey.size() != C) { set_error("vslam_system_close_loop: %d correspondences, %d pairs", C, (int)byKey.size()); return VSLAM_ERR_HIP; }
+        std::lock_guard<std::mutex> lk(mapMutex);
+        std::vector<int> votes(keyFrames.size(), 0);
+        for (int c = 0; c < C; c++) {
+            if (!flags[c]) continue;
+            for (const KfMatch& o : mapPoints[rlIds[byKey[c].second]].kfm) if (o.kf != latestKF) votes[o.kf]++;
+        }
+        int best = -1;
+        for (int k = 0; k < (int)votes.size(); k++) if (votes[k] > 0 && (best < 0 || votes[k] > votes[best])) best = k;
+        if (best < 0) return VSLAM_OK;
+        rep->kf_loop = best;
+    }
+    rep->success = 1;
+    const M4 T_corr = m4_rigid_inv(m4_from(T_cw));
+    loop_drift(T_corr, camPoseInv, rep);
+    if (P.detect_only) return VSLAM_OK;
+    return loop_apply(rep->kf_loop, T_corr, P, rep);
+}
+
+extern "C" {
+
+vslam_status vslam_system_correct_loop(vslam_system* s, int32_t kf_loop, const double* T_wc_corrected, const vslam_loop_params* params,
+                                       vslam_loop_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    const vslam_status st = s->correct_loop(kf_loop, T_wc_corrected, params, report);
+    if (st == VSLAM_OK) memcpy(report->T_wc, s->camPose.data(), 16 * sizeof(double));
+    return st;
+}
+
+vslam_status vslam_system_close_loop(vslam_system* s, const vslam_loop_params* params, vslam_loop_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    const vslam_status st = s->close_loop(params, report);
+    if (st == VSLAM_OK) memcpy(report->T_wc, s->camPose.data(), 16 * sizeof(double));
+    return st;
+}
+
+vslam_status vslam_system_active_points(vslam_system* s, int32_t cap, int32_t* n_out, int32_t* index) {
+    if (!s || !n_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    const int n = (int)s->active.size();
+    *n_out = n;
+    if (n > cap) return VSLAM_ERR_CAPACITY;
+    if (index) for (int i = 0; i < n; i++) index[i] = s->active[i];
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system_covisibility(vslam_system* s, int32_t cap, int32_t* n_out, int32_t* triples) {
+    if (!s || !n_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    int n = 0;
+    for (const SysKF& kf : s->keyFrames) n += (int)kf.sortedKFWeights.size();
+    *n_out = n;
+    if (n > cap) return VSLAM_ERR_CAPACITY;
+    if (!triples) return VSLAM_OK;
+    int q = 0;
+    for (const SysKF& kf : s->keyFrames)
+        for (const auto& c : kf.sortedKFWeights) { triples[3 * q] = kf.numb; triples[3 * q + 1] = c.second; triples[3 * q + 2] = c.first; q++; }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system_map_point_keyframes(vslam_system* s, int32_t cap, int32_t* n_out, int32_t* first_observer, int32_t* creator) {
+    if (!s || !n_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    const int n = (int)s->mapPoints.size();
+    *n_out = n;
+    if (n > cap) return VSLAM_ERR_CAPACITY;
+    for (int i = 0; i < n; i++) {
+        if (first_observer) first_observer[i] = s->mapPoints[i].kfm.empty() ? -1 : s->mapPoints[i].kfm[0].kf;
+        if (creator) creator[i] = (int32_t)s->mapPoints[i].kdx;
+    }
+    return VSLAM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,645 @@
+// Pose-graph optimisation on the device (no reference counterpart; DESIGN.md section 6 item 24, restated by tests/pgo_ref.py):
+// Levenberg-Marquardt over SE(3) poses tied by relative-pose edges, the damped normal equations solved DIRECTLY by a
+// block-banded Cholesky of 6x6 fp64 blocks after a reverse Cuthill-McKee reordering of the free poses on the host.
+//   k_pgo_linearize   one thread per edge: residual, both 6x6 Jacobians, the edge's cost term
+//   k_pgo_assemble    one wave per free pose, one lane per block element: a gather over the pose's incidence list (CSR, built
+//                     once per call, ascending edge index) into the band's column and the gradient.  No atomics; every sum
+//                     runs in list order.
+//   k_pgo_band_chol   one workgroup walks the block columns: factor, forward substitution (carried as an extra row), back
+//                     substitution.  Nothing on the host waits inside it.
+//   k_pgo_retract / k_pgo_cost / k_pgo_reduce   the trial poses, their per-edge cost, the fixed-order sum and |delta|_inf
+//   k_pgo_move_points one thread per map point: X' = T_new[ref] * T_old[ref]^-1 * X
+// The accept / reject decision is the host's: one wait per trial.
+#include "common.hpp"
+#include "dmath.hpp"
+#include <cmath>
+#include <numeric>
+
+using namespace vslam;
+
+namespace {
+
+constexpr int PGO_MAX_POSES = 16384, PGO_MAX_EDGES = 262144, PGO_MAX_BLOCKS = 262144;
+constexpr int PGO_CHOL_NT = 256;       // threads of the factorisation's workgroup
+constexpr int PGO_RED_NT = 256;
+constexpr int PGO_BACK_PARTS = 10;     // back substitution: 10 x 6 lanes of wave 0 share a column's off-diagonal blocks
+
+// a pose on the device: R row-major [9], t [3]
+struct PgoEdge { int i, j; double Rz[9], tz[3], wr, wt; };
+
+// SO(3) logarithm: the rule of dmath.hpp's so3_logmap, written out so that the restatement can follow it line by line
+__device__ __forceinline__ void pgo_log(const double* R, double* w) {
+    const double tr = R[0] + R[4] + R[8];
+    const double tr_3 = tr - 3.0;
+    double mag;
+    if (tr_3 < -1e-6) {
+        double c = (tr - 1.0) / 2.0;
+        c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+        const double theta = acos(c);
+        mag = theta / (2.0 * sin(theta));
+    } else {
+        mag = 0.5 - tr_3 / 12.0 + tr_3 * tr_3 / 60.0;
+    }
+    w[0] = mag * (R[7] - R[5]);
+    w[1] = mag * (R[2] - R[6]);
+    w[2] = mag * (R[3] - R[1]);
+}
+
+// E = Z^-1 * T_i^-1 * T_j with rigid inverses; RD / tD = T_i^-1 * T_j
+__device__ __forceinline__ void pgo_error(const double* Pi, const double* Pj, const PgoEdge& e, double* RD, double* tD, double* RE, double* tE) {
+    double RiT[9], RzT[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) { RiT[3 * a + b] = Pi[3 * b + a]; RzT[3 * a + b] = e.Rz[3 * b + a]; }
+    mat3_mul(RiT, Pj, RD);
+    const double dt[3] = {Pj[9] - Pi[9], Pj[10] - Pi[10], Pj[11] - Pi[11]};
+    mat3_vec(RiT, dt, tD);
+    mat3_mul(RzT, RD, RE);
+    const double dz[3] = {tD[0] - e.tz[0], tD[1] - e.tz[1], tD[2] - e.tz[2]};
+    mat3_vec(RzT, dz, tE);
+}
+
+// per edge: r [6], Ji [36], Jj [36] (row = residual component, column = parameter (a, b) of the pose), cost term
+__global__ __launch_bounds__(256) void k_pgo_linearize(int m, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
+                                                       double* __restrict__ res, double* __restrict__ Ji, double* __restrict__ Jj,
+                                                       double* __restrict__ cost) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m) return;
+    const PgoEdge E = edges[e];
+    double Pi[12], Pj[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) { Pi[k] = poses[(size_t)E.i * 12 + k]; Pj[k] = poses[(size_t)E.j * 12 + k]; }
+    double RD[9], tD[3], RE[9], tE[3], w[3];
+    pgo_error(Pi, Pj, E, RD, tD, RE, tE);
+    pgo_log(RE, w);
+    // inverse right Jacobian of SO(3): I + W / 2 + c W^2
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double c;
+    if (th2 < 1e-10) c = 1.0 / 12.0;
+    else { const double th = sqrt(th2); c = 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th)); }
+    double W[9], WW[9], Jri[9];
+    skew3(w, W);
+    mat3_mul(W, W, WW);
+#pragma unroll
+    for (int k = 0; k < 9; k++) Jri[k] = ((k % 4 == 0) ? 1.0 : 0.0) + 0.5 * W[k] + c * WW[k];
+    double RDT[9], RzT[9], A[9], S[9], B[9];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) { RDT[3 * a + b] = RD[3 * b + a]; RzT[3 * a + b] = E.Rz[3 * b + a]; }
+    mat3_mul(Jri, RDT, A);          // d r_w / d a_i = -A
+    skew3(tD, S);
+    mat3_mul(RzT, S, B);            // d r_t / d a_i = B;  d r_t / d b_i = -RzT
+    double* ji = Ji + (size_t)e * 36;
+    double* jj = Jj + (size_t)e * 36;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            ji[6 * a + b] = -A[3 * a + b];        ji[6 * a + 3 + b] = 0.0;
+            ji[6 * (a + 3) + b] = B[3 * a + b];   ji[6 * (a + 3) + 3 + b] = -RzT[3 * a + b];
+            jj[6 * a + b] = Jri[3 * a + b];       jj[6 * a + 3 + b] = 0.0;
+            jj[6 * (a + 3) + b] = 0.0;            jj[6 * (a + 3) + 3 + b] = RE[3 * a + b];
+        }
+    double* r = res + (size_t)e * 6;
+    r[0] = w[0]; r[1] = w[1]; r[2] = w[2]; r[3] = tE[0]; r[4] = tE[1]; r[5] = tE[2];
+    cost[e] = E.wr * th2 + E.wt * (tE[0] * tE[0] + tE[1] * tE[1] + tE[2] * tE[2]);
+}
+
+// the cost term alone, for trial poses
+__global__ __launch_bounds__(256) void k_pgo_cost(int m, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
+                                                   double* __restrict__ cost) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m) return;
+    const PgoEdge E = edges[e];
+    double Pi[12], Pj[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) { Pi[k] = poses[(size_t)E.i * 12 + k]; Pj[k] = poses[(size_t)E.j * 12 + k]; }
+    double RD[9], tD[3], RE[9], tE[3], w[3];
+    pgo_error(Pi, Pj, E, RD, tD, RE, tE);
+    pgo_log(RE, w);
+    cost[e] = E.wr * (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) + E.wt * (tE[0] * tE[0] + tE[1] * tE[1] + tE[2] * tE[2]);
+}
+
+// Band storage: block (c, d), d = 0 .. b, is H[c + d][c] (lower), 36 doubles row-major, at ((c * (b + 1)) + d) * 36.
+// One wave per free pose (band position c).  Lane e < 36 owns element e = 6 r + s of every block of column c; lanes 36 .. 41 own
+// the gradient's components.  inc[k] = edge << 1 | side (1: the pose is the edge's j), ascending; pos[] = band position or -1.
+__global__ __launch_bounds__(64) void k_pgo_assemble(int nf, int b, const int* __restrict__ pos,
+                                                     const int* __restrict__ rowStart, const int* __restrict__ inc,
+                                                     const PgoEdge* __restrict__ edges, const double* __restrict__ res,
+                                                     const double* __restrict__ Ji, const double* __restrict__ Jj,
+                                                     double* __restrict__ band, double* __restrict__ diagH, double* __restrict__ rhs) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (c >= nf || lane >= 42) return;
+    const int bc = min(b, nf - 1 - c);
+    double* col = band + (size_t)c * (b + 1) * 36;
+    const int r = lane / 6, s = lane % 6;
+    if (lane < 36) for (int d = 1; d <= bc; d++) col[(size_t)d * 36 + lane] = 0.0;
+    double acc = 0.0;
+    for (int k = rowStart[c]; k < rowStart[c + 1]; k++) {
+        const int e = inc[k] >> 1, side = inc[k] & 1;
+        const double* Jc = (side ? Jj : Ji) + (size_t)e * 36;
+        const double wr = edges[e].wr, wt = edges[e].wt;
+        if (lane < 36) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < 6; q++) v += Jc[6 * q + r] * (q < 3 ? wr : wt) * Jc[6 * q + s];
+            acc += v;
+            const int other = side ? edges[e].i : edges[e].j;
+            const int o = pos[other];
+            if (o > c) {                     // H[o][c] = Jo^T W Jc: the lower block of the pair, written by the lower position's wave
+                const double* Jo = (side ? Ji : Jj) + (size_t)e * 36;
+                double u = 0.0;
+#pragma unroll
+                for (int q = 0; q < 6; q++) u += Jo[6 * q + r] * (q < 3 ? wr : wt) * Jc[6 * q + s];
+                col[(size_t)(o - c) * 36 + lane] += u;
+            }
+        } else {
+            const double* rr = res + (size_t)e * 6;
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < 6; q++) v += Jc[6 * q + s] * (q < 3 ? wr : wt) * rr[q];
+            acc += v;
+        }
+    }
+    if (lane < 36) {
+        col[lane] = acc;
+        if (r == s) diagH[(size_t)c * 6 + r] = acc;
+    } else {
+        rhs[(size_t)c * 6 + s] = -acc;
+    }
+}
+
+// lower-triangular 6x6 in 21 named registers: L(i, j) = l[i (i + 1) / 2 + j]
+#define PGO_L(i, j) l[(i) * ((i) + 1) / 2 + (j)]
+
+// in-place Cholesky of the lower triangle; a pivot that is not positive raises *bad and is replaced by 1
+__device__ __forceinline__ void pgo_chol6(double* l, int* bad) {
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double d = PGO_L(j, j);
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= PGO_L(j, k) * PGO_L(j, k);
+        if (!(d > 0.0) || !(d < 1e300)) { *bad = 1; d = 1.0; }
+        const double sd = sqrt(d);
+        PGO_L(j, j) = sd;
+        const double inv = 1.0 / sd;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = PGO_L(i, j);
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= PGO_L(i, k) * PGO_L(j, k);
+            PGO_L(i, j) = v * inv;
+        }
+    }
+}
+// x L^T = h  (one block row against the column's diagonal factor): x[s] = (h[s] - sum_{k < s} x[k] L(s, k)) / L(s, s)
+__device__ __forceinline__ void pgo_row_solve(const double* l, double* x) {
+#pragma unroll
+    for (int s = 0; s < 6; s++) {
+        double v = x[s];
+#pragma unroll
+        for (int k = 0; k < s; k++) v -= x[k] * PGO_L(s, k);
+        x[s] = v / PGO_L(s, s);
+    }
+}
+// L^T x = v
+__device__ __forceinline__ void pgo_back_solve(const double* l, double* x) {
+#pragma unroll
+    for (int s = 5; s >= 0; s--) {
+        double v = x[s];
+#pragma unroll
+        for (int k = s + 1; k < 6; k++) v -= PGO_L(k, s) * x[k];
+        x[s] = v / PGO_L(s, s);
+    }
+}
+
+// (H + lambda diag(H)) delta = rhs, H in `band` (overwritten by its factor), rhs overwritten by the forward solution y.
+// One workgroup.  Per column c: (A) every thread factors the damped diagonal block and solves y_c in registers (redundantly: no
+// broadcast is needed), the threads share the 6 bc block rows below it; (B) the threads share the 36 bc (bc + 1) / 2 elements of
+// the trailing update and the 6 bc right-hand-side entries.  Two barriers per column; then the columns backwards.
+__global__ __launch_bounds__(PGO_CHOL_NT) void k_pgo_band_chol(int nf, int b, double lambda, double* __restrict__ band,
+                                                               const double* __restrict__ diagH, double* __restrict__ rhs,
+                                                               double* __restrict__ delta, int* __restrict__ flag) {
+    __shared__ double sPart[PGO_BACK_PARTS][6];
+    const int tid = threadIdx.x;
+    const size_t cs = (size_t)(b + 1) * 36;      // column stride
+    int bad = 0;
+    for (int c = 0; c < nf; c++) {
+        const int bc = min(b, nf - 1 - c);
+        double* col = band + (size_t)c * cs;
+        double l[21];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++) PGO_L(i, j) = col[6 * i + j];
+#pragma unroll
+        for (int i = 0; i < 6; i++) PGO_L(i, i) += lambda * diagH[(size_t)c * 6 + i];
+        pgo_chol6(l, &bad);
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) y[i] = rhs[(size_t)c * 6 + i];
+#pragma unroll
+        for (int s = 0; s < 6; s++) {          // L y = rhs
+            double v = y[s];
+#pragma unroll
+            for (int k = 0; k < s; k++) v -= PGO_L(s, k) * y[k];
+            y[s] = v / PGO_L(s, s);
+        }
+        __syncthreads();                          // (every thread has read the column's diagonal block and rhs)
+        for (int t = tid; t < 6 * bc; t += PGO_CHOL_NT) {
+            double* row = col + (size_t)(1 + t / 6) * 36 + 6 * (t % 6);
+            double x[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) x[k] = row[k];
+            pgo_row_solve(l, x);
+#pragma unroll
+            for (int k = 0; k < 6; k++) row[k] = x[k];
+        }
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) col[6 * i + j] = j <= i ? PGO_L(i, j) : 0.0;
+                rhs[(size_t)c * 6 + i] = y[i];
+            }
+        }
+        __syncthreads();
+        // trailing update: H[c + d1][c + d2] -= L[c + d1][c] L[c + d2][c]^T for bc >= d1 >= d2 >= 1
+        const int nsq = bc * bc * 36;
+        for (int t = tid; t < nsq; t += PGO_CHOL_NT) {
+            const int e = t % 36, pr = t / 36;
+            const int d1 = 1 + pr / bc, d2 = 1 + pr % bc;
+            if (d1 < d2) continue;
+            const double* a = col + (size_t)d1 * 36 + 6 * (e / 6);
+            const double* bb = col + (size_t)d2 * 36 + 6 * (e % 6);
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) v += a[k] * bb[k];
+            band[(size_t)(c + d2) * cs + (size_t)(d1 - d2) * 36 + e] -= v;
+        }
+        for (int t = tid; t < 6 * bc; t += PGO_CHOL_NT) {
+            const double* a = col + (size_t)(1 + t / 6) * 36 + 6 * (t % 6);
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) v += a[k] * y[k];
+            rhs[(size_t)(c + 1 + t / 6) * 6 + t % 6] -= v;
+        }
+        __syncthreads();
+    }
+    // back substitution: delta_c = L_cc^-T (y_c - sum_d L[c + d][c]^T delta_{c + d}); the sum in PGO_BACK_PARTS interleaved parts,
+    // each in ascending d, added up in part order
+    for (int c = nf - 1; c >= 0; c--) {
+        const int bc = min(b, nf - 1 - c);
+        const double* col = band + (size_t)c * cs;
+        if (tid < 6 * PGO_BACK_PARTS) {
+            const int s = tid % 6, part = tid / 6;
+            double acc = 0.0;
+            for (int d = 1 + part; d <= bc; d += PGO_BACK_PARTS) {
+                const double* blk = col + (size_t)d * 36;
+                const double* dl = delta + (size_t)(c + d) * 6;
+                double v = 0.0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) v += blk[6 * k + s] * dl[k];
+                acc += v;
+            }
+            sPart[part][s] = acc;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double l[21], x[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = 0; j <= i; j++) PGO_L(i, j) = col[6 * i + j];
+#pragma unroll
+            for (int s = 0; s < 6; s++) {
+                double v = rhs[(size_t)c * 6 + s];
+#pragma unroll
+                for (int q = 0; q < PGO_BACK_PARTS; q++) v -= sPart[q][s];
+                x[s] = v;
+            }
+            pgo_back_solve(l, x);
+#pragma unroll
+            for (int s = 0; s < 6; s++) delta[(size_t)c * 6 + s] = x[s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *flag = bad;
+}
+
+// trial poses: T_k [Exp(a_k), b_k; 0, 1] for a free pose, the pose itself otherwise
+__global__ __launch_bounds__(256) void k_pgo_retract(int n, const int* __restrict__ pos, const double* __restrict__ poses,
+                                                      const double* __restrict__ delta, double* __restrict__ trial) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    double P[12];
+#pragma unroll
+    for (int q = 0; q < 12; q++) P[q] = poses[(size_t)k * 12 + q];
+    const int c = pos[k];
+    if (c >= 0) {
+        double d[6], Ex[9], R[9], t[3];
+#pragma unroll
+        for (int q = 0; q < 6; q++) d[q] = delta[(size_t)c * 6 + q];
+        so3_expmap(d, Ex);
+        mat3_mul(P, Ex, R);
+        mat3_vec(P, d + 3, t);
+#pragma unroll
+        for (int q = 0; q < 9; q++) P[q] = R[q];
+#pragma unroll
+        for (int q = 0; q < 3; q++) P[9 + q] += t[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 12; q++) trial[(size_t)k * 12 + q] = P[q];
+}
+
+// out[0] = sum of cost[0 .. m) (thread t adds entries t, t + 256, ... in order; then a fixed tree), out[1] = max |delta|
+__global__ __launch_bounds__(PGO_RED_NT) void k_pgo_reduce(int m, const double* __restrict__ cost, int nd, const double* __restrict__ delta,
+                                                           double* __restrict__ out) {
+    __shared__ double sS[PGO_RED_NT], sM[PGO_RED_NT];
+    const int tid = threadIdx.x;
+    double s = 0.0, mx = 0.0;
+    for (int k = tid; k < m; k += PGO_RED_NT) s += cost[k];
+    for (int k = tid; k < nd; k += PGO_RED_NT) { const double a = fabs(delta[k]); if (!(a <= mx)) mx = a; }     // (a NaN sticks)
+    sS[tid] = s; sM[tid] = mx;
+    __syncthreads();
+    for (int h = PGO_RED_NT / 2; h > 0; h >>= 1) {
+        if (tid < h) { sS[tid] += sS[tid + h]; if (!(sM[tid + h] <= sM[tid])) sM[tid] = sM[tid + h]; }
+        __syncthreads();
+    }
+    if (tid == 0) { out[0] = sS[0]; out[1] = sM[0]; }
+}
+
+__global__ __launch_bounds__(256) void k_pgo_move_points(int n, const double* __restrict__ pts, const int* __restrict__ ref,
+                                                          const double* __restrict__ Told, const double* __restrict__ Tnew,
+                                                          double* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const double x = pts[3 * (size_t)k], y = pts[3 * (size_t)k + 1], z = pts[3 * (size_t)k + 2];
+    const int r = ref[k];
+    if (r < 0) { out[3 * (size_t)k] = x; out[3 * (size_t)k + 1] = y; out[3 * (size_t)k + 2] = z; return; }
+    const double* A = Told + (size_t)r * 16;
+    const double* B = Tnew + (size_t)r * 16;
+    const double dx = x - A[3], dy = y - A[7], dz = z - A[11];
+    const double cx = A[0] * dx + A[4] * dy + A[8] * dz, cy = A[1] * dx + A[5] * dy + A[9] * dz, cz = A[2] * dx + A[6] * dy + A[10] * dz;
+    out[3 * (size_t)k] = B[0] * cx + B[1] * cy + B[2] * cz + B[3];
+    out[3 * (size_t)k + 1] = B[4] * cx + B[5] * cy + B[6] * cz + B[7];
+    out[3 * (size_t)k + 2] = B[8] * cx + B[9] * cy + B[10] * cz + B[11];
+}
+
+inline bool finite16(const double* p, int n) { for (int k = 0; k < n; k++) if (!std::isfinite(p[k])) return false; return true; }
+
+thread_local std::vector<std::pair<const char*, float>> g_pgoTimes;
+thread_local bool g_pgoTimingOn = false;
+
+}  // namespace
+
+// Reverse Cuthill-McKee over the free-free graph (adjacency lists sorted, duplicates removed).  Components are taken in ascending
+// order of their lowest pose; a component starts at its pose of smallest degree (the lowest index on a tie); a pose's unvisited
+// neighbours join the queue in ascending (degree, index); the whole sequence is reversed at the end.
+static void pgo_rcm(int nf, const std::vector<std::vector<int>>& adj, std::vector<int>& order) {
+    std::vector<uint8_t> seen(nf, 0);
+    std::vector<int> comp, nb;
+    order.clear();
+    for (int s0 = 0; s0 < nf; s0++) {
+        if (seen[s0]) continue;
+        comp.clear(); comp.push_back(s0); seen[s0] = 1;
+        for (size_t h = 0; h < comp.size(); h++) for (int v : adj[comp[h]]) if (!seen[v]) { seen[v] = 1; comp.push_back(v); }
+        int start = comp[0];
+        for (int v : comp) if (adj[v].size() < adj[start].size() || (adj[v].size() == adj[start].size() && v < start)) start = v;
+        for (int v : comp) seen[v] = 2;            // 2: in the component, not queued
+        const size_t base = order.size();
+        order.push_back(start); seen[start] = 1;
+        for (size_t h = base; h < order.size(); h++) {
+            nb.clear();
+            for (int v : adj[order[h]]) if (seen[v] == 2) { seen[v] = 1; nb.push_back(v); }
+            std::sort(nb.begin(), nb.end(), [&](int a, int b) { return adj[a].size() != adj[b].size() ? adj[a].size() < adj[b].size() : a < b; });
+            order.insert(order.end(), nb.begin(), nb.end());
+        }
+    }
+    std::reverse(order.begin(), order.end());
+}
+
+extern "C" vslam_status vslam_pose_graph_set_timing(int32_t on) {
+    g_pgoTimingOn = on != 0;
+    g_pgoTimes.clear();
+    return VSLAM_OK;
+}
+
+extern "C" vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out) {
+    if (!n_out || cap < 0 || (cap > 0 && (!names || !ms))) return VSLAM_ERR_INVALID;
+    int n = 0;
+    for (const auto& t : g_pgoTimes) { if (n >= cap) break; names[n] = t.first; ms[n] = t.second; n++; }
+    *n_out = n;
+    return VSLAM_OK;
+}
+
+extern "C" vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
+                                                  const vslam_pgo_params* params, int32_t device, double* T_wc_out, vslam_pgo_report* report) {
+    if (!T_wc || !fixed || !T_wc_out || !report || n < 1 || m < 0 || (m > 0 && !edges)) { set_error("vslam_pose_graph_optimize: invalid arguments"); return VSLAM_ERR_INVALID; }
+    if (n > PGO_MAX_POSES || m > PGO_MAX_EDGES) { set_error("vslam_pose_graph_optimize: %d poses / %d edges exceed the limits (%d / %d)", n, m, PGO_MAX_POSES, PGO_MAX_EDGES); return VSLAM_ERR_CAPACITY; }
+    int maxIt = params ? params->max_iterations : 0;
+    double lambda = params ? params->lambda0 : 0.0;
+    if (maxIt < 0 || !(lambda >= 0.0) || !std::isfinite(lambda)) { set_error("vslam_pose_graph_optimize: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
+    if (maxIt == 0) maxIt = 20;
+    if (lambda == 0.0) lambda = 1e-4;
+    if (!finite16(T_wc, 16 * n)) { set_error("vslam_pose_graph_optimize: non-finite pose"); return VSLAM_ERR_INVALID; }
+    std::vector<int> deg(n, 0);
+    for (int e = 0; e < m; e++) {
+        const vslam_pgo_edge& E = edges[e];
+        if (E.i < 0 || E.j < 0 || E.i >= n || E.j >= n || E.i == E.j) { set_error("vslam_pose_graph_optimize: edge %d joins poses %d and %d (n = %d)", e, E.i, E.j, n); return VSLAM_ERR_INVALID; }
+        if (!finite16(E.Z, 16) || !std::isfinite(E.w_rot) || !std::isfinite(E.w_trans)) { set_error("vslam_pose_graph_optimize: edge %d has a non-finite value", e); return VSLAM_ERR_INVALID; }
+        if (E.w_rot < 0 || E.w_trans < 0) { set_error("vslam_pose_graph_optimize: edge %d has a negative weight", e); return VSLAM_ERR_INVALID; }
+        deg[E.i]++; deg[E.j]++;
+    }
+    // free poses (not fixed, at least one edge), numbered in ascending pose index
+    std::vector<int> fidx(n, -1), fpose;
+    int nIso = 0;
+    for (int k = 0; k < n; k++) {
+        if (fixed[k]) continue;
+        if (!deg[k]) { nIso++; continue; }
+        fidx[k] = (int)fpose.size(); fpose.push_back(k);
+    }
+    const int nf = (int)fpose.size();
+    std::vector<std::vector<int>> adj(nf);
+    std::vector<uint8_t> anchored(nf, 0);
+    for (int e = 0; e < m; e++) {
+        const int a = fidx[edges[e].i], b2 = fidx[edges[e].j];
+        if (a >= 0 && b2 >= 0) { adj[a].push_back(b2); adj[b2].push_back(a); }
+        else if (a >= 0) anchored[a] = 1;
+        else if (b2 >= 0) anchored[b2] = 1;
+    }
+    for (auto& v : adj) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); }
+    {   // every component of free poses needs an edge to a fixed pose
+        std::vector<uint8_t> seen(nf, 0);
+        std::vector<int> comp;
+        for (int s0 = 0; s0 < nf; s0++) {
+            if (seen[s0]) continue;
+            comp.clear(); comp.push_back(s0); seen[s0] = 1;
+            bool anc = false;
+            for (size_t h = 0; h < comp.size(); h++) {
+                anc = anc || anchored[comp[h]];
+                for (int v : adj[comp[h]]) if (!seen[v]) { seen[v] = 1; comp.push_back(v); }
+            }
+            if (!anc) { set_error("vslam_pose_graph_optimize: the free poses connected to pose %d have no edge to a fixed pose (free gauge)", fpose[s0]); return VSLAM_ERR_INVALID; }
+        }
+    }
+    std::vector<int> order;
+    pgo_rcm(nf, adj, order);
+    std::vector<int> pos(n, -1), perm(std::max(nf, 1), 0);
+    for (int c = 0; c < nf; c++) { perm[c] = fpose[order[c]]; pos[perm[c]] = c; }
+    int b = 0;
+    for (int e = 0; e < m; e++) { const int a = pos[edges[e].i], c = pos[edges[e].j]; if (a >= 0 && c >= 0) b = std::max(b, std::abs(a - c)); }
+    if ((long long)(b + 1) * nf > PGO_MAX_BLOCKS) { set_error("vslam_pose_graph_optimize: the band needs %lld blocks (limit %d)", (long long)(b + 1) * nf, PGO_MAX_BLOCKS); return VSLAM_ERR_CAPACITY; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    VS_HIP(hipSetDevice(device));
+    *report = vslam_pgo_report{};
+    report->n_free = nf; report->n_isolated = nIso; report->half_bandwidth = b; report->final_lambda = lambda;
+    // incidence lists by band position, ascending edge index
+    std::vector<int> rowStart(nf + 1, 0), inc;
+    for (int e = 0; e < m; e++) { if (pos[edges[e].i] >= 0) rowStart[pos[edges[e].i] + 1]++; if (pos[edges[e].j] >= 0) rowStart[pos[edges[e].j] + 1]++; }
+    for (int c = 0; c < nf; c++) rowStart[c + 1] += rowStart[c];
+    inc.assign(std::max(rowStart[nf], 1), 0);
+    {
+        std::vector<int> fill(rowStart.begin(), rowStart.end() - 1);
+        for (int e = 0; e < m; e++) {
+            if (pos[edges[e].i] >= 0) inc[fill[pos[edges[e].i]]++] = e << 1;
+            if (pos[edges[e].j] >= 0) inc[fill[pos[edges[e].j]]++] = e << 1 | 1;
+        }
+    }
+    std::vector<PgoEdge> he(std::max(m, 1));
+    for (int e = 0; e < m; e++) {
+        PgoEdge& o = he[e];
+        o.i = edges[e].i; o.j = edges[e].j; o.wr = edges[e].w_rot; o.wt = edges[e].w_trans;
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o.Rz[3 * r + c] = edges[e].Z[4 * r + c]; o.tz[r] = edges[e].Z[4 * r + 3]; }
+    }
+    std::vector<double> hp((size_t)n * 12);
+    for (int k = 0; k < n; k++)
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) hp[(size_t)k * 12 + 3 * r + c] = T_wc[(size_t)k * 16 + 4 * r + c]; hp[(size_t)k * 12 + 9 + r] = T_wc[(size_t)k * 16 + 4 * r + 3]; }
+
+    DevPool* pool = thread_pool(device);
+    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+    pool->pending.clear();
+    hipStream_t st = pool->stream;
+    const int mm = std::max(m, 1), nff = std::max(nf, 1);
+    PoolBuf<PgoEdge> dE(pool); PoolBuf<double> dP0(pool), dP1(pool), dRes(pool), dJi(pool), dJj(pool), dCost(pool), dBandH(pool), dBandL(pool),
+        dDiag(pool), dG(pool), dRhs(pool), dDelta(pool), dOut(pool);
+    PoolBuf<int> dPos(pool), dRow(pool), dInc(pool), dFlag(pool);
+    const size_t bandN = (size_t)(b + 1) * nff * 36;
+    VS_HIP(dE.up(he.data(), mm)); VS_HIP(dP0.up(hp.data(), (size_t)n * 12)); VS_HIP(dP1.alloc((size_t)n * 12));
+    VS_HIP(dRes.alloc((size_t)mm * 6)); VS_HIP(dJi.alloc((size_t)mm * 36)); VS_HIP(dJj.alloc((size_t)mm * 36)); VS_HIP(dCost.alloc(mm));
+    VS_HIP(dBandH.alloc(bandN)); VS_HIP(dBandL.alloc(bandN)); VS_HIP(dDiag.alloc((size_t)nff * 6)); VS_HIP(dG.alloc((size_t)nff * 6));
+    VS_HIP(dRhs.alloc((size_t)nff * 6)); VS_HIP(dDelta.alloc((size_t)nff * 6)); VS_HIP(dOut.alloc(4));
+    VS_HIP(dPos.up(pos.data(), n)); VS_HIP(dRow.up(rowStart.data(), nf + 1)); VS_HIP(dInc.up(inc.data(), inc.size()));
+    VS_HIP(dFlag.alloc(1));
+    struct TimerOwner { StageTimer t; ~TimerOwner() { t.destroy(); } } timerOwner;      // (the events go on every return path)
+    StageTimer& timer = timerOwner.t;
+    timer.stream = st; timer.multi = true; timer.enabled = g_pgoTimingOn;
+    double hOut[2] = {0, 0}; int hFlag = 0;
+    double* cur = dP0.p; double* trial = dP1.p;
+    auto fetch = [&](bool withFlag) -> vslam_status {
+        VS_HIP(hipGetLastError());
+        VS_HIP(pool->d2h(hOut, dOut.p, 2 * sizeof(double)));
+        if (withFlag) VS_HIP(pool->d2h(&hFlag, dFlag.p, sizeof(int)));
+        VS_HIP(pool->sync());
+        return VSLAM_OK;
+    };
+    auto finish_timing = [&]() {
+        if (!timer.enabled) return;
+        const char* names[8]; float ms[8];
+        const int k = timer.read(names, ms, 8);
+        g_pgoTimes.clear();
+        for (int q = 0; q < k; q++) g_pgoTimes.push_back({names[q], ms[q]});
+    };
+    int t = timer.begin("pgo_linearize");
+    if (m) hipLaunchKernelGGL(k_pgo_linearize, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, cur, dRes.p, dJi.p, dJj.p, dCost.p);
+    timer.end(t);
+    t = timer.begin("pgo_cost");
+    hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(PGO_RED_NT), 0, st, m, dCost.p, 0, dDelta.p, dOut.p);
+    timer.end(t);
+    VS_CHECK(fetch(false));
+    double cost = hOut[0];
+    report->initial_cost = report->final_cost = cost;
+    int acc = 0, rej = 0;
+    bool stop = !(cost > 1e-20) || nf == 0;
+    bool linearized = true;
+    while (!stop) {
+        if (!linearized) {
+            t = timer.begin("pgo_linearize");
+            hipLaunchKernelGGL(k_pgo_linearize, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, cur, dRes.p, dJi.p, dJj.p, dCost.p);
+            timer.end(t);
+        }
+        t = timer.begin("pgo_assemble");
+        hipLaunchKernelGGL(k_pgo_assemble, dim3(nf), dim3(64), 0, st, nf, b, dPos.p, dRow.p, dInc.p, dE.p, dRes.p, dJi.p, dJj.p,
+                           dBandH.p, dDiag.p, dG.p);
+        timer.end(t);
+        for (;;) {      // trials from this linearisation
+            t = timer.begin("pgo_band_chol");
+            VS_HIP(hipMemcpyAsync(dBandL.p, dBandH.p, bandN * sizeof(double), hipMemcpyDeviceToDevice, st));
+            VS_HIP(hipMemcpyAsync(dRhs.p, dG.p, (size_t)nf * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_pgo_band_chol, dim3(1), dim3(PGO_CHOL_NT), 0, st, nf, b, lambda, dBandL.p, dDiag.p, dRhs.p, dDelta.p, dFlag.p);
+            timer.end(t);
+            t = timer.begin("pgo_retract");
+            hipLaunchKernelGGL(k_pgo_retract, dim3((n + 255) / 256), dim3(256), 0, st, n, dPos.p, cur, dDelta.p, trial);
+            timer.end(t);
+            t = timer.begin("pgo_cost");
+            hipLaunchKernelGGL(k_pgo_cost, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, trial, dCost.p);
+            hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(PGO_RED_NT), 0, st, m, dCost.p, nf * 6, dDelta.p, dOut.p);
+            timer.end(t);
+            VS_CHECK(fetch(true));
+            const double cn = hOut[0], dmax = hOut[1];
+            const bool tiny = !hFlag && dmax < 1e-12;      // (a flagged factorisation's delta means nothing: the trial is only rejected)
+            if (!hFlag && std::isfinite(cn) && cn < cost) {
+                const double rel = (cost - cn) / cost;
+                std::swap(cur, trial);
+                cost = cn; acc++;
+                lambda = std::max(lambda / 3.0, 1e-12);
+                if (acc >= maxIt || rel < 1e-10 || tiny) stop = true;
+                linearized = false;
+                break;
+            }
+            rej++;
+            lambda *= 4.0;
+            if (lambda > 1e8 || tiny) { stop = true; break; }
+        }
+    }
+    report->accepted = acc; report->rejected = rej; report->iterations = acc + rej;
+    report->final_cost = cost; report->final_lambda = lambda;
+    VS_HIP(pool->d2h(hp.data(), cur, (size_t)n * 12 * sizeof(double)));
+    VS_HIP(pool->sync());
+    finish_timing();
+    for (int k = 0; k < n; k++) {
+        double* o = T_wc_out + (size_t)k * 16;
+        if (pos[k] < 0) { if (o != T_wc + (size_t)k * 16) memcpy(o, T_wc + (size_t)k * 16, 16 * sizeof(double)); continue; }
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o[4 * r + c] = hp[(size_t)k * 12 + 3 * r + c]; o[4 * r + 3] = hp[(size_t)k * 12 + 9 + r]; }
+        o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+    }
+    return VSLAM_OK;
+}
+
+extern "C" vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
+                                                     int32_t n_points, int32_t n_poses, int32_t device, double* points_out) {
+    if (n_points < 0 || n_poses < 0 || (n_points > 0 && (!points_xyz || !ref_index || !points_out)) || (n_poses > 0 && (!T_old || !T_new))) {
+        set_error("vslam_pose_graph_move_points: invalid arguments"); return VSLAM_ERR_INVALID;
+    }
+    for (int k = 0; k < n_points; k++) if (ref_index[k] >= n_poses) { set_error("vslam_pose_graph_move_points: point %d refers to pose %d of %d", k, ref_index[k], n_poses); return VSLAM_ERR_INVALID; }
+    if (n_points == 0) return VSLAM_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    VS_HIP(hipSetDevice(device));
+    DevPool* pool = thread_pool(device);
+    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+    pool->pending.clear();
+    PoolBuf<double> dX(pool), dA(pool), dB(pool), dO(pool); PoolBuf<int> dR(pool);
+    VS_HIP(dX.up(points_xyz, (size_t)n_points * 3)); VS_HIP(dR.up(ref_index, n_points));
+    VS_HIP(dA.up(T_old, (size_t)n_poses * 16)); VS_HIP(dB.up(T_new, (size_t)n_poses * 16)); VS_HIP(dO.alloc((size_t)n_points * 3));
+    hipLaunchKernelGGL(k_pgo_move_points, dim3((n_points + 255) / 256), dim3(256), 0, pool->stream, n_points, dX.p, dR.p, dA.p, dB.p, dO.p);
+    VS_HIP(hipGetLastError());
+    VS_HIP(pool->d2h(points_out, dO.p, (size_t)n_points * 3 * sizeof(double)));
+    VS_HIP(pool->sync());
+    return VSLAM_OK;
+}

@@ -284,6 +284,14 @@ struct vslam_system {
     vslam_status reloc_imu_check(const vslam_imu_bucket* imu, const char* fn, int lane) const;
     void reloc_imu_input(SysFrameCtx& c, const vslam_imu_bucket* imu);
     void reloc_imu_finish(const vslam_reloc_report& rep, vslam_reloc_imu_report& irep, const double* T_cw, const uint8_t* inF, double* T_wc_out);
+    // loop closing (loop.hip; no reference counterpart): detection over the map points the tracker has
+    // left behind, a pose graph over the keyframes, the commit
+    vslam_status loop_check(const char* fn) const;                 // the refusals of both calls
+    bool loop_busy() const { return cfg.local_mapping == 2 && (pass.stage != MapPass::IDLE || pass.collectDue); }
+    int loop_candidates(int minKfGap);                             // fills rlIds (then reloc_fill_upload serves them)
+    vslam_status loop_apply(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep);
+    vslam_status correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep);
+    vslam_status close_loop(const vslam_loop_params* prm, vslam_loop_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

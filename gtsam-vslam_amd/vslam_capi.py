@@ -326,6 +326,94 @@ def _reloc_debug(call):
     return dict(d=d3[:n], key_winner=kw[:nL], counts=hc[:H], flags=fl[:Cn])
 
 
+class PgoEdge(C.Structure):
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("Z", C.c_double * 16), ("w_rot", C.c_double), ("w_trans", C.c_double)]
+
+
+PGO_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("Z", "<f8", 16), ("w_rot", "<f8"), ("w_trans", "<f8")])
+assert PGO_EDGE_DTYPE.itemsize == C.sizeof(PgoEdge) == 152
+
+
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("lambda0", C.c_double)]
+
+
+class PgoReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("iterations", "accepted", "rejected", "n_free", "n_isolated", "half_bandwidth")] + \
+               [(n, C.c_double) for n in ("initial_cost", "final_cost", "final_lambda")]
+
+
+def _pgo_report_dict(rep):
+    return {f[0]: getattr(rep, f[0]) for f in PgoReport._fields_}
+
+
+def pgo_edges(edges):
+    """[(i, j, Z (4, 4), w_rot, w_trans), ...] -> the vslam_pgo_edge array"""
+    a = np.zeros(max(len(edges), 1), PGO_EDGE_DTYPE)
+    for k, (i, j, Z, wr, wt) in enumerate(edges):
+        a[k] = (i, j, np.asarray(Z, np.float64).reshape(16), wr, wt)
+    return a
+
+
+def pose_graph_optimize(poses, fixed, edges, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_pose_graph_optimize: poses (n, 4, 4) world <- camera, fixed (n), edges as pgo_edges takes them (or its array).
+    Returns (new poses, report dict)."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 4, 4)
+    fixed = np.ascontiguousarray(fixed, np.uint8)
+    assert len(fixed) == len(poses)
+    m = len(edges)
+    ea = edges if isinstance(edges, np.ndarray) else pgo_edges(edges)
+    prm = PgoParams(int(max_iterations), float(lambda0))
+    rep = PgoReport()
+    out = np.zeros_like(poses)
+    _chk(lib().vslam_pose_graph_optimize(_p(poses), _p(fixed), len(poses), _p(ea), m, C.byref(prm), int(device), _p(out), C.byref(rep)))
+    return out, _pgo_report_dict(rep)
+
+
+def pose_graph_move_points(points, ref_index, T_old, T_new, device=0):
+    """vslam_pose_graph_move_points: T_new[ref] * T_old[ref]^-1 * X per point (ref < 0: unchanged)"""
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref_index, np.int32)
+    A = np.ascontiguousarray(T_old, np.float64).reshape(-1, 4, 4)
+    B = np.ascontiguousarray(T_new, np.float64).reshape(-1, 4, 4)
+    assert len(ref) == len(points) and len(A) == len(B)
+    out = np.zeros((max(len(points), 1), 3))
+    _chk(lib().vslam_pose_graph_move_points(_p(points), _p(ref), _p(A), _p(B), len(points), len(A), int(device), _p(out)))
+    return out[:len(points)]
+
+
+def pose_graph_set_timing(on):
+    _chk(lib().vslam_pose_graph_set_timing(int(bool(on))))
+
+
+def pose_graph_timings():
+    """kernel group -> device ms of this thread's last pose_graph_optimize (after pose_graph_set_timing(True))"""
+    names = (C.c_char_p * 8)(); ms = (C.c_float * 8)(); n = C.c_int32()
+    _chk(lib().vslam_pose_graph_timings(names, ms, 8, C.byref(n)))
+    return {names[i].decode(): float(ms[i]) for i in range(n.value)}
+
+
+class LoopParams(C.Structure):
+    _fields_ = [("reloc", RelocParams), ("pgo", PgoParams), ("min_kf_gap", C.c_int32), ("covis_min", C.c_int32),
+                ("loop_weight", C.c_double), ("detect_only", C.c_int32)]
+
+
+class LoopReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("busy", "success", "corrected", "kf_loop", "n_candidates", "n_nodes", "n_sequential",
+                                         "n_covisibility", "n_edges", "points_moved", "n_active_after")] + \
+               [("drift_translation", C.c_double), ("drift_rotation", C.c_double), ("T_wc_corrected", C.c_double * 16),
+                ("T_wc", C.c_double * 16), ("reloc", RelocReport), ("pgo", PgoReport)]
+
+
+def _loop_report_dict(rep):
+    d = {f[0]: getattr(rep, f[0]) for f in LoopReport._fields_ if f[0] not in ("T_wc_corrected", "T_wc", "reloc", "pgo")}
+    d["T_wc_corrected"] = np.array(list(rep.T_wc_corrected)).reshape(4, 4)
+    d["T_wc"] = np.array(list(rep.T_wc)).reshape(4, 4)
+    d["reloc"] = _reloc_report_dict(rep.reloc)
+    d["pgo"] = _pgo_report_dict(rep.pgo)
+    return d
+
+
 def relocalize_batch(matchers, points, descs, T_out=None, **params):
     """vslam_relocalize_batch: matchers / points / descs per lane (a None matcher: the lane is idle).  Returns (T [lanes, 4, 4],
     reports, pairs): a lane's T row is written only on its success (T_out: the array to write into, e.g. pre-filled), its
@@ -1200,6 +1288,59 @@ class System:
         _chk(self.L.vslam_system_relocalize_imu(self.h_sys, lp, rp, int(st), int(on_device), int(frame_number),
                                                 C.byref(b) if b is not None else None, C.byref(prm), _p(T), C.byref(rep), C.byref(irep)))
         return T, _reloc_report_dict(rep), _reloc_imu_report_dict(irep)
+
+    @staticmethod
+    def _loop_params(params):
+        prm = LoopParams()
+        for k, v in params.items():
+            if k in ("max_iterations", "lambda0"):
+                setattr(prm.pgo, k, v)
+            elif k in ("min_kf_gap", "covis_min", "detect_only"):
+                setattr(prm, k, int(v))
+            elif k == "loop_weight":
+                prm.loop_weight = float(v)
+            else:
+                setattr(prm.reloc, k, int(v))       # the fields of RelocParams
+        return prm
+
+    def correct_loop(self, kf_loop, T_wc_corrected, **params):
+        """vslam_system_correct_loop: the current camera really is at T_wc_corrected, keyframe kf_loop anchors it.  params:
+        covis_min, loop_weight, max_iterations, lambda0.  Returns the report dict (busy: nothing was done)."""
+        T = np.ascontiguousarray(T_wc_corrected, np.float64).reshape(4, 4)
+        rep = LoopReport()
+        prm = self._loop_params(params)
+        _chk(self.L.vslam_system_correct_loop(self.h_sys, int(kf_loop), _p(T), C.byref(prm), C.byref(rep)))
+        return _loop_report_dict(rep)
+
+    def close_loop(self, **params):
+        """vslam_system_close_loop on the frame of the last track(): detection over the map points the tracker has left behind,
+        then (unless detect_only=1) the correction.  params: min_kf_gap, covis_min, loop_weight, detect_only, max_iterations,
+        lambda0 and the fields of RelocParams.  Returns the report dict."""
+        rep = LoopReport()
+        prm = self._loop_params(params)
+        _chk(self.L.vslam_system_close_loop(self.h_sys, C.byref(prm), C.byref(rep)))
+        return _loop_report_dict(rep)
+
+    def active_points(self):
+        """test tap: activeMapPoints as map-point indices"""
+        n = C.c_int32(); idx = np.zeros(max(self.counts()["active"], 1), np.int32)
+        _chk(self.L.vslam_system_active_points(self.h_sys, len(idx), C.byref(n), _p(idx)))
+        return idx[:n.value].copy()
+
+    def covisibility(self):
+        """test tap: every sortedKFWeights entry as rows (keyframe, other keyframe, weight)"""
+        n = C.c_int32()
+        self.L.vslam_system_covisibility(self.h_sys, 0, C.byref(n), None)
+        tr = np.zeros((max(n.value, 1), 3), np.int32)
+        _chk(self.L.vslam_system_covisibility(self.h_sys, len(tr), C.byref(n), _p(tr)))
+        return tr[:n.value].copy()
+
+    def map_point_keyframes(self):
+        """test tap: per map point (first observing keyframe or -1, creating keyframe)"""
+        n = C.c_int32(); cap = max(self.counts()["map_points"], 1)
+        fo = np.zeros(cap, np.int32); cr = np.zeros(cap, np.int32)
+        _chk(self.L.vslam_system_map_point_keyframes(self.h_sys, cap, C.byref(n), _p(fo), _p(cr)))
+        return fo[:n.value].copy(), cr[:n.value].copy()
 
     def imu_state(self):
         """test tap: dict(velocity, bias, bias_good, pending) of the session"""

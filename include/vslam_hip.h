@@ -416,6 +416,63 @@ vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lane
                                     double* T_cw_out, int32_t* const* pairs_out, vslam_reloc_report* reports);
 
 /* ---------------------------------------------------------------------------
+ * Pose-graph optimisation - NO reference counterpart (the reference closes no loops; DESIGN.md section 6 item 24 holds the
+ * exact rules, tests/pgo_ref.py restates them on the CPU with a dense solve).  n poses T_wc [n][16] (row-major, world <-
+ * camera, rigid), fixed[n], m edges {i, j, Z, w_rot, w_trans} where Z measures T_i^-1 * T_j:
+ *   residual    E = Z^-1 * T_i^-1 * T_j (rigid inverses), r = (Log_SO3(R_E), t_E);  cost = sum w_rot |r_w|^2 + w_trans |r_t|^2
+ *   retraction  T_k <- T_k * [Exp(a_k), b_k; 0, 1];  analytic Jacobians;  H = J^T W J, g = J^T W r
+ *   LM          (H + lambda diag(H)) delta = -g; a trial is accepted iff it lowers the cost: lambda <- max(lambda / 3, 1e-12),
+ *               else lambda <- 4 lambda and the trial is repeated from the same linearisation.  Stops after max_iterations
+ *               accepted trials, when an accepted trial lowers the cost by less than 1e-10 of it, when |delta|_inf < 1e-12, or
+ *               when lambda > 1e8.  An initial cost <= 1e-20 returns at once: zero iterations, poses unchanged.
+ *   solve       direct: the free poses reordered on the host by reverse Cuthill-McKee over the free-free edges, H as a
+ *               block-banded lower matrix of 6x6 fp64 blocks (half-bandwidth b blocks), factorised and solved on the device
+ *               by one workgroup walking the block columns (k_pgo_band_chol).  A pivot that is not positive makes the trial
+ *               a rejected one whatever its delta (it does not end the loop through the |delta|_inf rule).
+ *   kernels     k_pgo_linearize (one thread per edge), k_pgo_assemble (one wave per free pose gathers its incidence list in
+ *               ascending edge order: no atomics), k_pgo_band_chol, k_pgo_retract / k_pgo_cost / k_pgo_reduce (fixed-order
+ *               sum): two calls on the same input return the same bytes.  The accept / reject decision is taken on the
+ *               host: one wait per trial, none inside factor / solve; the calling thread's block cache serves every buffer,
+ *               so that a repeated call of unchanged size allocates and frees nothing.
+ * A free pose without any edge is treated as fixed (n_isolated); fixed and isolated poses come back bit for bit; an edge
+ * between two fixed poses only adds to the cost; duplicate edges add up.
+ * VSLAM_ERR_INVALID, nothing launched: i == j or an index out of range, a non-finite pose / measurement / weight / parameter,
+ * a negative weight or parameter, a connected component of free poses without an edge to a fixed pose (a free gauge).
+ * VSLAM_ERR_CAPACITY, nothing launched: n > 16384, m > 262144, (b + 1) * n_free > 262144 blocks.
+ * ------------------------------------------------------------------------- */
+typedef struct vslam_pgo_edge {
+    int32_t i, j;
+    double Z[16];             /* row-major measurement of T_i^-1 * T_j */
+    double w_rot, w_trans;    /* weights of the rotation / translation part (>= 0) */
+} vslam_pgo_edge;
+
+typedef struct vslam_pgo_params {     /* a zero field takes the default in brackets (NULL = all defaults) */
+    int32_t max_iterations;   /* [20]   accepted trials */
+    double lambda0;           /* [1e-4] */
+} vslam_pgo_params;
+
+typedef struct vslam_pgo_report {
+    int32_t iterations;       /* trials = accepted + rejected */
+    int32_t accepted, rejected;
+    int32_t n_free, n_isolated, half_bandwidth;
+    double initial_cost, final_cost, final_lambda;
+} vslam_pgo_report;
+
+vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
+                                       const vslam_pgo_params* params, int32_t device, double* T_wc_out /* [n][16]; may be T_wc */,
+                                       vslam_pgo_report* report);
+/* k_pgo_move_points: points_out[k] = T_new[r] * T_old[r]^-1 * points_xyz[k] with r = ref_index[k] (rigid inverse: R^T (X - t));
+ * r < 0 leaves the point as it is; r >= n_poses: VSLAM_ERR_INVALID, nothing launched.  points_out may be points_xyz. */
+vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
+                                          int32_t n_points, int32_t n_poses, int32_t device, double* points_out);
+/* measurement hook of tools/pgo_rate.py, not part of the supported surface: per-kernel-group device time of the calling
+ * thread's last vslam_pose_graph_optimize (HIP events; off by default; thread-local state).  Groups: pgo_linearize,
+ * pgo_assemble, pgo_band_chol (with the copies of band and right-hand side), pgo_retract, pgo_cost (k_pgo_cost and every
+ * k_pgo_reduce, the initial one included). */
+vslam_status vslam_pose_graph_set_timing(int32_t on);
+vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
+
+/* ---------------------------------------------------------------------------
  * Local bundle adjustment — replaces the numerical core of LocalMapper::localBA
  * (include/OptimizationBA.h:75, src/OptimizationBA.cpp:543-873): GenericProjectionFactor
  * (left, and right with the stereo extrinsics) per observation, BetweenFactor<Pose3>
@@ -906,6 +963,78 @@ vslam_status vslam_system_relocalize_imu(vslam_system* sys, const uint8_t* left,
                                          int32_t on_device, int32_t frame_number, const vslam_imu_bucket* imu,
                                          const vslam_reloc_params* params, double* T_wc_out, vslam_reloc_report* report,
                                          vslam_reloc_imu_report* imu_report);
+/* ---------------------------------------------------------------------------
+ * Loop closing of a stereo session (use_imu = 0) - NO reference counterpart.  Both calls are
+ * made BETWEEN tracked frames, e.g. after a frame whose report has keyframe_inserted.
+ *
+ * vslam_system_correct_loop: the caller states that the CURRENT camera really is at T_wc_corrected and that keyframe kf_loop
+ * anchors that knowledge (from vslam_system_close_loop's detection, a fiducial, an external detector).  With the drift
+ * D = T_wc_corrected * T_wc^-1 a pose graph over EVERY keyframe is solved by vslam_pose_graph_optimize (params->pgo):
+ *   fixed         keyframe 0 and kf_loop
+ *   sequential    (prevKF, kf) for every keyframe with a predecessor, in keyframe order; Z from the current poses, weights 1 / 1
+ *   covisibility  every sortedKFWeights entry (weight, other) of keyframe k with weight >= covis_min and other != k, keyframes
+ *                 in ascending order and entries in list order; an unordered pair enters once, as (min, max); Z from the
+ *                 current poses, weights 1 / 1.  (A pair that is also sequential is a duplicate edge: they add up.)
+ *   loop          (kf_loop, latestKF), Z = T_w,kfloop^-1 * D * T_w,latestKF, weights loop_weight / loop_weight
+ * with Z of a pair (a, b) = poseInv(a) * pose(b).  The commit, on the caller's (the tracker's) timeline under the map's mutex:
+ * every keyframe takes its new pose (setPose) and, with a predecessor, refPose = poseInv(prevKF) * pose; the camera pose,
+ * lastKFPoseInv and the predicted pose follow the latest keyframe as changePosesLCA derives them (camPose = pose(latestKF) *
+ * camRefPose, predNPose = camPose * predNPoseRef); plain frames of the trajectory follow through their keyframe.  Every map
+ * point with at least one observation moves with its first observing keyframe kFMatches[0] by vslam_pose_graph_move_points
+ * (outliers included).  activeMapPoints becomes, in creation order, every non-outlier map point (the most recent 65536) that
+ * vslam_world_to_frame places inside the left image under the new camera pose; MapPoint::inFrame follows; the last frame's
+ * match tables are cleared (the rule of vslam_system_relocalize's commit): the old copy of the place is handed back to the
+ * tracker.  No keyframe is inserted, no frame is recorded.  A local BA that has finished but whose changePosesLCA has not
+ * run yet (local_mapping = 1, right after a keyframe) is propagated first, as the next frame would.  Stored stereo depths of
+ * the keyframes are not refreshed (the next local BA over a keyframe does that).
+ * report->busy = 1, VSLAM_OK, nothing changed: a local-mapping pass is handed over and has not landed (local_mapping = 2,
+ * between hand-over and frame f + k); the call neither waits for it nor cancels it - call again after a later frame.
+ * VSLAM_ERR_INVALID, nothing changed: mono sessions, use_imu = 1 sessions (velocity and gravity frame would have to follow),
+ * no tracked frame yet, kf_loop out of range or equal to the latest keyframe, a non-finite T_wc_corrected, negative
+ * parameters.
+ *
+ * vslam_system_close_loop: detection on the frame the session's matcher still holds from the last
+ * vslam_system_track_stereo, then - unless detect_only - the correction above.  Candidates: map points that are not outliers,
+ * NOT in activeMapPoints, created by a keyframe (MapPoint::kdx) <= latestKF - min_kf_gap; in creation order, the most recent
+ * 65536.  Fewer than reloc.min_inliers candidates: success = 0.  Otherwise steps A-D of vslam_relocalize (params->reloc,
+ * either mode) over them.  On success kf_loop = the keyframe other than the latest that observes the most map points among the
+ * inliers of the winning hypothesis (the set step D refines; the lowest keyframe number on a tie; none: success = 0), and
+ * T_wc_corrected = the rigid inverse of the refined T_cw.  Step D's side effect on the matcher's stereo match does not reach
+ * the session: the four stereo arrays are saved before and restored after the stage.  A call that finds no loop, is busy or is
+ * detect_only leaves the session in a state from which the following frames track bit for bit as without the call.
+ * Refusals as above.
+ * ------------------------------------------------------------------------- */
+typedef struct vslam_loop_params {    /* a zero field takes the default in brackets (NULL = all defaults) */
+    vslam_reloc_params reloc;         /* detection (vslam_system_close_loop only) */
+    vslam_pgo_params pgo;
+    int32_t min_kf_gap;               /* [20]  a candidate's creating keyframe is at most latestKF - min_kf_gap */
+    int32_t covis_min;                /* [100] covisibility edges from this weight */
+    double loop_weight;               /* [10]  both parts of the loop edge */
+    int32_t detect_only;              /* 1: vslam_system_close_loop stops after detection */
+} vslam_loop_params;
+
+typedef struct vslam_loop_report {
+    int32_t busy;                     /* 1: a mapping pass is in flight, nothing was done */
+    int32_t success;                  /* detection found a loop (vslam_system_correct_loop: 1 unless busy) */
+    int32_t corrected;                /* the correction was committed */
+    int32_t kf_loop, n_candidates;
+    int32_t n_nodes, n_sequential, n_covisibility, n_edges;
+    int32_t points_moved, n_active_after;
+    double drift_translation, drift_rotation;     /* |t_D| in metres, rotation angle of D in radians */
+    double T_wc_corrected[16];
+    double T_wc[16];                  /* the camera pose after the call (the unchanged one when nothing was committed) */
+    vslam_reloc_report reloc;
+    vslam_pgo_report pgo;
+} vslam_loop_report;
+
+vslam_status vslam_system_correct_loop(vslam_system* sys, int32_t kf_loop, const double* T_wc_corrected,
+                                       const vslam_loop_params* params, vslam_loop_report* report);
+vslam_status vslam_system_close_loop(vslam_system* sys, const vslam_loop_params* params, vslam_loop_report* report);
+/* test taps: activeMapPoints (map-point indices, in order); every sortedKFWeights entry as (keyframe, other, weight) triples,
+ * keyframes ascending, entries in list order; per map point its first observing keyframe (-1: none) and creating keyframe */
+vslam_status vslam_system_active_points(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* index);
+vslam_status vslam_system_covisibility(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* triples);
+vslam_status vslam_system_map_point_keyframes(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* first_observer, int32_t* creator);
 /* test tap: the IMU state of a session; any pointer may be NULL */
 vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
 /* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with
