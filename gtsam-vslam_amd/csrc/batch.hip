@@ -189,6 +189,9 @@ struct vslam_batch {
     vslam_status relocalize(const uint8_t* const* L, const uint8_t* const* R, int stride, bool onDevice, const int* frames, const uint8_t* mask,
                             const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps, bool imuCall = false,
                             const vslam_imu_bucket* imu = nullptr, vslam_reloc_imu_report* ireps = nullptr);
+    // correct: vslam_batch_correct_loop (kfLoop [B], T_wc_corrected [B][16]); else vslam_batch_close_loop (both null)
+    vslam_status loop(bool correct, const uint8_t* mask, const int32_t* kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm,
+                      vslam_loop_report* reps);
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
     vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
@@ -963,6 +966,150 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
     return VSLAM_OK;
 }
 
+// Loop closing of the masked lanes, between two steps: per lane what vslam_system::close_loop / correct_loop does to a session, with the
+// detection through the batched relocalisation stage (one launch per stage for all lanes that have candidates), ONE batched pose-graph
+// solve and ONE move-points launch for all lanes that reach the solve.  A lane's outcome does not depend on the other lanes: a busy lane
+// reports busy, a lane that finds nothing reports success = 0, both untouched.  Refusals come first and change nothing in any lane.
+vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t* kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm,
+                               vslam_loop_report* reps) {
+    const char* const fn = correct ? "vslam_batch_correct_loop" : "vslam_batch_close_loop";
+    if (!mask || !reps || (correct && (!kfLoop || !T_wc_corrected))) { set_error("%s: invalid arguments", fn); return VSLAM_ERR_INVALID; }
+    if (useImu) { set_error("%s: an IMU batch cannot close loops yet (its velocity and gravity frame would have to follow)", fn); return VSLAM_ERR_INVALID; }
+    vslam_loop_params P;
+    vslam_reloc_params RP{};
+    if (!resolve_loop_params(prm, P)) { set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID; }
+    if (!correct) VS_CHECK(reloc_resolve_params(&P.reloc, RP));
+    char who[96];
+    int nOn = 0;
+    for (int b = 0; b < B; b++) {
+        if (!mask[b]) continue;
+        nOn++;
+        snprintf(who, sizeof who, "%s: lane %d", fn, b);
+        VS_CHECK(sys[b]->loop_check(who));
+        if (correct) VS_CHECK(sys[b]->loop_check_correct(who, kfLoop[b], T_wc_corrected + 16 * (size_t)b));
+        else VS_CHECK(sys[b]->loop_check_close(who));
+    }
+    if (!correct && nOn && !prefetched.empty()) {
+        set_error("%s: a prefetched extraction is in flight: the matchers no longer hold the tracked frames", fn);
+        return VSLAM_ERR_INVALID;
+    }
+    if (!nOn) return VSLAM_OK;
+    VS_HIP(hipSetDevice(device));
+    struct Solve { int lane, kf; M4 T_corr; };
+    std::vector<Solve> solve;
+    std::vector<int> detect;
+    std::vector<RelocBatchLane> rl((size_t)B);
+    for (int b = 0; b < B; b++) {
+        if (!mask[b]) continue;
+        vslam_loop_report& r = reps[b];
+        r = vslam_loop_report{};
+        r.kf_loop = correct ? kfLoop[b] : -1;
+        if (sys[b]->loop_busy()) { r.busy = 1; continue; }
+        if (correct) {
+            r.success = 1;
+            const M4 T_corr = m4_from(T_wc_corrected + 16 * (size_t)b);
+            loop_drift(T_corr, sys[b]->camPoseInv, &r);
+            solve.push_back({b, kfLoop[b], T_corr});
+            continue;
+        }
+        const int n = sys[b]->loop_candidates(P.min_kf_gap);
+        r.n_candidates = n;
+        r.reloc.n_points = n;
+        if (n < RP.min_inliers) continue;
+        rl[b].m = sys[b]->fm; rl[b].n = n; rl[b].wantInFrame = true;      // (the in-frame bytes are not used: the upload carries maxScaleDist anyway)
+        detect.push_back(b);
+    }
+    // ---- detection: the batched relocalisation stage over the candidates; nothing of it reaches the sessions ------------------------
+    if (!detect.empty()) {
+        RelocBatchPlan plan;
+        reloc_batch_plan(rl.data(), B, plan);
+        VS_CHECK(ensure_up(plan.upBytes));
+        VS_CHECK(ensure_dn(plan.dnBytes));
+        for (int b : detect) sys[b]->reloc_fill_upload((double*)(h_up + rl[b].oXyz), h_up + rl[b].oDesc, (float*)(h_up + rl[b].oMsd));
+        VS_CHECK(reloc_batch_check(rl.data(), B, device));
+        std::vector<double> Tcw((size_t)B * 16, 0.0);
+        std::vector<vslam_reloc_report> rr((size_t)B);
+        {
+            // step D may clear stereo matches of the frames the matchers hold: each lane's four stereo arrays are saved here and restored
+            // below, as close_loop does for one session
+            DevPool* tp = thread_pool(device);
+            if (!tp) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+            std::vector<size_t> off(detect.size() + 1, 0);
+            for (size_t i = 0; i < detect.size(); i++) off[i + 1] = off[i] + up256((size_t)sys[detect[i]]->fm->cap * 16);
+            PoolBuf<uint8_t> save(tp);
+            VS_HIP(save.alloc(off.back()));
+            for (size_t i = 0; i < detect.size(); i++) {
+                vslam_matcher* m = sys[detect[i]]->fm;
+                const size_t c = (size_t)m->cap;
+                uint8_t* s = save.p + off[i];
+                VS_HIP(hipMemcpyAsync(s, m->d_rightIdxs, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(s + c * 4, m->d_leftIdxs, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(s + c * 8, m->d_depth, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(s + c * 12, m->d_close, c, hipMemcpyDeviceToDevice, stream));
+            }
+            const RelocBlocks blk{h_up, d_up, h_dn, d_dn};
+            const vslam_status st = reloc_batch_run(rl.data(), B, plan, blk, stream, RP, (double)(float)std::log((double)shared.fe.scale), &timer,
+                                                    Tcw.data(), rr.data());
+            for (size_t i = 0; i < detect.size(); i++) {
+                vslam_matcher* m = sys[detect[i]]->fm;
+                const size_t c = (size_t)m->cap;
+                const uint8_t* s = save.p + off[i];
+                VS_HIP(hipMemcpyAsync(m->d_rightIdxs, s, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(m->d_leftIdxs, s + c * 4, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(m->d_depth, s + c * 8, c * 4, hipMemcpyDeviceToDevice, stream));
+                VS_HIP(hipMemcpyAsync(m->d_close, s + c * 12, c, hipMemcpyDeviceToDevice, stream));
+            }
+            VS_HIP(hipStreamSynchronize(stream));
+            VS_CHECK(st);
+        }
+        for (int b : detect) {
+            vslam_loop_report& r = reps[b];
+            r.reloc = rr[b];
+            if (!r.reloc.success) continue;
+            vslam_matcher* m = sys[b]->fm;
+            const int C = m->rlLast[3];
+            std::vector<uint8_t> flags(std::max(C, 1), 0);
+            VS_CHECK(m->relocalize_debug(nullptr, 0, nullptr, 0, nullptr, 0, flags.data(), C, nullptr));
+            snprintf(who, sizeof who, "%s: lane %d", fn, b);
+            int best = -1;
+            VS_CHECK(sys[b]->loop_vote((const int*)(h_dn + rl[b].oPairs), (size_t)rl[b].n, flags.data(), C, who, &best));
+            if (best < 0) continue;
+            r.kf_loop = best;
+            r.success = 1;
+            const M4 T_corr = m4_rigid_inv(m4_from(Tcw.data() + 16 * (size_t)b));
+            loop_drift(T_corr, sys[b]->camPoseInv, &r);
+            if (!P.detect_only) solve.push_back({b, best, T_corr});
+        }
+    }
+    // ---- correction: every lane's graph, one solve, one move-points launch, the commits ---------------------------------------------
+    if (!solve.empty()) {
+        const int ns = (int)solve.size();
+        std::vector<vslam_system::LoopGraph> G((size_t)ns);
+        std::vector<vslam_pgo_graph> graphs((size_t)ns);
+        std::vector<vslam_pgo_report> pr((size_t)ns);
+        std::vector<PgoMoveGraph> mv((size_t)ns);
+        {
+            std::vector<std::unique_lock<std::mutex>> locks;       // every lane's map stays as its graph saw it until its commit
+            for (int i = 0; i < ns; i++) {
+                vslam_system* s = sys[solve[i].lane];
+                locks.emplace_back(s->mapMutex);
+                VS_CHECK(s->loop_build(solve[i].kf, solve[i].T_corr, P, &reps[solve[i].lane], G[i]));
+                graphs[i] = vslam_pgo_graph{G[i].poses.data(), G[i].fixed.data(), G[i].K, G[i].edges.data(), (int32_t)G[i].edges.size(), G[i].fresh.data()};
+                mv[i] = PgoMoveGraph{G[i].xyz.data(), G[i].ref.data(), G[i].nMp, G[i].poses.data(), G[i].fresh.data(), G[i].K, G[i].moved.data()};
+            }
+            VS_CHECK(vslam_pose_graph_optimize_batch(graphs.data(), ns, &P.pgo, device, pr.data()));
+            VS_CHECK(pgo_move_points_batch(mv.data(), ns, device));
+            for (int i = 0; i < ns; i++) {
+                reps[solve[i].lane].pgo = pr[i];
+                sys[solve[i].lane]->loop_commit(G[i], &reps[solve[i].lane]);
+            }
+        }
+        for (int i = 0; i < ns; i++) VS_CHECK(sys[solve[i].lane]->loop_activate(&reps[solve[i].lane]));
+    }
+    for (int b = 0; b < B; b++) if (mask[b]) memcpy(reps[b].T_wc, sys[b]->camPose.data(), 16 * sizeof(double));
+    return VSLAM_OK;
+}
+
 // Ends a lane's session and starts a new one in its place, between two steps, on the thread that drives the group.  Nothing on the
 // device is allocated or freed (a device free waits for every group's kernels, and a service whose lanes restart for ever is the steady
 // state): the new session takes over the old one's matcher - same extractor images, stream and result-block slices; its rig and
@@ -1024,6 +1171,18 @@ vslam_status vslam_batch_relocalize(vslam_batch* b, const uint8_t* const* left, 
                                     vslam_reloc_report* reports) {
     if (!b) return VSLAM_ERR_INVALID;
     return b->relocalize(left, right, stride, on_device != 0, frame_numbers, lane_mask, params, T_wc_out, reports);
+}
+
+vslam_status vslam_batch_correct_loop(vslam_batch* b, const uint8_t* lane_mask, const int32_t* kf_loop, const double* T_wc_corrected,
+                                      const vslam_loop_params* params, vslam_loop_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    if (!kf_loop || !T_wc_corrected) { set_error("vslam_batch_correct_loop: invalid arguments"); return VSLAM_ERR_INVALID; }
+    return b->loop(true, lane_mask, kf_loop, T_wc_corrected, params, reports);
+}
+
+vslam_status vslam_batch_close_loop(vslam_batch* b, const uint8_t* lane_mask, const vslam_loop_params* params, vslam_loop_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->loop(false, lane_mask, nullptr, nullptr, params, reports);
 }
 
 vslam_status vslam_batch_relocalize_imu(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride, int32_t on_device,

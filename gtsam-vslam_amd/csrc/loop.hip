@@ -7,8 +7,7 @@
 using namespace vslam;
 using namespace vslam_sys;
 
-namespace {
-bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P) {
+bool vslam_sys::resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P) {
     P = prm ? *prm : vslam_loop_params{};
     if (P.min_kf_gap < 0 || P.covis_min < 0 || !(P.loop_weight >= 0.0) || !std::isfinite(P.loop_weight)) return false;
     if (P.min_kf_gap == 0) P.min_kf_gap = 20;
@@ -16,7 +15,6 @@ bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P) {
     if (P.loop_weight == 0.0) P.loop_weight = 10.0;
     return true;
 }
-}  // namespace
 
 vslam_status vslam_system::loop_check(const char* fn) const {
     if (monoMode) { set_error("%s: a mono session cannot close loops (stereo fixes the scale of the correction)", fn); return VSLAM_ERR_INVALID; }
@@ -38,65 +36,70 @@ int vslam_system::loop_candidates(int minKfGap) {
     return (int)rlIds.size();
 }
 
-vslam_status vslam_system::loop_apply(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep) {
-    VS_HIP(hipSetDevice(cfg.device));
-    {
-        std::lock_guard<std::mutex> lk(mapMutex);
-        if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
-            VS_CHECK(change_poses_lca(endLBAIdx));
-            LBADone = false;
-        }
-        const int K = (int)keyFrames.size();
-        std::vector<double> poses((size_t)K * 16), fresh((size_t)K * 16);
-        std::vector<uint8_t> fixed(K, 0);
-        fixed[0] = fixed[kfLoop] = 1;
-        for (int k = 0; k < K; k++) memcpy(&poses[16 * (size_t)k], keyFrames[k].pose.data(), 16 * sizeof(double));
-        std::vector<vslam_pgo_edge> edges;
-        auto add = [&](int a, int b, const M4& Z, double w) {
-            vslam_pgo_edge e{};
-            e.i = a; e.j = b; e.w_rot = e.w_trans = w;
-            memcpy(e.Z, Z.data(), 16 * sizeof(double));
-            edges.push_back(e);
-        };
-        for (int k = 0; k < K; k++) {
-            const int p = keyFrames[k].prevKF;
-            if (p >= 0) add(p, k, m4_mul(keyFrames[p].poseInv, keyFrames[k].pose), 1.0);
-        }
-        rep->n_sequential = (int)edges.size();
-        std::set<std::pair<int, int>> seen;
-        for (int k = 0; k < K; k++)
-            for (const auto& c : keyFrames[k].sortedKFWeights) {
-                if (c.first < P.covis_min || c.second == k || c.second < 0 || c.second >= K) continue;
-                const int a = std::min(k, c.second), b = std::max(k, c.second);
-                if (!seen.insert({a, b}).second) continue;
-                add(a, b, m4_mul(keyFrames[a].poseInv, keyFrames[b].pose), 1.0);
-            }
-        rep->n_covisibility = (int)edges.size() - rep->n_sequential;
-        const M4 D = m4_mul(T_corr, camPoseInv);
-        add(kfLoop, latestKF, m4_mul(keyFrames[kfLoop].poseInv, m4_mul(D, keyFrames[latestKF].pose)), P.loop_weight);
-        rep->n_nodes = K; rep->n_edges = (int)edges.size();
-        VS_CHECK(vslam_pose_graph_optimize(poses.data(), fixed.data(), K, edges.data(), (int)edges.size(), &P.pgo, cfg.device, fresh.data(), &rep->pgo));
-        // ---- the commit ---------------------------------------------------------------------------------------------------------
-        const int nMp = (int)mapPoints.size();
-        std::vector<double> xyz((size_t)std::max(nMp, 1) * 3), moved((size_t)std::max(nMp, 1) * 3);
-        std::vector<int> ref(std::max(nMp, 1), -1);
-        int nMoved = 0;
-        for (int m = 0; m < nMp; m++) {
-            const SysMP& mp = mapPoints[m];
-            for (int c = 0; c < 3; c++) xyz[3 * (size_t)m + c] = mp.wp[c];
-            if (!mp.kfm.empty()) { ref[m] = mp.kfm[0].kf; nMoved++; }
-        }
-        VS_CHECK(vslam_pose_graph_move_points(xyz.data(), ref.data(), poses.data(), fresh.data(), nMp, K, cfg.device, moved.data()));
-        for (int m = 0; m < nMp; m++) for (int c = 0; c < 3; c++) mapPoints[m].wp[c] = moved[3 * (size_t)m + c];
-        for (int k = 0; k < K; k++) keyFrames[k].setPose(m4_from(&fresh[16 * (size_t)k]));
-        for (int k = 0; k < K; k++) {
-            const int p = keyFrames[k].prevKF;
-            if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
-        }
-        lca_finish(latestKF);
-        rep->points_moved = nMoved;
+// stage 1 (mapMutex held): a finished local BA is propagated, then the graph over every keyframe and the map points' references
+vslam_status vslam_system::loop_build(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, LoopGraph& G) {
+    if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
+        VS_CHECK(change_poses_lca(endLBAIdx));
+        LBADone = false;
     }
-    // the active set: reloc_commit's rule under the new camera pose
+    const int K = (int)keyFrames.size();
+    G.K = K;
+    G.poses.assign((size_t)K * 16, 0.0); G.fresh.assign((size_t)K * 16, 0.0);
+    G.fixed.assign(K, 0);
+    G.fixed[0] = G.fixed[kfLoop] = 1;
+    for (int k = 0; k < K; k++) memcpy(&G.poses[16 * (size_t)k], keyFrames[k].pose.data(), 16 * sizeof(double));
+    std::vector<vslam_pgo_edge>& edges = G.edges;
+    edges.clear();
+    auto add = [&](int a, int b, const M4& Z, double w) {
+        vslam_pgo_edge e{};
+        e.i = a; e.j = b; e.w_rot = e.w_trans = w;
+        memcpy(e.Z, Z.data(), 16 * sizeof(double));
+        edges.push_back(e);
+    };
+    for (int k = 0; k < K; k++) {
+        const int p = keyFrames[k].prevKF;
+        if (p >= 0) add(p, k, m4_mul(keyFrames[p].poseInv, keyFrames[k].pose), 1.0);
+    }
+    rep->n_sequential = (int)edges.size();
+    std::set<std::pair<int, int>> seen;
+    for (int k = 0; k < K; k++)
+        for (const auto& c : keyFrames[k].sortedKFWeights) {
+            if (c.first < P.covis_min || c.second == k || c.second < 0 || c.second >= K) continue;
+            const int a = std::min(k, c.second), b = std::max(k, c.second);
+            if (!seen.insert({a, b}).second) continue;
+            add(a, b, m4_mul(keyFrames[a].poseInv, keyFrames[b].pose), 1.0);
+        }
+    rep->n_covisibility = (int)edges.size() - rep->n_sequential;
+    const M4 D = m4_mul(T_corr, camPoseInv);
+    add(kfLoop, latestKF, m4_mul(keyFrames[kfLoop].poseInv, m4_mul(D, keyFrames[latestKF].pose)), P.loop_weight);
+    rep->n_nodes = K; rep->n_edges = (int)edges.size();
+    const int nMp = (int)mapPoints.size();
+    G.nMp = nMp; G.nMoved = 0;
+    G.xyz.assign((size_t)std::max(nMp, 1) * 3, 0.0); G.moved.assign((size_t)std::max(nMp, 1) * 3, 0.0);
+    G.ref.assign(std::max(nMp, 1), -1);
+    for (int m = 0; m < nMp; m++) {
+        const SysMP& mp = mapPoints[m];
+        for (int c = 0; c < 3; c++) G.xyz[3 * (size_t)m + c] = mp.wp[c];
+        if (!mp.kfm.empty()) { G.ref[m] = mp.kfm[0].kf; G.nMoved++; }
+    }
+    return VSLAM_OK;
+}
+
+// stage 3 (mapMutex held): G.fresh and G.moved into the map
+void vslam_system::loop_commit(const LoopGraph& G, vslam_loop_report* rep) {
+    const int K = G.K;
+    for (int m = 0; m < G.nMp; m++) for (int c = 0; c < 3; c++) mapPoints[m].wp[c] = G.moved[3 * (size_t)m + c];
+    for (int k = 0; k < K; k++) keyFrames[k].setPose(m4_from(&G.fresh[16 * (size_t)k]));
+    for (int k = 0; k < K; k++) {
+        const int p = keyFrames[k].prevKF;
+        if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
+    }
+    lca_finish(latestKF);
+    rep->points_moved = G.nMoved;
+}
+
+// the active set: reloc_commit's rule under the new camera pose
+vslam_status vslam_system::loop_activate(vslam_loop_report* rep) {
     const size_t n = (size_t)reloc_candidates();
     std::vector<double> xyz(3 * std::max<size_t>(n, 1)); std::vector<uint8_t> desc(32 * std::max<size_t>(n, 1)); std::vector<float> msd(std::max<size_t>(n, 1));
     reloc_fill_upload(xyz.data(), desc.data(), msd.data());
@@ -118,7 +121,20 @@ vslam_status vslam_system::loop_apply(int kfLoop, const M4& T_corr, const vslam_
     return VSLAM_OK;
 }
 
-static void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep) {
+vslam_status vslam_system::loop_apply(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep) {
+    VS_HIP(hipSetDevice(cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        LoopGraph G;
+        VS_CHECK(loop_build(kfLoop, T_corr, P, rep, G));
+        VS_CHECK(vslam_pose_graph_optimize(G.poses.data(), G.fixed.data(), G.K, G.edges.data(), (int)G.edges.size(), &P.pgo, cfg.device, G.fresh.data(), &rep->pgo));
+        VS_CHECK(vslam_pose_graph_move_points(G.xyz.data(), G.ref.data(), G.poses.data(), G.fresh.data(), G.nMp, G.K, cfg.device, G.moved.data()));
+        loop_commit(G, rep);
+    }
+    return loop_activate(rep);
+}
+
+void vslam_sys::loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep) {
     const M4 D = m4_mul(T_corr, camPoseInv);
     rep->drift_translation = std::sqrt(D[3] * D[3] + D[7] * D[7] + D[11] * D[11]);
     const double c = std::min(1.0, std::max(-1.0, (D[0] + D[5] + D[10] - 1.0) / 2.0));
@@ -126,16 +142,26 @@ static void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report
     memcpy(rep->T_wc_corrected, T_corr.data(), 16 * sizeof(double));
 }
 
+vslam_status vslam_system::loop_check_correct(const char* fn, int kfLoop, const double* T_wc_corrected) const {
+    if (kfLoop < 0 || kfLoop >= (int)keyFrames.size() || kfLoop == latestKF) {
+        set_error("%s: kf_loop %d (keyframes 0 .. %d, the latest excluded)", fn, kfLoop, (int)keyFrames.size() - 1);
+        return VSLAM_ERR_INVALID;
+    }
+    for (int k = 0; k < 16; k++) if (!std::isfinite(T_wc_corrected[k])) { set_error("%s: non-finite pose", fn); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system::loop_check_close(const char* fn) const {
+    if (!fm->stereoDone) { set_error("%s: the matcher holds no frame", fn); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
 vslam_status vslam_system::correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep) {
     if (!T_wc_corrected || !rep) return VSLAM_ERR_INVALID;
     VS_CHECK(loop_check("vslam_system_correct_loop"));
     vslam_loop_params P;
     if (!resolve_loop_params(prm, P)) { set_error("vslam_system_correct_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
-    if (kfLoop < 0 || kfLoop >= (int)keyFrames.size() || kfLoop == latestKF) {
-        set_error("vslam_system_correct_loop: kf_loop %d (keyframes 0 .. %d, the latest excluded)", kfLoop, (int)keyFrames.size() - 1);
-        return VSLAM_ERR_INVALID;
-    }
-    for (int k = 0; k < 16; k++) if (!std::isfinite(T_wc_corrected[k])) { set_error("vslam_system_correct_loop: non-finite pose"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(loop_check_correct("vslam_system_correct_loop", kfLoop, T_wc_corrected));
     *rep = vslam_loop_report{};
     rep->kf_loop = kfLoop;
     if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
@@ -145,6 +171,25 @@ vslam_status vslam_system::correct_loop(int kfLoop, const double* T_wc_corrected
     return loop_apply(kfLoop, T_corr, P, rep);
 }
 
+// kf_loop: the keyframe (not the latest) that observes the most inliers of the winning hypothesis
+vslam_status vslam_system::loop_vote(const int* pairs, size_t n, const uint8_t* flags, int C, const char* fn, int* kfLoop) {
+    *kfLoop = -1;
+    std::vector<std::pair<int, int>> byKey;                // (key, candidate): correspondences are in ascending key order
+    for (size_t p = 0; p < n; p++) if (pairs[p] >= 0) byKey.push_back({pairs[p], (int)p});
+    std::sort(byKey.begin(), byKey.end());
+    if ((int)byKey.size() != C) { set_error("%s: %d correspondences, %d pairs", fn, C, (int)byKey.size()); return VSLAM_ERR_HIP; }
+    std::lock_guard<std::mutex> lk(mapMutex);
+    std::vector<int> votes(keyFrames.size(), 0);
+    for (int c = 0; c < C; c++) {
+        if (!flags[c]) continue;
+        for (const KfMatch& o : mapPoints[rlIds[byKey[c].second]].kfm) if (o.kf != latestKF) votes[o.kf]++;
+    }
+    int best = -1;
+    for (int k = 0; k < (int)votes.size(); k++) if (votes[k] > 0 && (best < 0 || votes[k] > votes[best])) best = k;
+    *kfLoop = best;
+    return VSLAM_OK;
+}
+
 vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_report* rep) {
     if (!rep) return VSLAM_ERR_INVALID;
     VS_CHECK(loop_check("vslam_system_close_loop"));
@@ -152,7 +197,7 @@ vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_r
     vslam_reloc_params RP;
     if (!resolve_loop_params(prm, P)) { set_error("vslam_system_close_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
     VS_CHECK(reloc_resolve_params(&P.reloc, RP));
-    if (!fm->stereoDone) { set_error("vslam_system_close_loop: the matcher holds no frame"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(loop_check_close("vslam_system_close_loop"));
     *rep = vslam_loop_report{};
     rep->kf_loop = -1;
     if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
@@ -187,23 +232,12 @@ vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_r
         VS_CHECK(st);
     }
     if (!rep->reloc.success) return VSLAM_OK;
-    // kf_loop: the keyframe (not the latest) that observes the most inliers of the winning hypothesis
     {
         const int C = fm->rlLast[3];
         std::vector<uint8_t> flags(std::max(C, 1), 0);
         VS_CHECK(fm->relocalize_debug(nullptr, 0, nullptr, 0, nullptr, 0, flags.data(), C, nullptr));
-        std::vector<std::pair<int, int>> byKey;                // (key, candidate): correspondences are in ascending key order
-        for (size_t p = 0; p < n; p++) if (pairs[p] >= 0) byKey.push_back({pairs[p], (int)p});
-        std::sort(byKey.begin(), byKey.end());
-        if ((int)byKey.size() != C) { set_error("vslam_system_close_loop: %d correspondences, %d pairs", C, (int)byKey.size()); return VSLAM_ERR_HIP; }
-        std::lock_guard<std::mutex> lk(mapMutex);
-        std::vector<int> votes(keyFrames.size(), 0);
-        for (int c = 0; c < C; c++) {
-            if (!flags[c]) continue;
-            for (const KfMatch& o : mapPoints[rlIds[byKey[c].second]].kfm) if (o.kf != latestKF) votes[o.kf]++;
-        }
         int best = -1;
-        for (int k = 0; k < (int)votes.size(); k++) if (votes[k] > 0 && (best < 0 || votes[k] > votes[best])) best = k;
+        VS_CHECK(loop_vote(pairs.data(), n, flags.data(), C, "vslam_system_close_loop", &best));
         if (best < 0) return VSLAM_OK;
         rep->kf_loop = best;
     }

@@ -290,6 +290,27 @@ struct vslam_system {
     bool loop_busy() const { return cfg.local_mapping == 2 && (pass.stage != MapPass::IDLE || pass.collectDue); }
     int loop_candidates(int minKfGap);                             // fills rlIds (then reloc_fill_upload serves them)
     vslam_status loop_apply(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep);
+    // loop_apply's stages.  The single call runs them back to back; vslam_batch_close_loop / _correct_loop run loop_build for every
+    // lane, ONE batched solve and ONE move-points launch, then loop_commit and loop_activate per lane.  loop_build and loop_commit
+    // are called with mapMutex held (by one holder across both: nothing may touch the map between graph and commit).
+    struct LoopGraph {
+        int K = 0, nMp = 0, nMoved = 0;
+        std::vector<double> poses, fresh;          // [K][16] keyframe poses: the graph's input, the solve's output
+        std::vector<uint8_t> fixed;
+        std::vector<vslam_pgo_edge> edges;
+        std::vector<double> xyz, moved;            // [nMp][3] map points before / after
+        std::vector<int> ref;                      // [nMp] first observing keyframe or -1
+    };
+    vslam_status loop_build(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, LoopGraph& G);
+    void loop_commit(const LoopGraph& G, vslam_loop_report* rep);
+    vslam_status loop_activate(vslam_loop_report* rep);            // the active set under the new camera pose (takes mapMutex itself)
+    // close_loop's vote: the keyframe (not the latest) that observes the most inliers of the winning hypothesis, or -1.
+    // pairs [n]: key index or -1 per candidate of rlIds; flags [C]: inlier bytes in correspondence (ascending key) order
+    vslam_status loop_vote(const int* pairs, size_t n, const uint8_t* flags, int C, const char* fn, int* kfLoop);
+    // the refusals of a call (fn names it in the message) - both calls' loop_check, correct_loop's kf_loop / pose tests, close_loop's
+    // "the matcher holds no frame"
+    vslam_status loop_check_correct(const char* fn, int kfLoop, const double* T_wc_corrected) const;
+    vslam_status loop_check_close(const char* fn) const;
     vslam_status correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep);
     vslam_status close_loop(const vslam_loop_params* prm, vslam_loop_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
@@ -355,3 +376,10 @@ struct vslam_system {
     void worker_loop();
 };
 
+
+namespace vslam_sys {
+// loop.hip, shared with the batched calls of batch.hip: the defaults and ranges of vslam_loop_params (false: out of range); the
+// report's drift fields from the corrected pose
+bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P);
+void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep);
+}  // namespace vslam_sys

@@ -370,6 +370,33 @@ def pose_graph_optimize(poses, fixed, edges, max_iterations=0, lambda0=0.0, devi
     return out, _pgo_report_dict(rep)
 
 
+class PgoGraph(C.Structure):
+    _fields_ = [("T_wc", C.c_void_p), ("fixed", C.c_void_p), ("n", C.c_int32), ("edges", C.c_void_p), ("m", C.c_int32),
+                ("T_wc_out", C.c_void_p)]
+
+
+def pose_graph_optimize_batch(graphs, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_pose_graph_optimize_batch: graphs = [(poses, fixed, edges) or None (an idle lane), ...], one parameter set for all.
+    Returns [(new poses, report dict) or None, ...]."""
+    B = len(graphs)
+    tab = (PgoGraph * max(B, 1))()
+    reps = (PgoReport * max(B, 1))()
+    keep, outs = [], [None] * B
+    for g, gr in enumerate(graphs):
+        if gr is None:
+            continue
+        poses = np.ascontiguousarray(gr[0], np.float64).reshape(-1, 4, 4)
+        fixed = np.ascontiguousarray(gr[1], np.uint8)
+        assert len(fixed) == len(poses)
+        ea = gr[2] if isinstance(gr[2], np.ndarray) else pgo_edges(gr[2])
+        outs[g] = np.zeros_like(poses)
+        keep.append((poses, fixed, ea))
+        tab[g] = PgoGraph(poses.ctypes.data, fixed.ctypes.data, len(poses), ea.ctypes.data, len(gr[2]), outs[g].ctypes.data)
+    prm = PgoParams(int(max_iterations), float(lambda0))
+    _chk(lib().vslam_pose_graph_optimize_batch(tab, B, C.byref(prm), int(device), reps))
+    return [None if outs[g] is None else (outs[g], _pgo_report_dict(reps[g])) for g in range(B)]
+
+
 def pose_graph_move_points(points, ref_index, T_old, T_new, device=0):
     """vslam_pose_graph_move_points: T_new[ref] * T_old[ref]^-1 * X per point (ref < 0: unchanged)"""
     points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
@@ -1815,6 +1842,34 @@ class Batch:
         on = [mask is None or bool(mask[b]) for b in range(B)]
         return (T, [_reloc_report_dict(reps[b]) if on[b] else None for b in range(B)],
                 [_reloc_imu_report_dict(ireps[b]) if on[b] else None for b in range(B)])
+
+    def _loop_mask(self, mask):
+        mk = np.ones(self.lanes, np.uint8) if mask is None else np.ascontiguousarray(mask, np.uint8)
+        assert len(mk) == self.lanes
+        return mk
+
+    def close_loop(self, mask=None, **params):
+        """vslam_batch_close_loop on the frames of the last track(): per masked lane (None: all) what System.close_loop does, the
+        detection and the pose-graph solves batched.  Returns the per-lane report dicts (None for lanes outside the mask)."""
+        mk = self._loop_mask(mask)
+        reps = (LoopReport * self.lanes)()
+        prm = System._loop_params(params)
+        _chk(self.L.vslam_batch_close_loop(self.h_b, _p(mk), C.byref(prm), reps))
+        return [_loop_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
+
+    def correct_loop(self, kf_loops, poses, mask=None, **params):
+        """vslam_batch_correct_loop: kf_loops [lanes], poses [lanes, 4, 4] (read for the masked lanes; None entries allowed
+        elsewhere).  Returns the per-lane report dicts (None for lanes outside the mask)."""
+        mk = self._loop_mask(mask)
+        kf = np.array([int(k) if k is not None else 0 for k in kf_loops], np.int32)
+        T = np.zeros((self.lanes, 4, 4))
+        for b in range(self.lanes):
+            if poses[b] is not None:
+                T[b] = np.asarray(poses[b], np.float64).reshape(4, 4)
+        reps = (LoopReport * self.lanes)()
+        prm = System._loop_params(params)
+        _chk(self.L.vslam_batch_correct_loop(self.h_b, _p(mk), _p(kf), _p(T), C.byref(prm), reps))
+        return [_loop_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
 
     def relocalize_debug(self, lane):
         """Matcher.relocalize_debug of lane `lane`: its part of the last relocalize call (test tap)"""

@@ -461,6 +461,29 @@ typedef struct vslam_pgo_report {
 vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
                                        const vslam_pgo_params* params, int32_t device, double* T_wc_out /* [n][16]; may be T_wc */,
                                        vslam_pgo_report* report);
+/* The same for `lanes` independent graphs in one call, one launch per stage for all of them (the _b kernels of csrc/pgo.hip,
+ * blockIdx = lane; the 6x6 arithmetic is the single call's, shared as __device__ functions).  THE RULE: a lane's T_wc_out and
+ * report are, byte for byte, what vslam_pose_graph_optimize returns for that graph alone with the same params (one params set
+ * per call); order and company of the lanes do not matter.  A lane with n == 0 is idle: its output and report are not written.
+ *   host      per lane the single call's validation, numbering, gauge check, reordering and packing (one shared function)
+ *   device    the lanes' arrays concatenated in two blocks from the calling thread's cache (one upload); a lane table
+ *             {n, m, n_free, b, offsets}; a control block per lane {active, need_linearize, cur, lambda, cost, accepted,
+ *             rejected}.  One ROUND is one trial of every active lane: linearise (lanes whose last trial was accepted),
+ *             assemble, copy of the active lanes' bands and gradients (k_pgo_band_copy_b), factor + solve
+ *             (k_pgo_band_chol_b: one workgroup per lane), retract, cost, reduce, decide (k_pgo_decide_b: one thread per lane applies the accept / reject rule
+ *             above in fp64, the host's operations in the host's order).  A lane that has stopped costs its workgroups one
+ *             load.  The host waits once per round, for one int: the number of lanes still active.
+ * VSLAM_ERR_INVALID, nothing launched, no lane written: lanes < 1, NULL graphs / reports, a bad parameter, or any lane the
+ * single call would refuse as invalid (the error text names the lane).
+ * VSLAM_ERR_CAPACITY, likewise: a lane beyond the single call's limits; lanes > 1024; in all lanes together more than 262144
+ * poses, 1048576 edges or 1048576 band blocks (b + 1) * n_free. */
+typedef struct vslam_pgo_graph {     /* one lane; n == 0: idle lane (its report and output are not written) */
+    const double* T_wc; const uint8_t* fixed; int32_t n;
+    const vslam_pgo_edge* edges; int32_t m;
+    double* T_wc_out;                /* [n][16]; may be T_wc */
+} vslam_pgo_graph;
+vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
+                                             int32_t device, vslam_pgo_report* reports /* [lanes] */);
 /* k_pgo_move_points: points_out[k] = T_new[r] * T_old[r]^-1 * points_xyz[k] with r = ref_index[k] (rigid inverse: R^T (X - t));
  * r < 0 leaves the point as it is; r >= n_poses: VSLAM_ERR_INVALID, nothing launched.  points_out may be points_xyz. */
 vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
@@ -1219,6 +1242,28 @@ vslam_status vslam_batch_relocalize_imu(vslam_batch* batch, const uint8_t* const
 vslam_status vslam_batch_relocalize_debug(vslam_batch* batch, int32_t lane, int32_t* d1_i1_d2, int32_t cap_points, int32_t* key_winner,
                                           int32_t cap_keys, int32_t* hyp_counts, int32_t cap_hypotheses, uint8_t* inlier_flags,
                                           int32_t cap_pairs, int32_t* sizes4);
+/* Loop closing of the lanes in lane_mask, between two vslam_batch_track_stereo calls: a masked lane gets what
+ * vslam_system_close_loop / vslam_system_correct_loop does to a session - candidates, detection, kf_loop vote, graph, commit,
+ * active set, busy, detect_only and every report field by the same rules - in the batch's
+ * shape:
+ *   detection   the batched relocalisation stage (one launch per stage) over the masked lanes that are not busy and have at least
+ *               reloc.min_inliers candidates; each lane's four stereo arrays are saved before and restored after it
+ *   correction  every lane that reaches it builds its graph (a finished local BA is propagated first), then ONE
+ *               vslam_pose_graph_optimize_batch and ONE k_pgo_move_points_b launch for all of them, then the commit and the
+ *               active set per lane.  If no lane reaches the solve, nothing is launched for it.
+ * A lane's outcome does not depend on the other lanes: a busy lane reports busy = 1 and is untouched, a lane that finds nothing
+ * reports success = 0 and is untouched, while the others proceed.  Lanes outside the mask are not touched: session, matcher
+ * state, report entry.  reports [lanes]: written for the masked lanes.  vslam_batch_correct_loop reads kf_loop [lanes] and
+ * T_wc_corrected [lanes][16] for the masked lanes.
+ * VSLAM_ERR_INVALID with a message that names the lane, nothing changed in any lane: an IMU batch; a masked lane without a
+ * tracked frame (also a restarted lane) or, for vslam_batch_close_loop, whose matcher holds no frame (also: a prefetched
+ * extraction is in flight); for vslam_batch_correct_loop a masked lane's kf_loop out of range or the latest keyframe, or a
+ * non-finite pose; negative parameters; a NULL mask or reports. */
+vslam_status vslam_batch_correct_loop(vslam_batch* batch, const uint8_t* lane_mask, const int32_t* kf_loop /* [lanes] */,
+                                      const double* T_wc_corrected /* [lanes][16] */, const vslam_loop_params* params,
+                                      vslam_loop_report* reports /* [lanes] */);
+vslam_status vslam_batch_close_loop(vslam_batch* batch, const uint8_t* lane_mask, const vslam_loop_params* params,
+                                    vslam_loop_report* reports /* [lanes] */);
 /* key slabs the batch has allocated in total (bytes), and how many of them sessions hold / the free list holds; any
  * pointer may be NULL */
 vslam_status vslam_batch_memory(vslam_batch* batch, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free);

@@ -10,7 +10,14 @@ calls, then `reps` repetitions of `calls` calls, median and range over the repet
 the LM trials, the costs; then, from one more repetition with the library's HIP-event timing on, the device time per kernel
 group of a call.  Beside it, as context only, the time of the numpy restatement (tests/pgo_ref.py, dense solve) for the sizes a
 dense solve can hold (200 and 1 000 poses), with the thread count numpy ran with.
-usage: python tools/pgo_rate.py [out.json] [calls] [reps]"""
+usage: python tools/pgo_rate.py [out.json] [calls] [reps]
+
+python tools/pgo_rate.py --lanes G [out.json] [calls] [reps] times vslam_pose_graph_optimize_batch instead: per nominal size (200 and
+1 000 poses) G such chains of DIFFERENT lengths, spread evenly over 0.7 .. 1.3 of the nominal size, each with its own noise, so that
+the lanes stop in different rounds.  Same protocol; reported per nominal size: the batched call, the G single calls of the same
+graphs one after another, the single call on the nominal chain alone (the figure profiles/pgo_rate.json holds for the single call),
+the rounds of the batched call (its longest lane's trials) against every lane's trials, and whether every lane's poses equal its
+single call's bytes.  Default output: profiles/pgo_batch_rate.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("gtsam-vslam_amd", "tests"):
@@ -21,6 +28,7 @@ import vslam_capi as vc
 
 SIZES = (200, 1000, 4000)
 REF_SIZES = (200, 1000)
+BATCH_SIZES = (200, 1000)
 
 
 def out_and_back(n, seed=1):
@@ -42,7 +50,55 @@ def out_and_back(n, seed=1):
     return np.array(poses), fixed, edges
 
 
+def timed(fn, calls, reps):
+    for _ in range(2):
+        fn()
+    per = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        per.append((time.perf_counter() - t0) / calls * 1e3)
+    return dict(median=float(np.median(per)), min=float(min(per)), max=float(max(per)))
+
+
+def main_lanes(G, argv):
+    out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "pgo_batch_rate.json")
+    calls = int(argv[1]) if len(argv) > 1 else 3
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    res = dict(protocol="2 warm-up calls, %d repetitions of %d calls, host clock around calls that end in a device synchronise" % (reps, calls),
+               lanes=G, sizes={})
+    for nominal in BATCH_SIZES:
+        ns = [int(round(nominal * (0.7 + 0.6 * g / max(G - 1, 1)))) for g in range(G)]
+        graphs = []
+        for g, n in enumerate(ns):
+            poses, fixed, edges = out_and_back(n, seed=1 + g)
+            graphs.append((poses, fixed, vc.pgo_edges(edges)))
+        nom = out_and_back(nominal)
+        nom = (nom[0], nom[1], vc.pgo_edges(nom[2]))
+        batched = vc.pose_graph_optimize_batch(graphs)
+        singles = [vc.pose_graph_optimize(*g) for g in graphs]
+        same = all(b[0].tobytes() == s[0].tobytes() and b[1] == s[1] for b, s in zip(batched, singles))
+        t_batch = timed(lambda: vc.pose_graph_optimize_batch(graphs), calls, reps)
+        t_singles = timed(lambda: [vc.pose_graph_optimize(*g) for g in graphs], calls, reps)
+        t_longest = timed(lambda: vc.pose_graph_optimize(*graphs[-1]), calls, reps)
+        t_nominal = timed(lambda: vc.pose_graph_optimize(*nom), calls, reps)
+        trials = [r[1]["iterations"] for r in batched]
+        r = dict(nominal_poses=nominal, lane_poses=ns, lane_trials=trials, rounds=max(trials), sum_of_trials=sum(trials),
+                 half_bandwidth=[b[1]["half_bandwidth"] for b in batched], lanes_equal_single_calls_bitwise=bool(same),
+                 ms_batched_call=t_batch, ms_single_calls_in_sequence=t_singles, ms_single_call_longest_lane=t_longest,
+                 ms_single_call_nominal_chain=t_nominal)
+        res["sizes"][str(nominal)] = r
+        print(json.dumps(r), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main(argv):
+    if "--lanes" in argv:
+        k = argv.index("--lanes")
+        return main_lanes(int(argv[k + 1]), argv[:k] + argv[k + 2:])
     out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "pgo_rate.json")
     calls = int(argv[1]) if len(argv) > 1 else 3
     reps = int(argv[2]) if len(argv) > 2 else 3
