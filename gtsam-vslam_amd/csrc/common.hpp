@@ -263,8 +263,9 @@ struct PoolBuf {
     }
 };
 
-// pgo.hip: k_pgo_move_points_b, ONE launch for the map points of several graphs (what vslam_pose_graph_move_points does per graph:
-// a point's result is that call's by construction).  ref entries index the lane's own poses; ref >= n_poses: VSLAM_ERR_INVALID.
+// pgo.hip: k_pgo_move_points_b, ONE launch for the map points of several graphs (vslam_pose_graph_move_points is its own argument
+// checks and a one-lane call of this function: a point's result is that call's by construction).  ref entries index the lane's
+// own poses; ref >= n_poses: VSLAM_ERR_INVALID.
 struct PgoMoveGraph { const double* xyz; const int* ref; int n_points; const double* T_old; const double* T_new; int n_poses; double* out; };
 vslam_status pgo_move_points_batch(const PgoMoveGraph* graphs, int lanes, int device);
 

@@ -1,18 +1,20 @@
 // Pose-graph optimisation on the device (no reference counterpart; DESIGN.md section 6 item 24, restated by tests/pgo_ref.py):
 // Levenberg-Marquardt over SE(3) poses tied by relative-pose edges, the damped normal equations solved DIRECTLY by a
 // block-banded Cholesky of 6x6 fp64 blocks after a reverse Cuthill-McKee reordering of the free poses on the host.
-//   k_pgo_linearize   one thread per edge: residual, both 6x6 Jacobians, the edge's cost term
-//   k_pgo_assemble    one wave per free pose, one lane per block element: a gather over the pose's incidence list (CSR, built
-//                     once per call, ascending edge index) into the band's column and the gradient.  No atomics; every sum
-//                     runs in list order.
-//   k_pgo_band_chol   one workgroup walks the block columns: factor, forward substitution (carried as an extra row), back
-//                     substitution.  Nothing on the host waits inside it.
-//   k_pgo_retract / k_pgo_cost / k_pgo_reduce   the trial poses, their per-edge cost, the fixed-order sum and |delta|_inf
-//   k_pgo_move_points one thread per map point: X' = T_new[ref] * T_old[ref]^-1 * X
-// The accept / reject decision is the host's: one wait per trial.
-// vslam_pose_graph_optimize_batch solves several graphs (lanes) at once with the _b forms of these kernels, which call the same
-// __device__ bodies on a lane's part of concatenated arrays; there the decision is k_pgo_decide_b's, a thread per lane on a device
-// control block, and the host waits once per ROUND (one trial of every active lane).  A lane's bytes are the single call's.
+// There is ONE solve path (pgo_solve): several graphs (lanes) at once, one launch per stage for all of them, each kernel working on
+// a lane's part of concatenated arrays.  vslam_pose_graph_optimize is its one-lane case, so a lane's bytes are the single call's
+// by construction.
+//   k_pgo_linearize_b   one thread per edge: residual, both 6x6 Jacobians, the edge's cost term
+//   k_pgo_assemble_b    one wave per free pose, one lane per block element: a gather over the pose's incidence list (CSR, built
+//                       once per call, ascending edge index) into the band's column and the gradient.  No atomics; every sum
+//                       runs in list order.
+//   k_pgo_band_copy_b / k_pgo_band_chol_b   H and g into the factor's arrays; one workgroup per lane walks the block columns:
+//                       factor, forward substitution (carried as an extra row), back substitution.  Nothing on the host waits
+//                       inside it.
+//   k_pgo_retract_b / k_pgo_cost_b / k_pgo_reduce_b   the trial poses, their per-edge cost, the fixed-order sum and |delta|_inf
+//   k_pgo_decide_b      the accept / reject rule, a thread per lane on a device control block
+//   k_pgo_move_points_b one thread per map point: X' = T_new[ref] * T_old[ref]^-1 * X
+// The host waits once per ROUND (one trial of every active lane), for how many lanes are still active.
 #include "common.hpp"
 #include "dmath.hpp"
 #include <cmath>
@@ -64,7 +66,7 @@ __device__ __forceinline__ void pgo_error(const double* Pi, const double* Pj, co
 }
 
 // per edge: r [6], Ji [36], Jj [36] (row = residual component, column = parameter (a, b) of the pose), cost term
-// (the bodies below take one graph's arrays: the single-call kernels pass theirs, the _b kernels a lane's part of the pooled ones)
+// (the bodies below take one graph's arrays: the kernels pass a lane's part of the pooled ones)
 __device__ __forceinline__ void pgo_linearize_edge(int e, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
                                                    double* __restrict__ res, double* __restrict__ Ji, double* __restrict__ Jj,
                                                    double* __restrict__ cost) {
@@ -108,13 +110,6 @@ __device__ __forceinline__ void pgo_linearize_edge(int e, const PgoEdge* __restr
     r[0] = w[0]; r[1] = w[1]; r[2] = w[2]; r[3] = tE[0]; r[4] = tE[1]; r[5] = tE[2];
     cost[e] = E.wr * th2 + E.wt * (tE[0] * tE[0] + tE[1] * tE[1] + tE[2] * tE[2]);
 }
-__global__ __launch_bounds__(256) void k_pgo_linearize(int m, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
-                                                       double* __restrict__ res, double* __restrict__ Ji, double* __restrict__ Jj,
-                                                       double* __restrict__ cost) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m) return;
-    pgo_linearize_edge(e, edges, poses, res, Ji, Jj, cost);
-}
 
 // the cost term alone, for trial poses
 __device__ __forceinline__ void pgo_cost_edge(int e, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
@@ -127,12 +122,6 @@ __device__ __forceinline__ void pgo_cost_edge(int e, const PgoEdge* __restrict__
     pgo_error(Pi, Pj, E, RD, tD, RE, tE);
     pgo_log(RE, w);
     cost[e] = E.wr * (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) + E.wt * (tE[0] * tE[0] + tE[1] * tE[1] + tE[2] * tE[2]);
-}
-__global__ __launch_bounds__(256) void k_pgo_cost(int m, const PgoEdge* __restrict__ edges, const double* __restrict__ poses,
-                                                   double* __restrict__ cost) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m) return;
-    pgo_cost_edge(e, edges, poses, cost);
 }
 
 // Band storage: block (c, d), d = 0 .. b, is H[c + d][c] (lower), 36 doubles row-major, at ((c * (b + 1)) + d) * 36.
@@ -180,15 +169,6 @@ __device__ __forceinline__ void pgo_assemble_column(int c, int lane, int nf, int
     } else {
         rhs[(size_t)c * 6 + s] = -acc;
     }
-}
-__global__ __launch_bounds__(64) void k_pgo_assemble(int nf, int b, const int* __restrict__ pos,
-                                                     const int* __restrict__ rowStart, const int* __restrict__ inc,
-                                                     const PgoEdge* __restrict__ edges, const double* __restrict__ res,
-                                                     const double* __restrict__ Ji, const double* __restrict__ Jj,
-                                                     double* __restrict__ band, double* __restrict__ diagH, double* __restrict__ rhs) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    if (c >= nf || lane >= 42) return;
-    pgo_assemble_column(c, lane, nf, b, pos, rowStart, inc, edges, res, Ji, Jj, band, diagH, rhs);
 }
 
 // lower-triangular 6x6 in 21 named registers: L(i, j) = l[i (i + 1) / 2 + j]
@@ -349,11 +329,6 @@ __device__ __forceinline__ void pgo_band_chol_walk(int nf, int b, double lambda,
     }
     if (tid == 0) *flag = bad;
 }
-__global__ __launch_bounds__(PGO_CHOL_NT) void k_pgo_band_chol(int nf, int b, double lambda, double* __restrict__ band,
-                                                               const double* __restrict__ diagH, double* __restrict__ rhs,
-                                                               double* __restrict__ delta, int* __restrict__ flag) {
-    pgo_band_chol_walk(nf, b, lambda, band, diagH, rhs, delta, flag);
-}
 
 // trial poses: T_k [Exp(a_k), b_k; 0, 1] for a free pose, the pose itself otherwise
 __device__ __forceinline__ void pgo_retract_pose(int k, const int* __restrict__ pos, const double* __restrict__ poses,
@@ -377,12 +352,6 @@ __device__ __forceinline__ void pgo_retract_pose(int k, const int* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 12; q++) trial[(size_t)k * 12 + q] = P[q];
 }
-__global__ __launch_bounds__(256) void k_pgo_retract(int n, const int* __restrict__ pos, const double* __restrict__ poses,
-                                                      const double* __restrict__ delta, double* __restrict__ trial) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    pgo_retract_pose(k, pos, poses, delta, trial);
-}
 
 // out[0] = sum of cost[0 .. m) (thread t adds entries t, t + 256, ... in order; then a fixed tree), out[1] = max |delta|
 __device__ __forceinline__ void pgo_reduce_sum(int tid, int m, const double* __restrict__ cost, int nd, const double* __restrict__ delta,
@@ -397,11 +366,6 @@ __device__ __forceinline__ void pgo_reduce_sum(int tid, int m, const double* __r
         __syncthreads();
     }
     if (tid == 0) { out[0] = sS[0]; out[1] = sM[0]; }
-}
-__global__ __launch_bounds__(PGO_RED_NT) void k_pgo_reduce(int m, const double* __restrict__ cost, int nd, const double* __restrict__ delta,
-                                                           double* __restrict__ out) {
-    __shared__ double sS[PGO_RED_NT], sM[PGO_RED_NT];
-    pgo_reduce_sum(threadIdx.x, m, cost, nd, delta, out, sS, sM);
 }
 
 __device__ __forceinline__ void pgo_move_point(int k, const double* __restrict__ pts, const int* __restrict__ ref,
@@ -418,18 +382,11 @@ __device__ __forceinline__ void pgo_move_point(int k, const double* __restrict__
     out[3 * (size_t)k + 1] = B[4] * cx + B[5] * cy + B[6] * cz + B[7];
     out[3 * (size_t)k + 2] = B[8] * cx + B[9] * cy + B[10] * cz + B[11];
 }
-__global__ __launch_bounds__(256) void k_pgo_move_points(int n, const double* __restrict__ pts, const int* __restrict__ ref,
-                                                          const double* __restrict__ Told, const double* __restrict__ Tnew,
-                                                          double* __restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    pgo_move_point(k, pts, ref, Told, Tnew, out);
-}
 
-// ---- the batched call: G graphs (lanes) in one launch per stage, blockIdx.y (or .x of the one-workgroup-per-lane kernels) = lane.
+// ---- the kernels: G graphs (lanes) in one launch per stage, blockIdx.y (or .x of the one-workgroup-per-lane kernels) = lane.
 // The lanes' arrays are concatenated; a lane's entry of the table holds its sizes and where its parts begin.  Indices inside
-// a lane's arrays (edge ends, incidence entries, band positions) are lane-local, so every body above sees what the single
-// call would give it.  The control block is the loop state the single call keeps on the host.
+// a lane's arrays (edge ends, incidence entries, band positions) are lane-local, so every body above sees one graph's arrays
+// whatever the other lanes are.  The control block is a lane's Levenberg-Marquardt loop state.
 constexpr int PGO_MAX_LANES = 1024;                 // (k_pgo_decide_b is ONE workgroup with a thread per lane)
 constexpr int PGO_SUM_POSES = 262144, PGO_SUM_EDGES = 1048576, PGO_SUM_BLOCKS = 1048576;
 constexpr int PGO_NEED_H = 1, PGO_NEED_J = 2;       // need_linearize: assemble H and g (1), from a fresh linearisation (1 | 2)
@@ -488,9 +445,9 @@ __global__ __launch_bounds__(64) void k_pgo_assemble_b(const PgoLane* __restrict
                         Ji + e0 * 36, Jj + e0 * 36, band + (size_t)L->band0 * 36, diagH + f0, g + f0);
 }
 
-// every active lane's H band and gradient into the factor and the right-hand side, one element per thread (the single call's two
-// device-to-device copies, without the stopped lanes' parts; one workgroup copying its lane's band ahead of the walk was measured:
-// 0.3 ms per round at 1 300 poses, a chain of ~900 dependent load / store pairs per thread)
+// every active lane's H band and gradient into the factor and the right-hand side, one element per thread (H and g survive a
+// rejected trial; one workgroup copying its lane's band ahead of the walk was measured: 0.3 ms per round at 1 300 poses, a chain
+// of ~900 dependent load / store pairs per thread)
 __global__ __launch_bounds__(256) void k_pgo_band_copy_b(const PgoLane* __restrict__ tab, const PgoCtl* __restrict__ ctl,
                                                          const double* __restrict__ bandH, const double* __restrict__ g,
                                                          double* __restrict__ bandL, double* __restrict__ rhs) {
@@ -537,7 +494,7 @@ __global__ __launch_bounds__(PGO_RED_NT) void k_pgo_reduce_b(const PgoLane* __re
     pgo_reduce_sum(threadIdx.x, L->m, cost + L->edge0, init ? 0 : L->nf * 6, delta + (size_t)L->free0 * 6, out + 2 * (size_t)blockIdx.x, sS, sM);
 }
 
-// The accept / reject rule of vslam_pose_graph_optimize's loop, one thread per lane, the same fp64 operations in the same order.
+// THE accept / reject rule of the Levenberg-Marquardt loop (include/vslam_hip.h), one thread per lane, fp64.
 // init: the lanes' initial costs have been summed; a lane with a cost <= 1e-20 or no free pose never becomes active.
 // *nActive: what the host reads once per round.
 __global__ __launch_bounds__(PGO_MAX_LANES) void k_pgo_decide_b(int lanes, int init, int maxIt, const PgoLane* __restrict__ tab,
@@ -594,6 +551,25 @@ inline bool finite16(const double* p, int n) { for (int k = 0; k < n; k++) if (!
 thread_local std::vector<std::pair<const char*, float>> g_pgoTimes;
 thread_local bool g_pgoTimingOn = false;
 
+// what every entry point does before its first device call: `device` names a device, the calling thread's pool with nothing pending
+vslam_status pgo_device_pool(int device, DevPool** out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    VS_HIP(hipSetDevice(device));
+    DevPool* pool = thread_pool(device);
+    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+    pool->pending.clear();
+    *out = pool;
+    return VSLAM_OK;
+}
+
+// the sections of one device block, at 256-byte steps: section() returns where the next one begins
+struct PgoLayout {
+    size_t bytes = 0;
+    size_t section(size_t n) { const size_t at = bytes; bytes = align_up_sz(bytes + std::max<size_t>(n, 8), 256); return at; }
+};
+
 }  // namespace
 
 // Reverse Cuthill-McKee over the free-free graph (adjacency lists sorted, duplicates removed).  Components are taken in ascending
@@ -639,8 +615,8 @@ extern "C" vslam_status vslam_pose_graph_timings(const char** names, float* ms, 
 namespace {
 
 // What the host derives from one graph before anything is launched: the free poses' band positions, the band width, the incidence
-// lists and the device forms of edges and poses.  vslam_pose_graph_optimize and every lane of the batched call go through
-// pgo_check_sizes and pgo_prepare; `who` (the entry point, with the lane for a batched call) starts every error text.
+// lists and the device forms of edges and poses.  Every lane goes through pgo_check_sizes and pgo_prepare; `who` (the entry
+// point, with the lane for a batched call) starts every error text.
 struct PgoPrep {
     int n = 0, m = 0, nf = 0, nIso = 0, b = 0;
     std::vector<int> pos, rowStart, inc;      // pos [n]: band position or -1; rowStart [nf + 1]; inc: edge << 1 | side, ascending
@@ -752,145 +728,21 @@ void pgo_write_out(const PgoPrep& G, const double* hp, const double* T_wc, doubl
     }
 }
 
-}  // namespace
-
-extern "C" vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
-                                                  const vslam_pgo_params* params, int32_t device, double* T_wc_out, vslam_pgo_report* report) {
-    static const char* const who = "vslam_pose_graph_optimize";
-    if (!report) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
-    VS_CHECK(pgo_check_sizes(who, T_wc, fixed, n, edges, m, T_wc_out));
-    int maxIt = 0;
-    double lambda = 0.0;
-    VS_CHECK(pgo_check_params(who, params, &maxIt, &lambda));
-    PgoPrep G;
-    VS_CHECK(pgo_prepare(who, T_wc, fixed, n, edges, m, G));
-    const int nf = G.nf, b = G.b;
-    const std::vector<int>& pos = G.pos;
-    const std::vector<int>& rowStart = G.rowStart;
-    const std::vector<int>& inc = G.inc;
-    const std::vector<PgoEdge>& he = G.he;
-    std::vector<double>& hp = G.hp;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
-    *report = vslam_pgo_report{};
-    report->n_free = nf; report->n_isolated = G.nIso; report->half_bandwidth = b; report->final_lambda = lambda;
-
-    DevPool* pool = thread_pool(device);
-    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
-    pool->pending.clear();
-    hipStream_t st = pool->stream;
-    const int mm = std::max(m, 1), nff = std::max(nf, 1);
-    PoolBuf<PgoEdge> dE(pool); PoolBuf<double> dP0(pool), dP1(pool), dRes(pool), dJi(pool), dJj(pool), dCost(pool), dBandH(pool), dBandL(pool),
-        dDiag(pool), dG(pool), dRhs(pool), dDelta(pool), dOut(pool);
-    PoolBuf<int> dPos(pool), dRow(pool), dInc(pool), dFlag(pool);
-    const size_t bandN = (size_t)(b + 1) * nff * 36;
-    VS_HIP(dE.up(he.data(), mm)); VS_HIP(dP0.up(hp.data(), (size_t)n * 12)); VS_HIP(dP1.alloc((size_t)n * 12));
-    VS_HIP(dRes.alloc((size_t)mm * 6)); VS_HIP(dJi.alloc((size_t)mm * 36)); VS_HIP(dJj.alloc((size_t)mm * 36)); VS_HIP(dCost.alloc(mm));
-    VS_HIP(dBandH.alloc(bandN)); VS_HIP(dBandL.alloc(bandN)); VS_HIP(dDiag.alloc((size_t)nff * 6)); VS_HIP(dG.alloc((size_t)nff * 6));
-    VS_HIP(dRhs.alloc((size_t)nff * 6)); VS_HIP(dDelta.alloc((size_t)nff * 6)); VS_HIP(dOut.alloc(4));
-    VS_HIP(dPos.up(pos.data(), n)); VS_HIP(dRow.up(rowStart.data(), nf + 1)); VS_HIP(dInc.up(inc.data(), inc.size()));
-    VS_HIP(dFlag.alloc(1));
-    struct TimerOwner { StageTimer t; ~TimerOwner() { t.destroy(); } } timerOwner;      // (the events go on every return path)
-    StageTimer& timer = timerOwner.t;
-    timer.stream = st; timer.multi = true; timer.enabled = g_pgoTimingOn;
-    double hOut[2] = {0, 0}; int hFlag = 0;
-    double* cur = dP0.p; double* trial = dP1.p;
-    auto fetch = [&](bool withFlag) -> vslam_status {
-        VS_HIP(hipGetLastError());
-        VS_HIP(pool->d2h(hOut, dOut.p, 2 * sizeof(double)));
-        if (withFlag) VS_HIP(pool->d2h(&hFlag, dFlag.p, sizeof(int)));
-        VS_HIP(pool->sync());
-        return VSLAM_OK;
-    };
-    auto finish_timing = [&]() {
-        if (!timer.enabled) return;
-        const char* names[8]; float ms[8];
-        const int k = timer.read(names, ms, 8);
-        g_pgoTimes.clear();
-        for (int q = 0; q < k; q++) g_pgoTimes.push_back({names[q], ms[q]});
-    };
-    int t = timer.begin("pgo_linearize");
-    if (m) hipLaunchKernelGGL(k_pgo_linearize, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, cur, dRes.p, dJi.p, dJj.p, dCost.p);
-    timer.end(t);
-    t = timer.begin("pgo_cost");
-    hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(PGO_RED_NT), 0, st, m, dCost.p, 0, dDelta.p, dOut.p);
-    timer.end(t);
-    VS_CHECK(fetch(false));
-    double cost = hOut[0];
-    report->initial_cost = report->final_cost = cost;
-    int acc = 0, rej = 0;
-    bool stop = !(cost > 1e-20) || nf == 0;
-    bool linearized = true;
-    while (!stop) {
-        if (!linearized) {
-            t = timer.begin("pgo_linearize");
-            hipLaunchKernelGGL(k_pgo_linearize, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, cur, dRes.p, dJi.p, dJj.p, dCost.p);
-            timer.end(t);
-        }
-        t = timer.begin("pgo_assemble");
-        hipLaunchKernelGGL(k_pgo_assemble, dim3(nf), dim3(64), 0, st, nf, b, dPos.p, dRow.p, dInc.p, dE.p, dRes.p, dJi.p, dJj.p,
-                           dBandH.p, dDiag.p, dG.p);
-        timer.end(t);
-        for (;;) {      // trials from this linearisation
-            t = timer.begin("pgo_band_chol");
-            VS_HIP(hipMemcpyAsync(dBandL.p, dBandH.p, bandN * sizeof(double), hipMemcpyDeviceToDevice, st));
-            VS_HIP(hipMemcpyAsync(dRhs.p, dG.p, (size_t)nf * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_pgo_band_chol, dim3(1), dim3(PGO_CHOL_NT), 0, st, nf, b, lambda, dBandL.p, dDiag.p, dRhs.p, dDelta.p, dFlag.p);
-            timer.end(t);
-            t = timer.begin("pgo_retract");
-            hipLaunchKernelGGL(k_pgo_retract, dim3((n + 255) / 256), dim3(256), 0, st, n, dPos.p, cur, dDelta.p, trial);
-            timer.end(t);
-            t = timer.begin("pgo_cost");
-            hipLaunchKernelGGL(k_pgo_cost, dim3((m + 255) / 256), dim3(256), 0, st, m, dE.p, trial, dCost.p);
-            hipLaunchKernelGGL(k_pgo_reduce, dim3(1), dim3(PGO_RED_NT), 0, st, m, dCost.p, nf * 6, dDelta.p, dOut.p);
-            timer.end(t);
-            VS_CHECK(fetch(true));
-            const double cn = hOut[0], dmax = hOut[1];
-            const bool tiny = !hFlag && dmax < 1e-12;      // (a flagged factorisation's delta means nothing: the trial is only rejected)
-            if (!hFlag && std::isfinite(cn) && cn < cost) {
-                const double rel = (cost - cn) / cost;
-                std::swap(cur, trial);
-                cost = cn; acc++;
-                lambda = std::max(lambda / 3.0, 1e-12);
-                if (acc >= maxIt || rel < 1e-10 || tiny) stop = true;
-                linearized = false;
-                break;
-            }
-            rej++;
-            lambda *= 4.0;
-            if (lambda > 1e8 || tiny) { stop = true; break; }
-        }
-    }
-    report->accepted = acc; report->rejected = rej; report->iterations = acc + rej;
-    report->final_cost = cost; report->final_lambda = lambda;
-    VS_HIP(pool->d2h(hp.data(), cur, (size_t)n * 12 * sizeof(double)));
-    VS_HIP(pool->sync());
-    finish_timing();
-    pgo_write_out(G, hp.data(), T_wc, T_wc_out);
-    return VSLAM_OK;
-}
-
-// The batched call.  Host work per lane is pgo_prepare; the lanes' arrays then go up as ONE block (table, control blocks, edges,
+// THE solve, behind both entry points: `lanes` graphs, the checked parameters.  A lane with n == 0 is idle (the single call never
+// passes one).  Host work per lane is pgo_prepare; the lanes' arrays then go up as ONE block (table, control blocks, edges,
 // poses, positions, incidence lists) and the device's own arrays are one more block from the thread's cache.  A round is one
 // trial of every active lane: eight launches and one wait, for a single int (how many lanes are still active).
-extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
-                                                        int32_t device, vslam_pgo_report* reports) {
-    static const char* const who = "vslam_pose_graph_optimize_batch";
-    if (!graphs || !reports || lanes < 1) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
-    if (lanes > PGO_MAX_LANES) { set_error("%s: %d lanes exceed the limit (%d)", who, lanes, PGO_MAX_LANES); return VSLAM_ERR_CAPACITY; }
-    int maxIt = 0;
-    double lambda0 = 0.0;
-    VS_CHECK(pgo_check_params(who, params, &maxIt, &lambda0));
+// `who` starts every error text, with the lane where `nameLane` says so.  Nothing is written before the last wait has returned.
+vslam_status pgo_solve(const char* who, bool nameLane, const vslam_pgo_graph* graphs, int lanes, int maxIt, double lambda0, int device,
+                       vslam_pgo_report* reports) {
     char lw[96];
+    auto lane_text = [&](int g) { if (nameLane) snprintf(lw, sizeof lw, "%s: lane %d", who, g); else snprintf(lw, sizeof lw, "%s", who); return lw; };
     std::vector<int> live;                  // the lanes that hold a graph, in call order: the device's lanes
     long long sumN = 0, sumM = 0;
     for (int g = 0; g < lanes; g++) {
         const vslam_pgo_graph& Q = graphs[g];
         if (Q.n == 0) continue;
-        snprintf(lw, sizeof lw, "%s: lane %d", who, g);
-        VS_CHECK(pgo_check_sizes(lw, Q.T_wc, Q.fixed, Q.n, Q.edges, Q.m, Q.T_wc_out));
+        VS_CHECK(pgo_check_sizes(lane_text(g), Q.T_wc, Q.fixed, Q.n, Q.edges, Q.m, Q.T_wc_out));
         sumN += Q.n; sumM += Q.m;
         live.push_back(g);
     }
@@ -906,8 +758,7 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
     size_t maxBand = 0;                     // doubles of the largest lane's band
     for (int l = 0; l < nl; l++) {
         const vslam_pgo_graph& Q = graphs[live[l]];
-        snprintf(lw, sizeof lw, "%s: lane %d", who, live[l]);
-        VS_CHECK(pgo_prepare(lw, Q.T_wc, Q.fixed, Q.n, Q.edges, Q.m, prep[l]));
+        VS_CHECK(pgo_prepare(lane_text(live[l]), Q.T_wc, Q.fixed, Q.n, Q.edges, Q.m, prep[l]));
         const PgoPrep& G = prep[l];
         if (sumB + (long long)(G.b + 1) * G.nf > PGO_SUM_BLOCKS) {
             set_error("%s: the lanes' bands need more than %d blocks in all (reached at lane %d)", who, PGO_SUM_BLOCKS, live[l]);
@@ -919,31 +770,24 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
         maxBand = std::max(maxBand, (size_t)(G.b + 1) * G.nf * 36);
     }
     if (nl == 0) return VSLAM_OK;           // (every lane idle: nothing to solve, nothing written)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
-    DevPool* pool = thread_pool(device);
-    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
-    pool->pending.clear();
+    DevPool* pool = nullptr;
+    VS_CHECK(pgo_device_pool(device, &pool));
     hipStream_t st = pool->stream;
 
-    // the upload block and the work block: sections at 256-byte steps
-    size_t upBytes = 0, wkBytes = 0;
-    auto section = [](size_t& total, size_t bytes) { const size_t at = total; total = align_up_sz(total + std::max<size_t>(bytes, 8), 256); return at; };
-    const size_t oTab = section(upBytes, nl * sizeof(PgoLane)), oCtl = section(upBytes, nl * sizeof(PgoCtl));
-    const size_t oE = section(upBytes, (size_t)M * sizeof(PgoEdge)), oP0 = section(upBytes, (size_t)N * 12 * sizeof(double));
-    const size_t oPos = section(upBytes, (size_t)N * sizeof(int)), oRow = section(upBytes, (size_t)(NF + nl) * sizeof(int));
-    const size_t oInc = section(upBytes, (size_t)INC * sizeof(int));
+    PgoLayout up, wk;                       // the upload block and the work block
+    const size_t oTab = up.section(nl * sizeof(PgoLane)), oCtl = up.section(nl * sizeof(PgoCtl));
+    const size_t oE = up.section((size_t)M * sizeof(PgoEdge)), oP0 = up.section((size_t)N * 12 * sizeof(double));
+    const size_t oPos = up.section((size_t)N * sizeof(int)), oRow = up.section((size_t)(NF + nl) * sizeof(int));
+    const size_t oInc = up.section((size_t)INC * sizeof(int));
     const size_t bandBytes = (size_t)sumB * 36 * sizeof(double), vecBytes = (size_t)NF * 6 * sizeof(double);
-    const size_t oP1 = section(wkBytes, (size_t)N * 12 * sizeof(double)), oRes = section(wkBytes, (size_t)M * 6 * sizeof(double));
-    const size_t oJi = section(wkBytes, (size_t)M * 36 * sizeof(double)), oJj = section(wkBytes, (size_t)M * 36 * sizeof(double));
-    const size_t oCost = section(wkBytes, (size_t)M * sizeof(double));
-    const size_t oBandH = section(wkBytes, bandBytes), oBandL = section(wkBytes, bandBytes);
-    const size_t oDiag = section(wkBytes, vecBytes), oG = section(wkBytes, vecBytes), oRhs = section(wkBytes, vecBytes), oDelta = section(wkBytes, vecBytes);
-    const size_t oOut = section(wkBytes, (size_t)nl * 2 * sizeof(double)), oFlag = section(wkBytes, (size_t)nl * sizeof(int));
-    const size_t oAct = section(wkBytes, sizeof(int));
-    std::vector<uint8_t> hUp(upBytes, 0);
+    const size_t oP1 = wk.section((size_t)N * 12 * sizeof(double)), oRes = wk.section((size_t)M * 6 * sizeof(double));
+    const size_t oJi = wk.section((size_t)M * 36 * sizeof(double)), oJj = wk.section((size_t)M * 36 * sizeof(double));
+    const size_t oCost = wk.section((size_t)M * sizeof(double));
+    const size_t oBandH = wk.section(bandBytes), oBandL = wk.section(bandBytes);
+    const size_t oDiag = wk.section(vecBytes), oG = wk.section(vecBytes), oRhs = wk.section(vecBytes), oDelta = wk.section(vecBytes);
+    const size_t oOut = wk.section((size_t)nl * 2 * sizeof(double)), oFlag = wk.section((size_t)nl * sizeof(int));
+    const size_t oAct = wk.section(sizeof(int));
+    std::vector<uint8_t> hUp(up.bytes, 0);
     memcpy(hUp.data() + oTab, tab.data(), nl * sizeof(PgoLane));
     for (int l = 0; l < nl; l++) {
         const PgoPrep& G = prep[l];
@@ -957,7 +801,7 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
         memcpy(hUp.data() + oInc + (size_t)tab[l].inc0 * sizeof(int), G.inc.data(), (size_t)G.rowStart[G.nf] * sizeof(int));
     }
     PoolBuf<uint8_t> dUp(pool), dWk(pool);
-    VS_HIP(dUp.up(hUp.data(), upBytes)); VS_HIP(dWk.alloc(wkBytes));
+    VS_HIP(dUp.up(hUp.data(), up.bytes)); VS_HIP(dWk.alloc(wk.bytes));
     const PgoLane* dTab = (const PgoLane*)(dUp.p + oTab);
     PgoCtl* dCtl = (PgoCtl*)(dUp.p + oCtl);
     const PgoEdge* dE = (const PgoEdge*)(dUp.p + oE);
@@ -971,26 +815,41 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
     double* dRhs = (double*)(dWk.p + oRhs); double* dDelta = (double*)(dWk.p + oDelta); double* dOut = (double*)(dWk.p + oOut);
     int* dFlag = (int*)(dWk.p + oFlag); int* dAct = (int*)(dWk.p + oAct);
 
+    struct TimerOwner { StageTimer t; ~TimerOwner() { t.destroy(); } } timerOwner;      // (the events go on every return path)
+    StageTimer& timer = timerOwner.t;
+    timer.stream = st; timer.multi = true; timer.enabled = g_pgoTimingOn;
     const dim3 gEdge((maxM + 255) / 256, nl), gPose((maxN + 255) / 256, nl);
     int nActive = 0;
-    auto decide = [&](int init) -> vslam_status {
+    auto decide = [&](int init, int t) -> vslam_status {        // closes the pgo_cost group `t`, then the round's one wait
         hipLaunchKernelGGL(k_pgo_reduce_b, dim3(nl), dim3(PGO_RED_NT), 0, st, dTab, dCtl, init, dCost, dDelta, dOut);
         hipLaunchKernelGGL(k_pgo_decide_b, dim3(1), dim3(PGO_MAX_LANES), 0, st, nl, init, maxIt, dTab, dCtl, dOut, dFlag, dAct);
+        timer.end(t);
         VS_HIP(hipGetLastError());
         VS_HIP(pool->d2h(&nActive, dAct, sizeof(int)));
         VS_HIP(pool->sync());
         return VSLAM_OK;
     };
+    int t = timer.begin("pgo_linearize");
     if (maxM) hipLaunchKernelGGL(k_pgo_linearize_b, gEdge, dim3(256), 0, st, dTab, dCtl, 1, dE, dP0, dP1, dRes, dJi, dJj, dCost);
-    VS_CHECK(decide(1));
+    timer.end(t);
+    VS_CHECK(decide(1, timer.begin("pgo_cost")));
     while (nActive > 0) {       // one round
+        t = timer.begin("pgo_linearize");
         hipLaunchKernelGGL(k_pgo_linearize_b, gEdge, dim3(256), 0, st, dTab, dCtl, 0, dE, dP0, dP1, dRes, dJi, dJj, dCost);
+        timer.end(t);
+        t = timer.begin("pgo_assemble");
         hipLaunchKernelGGL(k_pgo_assemble_b, dim3(maxNf, nl), dim3(64), 0, st, dTab, dCtl, dPos, dRow, dInc, dE, dRes, dJi, dJj, dBandH, dDiag, dG);
+        timer.end(t);
+        t = timer.begin("pgo_band_chol");
         hipLaunchKernelGGL(k_pgo_band_copy_b, dim3((unsigned)((maxBand + 255) / 256), nl), dim3(256), 0, st, dTab, dCtl, dBandH, dG, dBandL, dRhs);
         hipLaunchKernelGGL(k_pgo_band_chol_b, dim3(nl), dim3(PGO_CHOL_NT), 0, st, dTab, dCtl, dBandL, dDiag, dRhs, dDelta, dFlag);
+        timer.end(t);
+        t = timer.begin("pgo_retract");
         hipLaunchKernelGGL(k_pgo_retract_b, gPose, dim3(256), 0, st, dTab, dCtl, dPos, dP0, dP1, dDelta);
+        timer.end(t);
+        t = timer.begin("pgo_cost");
         hipLaunchKernelGGL(k_pgo_cost_b, gEdge, dim3(256), 0, st, dTab, dCtl, dE, dP0, dP1, dCost);
-        VS_CHECK(decide(0));
+        VS_CHECK(decide(0, t));
     }
     std::vector<PgoCtl> ctl(nl);
     VS_HIP(pool->d2h(ctl.data(), dCtl, nl * sizeof(PgoCtl)));
@@ -998,6 +857,12 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
     for (int l = 0; l < nl; l++)
         if (ctl[l].accepted) VS_HIP(pool->d2h(prep[l].hp.data(), (ctl[l].cur ? dP1 : dP0) + (size_t)tab[l].pose0 * 12, (size_t)prep[l].n * 12 * sizeof(double)));
     VS_HIP(pool->sync());
+    if (timer.enabled) {
+        const char* names[8]; float ms[8];
+        const int k = timer.read(names, ms, 8);
+        g_pgoTimes.clear();
+        for (int q = 0; q < k; q++) g_pgoTimes.push_back({names[q], ms[q]});
+    }
     for (int l = 0; l < nl; l++) {
         const vslam_pgo_graph& Q = graphs[live[l]];
         const PgoPrep& G = prep[l];
@@ -1009,6 +874,31 @@ extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* g
         R.initial_cost = ctl[l].initial_cost; R.final_cost = ctl[l].cost; R.final_lambda = ctl[l].lambda;
     }
     return VSLAM_OK;
+}
+
+}  // namespace
+
+// the one-lane case of pgo_solve (no idle lane: n < 1 is refused; its error texts name no lane)
+extern "C" vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
+                                                  const vslam_pgo_params* params, int32_t device, double* T_wc_out, vslam_pgo_report* report) {
+    static const char* const who = "vslam_pose_graph_optimize";
+    if (!report || n < 1) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
+    int maxIt = 0;
+    double lambda0 = 0.0;
+    VS_CHECK(pgo_check_params(who, params, &maxIt, &lambda0));
+    const vslam_pgo_graph graph{T_wc, fixed, n, edges, m, T_wc_out};
+    return pgo_solve(who, false, &graph, 1, maxIt, lambda0, device, report);
+}
+
+extern "C" vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
+                                                        int32_t device, vslam_pgo_report* reports) {
+    static const char* const who = "vslam_pose_graph_optimize_batch";
+    if (!graphs || !reports || lanes < 1) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
+    if (lanes > PGO_MAX_LANES) { set_error("%s: %d lanes exceed the limit (%d)", who, lanes, PGO_MAX_LANES); return VSLAM_ERR_CAPACITY; }
+    int maxIt = 0;
+    double lambda0 = 0.0;
+    VS_CHECK(pgo_check_params(who, params, &maxIt, &lambda0));
+    return pgo_solve(who, true, graphs, lanes, maxIt, lambda0, device, reports);
 }
 
 vslam_status vslam::pgo_move_points_batch(const PgoMoveGraph* graphs, int lanes, int device) {
@@ -1034,18 +924,12 @@ vslam_status vslam::pgo_move_points_batch(const PgoMoveGraph* graphs, int lanes,
     }
     const int nl = (int)live.size();
     if (!nl) return VSLAM_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
-    DevPool* pool = thread_pool(device);
-    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
-    pool->pending.clear();
-    size_t upBytes = 0;
-    auto section = [&](size_t bytes) { const size_t at = upBytes; upBytes = align_up_sz(upBytes + std::max<size_t>(bytes, 8), 256); return at; };
-    const size_t oTab = section(nl * sizeof(PgoMoveLane)), oPts = section(nPts * 24), oRef = section(nPts * 4);
-    const size_t oOld = section(nPoses * 128), oNew = section(nPoses * 128);
-    std::vector<uint8_t> hUp(upBytes, 0);
+    DevPool* pool = nullptr;
+    VS_CHECK(pgo_device_pool(device, &pool));
+    PgoLayout up;
+    const size_t oTab = up.section(nl * sizeof(PgoMoveLane)), oPts = up.section(nPts * 24), oRef = up.section(nPts * 4);
+    const size_t oOld = up.section(nPoses * 128), oNew = up.section(nPoses * 128);
+    std::vector<uint8_t> hUp(up.bytes, 0);
     memcpy(hUp.data() + oTab, tab.data(), nl * sizeof(PgoMoveLane));
     for (int l = 0; l < nl; l++) {
         const PgoMoveGraph& Q = graphs[live[l]];
@@ -1057,7 +941,7 @@ vslam_status vslam::pgo_move_points_batch(const PgoMoveGraph* graphs, int lanes,
         }
     }
     PoolBuf<uint8_t> dUp(pool); PoolBuf<double> dOut(pool);
-    VS_HIP(dUp.up(hUp.data(), upBytes)); VS_HIP(dOut.alloc(nPts * 3));
+    VS_HIP(dUp.up(hUp.data(), up.bytes)); VS_HIP(dOut.alloc(nPts * 3));
     hipLaunchKernelGGL(k_pgo_move_points_b, dim3((maxPts + 255) / 256, nl), dim3(256), 0, pool->stream, (const PgoMoveLane*)(dUp.p + oTab),
                        (const double*)(dUp.p + oPts), (const int*)(dUp.p + oRef), (const double*)(dUp.p + oOld), (const double*)(dUp.p + oNew), dOut.p);
     VS_HIP(hipGetLastError());
@@ -1066,26 +950,13 @@ vslam_status vslam::pgo_move_points_batch(const PgoMoveGraph* graphs, int lanes,
     return VSLAM_OK;
 }
 
+// its own checks (its own wording), then the one-lane case of pgo_move_points_batch
 extern "C" vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
                                                      int32_t n_points, int32_t n_poses, int32_t device, double* points_out) {
     if (n_points < 0 || n_poses < 0 || (n_points > 0 && (!points_xyz || !ref_index || !points_out)) || (n_poses > 0 && (!T_old || !T_new))) {
         set_error("vslam_pose_graph_move_points: invalid arguments"); return VSLAM_ERR_INVALID;
     }
     for (int k = 0; k < n_points; k++) if (ref_index[k] >= n_poses) { set_error("vslam_pose_graph_move_points: point %d refers to pose %d of %d", k, ref_index[k], n_poses); return VSLAM_ERR_INVALID; }
-    if (n_points == 0) return VSLAM_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
-    DevPool* pool = thread_pool(device);
-    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
-    pool->pending.clear();
-    PoolBuf<double> dX(pool), dA(pool), dB(pool), dO(pool); PoolBuf<int> dR(pool);
-    VS_HIP(dX.up(points_xyz, (size_t)n_points * 3)); VS_HIP(dR.up(ref_index, n_points));
-    VS_HIP(dA.up(T_old, (size_t)n_poses * 16)); VS_HIP(dB.up(T_new, (size_t)n_poses * 16)); VS_HIP(dO.alloc((size_t)n_points * 3));
-    hipLaunchKernelGGL(k_pgo_move_points, dim3((n_points + 255) / 256), dim3(256), 0, pool->stream, n_points, dX.p, dR.p, dA.p, dB.p, dO.p);
-    VS_HIP(hipGetLastError());
-    VS_HIP(pool->d2h(points_out, dO.p, (size_t)n_points * 3 * sizeof(double)));
-    VS_HIP(pool->sync());
-    return VSLAM_OK;
+    const PgoMoveGraph graph{points_xyz, ref_index, n_points, T_old, T_new, n_poses, points_out};
+    return pgo_move_points_batch(&graph, 1, device);
 }

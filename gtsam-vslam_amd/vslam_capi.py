@@ -414,7 +414,8 @@ def pose_graph_set_timing(on):
 
 
 def pose_graph_timings():
-    """kernel group -> device ms of this thread's last pose_graph_optimize (after pose_graph_set_timing(True))"""
+    """kernel group -> device ms of this thread's last pose_graph_optimize or pose_graph_optimize_batch (after
+    pose_graph_set_timing(True)); the timers sit in the loop both calls share, so a batched call's figures cover all its lanes"""
     names = (C.c_char_p * 8)(); ms = (C.c_float * 8)(); n = C.c_int32()
     _chk(lib().vslam_pose_graph_timings(names, ms, 8, C.byref(n)))
     return {names[i].decode(): float(ms[i]) for i in range(n.value)}

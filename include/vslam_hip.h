@@ -427,13 +427,15 @@ vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lane
  *               when lambda > 1e8.  An initial cost <= 1e-20 returns at once: zero iterations, poses unchanged.
  *   solve       direct: the free poses reordered on the host by reverse Cuthill-McKee over the free-free edges, H as a
  *               block-banded lower matrix of 6x6 fp64 blocks (half-bandwidth b blocks), factorised and solved on the device
- *               by one workgroup walking the block columns (k_pgo_band_chol).  A pivot that is not positive makes the trial
+ *               by one workgroup walking the block columns (k_pgo_band_chol_b).  A pivot that is not positive makes the trial
  *               a rejected one whatever its delta (it does not end the loop through the |delta|_inf rule).
- *   kernels     k_pgo_linearize (one thread per edge), k_pgo_assemble (one wave per free pose gathers its incidence list in
- *               ascending edge order: no atomics), k_pgo_band_chol, k_pgo_retract / k_pgo_cost / k_pgo_reduce (fixed-order
- *               sum): two calls on the same input return the same bytes.  The accept / reject decision is taken on the
- *               host: one wait per trial, none inside factor / solve; the calling thread's block cache serves every buffer,
- *               so that a repeated call of unchanged size allocates and frees nothing.
+ *   kernels     k_pgo_linearize_b (one thread per edge), k_pgo_assemble_b (one wave per free pose gathers its incidence list
+ *               in ascending edge order: no atomics), k_pgo_band_copy_b, k_pgo_band_chol_b, k_pgo_retract_b / k_pgo_cost_b /
+ *               k_pgo_reduce_b (fixed-order sum): two calls on the same input return the same bytes.  The accept / reject
+ *               decision is taken on the device (k_pgo_decide_b, on a control block): the host waits once per trial, for one
+ *               int, never inside factor / solve; the calling thread's block cache serves every buffer, so that a repeated
+ *               call of unchanged size allocates and frees nothing.  The call is the ONE-LANE CASE of the batched call below:
+ *               the same host function, the same kernels.
  * A free pose without any edge is treated as fixed (n_isolated); fixed and isolated poses come back bit for bit; an edge
  * between two fixed poses only adds to the cost; duplicate edges add up.
  * VSLAM_ERR_INVALID, nothing launched: i == j or an index out of range, a non-finite pose / measurement / weight / parameter,
@@ -461,18 +463,20 @@ typedef struct vslam_pgo_report {
 vslam_status vslam_pose_graph_optimize(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
                                        const vslam_pgo_params* params, int32_t device, double* T_wc_out /* [n][16]; may be T_wc */,
                                        vslam_pgo_report* report);
-/* The same for `lanes` independent graphs in one call, one launch per stage for all of them (the _b kernels of csrc/pgo.hip,
- * blockIdx = lane; the 6x6 arithmetic is the single call's, shared as __device__ functions).  THE RULE: a lane's T_wc_out and
- * report are, byte for byte, what vslam_pose_graph_optimize returns for that graph alone with the same params (one params set
- * per call); order and company of the lanes do not matter.  A lane with n == 0 is idle: its output and report are not written.
- *   host      per lane the single call's validation, numbering, gauge check, reordering and packing (one shared function)
+/* The same for `lanes` independent graphs in one call, one launch per stage for all of them (the kernels of csrc/pgo.hip,
+ * blockIdx = lane, each on a lane's part of concatenated arrays).  THE RULE: a lane's T_wc_out and report are, byte for byte,
+ * what vslam_pose_graph_optimize returns for that graph alone with the same params (one params set per call) - by construction,
+ * since that call is this one with one lane; order and company of the lanes do not matter.  A lane with n == 0 is idle: its
+ * output and report are not written (the single call refuses n < 1).
+ *   host      per lane validation, numbering, gauge check, reordering and packing
  *   device    the lanes' arrays concatenated in two blocks from the calling thread's cache (one upload); a lane table
  *             {n, m, n_free, b, offsets}; a control block per lane {active, need_linearize, cur, lambda, cost, accepted,
  *             rejected}.  One ROUND is one trial of every active lane: linearise (lanes whose last trial was accepted),
  *             assemble, copy of the active lanes' bands and gradients (k_pgo_band_copy_b), factor + solve
- *             (k_pgo_band_chol_b: one workgroup per lane), retract, cost, reduce, decide (k_pgo_decide_b: one thread per lane applies the accept / reject rule
- *             above in fp64, the host's operations in the host's order).  A lane that has stopped costs its workgroups one
- *             load.  The host waits once per round, for one int: the number of lanes still active.
+ *             (k_pgo_band_chol_b: one workgroup per lane), retract, cost, reduce, decide (k_pgo_decide_b: one thread per lane
+ *             applies the accept / reject rule above in fp64; it is the only place that rule is written).  A lane that has
+ *             stopped costs its workgroups one load.  The host waits once per round, for one int: the number of lanes still
+ *             active.
  * VSLAM_ERR_INVALID, nothing launched, no lane written: lanes < 1, NULL graphs / reports, a bad parameter, or any lane the
  * single call would refuse as invalid (the error text names the lane).
  * VSLAM_ERR_CAPACITY, likewise: a lane beyond the single call's limits; lanes > 1024; in all lanes together more than 262144
@@ -484,14 +488,15 @@ typedef struct vslam_pgo_graph {     /* one lane; n == 0: idle lane (its report 
 } vslam_pgo_graph;
 vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
                                              int32_t device, vslam_pgo_report* reports /* [lanes] */);
-/* k_pgo_move_points: points_out[k] = T_new[r] * T_old[r]^-1 * points_xyz[k] with r = ref_index[k] (rigid inverse: R^T (X - t));
- * r < 0 leaves the point as it is; r >= n_poses: VSLAM_ERR_INVALID, nothing launched.  points_out may be points_xyz. */
+/* k_pgo_move_points_b with one lane: points_out[k] = T_new[r] * T_old[r]^-1 * points_xyz[k] with r = ref_index[k] (rigid inverse:
+ * R^T (X - t)); r < 0 leaves the point as it is; r >= n_poses: VSLAM_ERR_INVALID, nothing launched.  points_out may be points_xyz. */
 vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
                                           int32_t n_points, int32_t n_poses, int32_t device, double* points_out);
 /* measurement hook of tools/pgo_rate.py, not part of the supported surface: per-kernel-group device time of the calling
- * thread's last vslam_pose_graph_optimize (HIP events; off by default; thread-local state).  Groups: pgo_linearize,
- * pgo_assemble, pgo_band_chol (with the copies of band and right-hand side), pgo_retract, pgo_cost (k_pgo_cost and every
- * k_pgo_reduce, the initial one included). */
+ * thread's last vslam_pose_graph_optimize or vslam_pose_graph_optimize_batch - the timers sit in the loop both share, so a
+ * batched call's figures are those of all its lanes together (HIP events; off by default; thread-local state).  Groups:
+ * pgo_linearize, pgo_assemble, pgo_band_chol (with the copy of band and right-hand side), pgo_retract, pgo_cost (k_pgo_cost_b,
+ * k_pgo_reduce_b and k_pgo_decide_b, the initial reduce and decide included). */
 vslam_status vslam_pose_graph_set_timing(int32_t on);
 vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
 

@@ -5,6 +5,7 @@ every refusal.  Tolerances: 1e-7 absolute per pose entry (the closed-loop tests'
 across), 1e-9 relative on the final cost, and the solver-independent stationarity |J^T W r|_inf <= 1e-6 of its initial value,
 evaluated by the restatement on the device's result."""
 import functools
+import os
 import numpy as np
 import pytest
 import pgo_ref as pr
@@ -67,6 +68,29 @@ def test_against_restatement(capi, name):
     # two calls on the same input return the same bytes
     out2, rep2 = capi.pose_graph_optimize(poses, fixed, edges)
     assert out2.tobytes() == out.tobytes() and rep2 == rep
+
+
+def test_single_call_returns_recorded_bytes(capi):
+    """The single call is the one-lane case of the batched solve; tests/golden/pgo_single.npz holds what the last single call
+    with kernels and a host loop of its own returned (tests/golden/make_pgo_single.py says from which commit and how to
+    re-record): every graph above, the singular ring, the exact graph, all poses fixed, max_iterations = 2 with lambda0 = 10,
+    and the moved points of test_move_points.  Pose bytes and every report field are equal."""
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pgo_single.npz")) as z:
+        gold = {k: z[k] for k in z.files}
+    fields = [str(f) for f in gold["report_fields"]]
+    assert fields == [f[0] for f in capi.PgoReport._fields_]
+    names = [str(n) for n in gold["names"]]
+    assert set(GRAPHS) < set(names) and len(names) == len(GRAPHS) + 4
+    for name in names:
+        g = lambda k: gold[name + "/" + k]
+        out, rep = capi.pose_graph_optimize(g("poses"), g("fixed"), g("edges"), max_iterations=int(g("params")[0]), lambda0=float(g("params")[1]))
+        want = dict(zip(fields[:6], (int(v) for v in g("report_int"))), **dict(zip(fields[6:], (float(v) for v in g("report_f64")))))
+        print(name, rep)
+        assert rep == want, name
+        assert out.tobytes() == g("out").tobytes(), name
+    for n in (1, 255, 257):
+        g = lambda k: gold["move%d/%s" % (n, k)]
+        assert capi.pose_graph_move_points(g("X"), g("ref"), g("A"), g("B")).tobytes() == g("out").tobytes(), n
 
 
 def test_bandwidths(capi):
