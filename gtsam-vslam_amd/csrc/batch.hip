@@ -952,7 +952,7 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
     std::vector<double> Tcw((size_t)B * 16, 0.0);
     const RelocBlocks blk{h_up, d_up, h_dn, d_dn};
     if (imuCall) for (int b = 0; b < B; b++) if (ls[b].on) ireps[b] = vslam_reloc_imu_report{};
-    VS_CHECK(reloc_batch_run_imu(rl.data(), B, plan, blk, stream, P, (double)(float)std::log((double)shared.fe.scale), &timer, Tcw.data(), reps,
+    VS_CHECK(reloc_batch_run(rl.data(), B, plan, blk, stream, P, (double)(float)std::log((double)shared.fe.scale), &timer, Tcw.data(), reps,
                                  imuCall ? ireps : nullptr));
     // ---- host: commit per lane (a failure changes nothing in its session) ----------------------------------------------------------
     pool.run(B, [&](int b) {

@@ -120,25 +120,21 @@ struct vslam_matcher {
     vslam_status imu_predict(const vslam_imu_input* imu, const double* predVelocity, double lastDt, double* T_wc_out, double* vel_out);
     vslam_status estimate_pose(vslam_pose_problem* prob, int* nIn, int* nStereo, vslam_lm_report* rep);
 
-    // relocalisation (reloc.hip): global descriptor match of a map against the current frame, pose hypotheses, refinement
-    int rlCap = 0;                   // map-point capacity of d_rlPts / d_rlDesc / d_rlPairs
+    // relocalisation (reloc.hip): global descriptor match of a map against the current frame, pose hypotheses, refinement.  Map points,
+    // pairs and key winners live in the call's upload / download blocks (RelocBatchLane below); the rest is the matcher's
     int rlDCap = 0;                  // map-point capacity of d_rlD
-    double* d_rlPts = nullptr;       // [N][3]
-    uint8_t* d_rlDesc = nullptr;     // [N][32]
     int* d_rlD = nullptr;            // [N][3]: d1, i1, d2
-    int* d_rlPairs = nullptr;        // [N]: key index of the point's correspondence or -1
-    unsigned long long* d_rlKeyWin = nullptr;   // [RELOC_MAX_KEYS]: (d1 << 32 | point) of the key's best proposer
-    int* d_rlKeyWinner = nullptr;    // [RELOC_MAX_KEYS]: that point or -1
+    int* d_rlKeyWinner = nullptr;    // [RELOC_MAX_KEYS]: the map point that won the key or -1
     void* d_rlRec = nullptr;         // [RELOC_MAX_KEYS] correspondence records
     uint8_t* d_rlFlags = nullptr;    // [RELOC_MAX_KEYS] the winner's inlier flags
     int* d_rlCounts = nullptr;       // [RELOC_MAX_HYP]
     double* d_rlPoses = nullptr;     // [RELOC_MAX_HYP][12]: R row-major, t
-    double* d_rlOut = nullptr;       // T_cw[16] of the winner, then ints {C, best hypothesis, best count}
+    double* d_rlOut = nullptr;       // T_cw[16] of the winner, then ints {C, best hypothesis, best count, problem size, gate}
     int rlLast[4] = {0, 0, 0, 0};    // sizes of the last call: points, keys, hypotheses, correspondences
-    std::vector<uint8_t> rlHost;     // download block of the last call
-    vslam_status ensure_reloc_cap(int n, bool uploads = true);      // uploads: d_rlPts / d_rlDesc / d_rlPairs as well (the one-session call)
-    uint8_t* rlBlk[4] = {nullptr, nullptr, nullptr, nullptr}; size_t rlBlkCap[2] = {0, 0};      // vslam_relocalize_batch with this matcher first:
-                                                                                                  // pinned / device upload block, pinned / device download block
+    vslam_status ensure_reloc_cap(int n);
+    uint8_t* rlBlk[4] = {nullptr, nullptr, nullptr, nullptr}; size_t rlBlkCap[2] = {0, 0};      // blocks of a call whose first (or only) lane is this
+                                                                                                  // matcher: pinned / device upload, pinned / device download
+    // one lane through reloc_batch_run on this matcher's own blocks and stream
     vslam_status relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
                             int32_t* pairsOut, vslam_reloc_report* rep);
     vslam_status relocalize_debug(int32_t* d3, int capPoints, int32_t* keyWinner, int capKeys, int32_t* counts, int capHyp,
@@ -257,7 +253,7 @@ void launch_proj_resolve(hipStream_t s, const ProjArgs& A, const unsigned long l
                          int* matches, int* out);
 
 // ---- batched relocalisation (reloc.hip): one launch per stage for all lanes ---------------------------------------------------
-// Both blocks are the caller's (vslam_relocalize_batch: the first matcher's; vslam_batch: the group's upload / download blocks).
+// Both blocks are the caller's (vslam_relocalize, vslam_relocalize_batch, a session: the first matcher's own; vslam_batch: the group's).
 //   upload block    lane tables | per lane: xyz [n][3], descriptors [n][32], maxScaleDist [n] (if wanted) | per lane: key winners
 //                   (device side only); everything before the key winners goes up in ONE copy
 //   download block  per lane: summary | pairs [n] | in-frame bytes [n] (if wanted); comes down in ONE copy
@@ -276,20 +272,20 @@ struct RelocBatchLane {
 struct RelocBatchPlan { size_t oPose = 0, oImuTab = 0, upCopyBytes = 0, upBytes = 0, dnBytes = 0; int maxN = 0, nOn = 0, nImu = 0; };
 struct RelocBlocks { uint8_t* h_up; uint8_t* d_up; uint8_t* h_dn; uint8_t* d_dn; };
 vslam_status reloc_resolve_params(const vslam_reloc_params* prm, vslam_reloc_params& P);
-// per-lane argument checks of the batched call (limits and status rules of vslam_relocalize); nothing is changed
-vslam_status reloc_batch_check(const RelocBatchLane* lanes, int B, int device);
+// per-lane argument checks (limits and status rules of vslam_relocalize); nothing is changed.  nameLanes false: the call has one lane
+// and its messages name none
+vslam_status reloc_batch_check(const RelocBatchLane* lanes, int B, int device, bool nameLanes = true);
 void reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan);
-// The caller has filled the lanes' map arrays in h_up.  Keys are refreshed, capacities ensured, then tables, upload, the stages,
-// download and ONE wait on `stream`; reports and T_cw_out ([B][16], written per lane only on success) are filled per active lane.
-vslam_status reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
-                             const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps);
-// The same with the velocity rule for the lanes that carry a bucket (RelocBatchLane::imu): their buckets staged into the upload block and
-// pre-integrated by ONE k_imu_preintegrate_b launch ahead of the stages, k_reloc_velocity_b after them.  imuReps [B]: phase (2 on
+// The one driver of every relocalisation.  The caller has filled the lanes' map arrays in h_up.  Keys are refreshed, capacities ensured,
+// then tables, upload, the stages, download and ONE wait on `stream`; reports and T_cw_out ([B][16], written per lane only on success)
+// are filled per active lane.
+// Lanes that carry a bucket (RelocBatchLane::imu) get the velocity rule: their buckets staged into the upload block and pre-integrated by
+// ONE k_imu_preintegrate_b launch ahead of the stages, k_reloc_velocity_b after them.  imuReps [B] (needed only then): phase (2 on
 // success, else 0), dt, velocity_prev, velocity, rot_residual of those lanes (bias is the caller's).  A bucket whose covariance has no
-// Cholesky factor: VSLAM_ERR_INVALID naming the lane, after the wait - the caller commits nothing.
-vslam_status reloc_batch_run_imu(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
-                                 const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
-                                 vslam_reloc_imu_report* imuReps);
-// pinned + device blocks of a matcher's own (vslam_relocalize_batch with this matcher first; a session's relocalize_imu): grown on demand
+// Cholesky factor: VSLAM_ERR_INVALID after the wait - the caller commits nothing.
+vslam_status reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
+                             const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
+                             vslam_reloc_imu_report* imuReps = nullptr, bool nameLanes = true);
+// pinned + device blocks of a matcher's own, grown on demand
 vslam_status reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dnBytes);
 }  // namespace vslam

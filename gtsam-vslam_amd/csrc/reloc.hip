@@ -1,26 +1,25 @@
 // Relocalisation on gfx950: recover the pose of the matcher's current stereo frame from a map WITHOUT a pose prior.
 // This stage has no counterpart in the reference; its definition is the one in include/vslam_hip.h,
 // restated on the CPU by tests/reloc_ref.py.
-//   k_reloc_match   brute-force 256-bit Hamming search of every map point against every left key: one lane owns one map
-//                   point (eight descriptor dwords in registers), a workgroup stages the frame's descriptors through LDS in
-//                   tiles of 2048 (64 KB: two workgroups per CU), every lane reads the same LDS address (a broadcast);
-//                   best / second-best distance, the acceptance tests, one 64-bit atomicMin per proposal
-//   k_reloc_pairs   one workgroup: winning pairs whose key has stereo depth, compacted in ascending key index
-//   k_reloc_ransac  one wave per hypothesis: three sampled correspondences -> rigid pose (fp64), scored over all records
-//   k_reloc_best    one wave: the winning hypothesis and its inlier flags
-// The winner's inliers are refined by the existing motion-only LM (vslam_matcher::estimate_pose).
-// vslam_reloc_params::mode = 1 (hypotheses from 2D-3D correspondences, restated by tests/reloc_p3p_ref.py): the same bodies with
-// MODE = 1 behind k_reloc_pairs_p3p (every winning pair, the key's unit bearing in the X_c slot), k_reloc_ransac_p3p (a P3P solver
-// in fp64: up to four poses per hypothesis, all scored in one pass over the records) and k_reloc_best_p3p; k_reloc_match is shared.
-// Several lanes in one call (vslam_relocalize_batch, vslam_batch_relocalize): the k_*_b forms of the four kernels - the same bodies,
-// the lane as a grid dimension, arguments from a RelocLane table - then
-//   k_reloc_problem_b  the refinement problem built on the device (no wait before step D), refined by k_pose_lm_b behind a gate
+// Every call runs the same kernels over a RelocLane table, the lane as a grid dimension: vslam_relocalize, a session's call and a
+// loop detection are the one-lane case of vslam_relocalize_batch / vslam_batch_relocalize (one driver: reloc_batch_run).
+//   k_reloc_match_b    brute-force 256-bit Hamming search of every map point against every left key: one lane owns one map
+//                      point (eight descriptor dwords in registers), a workgroup stages the frame's descriptors through LDS in
+//                      tiles of 2048 (64 KB: two workgroups per CU), every lane reads the same LDS address (a broadcast);
+//                      best / second-best distance, the acceptance tests, one 64-bit atomicMin per proposal
+//   k_reloc_pairs_b    one workgroup: winning pairs whose key has stereo depth, compacted in ascending key index
+//   k_reloc_ransac_b   one wave per hypothesis: three sampled correspondences -> rigid pose (fp64), scored over all records
+//   k_reloc_best_b     one wave: the winning hypothesis and its inlier flags
+//   k_reloc_problem_b  the refinement problem (the winner's inliers) built on the device, no wait before step D; refined by the
+//                      motion-only LM (k_pose_lm_b, pose.hip) behind a gate
 //   k_reloc_inframe_b  the lane's results into the download block; the left-image test of the map under the refined pose
+// vslam_reloc_params::mode = 1 (hypotheses from 2D-3D correspondences, restated by tests/reloc_p3p_ref.py): the same bodies with
+// MODE = 1 behind k_reloc_pairs_p3p_b (every winning pair, the key's unit bearing in the X_c slot), k_reloc_ransac_p3p_b (a P3P solver
+// in fp64: up to four poses per hypothesis, all scored in one pass over the records) and k_reloc_best_p3p_b; k_reloc_match_b is shared.
 // Stereo + IMU sessions (vslam_system_relocalize_imu, vslam_batch_relocalize_imu; restated by tests/reloc_imu_ref.py): the second of two
 // relocalised poses re-initialises the velocity - the bucket between the poses through k_imu_preintegrate_b (pose_imu.hip) ahead of the
 // stages, then
-//   k_reloc_velocity_b  one wave per lane: the start velocity for which the IMU prediction lands on the new pose (k_reloc_velocity: the
-//                       same body with its arguments by value, for the rule's test tap)
+//   k_reloc_velocity_b  one wave per lane: the start velocity for which the IMU prediction lands on the new pose
 #include "pose_dev.hpp"
 #include "track_dev.hpp"
 #include "imu_dev.hpp"
@@ -46,8 +45,7 @@ __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, cons
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-// The bodies below are shared by the one-session kernels (arguments by value) and the lane-table forms (k_*_b: the lane is a grid
-// dimension, arguments from a RelocLane entry): one copy of every rule.
+// The rules are the bodies below; the kernels (k_*_b) hand them the arguments of a RelocLane entry, the lane being a grid dimension.
 __device__ __forceinline__ void reloc_match_body(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
                                                  int maxHamming, int ratioPct, int* __restrict__ dOut,
                                                  unsigned long long* __restrict__ keyWin) {
@@ -76,11 +74,6 @@ __device__ __forceinline__ void reloc_match_body(int nP, const uint4* __restrict
         atomicMin(&keyWin[i1], ((unsigned long long)d1 << 32) | (unsigned)p);
 }
 
-__global__ __launch_bounds__(256) void k_reloc_match(int nP, const uint4* __restrict__ descP, int nL, const uint4* __restrict__ descL,
-                                                     int maxHamming, int ratioPct, int* __restrict__ dOut,
-                                                     unsigned long long* __restrict__ keyWin) {
-    reloc_match_body(nP, descP, nL, descL, maxHamming, ratioPct, dOut, keyWin);
-}
 // grid (ceil(max nP / 256), lanes).  A workgroup past its lane's points leaves as a whole, before the body's first barrier.
 __global__ __launch_bounds__(256) void k_reloc_match_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.y);
@@ -137,22 +130,6 @@ __device__ __forceinline__ void reloc_pairs_body(int nL, const unsigned long lon
     if (threadIdx.x == 0) out[0] = run;
 }
 
-__global__ __launch_bounds__(1024) void k_reloc_pairs(int nL, const unsigned long long* __restrict__ keyWin,
-                                                      const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
-                                                      const float* __restrict__ depth, const int* __restrict__ rightIdxs,
-                                                      const double* __restrict__ pts, double fx, double fy, double cx, double cy,
-                                                      RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
-                                                      int* __restrict__ out) {
-    reloc_pairs_body<0>(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
-}
-__global__ __launch_bounds__(1024) void k_reloc_pairs_p3p(int nL, const unsigned long long* __restrict__ keyWin,
-                                                          const vslam_keypoint* __restrict__ kpsL, const vslam_keypoint* __restrict__ kpsR,
-                                                          const float* __restrict__ depth, const int* __restrict__ rightIdxs,
-                                                          const double* __restrict__ pts, double fx, double fy, double cx, double cy,
-                                                          RelocRec* __restrict__ rec, int* __restrict__ pairs, int* __restrict__ keyWinner,
-                                                          int* __restrict__ out) {
-    reloc_pairs_body<1>(nL, keyWin, kpsL, kpsR, depth, rightIdxs, pts, fx, fy, cx, cy, rec, pairs, keyWinner, out);
-}
 // one workgroup per lane
 __global__ __launch_bounds__(1024) void k_reloc_pairs_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.x);
@@ -510,14 +487,6 @@ __device__ __forceinline__ void reloc_ransac_body(const PoseArgs& A, const Reloc
     }
 }
 
-__global__ __launch_bounds__(64) void k_reloc_ransac(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
-                                                     unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
-    reloc_ransac_body<0>(A, rec, nRec, seed, counts, poses);
-}
-__global__ __launch_bounds__(64) void k_reloc_ransac_p3p(PoseArgs A, const RelocRec* __restrict__ rec, const int* __restrict__ nRec,
-                                                         unsigned seed, int* __restrict__ counts, double* __restrict__ poses) {
-    reloc_ransac_body<1>(A, rec, nRec, seed, counts, poses);
-}
 // grid (hypotheses, lanes)
 __global__ __launch_bounds__(64) void k_reloc_ransac_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.y);
@@ -568,14 +537,6 @@ __device__ __forceinline__ void reloc_best_body(const PoseArgs& A, const RelocRe
     }
 }
 
-__global__ __launch_bounds__(64) void k_reloc_best(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
-                                                   const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
-    reloc_best_body<0>(A, rec, nHyp, counts, poses, out, flags);
-}
-__global__ __launch_bounds__(64) void k_reloc_best_p3p(PoseArgs A, const RelocRec* __restrict__ rec, int nHyp, const int* __restrict__ counts,
-                                                       const double* __restrict__ poses, double* __restrict__ out, uint8_t* __restrict__ flags) {
-    reloc_best_body<1>(A, rec, nHyp, counts, poses, out, flags);
-}
 // one wave per lane
 __global__ __launch_bounds__(64) void k_reloc_best_b(const RelocLane* __restrict__ lanes) {
     const RelocLane& L = *lane_entry(lanes, blockIdx.x);
@@ -586,8 +547,7 @@ __global__ __launch_bounds__(64) void k_reloc_best_p3p_b(const RelocLane* __rest
     reloc_best_body<1>(L.A, L.rec, L.nHyp, L.counts, L.poses, L.out, L.flags);
 }
 
-// The refinement problem of a lane, built where the one-session call builds it on the host: the winner's inlier correspondences, in
-// correspondence order, into the lane's matcher's pose buffers - points = X_w, matches = (i, rightIdxs[i]), both in-frame flags 1,
+// The refinement problem of a lane: the winner's inlier correspondences, in correspondence order, into the lane's matcher's pose buffers - points = X_w, matches = (i, rightIdxs[i]), both in-frame flags 1,
 // both outlier flags 0, poseIO = the winning hypothesis - and the two words the pose kernel reads on the device: the problem size
 // (PoseArgs::Mdev) and the gate (0: fewer than three correspondences or no inlier, the lane is not refined).  One workgroup per lane.
 __global__ __launch_bounds__(1024) void k_reloc_problem_b(const RelocLane* __restrict__ lanes) {
@@ -679,10 +639,6 @@ __device__ __forceinline__ void reloc_velocity_body(const double* __restrict__ T
     }
 }
 
-__global__ __launch_bounds__(64) void k_reloc_velocity(const double* __restrict__ Tcw, const double* __restrict__ pim, const double* __restrict__ pred,
-                                                       double* __restrict__ out) {
-    reloc_velocity_body(Tcw, pim, pred, out);
-}
 // One wave per lane, after k_reloc_inframe_b.  A lane without a pre-integrated bucket (phase 1) leaves at once; the pre-integration's
 // status goes to the summary whatever the relocalisation gave; the rule runs behind the success word k_reloc_inframe_b tests.
 __global__ __launch_bounds__(64) void k_reloc_velocity_b(const RelocLane* __restrict__ lanes) {
@@ -700,9 +656,8 @@ __global__ __launch_bounds__(64) void k_reloc_velocity_b(const RelocLane* __rest
 
 using namespace vslam;
 
-vslam_status vslam_matcher::ensure_reloc_cap(int n, bool uploads) {
-    if (!d_rlKeyWin) {
-        VS_HIP(poison_malloc(&d_rlKeyWin, (size_t)RELOC_MAX_KEYS * sizeof(unsigned long long)));
+vslam_status vslam_matcher::ensure_reloc_cap(int n) {
+    if (!d_rlKeyWinner) {
         VS_HIP(poison_malloc(&d_rlKeyWinner, (size_t)RELOC_MAX_KEYS * sizeof(int)));
         VS_HIP(poison_malloc(&d_rlRec, (size_t)RELOC_MAX_KEYS * sizeof(RelocRec)));
         VS_HIP(poison_malloc(&d_rlFlags, (size_t)RELOC_MAX_KEYS));
@@ -710,20 +665,13 @@ vslam_status vslam_matcher::ensure_reloc_cap(int n, bool uploads) {
         VS_HIP(poison_malloc(&d_rlPoses, (size_t)RELOC_MAX_HYP * 12 * sizeof(double)));
         VS_HIP(poison_malloc(&d_rlOut, 20 * sizeof(double)));
     }
-    const int cap2 = vslam::align_up(std::max(n, 1), 1024);
-    if (n > rlDCap) {
+    if (n > rlDCap) {                                  // (map points, pairs and key winners live in the call's upload / download blocks)
         hipFree(d_rlD);
         d_rlD = nullptr; rlDCap = 0;
+        const int cap2 = vslam::align_up(std::max(n, 1), 1024);
         VS_HIP(poison_malloc(&d_rlD, (size_t)cap2 * 3 * sizeof(int)));
         rlDCap = cap2;
     }
-    if (!uploads || n <= rlCap) return VSLAM_OK;     // (the batched call keeps map points and pairs in its own blocks)
-    hipFree(d_rlPts); hipFree(d_rlDesc); hipFree(d_rlPairs);
-    d_rlPts = nullptr; d_rlDesc = nullptr; d_rlPairs = nullptr; rlCap = 0;
-    VS_HIP(poison_malloc(&d_rlPts, (size_t)cap2 * 3 * sizeof(double)));
-    VS_HIP(poison_malloc(&d_rlDesc, (size_t)cap2 * 32));
-    VS_HIP(poison_malloc(&d_rlPairs, (size_t)cap2 * sizeof(int)));
-    rlCap = cap2;
     return VSLAM_OK;
 }
 
@@ -747,93 +695,6 @@ vslam_status vslam::reloc_resolve_params(const vslam_reloc_params* prm, vslam_re
     return VSLAM_OK;
 }
 
-vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
-                                       int32_t* pairsOut, vslam_reloc_report* rep) {
-    if (n < 0 || (n > 0 && (!xyz || !desc)) || !T_cw_out || !rep) { set_error("relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
-    if (mono) { set_error("relocalize on a mono matcher"); return VSLAM_ERR_INVALID; }
-    vslam_reloc_params P;
-    VS_CHECK(reloc_resolve_params(prm, P));
-    if (!stereoDone) { set_error("relocalize needs a completed stereo match"); return VSLAM_ERR_INVALID; }
-    if (n > RELOC_MAX_POINTS) { set_error("relocalize: %d map points exceed the limit (%d)", n, RELOC_MAX_POINTS); return VSLAM_ERR_CAPACITY; }
-    VS_HIP(hipSetDevice(device));
-    const int H = P.n_hypotheses;
-    int nL = 0;
-    {
-        UseMark mark{this};
-        VS_CHECK(refresh_keys());
-        nL = nKeys[0];
-        if (nL > RELOC_MAX_KEYS) { set_error("relocalize: %d left keypoints exceed the limit (%d)", nL, RELOC_MAX_KEYS); return VSLAM_ERR_CAPACITY; }
-        VS_CHECK(ensure_reloc_cap(n));
-        *rep = vslam_reloc_report{};
-        rep->n_points = n;
-        rlLast[0] = n; rlLast[1] = nL; rlLast[2] = H; rlLast[3] = 0;
-        if (n) {
-            VS_HIP(hipMemcpyAsync(d_rlPts, xyz, (size_t)n * 24, hipMemcpyHostToDevice, stream));
-            VS_HIP(hipMemcpyAsync(d_rlDesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, stream));
-            VS_HIP(hipMemsetAsync(d_rlPairs, 0xFF, (size_t)n * sizeof(int), stream));
-        }
-        if (nL) VS_HIP(hipMemsetAsync(d_rlKeyWin, 0xFF, (size_t)nL * sizeof(unsigned long long), stream));
-        PoseArgs A{};
-        A.fx = rig.fx; A.fy = rig.fy; A.cx = rig.cx; A.cy = rig.cy; A.b = (double)rig.baseline; A.thres = 7.815;
-        for (int l = 0; l < feL->nLevels; l++) A.invSigma[l] = feL->InvSigmaFactor[l];
-        int* outI = (int*)(d_rlOut + 16);
-        int t = timer.begin("reloc_match");
-        if (n) hipLaunchKernelGGL(k_reloc_match, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const uint4*)d_rlDesc, nL, (const uint4*)d_desc[0],
-                                  P.max_hamming, P.ratio_pct, d_rlD, d_rlKeyWin);
-        timer.end(t);
-        t = timer.begin("reloc_pairs");
-        hipLaunchKernelGGL(P.mode ? k_reloc_pairs_p3p : k_reloc_pairs, dim3(1), dim3(1024), 0, stream, nL, d_rlKeyWin, d_kps[0], d_kps[1], d_depth,
-                           d_rightIdxs, d_rlPts, rig.fx, rig.fy, rig.cx, rig.cy, (RelocRec*)d_rlRec, d_rlPairs, d_rlKeyWinner, outI);
-        timer.end(t);
-        t = timer.begin("reloc_ransac");
-        hipLaunchKernelGGL(P.mode ? k_reloc_ransac_p3p : k_reloc_ransac, dim3(H), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, outI, P.seed,
-                           d_rlCounts, d_rlPoses);
-        hipLaunchKernelGGL(P.mode ? k_reloc_best_p3p : k_reloc_best, dim3(1), dim3(64), 0, stream, A, (const RelocRec*)d_rlRec, H, d_rlCounts,
-                           d_rlPoses, d_rlOut, d_rlFlags);
-        timer.end(t);
-        VS_HIP(hipGetLastError());
-        // one download block: out (T_cw, ints) | records | rightIdxs | flags
-        const size_t oRec = 20 * sizeof(double), oRi = oRec + (size_t)nL * sizeof(RelocRec), oFl = oRi + (size_t)nL * sizeof(int);
-        rlHost.resize(oFl + (size_t)nL + 8);
-        VS_HIP(hipMemcpyAsync(rlHost.data(), d_rlOut, 20 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (nL) {
-            VS_HIP(hipMemcpyAsync(rlHost.data() + oRec, d_rlRec, (size_t)nL * sizeof(RelocRec), hipMemcpyDeviceToHost, stream));
-            VS_HIP(hipMemcpyAsync(rlHost.data() + oRi, d_rightIdxs, (size_t)nL * sizeof(int), hipMemcpyDeviceToHost, stream));
-            VS_HIP(hipMemcpyAsync(rlHost.data() + oFl, d_rlFlags, (size_t)nL, hipMemcpyDeviceToHost, stream));
-        }
-        if (pairsOut && n) VS_HIP(hipMemcpyAsync(pairsOut, d_rlPairs, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream));
-        VS_HIP(hipStreamSynchronize(stream));
-    }
-    const double* hT = (const double*)rlHost.data();
-    const int* hI = (const int*)(rlHost.data() + 16 * sizeof(double));
-    const RelocRec* hRec = (const RelocRec*)(rlHost.data() + 20 * sizeof(double));
-    const int* rIdx = (const int*)(hRec + nL);
-    const uint8_t* hFl = (const uint8_t*)(rIdx + nL);
-    const int C = hI[0];
-    rlLast[3] = C;
-    rep->n_pairs = C; rep->best_hypothesis = hI[1]; rep->best_count = hI[2];
-    if (C < 3 || hI[2] <= 0) return VSLAM_OK;               // success = 0
-    // ---- refinement: the winner's inliers, in correspondence order, through the motion-only LM -----------------------------------
-    std::vector<double> pts; std::vector<int> mt;
-    for (int c = 0; c < C; c++) {
-        if (!hFl[c]) continue;
-        pts.insert(pts.end(), hRec[c].Xw, hRec[c].Xw + 3);
-        mt.push_back(hRec[c].i); mt.push_back(rIdx[hRec[c].i]);
-    }
-    const int M = (int)mt.size() / 2;
-    std::vector<uint8_t> ones((size_t)M, 1), zeros((size_t)M, 0), outl((size_t)M, 0);
-    vslam_pose_problem prob{};
-    prob.n_mps = M; prob.points_xyz = pts.data(); prob.in_frame = ones.data(); prob.in_frame_r = ones.data();
-    prob.mp_is_outlier = zeros.data(); prob.matches = mt.data(); prob.mps_outliers = outl.data();
-    memcpy(prob.T_cw, hT, 16 * sizeof(double));
-    int nIn = 0, nSt = 0;
-    VS_CHECK(estimate_pose(&prob, &nIn, &nSt, &rep->lm));
-    rep->n_inliers = nIn; rep->n_stereo = nSt;
-    rep->success = nIn >= P.min_inliers ? 1 : 0;
-    if (rep->success) memcpy(T_cw_out, prob.T_cw, 16 * sizeof(double));
-    return VSLAM_OK;
-}
-
 vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t* keyWinner, int capKeys, int32_t* counts, int capHyp,
                                              uint8_t* flags, int capPairs, int32_t* sizes4) {
     const int n = rlLast[0], nL = rlLast[1], H = rlLast[2], C = rlLast[3];
@@ -841,7 +702,7 @@ vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t
     if ((d3 && capPoints < n) || (keyWinner && capKeys < nL) || (counts && capHyp < H) || (flags && capPairs < C)) {
         set_error("relocalize_debug: capacity"); return VSLAM_ERR_CAPACITY;
     }
-    if (!d_rlKeyWin) return VSLAM_OK;                       // no call yet: all sizes 0
+    if (!d_rlKeyWinner) return VSLAM_OK;                    // no call yet: all sizes 0
     VS_HIP(hipSetDevice(device));
     if (d3 && n) VS_HIP(hipMemcpyAsync(d3, d_rlD, (size_t)n * 12, hipMemcpyDeviceToHost, stream));
     if (keyWinner && nL) VS_HIP(hipMemcpyAsync(keyWinner, d_rlKeyWinner, (size_t)nL * 4, hipMemcpyDeviceToHost, stream));
@@ -851,7 +712,7 @@ vslam_status vslam_matcher::relocalize_debug(int32_t* d3, int capPoints, int32_t
     return VSLAM_OK;
 }
 
-// ---- the batched call ---------------------------------------------------------------------------------------------------------------
+// ---- the driver of every call: checks, block layout, the stages once for all lanes ------------------------------------------------------
 namespace vslam {
 void launch_pose_batch(hipStream_t s, const PoseLane* dLanes, int B);
 void launch_imu_batch(hipStream_t s, const ImuLane* dLanes, int B);
@@ -859,22 +720,32 @@ void launch_imu_batch(hipStream_t s, const ImuLane* dLanes, int B);
 
 namespace {
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// the subject of a refusal, in the wording of vslam_system::reloc_imu_check: a call of several lanes names the lane, a single call none
+struct RelocWho {
+    char s[48];
+    RelocWho(bool nameLanes, int lane) {
+        if (nameLanes) snprintf(s, sizeof(s), "relocalize_batch: lane %d: ", lane);
+        else snprintf(s, sizeof(s), "relocalize: ");
+    }
+};
 }
 
-vslam_status vslam::reloc_batch_check(const RelocBatchLane* lanes, int B, int device) {
+vslam_status vslam::reloc_batch_check(const RelocBatchLane* lanes, int B, int device, bool nameLanes) {
     for (int b = 0; b < B; b++) {
         const vslam_matcher* m = lanes[b].m;
         if (!m) continue;
-        if (m->mono) { set_error("relocalize_batch: lane %d is a mono matcher", b); return VSLAM_ERR_INVALID; }
-        if (m->device != device) { set_error("relocalize_batch: lane %d is on device %d, the first lane on %d", b, m->device, device); return VSLAM_ERR_INVALID; }
-        if (!m->stereoDone) { set_error("relocalize_batch: lane %d needs a completed stereo match", b); return VSLAM_ERR_INVALID; }
-        if (lanes[b].n < 0) { set_error("relocalize_batch: lane %d: invalid arguments", b); return VSLAM_ERR_INVALID; }
+        const RelocWho who(nameLanes, b);
+        if (m->mono) { set_error("%sa mono matcher", who.s); return VSLAM_ERR_INVALID; }
+        if (m->device != device) { set_error("%sthe matcher is on device %d, the first lane's on %d", who.s, m->device, device); return VSLAM_ERR_INVALID; }
+        if (!m->stereoDone) { set_error("%sa completed stereo match is needed", who.s); return VSLAM_ERR_INVALID; }
+        if (lanes[b].n < 0) { set_error("%sinvalid arguments", who.s); return VSLAM_ERR_INVALID; }
         for (int a = 0; a < b; a++)
             if (lanes[a].m == m) { set_error("relocalize_batch: lanes %d and %d are the same matcher", a, b); return VSLAM_ERR_INVALID; }
     }
     for (int b = 0; b < B; b++)
         if (lanes[b].m && lanes[b].n > RELOC_MAX_POINTS) {
-            set_error("relocalize_batch: lane %d: %d map points exceed the limit (%d)", b, lanes[b].n, RELOC_MAX_POINTS);
+            set_error("%s%d map points exceed the limit (%d)", RelocWho(nameLanes, b).s, lanes[b].n, RELOC_MAX_POINTS);
             return VSLAM_ERR_CAPACITY;
         }
     return VSLAM_OK;
@@ -907,13 +778,8 @@ void vslam::reloc_batch_plan(RelocBatchLane* lanes, int B, RelocBatchPlan& plan)
 }
 
 vslam_status vslam::reloc_batch_run(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
-                                    const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps) {
-    return reloc_batch_run_imu(lanes, B, plan, blk, stream, P, logScale, tm, T_cw_out, reps, nullptr);
-}
-
-vslam_status vslam::reloc_batch_run_imu(RelocBatchLane* lanes, int B, const RelocBatchPlan& plan, const RelocBlocks& blk, hipStream_t stream,
-                                        const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
-                                        vslam_reloc_imu_report* imuReps) {
+                                    const vslam_reloc_params& P, double logScale, StageTimer* tm, double* T_cw_out, vslam_reloc_report* reps,
+                                    vslam_reloc_imu_report* imuReps, bool nameLanes) {
     if (!plan.nOn) return VSLAM_OK;
     if (plan.nImu && !imuReps) { set_error("relocalize_batch: a lane carries an IMU bucket but no report array was given"); return VSLAM_ERR_INVALID; }
     const int H = P.n_hypotheses, nOn = plan.nOn;
@@ -930,14 +796,14 @@ vslam_status vslam::reloc_batch_run_imu(RelocBatchLane* lanes, int B, const Relo
         VS_CHECK(m->refresh_keys(false));
         lanes[b].nL = m->nKeys[0];
         if (lanes[b].nL > RELOC_MAX_KEYS) {
-            set_error("relocalize_batch: lane %d: %d left keypoints exceed the limit (%d)", b, lanes[b].nL, RELOC_MAX_KEYS);
+            set_error("%s%d left keypoints exceed the limit (%d)", RelocWho(nameLanes, b).s, lanes[b].nL, RELOC_MAX_KEYS);
             return VSLAM_ERR_CAPACITY;
         }
     }
     for (int b = 0; b < B; b++) {
         vslam_matcher* m = lanes[b].m;
         if (!m) continue;
-        VS_CHECK(m->ensure_reloc_cap(lanes[b].n, false));
+        VS_CHECK(m->ensure_reloc_cap(lanes[b].n));
         VS_CHECK(m->ensure_pose_cap(std::max(lanes[b].nL, 1)));      // the refinement: at most one factor per left key
         VS_CHECK(m->ensure_proj_cap(std::max(lanes[b].nL, 1)));
     }
@@ -1055,7 +921,7 @@ vslam_status vslam::reloc_batch_run_imu(RelocBatchLane* lanes, int B, const Relo
         }
     }
     if (noFactor >= 0) {
-        set_error("relocalize: lane %d: IMU pre-integration: the 15x15 covariance has no Cholesky factor (no information matrix, no IMU factor)", noFactor);
+        set_error("%sIMU pre-integration: the 15x15 covariance has no Cholesky factor (no information matrix, no IMU factor)", RelocWho(nameLanes, noFactor).s);
         return VSLAM_ERR_INVALID;
     }
     return VSLAM_OK;
@@ -1077,14 +943,13 @@ vslam_status vslam::reloc_own_blocks(vslam_matcher* m, size_t upBytes, size_t dn
     return VSLAM_OK;
 }
 
-// Test taps of the velocity rule: B buckets through ONE k_imu_preintegrate_b launch, then k_reloc_velocity (laneForm false: B = 1, the
-// arguments by value) or ONE k_reloc_velocity_b launch over a RelocLane table whose entries hold what the kernel reads - the pose where
-// step D leaves it, an open gate, the pre-integration's outputs.  Everything lives in one temporary block; the rows of `out` are uploaded
+// Test tap of the velocity rule: B buckets through ONE k_imu_preintegrate_b launch, then ONE k_reloc_velocity_b launch over a RelocLane
+// table whose entries hold what the kernel reads - the pose where step D leaves it, an open gate, the pre-integration's outputs.  Everything lives in one temporary block; the rows of `out` are uploaded
 // first, so an idle lane's row comes back as the caller filled it.
-static vslam_status reinit_velocity_tap(vslam_matcher* m, int B, const vslam_imu_input* imus, const double* Tcw, double* out, bool laneForm) {
-    if (!m || B <= 0 || !imus || !Tcw || !out || (!laneForm && B != 1)) { set_error("IMU velocity tap: invalid arguments"); return VSLAM_ERR_INVALID; }
+static vslam_status reinit_velocity_tap(vslam_matcher* m, int B, const vslam_imu_input* imus, const double* Tcw, double* out) {
+    if (!m || B <= 0 || !imus || !Tcw || !out) { set_error("IMU velocity tap: invalid arguments"); return VSLAM_ERR_INVALID; }
     for (int b = 0; b < B; b++)
-        if (imus[b].n_samples < 0 || (!laneForm && imus[b].n_samples == 0)) { set_error("IMU velocity tap: lane %d: bucket length %d", b, imus[b].n_samples); return VSLAM_ERR_INVALID; }
+        if (imus[b].n_samples < 0) { set_error("IMU velocity tap: lane %d: bucket length %d", b, imus[b].n_samples); return VSLAM_ERR_INVALID; }
     VS_HIP(hipSetDevice(m->device));
     constexpr size_t PD = sizeof(DPim) / sizeof(double), ND = sizeof(DNav) / sizeof(double);
     // per lane (doubles): poseIO 32 | out 20 | pose-kernel ints 2 | summary | DPim | Lam 225 | DNav | status 1 | samples 7 n + 6
@@ -1123,9 +988,7 @@ static vslam_status reinit_velocity_tap(vslam_matcher* m, int B, const vslam_imu
         VS_HIP(hipMemcpyAsync(dR, rl.data(), (size_t)B * sizeof(RelocLane), hipMemcpyHostToDevice, st));
         VS_HIP(hipMemcpyAsync(dI, il.data(), (size_t)B * sizeof(ImuLane), hipMemcpyHostToDevice, st));
         launch_imu_batch(st, dI, B);
-        if (laneForm) hipLaunchKernelGGL(k_reloc_velocity_b, dim3(B), dim3(64), 0, st, (const RelocLane*)dR);
-        else hipLaunchKernelGGL(k_reloc_velocity, dim3(1), dim3(64), 0, st, (const double*)d, (const double*)(d + O_PIM), (const double*)(d + O_PRED),
-                                d + O_SUM + RELOC_SUM_VEL);
+        hipLaunchKernelGGL(k_reloc_velocity_b, dim3(B), dim3(64), 0, st, (const RelocLane*)dR);
         VS_HIP(hipGetLastError());
         VS_HIP(hipMemcpyAsync(h.data(), d, off[B] * sizeof(double), hipMemcpyDeviceToHost, st));
         VS_HIP(hipStreamSynchronize(st));
@@ -1148,14 +1011,58 @@ static vslam_status reinit_velocity_tap(vslam_matcher* m, int B, const vslam_imu
     return VSLAM_OK;
 }
 
+// The host side of vslam_relocalize (one lane, no lane named) and vslam_relocalize_batch: the lanes on the first matcher's own blocks and
+// stream, the maps copied into the pinned block, the one driver, the pairs copied out.  The entries have checked the pointers.
+static vslam_status reloc_run_matchers(vslam_matcher* const* matchers, int B, const double* const* xyz, const uint8_t* const* desc, const int32_t* n,
+                                       const vslam_reloc_params& P, double* T_cw_out, int32_t* const* pairsOut, vslam_reloc_report* reps, bool nameLanes) {
+    std::vector<RelocBatchLane> q((size_t)B);
+    vslam_matcher* first = nullptr;
+    for (int b = 0; b < B; b++) {
+        if (!matchers[b]) continue;
+        q[b].m = matchers[b]; q[b].n = n[b];
+        if (!first) first = matchers[b];
+    }
+    if (!first) return VSLAM_OK;
+    VS_CHECK(reloc_batch_check(q.data(), B, first->device, nameLanes));
+    VS_HIP(hipSetDevice(first->device));
+    for (int b = 0; b < B; b++)                             // work of the other matchers' own streams (key uploads, stereo) ends first
+        if (q[b].m && q[b].m->stream != first->stream) VS_HIP(hipStreamSynchronize(q[b].m->stream));
+    RelocBatchPlan plan;
+    reloc_batch_plan(q.data(), B, plan);
+    VS_CHECK(reloc_own_blocks(first, plan.upBytes, plan.dnBytes));
+    const RelocBlocks blk{first->rlBlk[0], first->rlBlk[1], first->rlBlk[2], first->rlBlk[3]};
+    for (int b = 0; b < B; b++) {
+        if (!q[b].m || q[b].n <= 0) continue;
+        memcpy(blk.h_up + q[b].oXyz, xyz[b], (size_t)q[b].n * 24);
+        memcpy(blk.h_up + q[b].oDesc, desc[b], (size_t)q[b].n * 32);
+    }
+    VS_CHECK(reloc_batch_run(q.data(), B, plan, blk, first->stream, P, 1.0, &first->timer, T_cw_out, reps, nullptr, nameLanes));
+    for (int b = 0; b < B; b++)
+        if (q[b].m && q[b].n > 0 && pairsOut && pairsOut[b]) memcpy(pairsOut[b], blk.h_dn + q[b].oPairs, (size_t)q[b].n * sizeof(int));
+    return VSLAM_OK;
+}
+
+vslam_status vslam_matcher::relocalize(const double* xyz, const uint8_t* desc, int n, const vslam_reloc_params* prm, double* T_cw_out,
+                                       int32_t* pairsOut, vslam_reloc_report* rep) {
+    if (n < 0 || (n > 0 && (!xyz || !desc)) || !T_cw_out || !rep) { set_error("relocalize: invalid arguments"); return VSLAM_ERR_INVALID; }
+    if (mono) { set_error("relocalize on a mono matcher"); return VSLAM_ERR_INVALID; }
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(prm, P));
+    VS_HIP(hipSetDevice(device));
+    UseMark mark{this};
+    vslam_matcher* self = this;
+    return reloc_run_matchers(&self, 1, &xyz, &desc, &n, P, T_cw_out, &pairsOut, rep, false);
+}
+
 extern "C" {
 
 vslam_status vslam_imu_reinit_velocity(vslam_matcher* m, const vslam_imu_input* imu, const double* T_cw_new, double* out) {
-    return reinit_velocity_tap(m, 1, imu, T_cw_new, out, false);
+    if (m && imu && T_cw_new && out && imu->n_samples == 0) { set_error("IMU velocity tap: bucket length 0"); return VSLAM_ERR_INVALID; }
+    return reinit_velocity_tap(m, 1, imu, T_cw_new, out);
 }
 
 vslam_status vslam_imu_reinit_velocity_batch(vslam_matcher* m, int32_t n_lanes, const vslam_imu_input* imus, const double* T_cw_new, double* out) {
-    return reinit_velocity_tap(m, n_lanes, imus, T_cw_new, out, true);
+    return reinit_velocity_tap(m, n_lanes, imus, T_cw_new, out);
 }
 
 vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lanes, const double* const* points_xyz, const uint8_t* const* desc,
@@ -1164,35 +1071,12 @@ vslam_status vslam_relocalize_batch(vslam_matcher* const* matchers, int32_t lane
     if (!matchers || lanes <= 0 || !n_points || !T_cw_out || !reports) { set_error("relocalize_batch: invalid arguments"); return VSLAM_ERR_INVALID; }
     vslam_reloc_params P;
     VS_CHECK(reloc_resolve_params(params, P));
-    std::vector<RelocBatchLane> q((size_t)lanes);
-    vslam_matcher* first = nullptr;
-    for (int b = 0; b < lanes; b++) {
-        if (!matchers[b]) continue;
-        q[b].m = matchers[b]; q[b].n = n_points[b];
-        if (!first) first = matchers[b];
-        if (n_points[b] > 0 && (!points_xyz || !desc || !points_xyz[b] || !desc[b])) {
+    for (int b = 0; b < lanes; b++)
+        if (matchers[b] && n_points[b] > 0 && (!points_xyz || !desc || !points_xyz[b] || !desc[b])) {
             set_error("relocalize_batch: lane %d: invalid arguments", b);
             return VSLAM_ERR_INVALID;
         }
-    }
-    if (!first) return VSLAM_OK;
-    VS_CHECK(reloc_batch_check(q.data(), lanes, first->device));
-    VS_HIP(hipSetDevice(first->device));
-    for (int b = 0; b < lanes; b++)                         // work of the other matchers' own streams (key uploads, stereo) ends first
-        if (q[b].m && q[b].m->stream != first->stream) VS_HIP(hipStreamSynchronize(q[b].m->stream));
-    RelocBatchPlan plan;
-    reloc_batch_plan(q.data(), lanes, plan);
-    VS_CHECK(reloc_own_blocks(first, plan.upBytes, plan.dnBytes));
-    const RelocBlocks blk{first->rlBlk[0], first->rlBlk[1], first->rlBlk[2], first->rlBlk[3]};
-    for (int b = 0; b < lanes; b++) {
-        if (!q[b].m || q[b].n <= 0) continue;
-        memcpy(blk.h_up + q[b].oXyz, points_xyz[b], (size_t)q[b].n * 24);
-        memcpy(blk.h_up + q[b].oDesc, desc[b], (size_t)q[b].n * 32);
-    }
-    VS_CHECK(reloc_batch_run(q.data(), lanes, plan, blk, first->stream, P, 1.0, &first->timer, T_cw_out, reports));
-    for (int b = 0; b < lanes; b++)
-        if (q[b].m && q[b].n > 0 && pairs_out && pairs_out[b]) memcpy(pairs_out[b], blk.h_dn + q[b].oPairs, (size_t)q[b].n * sizeof(int));
-    return VSLAM_OK;
+    return reloc_run_matchers(matchers, lanes, points_xyz, desc, n_points, P, T_cw_out, pairs_out, reports, true);
 }
 
 vslam_status vslam_relocalize(vslam_matcher* m, const double* points_xyz, const uint8_t* desc, int32_t n_points,

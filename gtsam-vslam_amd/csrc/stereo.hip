@@ -554,8 +554,7 @@ void vslam_matcher::release() {
     hipFree(d_mpv); hipFree(d_topk); hipFree(d_matches); hipFree(d_matchedL); hipFree(d_matchedR); hipFree(d_projOut);
     for (int s = 0; s < 2; s++) { hipFree(d_cellStart[s]); hipFree(d_cellIdx[s]); }
     hipFree(d_win); d_win = nullptr; winCap = 0;
-    hipFree(d_rlPts); hipFree(d_rlDesc); hipFree(d_rlD); hipFree(d_rlPairs); hipFree(d_rlKeyWin); hipFree(d_rlKeyWinner);
-    hipFree(d_rlRec); hipFree(d_rlFlags); hipFree(d_rlCounts); hipFree(d_rlPoses); hipFree(d_rlOut);
+    hipFree(d_rlD); hipFree(d_rlKeyWinner); hipFree(d_rlRec); hipFree(d_rlFlags); hipFree(d_rlCounts); hipFree(d_rlPoses); hipFree(d_rlOut);
     if (rlBlk[0]) hipHostFree(rlBlk[0]);
     if (rlBlk[2]) hipHostFree(rlBlk[2]);
     hipFree(rlBlk[1]); hipFree(rlBlk[3]);

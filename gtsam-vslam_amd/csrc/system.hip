@@ -740,8 +740,34 @@ vslam_status vslam_system::track(const uint8_t* L, const uint8_t* R, int stride,
     return frame_post(c, st, T_wc_out, rep);
 }
 
-// Relocalisation (no reference counterpart): the frame's front end as track() runs it, vslam_matcher::relocalize over the
-// session's non-outlier map points, then - on success only - the pose state of a frame tracked with zero predicted motion.
+// Relocalisation (no reference counterpart).  The body of both session calls: the frame's front end as track() runs it, then the session's
+// non-outlier map points as ONE lane through the batched stages (reloc.hip: reloc_batch_run) on the matcher's own blocks and stream - a
+// lane of vslam_batch_relocalize / vslam_batch_relocalize_imu gives this result by construction.  imu: the bucket of a second IMU pose,
+// else null.  inF: per candidate, inside the left image under the refined pose (in the matcher's download block; valid on success).
+vslam_status vslam_system::reloc_run(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
+                                     const vslam_reloc_params& P, double* T_cw, const uint8_t** inF, vslam_reloc_report* rep,
+                                     vslam_reloc_imu_report* irep) {
+    SysFrameCtx& c = ctx;
+    VS_CHECK(frame_begin(c, frame, imu, false));            // (an IMU session's first pose needs no bucket; the second's is checked by the caller)
+    VS_CHECK(frame_mid());
+    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
+    else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
+    VS_CHECK(vslam_extractor_run(fe));
+    VS_CHECK(fm->stereo_match());
+    if (imu) reloc_imu_input(c, imu);
+    RelocBatchLane q;
+    q.m = fm; q.n = reloc_candidates(); q.wantInFrame = true; q.imu = imu ? &c.in : nullptr;
+    RelocBatchPlan plan;
+    reloc_batch_plan(&q, 1, plan);
+    VS_CHECK(reloc_own_blocks(fm, plan.upBytes, plan.dnBytes));
+    const RelocBlocks blk{fm->rlBlk[0], fm->rlBlk[1], fm->rlBlk[2], fm->rlBlk[3]};
+    reloc_fill_upload((double*)(blk.h_up + q.oXyz), blk.h_up + q.oDesc, (float*)(blk.h_up + q.oMsd));
+    VS_CHECK(reloc_batch_check(&q, 1, cfg.device, false));
+    *inF = blk.h_dn + q.oInF;
+    return reloc_batch_run(&q, 1, plan, blk, fm->stream, P, (double)(float)std::log((double)cfg.fe.scale), &fm->timer, T_cw, rep, irep, false);
+}
+
+// On success only: the pose state of a frame tracked with zero predicted motion.
 vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_reloc_params* prm,
                                       double* T_wc_out, vslam_reloc_report* rep) {
     if (!L || !R || !T_wc_out || !rep) return VSLAM_ERR_INVALID;
@@ -751,24 +777,13 @@ vslam_status vslam_system::relocalize(const uint8_t* L, const uint8_t* R, int st
         return VSLAM_ERR_INVALID;
     }
     if (keyFrames.empty()) { set_error("vslam_system_relocalize: the session has no map (track frame 0 first)"); return VSLAM_ERR_INVALID; }
-    SysFrameCtx& c = ctx;
-    VS_CHECK(frame_begin(c, frame, nullptr));
-    VS_CHECK(frame_mid());
-    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
-    else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
-    VS_CHECK(vslam_extractor_run(fe));
-    VS_CHECK(fm->stereo_match());
-    const size_t n = (size_t)reloc_candidates();
-    std::vector<double> xyz(3 * n); std::vector<uint8_t> desc(32 * n); std::vector<float> msd(n);
-    reloc_fill_upload(xyz.data(), desc.data(), msd.data());
-    double T_cw[16];
-    VS_CHECK(fm->relocalize(xyz.data(), desc.data(), (int)n, prm, T_cw, nullptr, rep));
+    vslam_reloc_params P;
+    VS_CHECK(reloc_resolve_params(prm, P));
+    double T_cw[16] = {0};
+    const uint8_t* inF = nullptr;
+    VS_CHECK(reloc_run(L, R, stride, onDevice, frame, nullptr, P, T_cw, &inF, rep, nullptr));
     if (!rep->success) { memcpy(T_wc_out, camPose.data(), sizeof(double) * 16); return VSLAM_OK; }
-    // the map points the new pose places inside the left image
-    std::vector<float> pl(2 * n), pr(2 * n); std::vector<int> ll(n), lr(n); std::vector<uint8_t> inF(n), inFR(n);
-    VS_CHECK(vslam_world_to_frame(fm, T_cw, (int)n, xyz.data(), msd.data(), (float)std::log((double)cfg.fe.scale), pl.data(), pr.data(),
-                                  ll.data(), lr.data(), inF.data(), inFR.data()));
-    reloc_commit(T_cw, inF.data(), T_wc_out);
+    reloc_commit(T_cw, inF, T_wc_out);
     return VSLAM_OK;
 }
 
@@ -796,7 +811,7 @@ void vslam_system::reloc_imu_input(SysFrameCtx& c, const vslam_imu_bucket* imu) 
     for (int k = 0; k < 6; k++) c.in.bias_prev[k] = biasGood[k];
 }
 
-// the outcome of a call on this session.  irep: a phase-2 lane's values from the device (reloc_batch_run_imu), else zero.
+// the outcome of a call on this session.  irep: a phase-2 lane's values from the device (reloc_batch_run), else zero.
 void vslam_system::reloc_imu_finish(const vslam_reloc_report& rep, vslam_reloc_imu_report& irep, const double* T_cw, const uint8_t* inF,
                                     double* T_wc_out) {
     const bool second = relocPending;
@@ -820,35 +835,17 @@ void vslam_system::reloc_imu_finish(const vslam_reloc_report& rep, vslam_reloc_i
     irep.phase = 2;
 }
 
-// One lane through the batched stages (reloc.hip: reloc_batch_run_imu), on the matcher's own blocks and stream: a lane of
-// vslam_batch_relocalize_imu gives this call's result by construction.
 vslam_status vslam_system::relocalize_imu(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
                                           const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* rep, vslam_reloc_imu_report* irep) {
     if (!L || !R || !T_wc_out || !rep || !irep) { set_error("vslam_system_relocalize_imu: invalid arguments"); return VSLAM_ERR_INVALID; }
     VS_CHECK(reloc_imu_check(imu, "vslam_system_relocalize_imu", -1));
     vslam_reloc_params P;
     VS_CHECK(reloc_resolve_params(prm, P));
-    const bool second = relocPending;
-    SysFrameCtx& c = ctx;
-    VS_CHECK(frame_begin(c, frame, second ? imu : nullptr, false));      // (the first pose needs no bucket; the second's was checked above)
-    VS_CHECK(frame_mid());
-    if (onDevice) { VS_CHECK(vslam_extractor_set_image_device(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_device(fe, img0 + 1, R, stride)); }
-    else { VS_CHECK(vslam_extractor_set_image_host(fe, img0, L, stride)); VS_CHECK(vslam_extractor_set_image_host(fe, img0 + 1, R, stride)); }
-    VS_CHECK(vslam_extractor_run(fe));
-    VS_CHECK(fm->stereo_match());
-    if (second) reloc_imu_input(c, imu);
-    RelocBatchLane q;
-    q.m = fm; q.n = reloc_candidates(); q.wantInFrame = true; q.imu = second ? &c.in : nullptr;
-    RelocBatchPlan plan;
-    reloc_batch_plan(&q, 1, plan);
-    VS_CHECK(reloc_own_blocks(fm, plan.upBytes, plan.dnBytes));
-    const RelocBlocks blk{fm->rlBlk[0], fm->rlBlk[1], fm->rlBlk[2], fm->rlBlk[3]};
-    reloc_fill_upload((double*)(blk.h_up + q.oXyz), blk.h_up + q.oDesc, (float*)(blk.h_up + q.oMsd));
-    VS_CHECK(reloc_batch_check(&q, 1, cfg.device));
     double T_cw[16] = {0};
+    const uint8_t* inF = nullptr;
     *irep = vslam_reloc_imu_report{};
-    VS_CHECK(reloc_batch_run_imu(&q, 1, plan, blk, fm->stream, P, (double)(float)std::log((double)cfg.fe.scale), &fm->timer, T_cw, rep, irep));
-    reloc_imu_finish(*rep, *irep, T_cw, blk.h_dn + q.oInF, T_wc_out);
+    VS_CHECK(reloc_run(L, R, stride, onDevice, frame, relocPending ? imu : nullptr, P, T_cw, &inF, rep, irep));
+    reloc_imu_finish(*rep, *irep, T_cw, inF, T_wc_out);
     return VSLAM_OK;
 }
 

@@ -268,6 +268,9 @@ struct vslam_system {
     // relocalisation from the session's own map, without a pose prior (no reference counterpart; vslam_hip.h)
     vslam_status relocalize(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_reloc_params* prm,
                             double* T_wc_out, vslam_reloc_report* rep);
+    // the body it shares with relocalize_imu: the front end and one lane through reloc_batch_run on the matcher's own blocks
+    vslam_status reloc_run(const uint8_t* L, const uint8_t* R, int stride, bool onDevice, int frame, const vslam_imu_bucket* imu,
+                           const vslam_reloc_params& P, double* T_cw, const uint8_t** inF, vslam_reloc_report* rep, vslam_reloc_imu_report* irep);
     // its host steps, shared with vslam_batch_relocalize: the candidate list (returns its size), the upload arrays, the commit of a success
     std::vector<int> rlIds;
     int reloc_candidates();

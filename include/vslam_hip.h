@@ -340,24 +340,25 @@ vslam_status vslam_world_to_frame(vslam_matcher* m, const double* T_cw, int32_t 
  * holds the exact rules, tests/reloc_ref.py restates them on the CPU).  Recovers the pose of the frame the matcher
  * currently holds (a completed vslam_stereo_match: keypoints, descriptors, rightIdxs, estimatedDepth in HBM) from a map,
  * without a pose prior:
- *   A  k_reloc_match: every map point against every left key, 256-bit Hamming.  d1 = smallest distance, i1 = lowest key
+ *   A  k_reloc_match_b: every map point against every left key, 256-bit Hamming.  d1 = smallest distance, i1 = lowest key
  *      index attaining it, d2 = smallest distance over all other keys (257 with a single key).  Point p proposes i1 iff
  *      d1 <= max_hamming and 100 * d1 < ratio_pct * d2; key i goes to the proposer with the smallest (d1 << 32 | p).
- *   B  k_reloc_pairs: winning pairs whose key has estimatedDepth > 0 and rightIdxs >= 0, in ascending key index, as
+ *   B  k_reloc_pairs_b: winning pairs whose key has estimatedDepth > 0 and rightIdxs >= 0, in ascending key index, as
  *      correspondences {X_w, X_c (the key back-projected with its depth), kx, ky, kxr, octave, p, i}; C of them.
  *      C < 3: success = 0, status VSLAM_OK.
- *   C  k_reloc_ransac / k_reloc_best: n_hypotheses poses, each from three correspondences sampled by a counter hash of
+ *   C  k_reloc_ransac_b / k_reloc_best_b: n_hypotheses poses, each from three correspondences sampled by a counter hash of
  *      (seed, hypothesis, draw), built in fp64 from the two point triples' orthonormal frames; scored by the number of
  *      correspondences with z > 0 whose (left u, left v, right u) residual, weighted by the octave's InvSigmaFactor,
  *      passes the chi2 bound 7.815.  The winner is the largest (count << 32 | 0xFFFFFFFF - h).
- *   D  the winner's inliers, in correspondence order, refined by vslam_estimate_pose from the hypothesis;
- *      success = n_inliers >= min_inliers.  T_cw_out is written only on success.
+ *   D  the winner's inliers, in correspondence order, refined from the hypothesis by the pose solve of vslam_estimate_pose
+ *      (the problem is built on the device, k_reloc_problem_b, and solved by the batched pose kernel behind a gate: a winner
+ *      without inliers or C < 3 is not refined); success = n_inliers >= min_inliers.  T_cw_out is written only on success.
  * params->mode = 1 builds the hypotheses from 2D-3D correspondences instead (no stereo depth is read before step D;
  * DESIGN.md section 6 item 22, restated by tests/reloc_p3p_ref.py).  Step A is unchanged; then
- *   B' k_reloc_pairs_p3p: EVERY winning pair, in ascending key index, as correspondences {X_w, y (the key's unit bearing:
+ *   B' k_reloc_pairs_p3p_b: EVERY winning pair, in ascending key index, as correspondences {X_w, y (the key's unit bearing:
  *      ((kx - cx) / fx, (ky - cy) / fy, 1) divided by its norm, fp64), kx, ky, kxr, octave, p, i, stereo}; stereo =
  *      estimatedDepth > 0 && rightIdxs >= 0, kxr is the matched right key's x with the flag and 0 without.  n_pairs = C.
- *   C' k_reloc_ransac_p3p / k_reloc_best_p3p: the sampling of step C; the three (X_w, y) pairs go through a P3P solver (fp64
+ *   C' k_reloc_ransac_p3p_b / k_reloc_best_p3p_b: the sampling of step C; the three (X_w, y) pairs go through a P3P solver (fp64
  *      + - * / and sqrt in a fixed order: a degenerate conic of the pencil of the three distance equations, its real root by
  *      16 Newton steps, two quadratics, 3 Gauss-Newton steps on the depths) that fills up to four solution slots with
  *      camera <- world poses.  A slot is void for collinear world points or coincident bearings (|.|^2 < 1e-12), a
@@ -367,7 +368,9 @@ vslam_status vslam_world_to_frame(vslam_matcher* m, const double* T_cw, int32_t 
  *      the winner is chosen as in step C.
  *   D  as above; a correspondence without a right match enters with matches = (i, -1): a left-only factor.
  * Any other mode: VSLAM_ERR_INVALID, nothing launched.  The mode belongs to the call (one params set per batched call).
- * Everything is enqueued on the matcher's stream; the call waits once before the refinement and once at its end.
+ * The call is the one-lane case of vslam_relocalize_batch below (same driver, same kernels): the map goes up from a pinned
+ * block of the matcher's own (allocated by the first call, grown on demand), everything is enqueued on the matcher's stream,
+ * and the call waits once, at its end.  Its error messages name no lane.
  * n_points <= 65536 and at most 7680 left keys, else VSLAM_ERR_CAPACITY; no completed stereo match, n_hypotheses above
  * 1024 or a negative parameter: VSLAM_ERR_INVALID.  Like vslam_estimate_pose, step D may clear the stereo match of a
  * key whose right observation fails the chi2 test.
@@ -400,10 +403,10 @@ vslam_status vslam_relocalize_debug(vslam_matcher* m, int32_t* d1_i1_d2, int32_t
 /* vslam_relocalize for several matchers ("lanes") in one call: one launch per stage for all of them (k_reloc_match_b,
  * k_reloc_pairs_b, k_reloc_ransac_b, k_reloc_best_b with the lane as a grid dimension and a per-lane argument table), one
  * upload, one download, one wait.  A lane's result IS what vslam_relocalize returns for that matcher, points and parameters,
- * including step D's side effect on its stereo match: the kernels share their bodies with the one-session kernels.  Step D's
- * problem is built on the device (k_reloc_problem_b: the winner's inliers compacted in correspondence order into the lane's
- * pose buffers, with the problem size and a gate word the pose kernel reads there), so that no wait separates steps C and D;
- * a lane with fewer than three correspondences or no inlier is not refined.
+ * including step D's side effect on its stereo match: vslam_relocalize is this call with one lane.  Step D's problem is built
+ * on the device (k_reloc_problem_b: the winner's inliers compacted in correspondence order into the lane's pose buffers, with
+ * the problem size and a gate word the pose kernel reads there), so that no wait separates steps C and D; a lane with fewer
+ * than three correspondences or no inlier is not refined.
  * matchers[b] = NULL: lane b is idle (its report, pairs and T_cw_out row are not written).  Every other matcher must be a
  * different stereo matcher with a completed stereo match, all on one device, else VSLAM_ERR_INVALID; per lane the limits of
  * vslam_relocalize (VSLAM_ERR_CAPACITY); after any error nothing has been launched.  params: one set for all lanes.
@@ -947,12 +950,13 @@ vslam_status vslam_system_track_stereo_raw(vslam_system* sys, const uint8_t* lef
 /* Relocalisation of a stereo session (use_imu = 0; gray frames) from its own map, without a pose prior - for a session whose
  * tracking is lost (fewer than 50 inliers).  No reference counterpart.  The call does what a tracked frame does first
  * (mapping results due at frame_number land, extraction, stereo match), then runs vslam_relocalize over every map point not
- * flagged an outlier, in creation order (the most recent 65536 if there are more).
+ * flagged an outlier, in creation order (the most recent 65536 if there are more) - as one lane of the batched stages, what a
+ * lane of vslam_batch_relocalize runs; params out of range are refused before anything is done.
  * Failure (report->success = 0, VSLAM_OK): nothing else in the session changes, T_wc_out = the unchanged camera pose.
  * Success: the camera pose is the result; the predicted motion is the identity (predNPose = camPose, predNPoseRef = I);
  * camRefPose = lastKFPoseInv * pose; the frame is recorded as addFrame records a non-keyframe frame; activeMapPoints
- * becomes, in creation order, every non-outlier map point that vslam_world_to_frame places inside the left image under the
- * new pose (MapPoint::inFrame follows); the last frame's match tables are cleared; no keyframe is inserted, and the next
+ * becomes, in creation order, every non-outlier map point that the left-camera test of vslam_world_to_frame (run on the
+ * device with the stage, k_reloc_inframe_b) places inside the left image under the new pose (MapPoint::inFrame follows); the last frame's match tables are cleared; no keyframe is inserted, and the next
  * vslam_system_track_stereo proceeds normally.  IMU sessions (their velocity would need re-initialising:
  * vslam_system_relocalize_imu below is their call) and mono sessions: VSLAM_ERR_INVALID with nothing changed. */
 vslam_status vslam_system_relocalize(vslam_system* sys, const uint8_t* left, const uint8_t* right, int32_t stride,
@@ -1067,7 +1071,7 @@ vslam_status vslam_system_map_point_keyframes(vslam_system* sys, int32_t cap, in
 vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
 /* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with
  * the integration bias imu->bias_prev and predicted from (imu->T_wc_prev, v = 0: imu->velocity_prev is not read), then
- * k_reloc_velocity applies the rule to the camera <- world pose T_cw_new[16].  out[8]: dt, velocity_prev[3], velocity[3],
+ * k_reloc_velocity_b applies the rule to the camera <- world pose T_cw_new[16].  out[8]: dt, velocity_prev[3], velocity[3],
  * rot_residual.  Errors as vslam_imu_preintegrate.  Invalidates the matcher's staged IMU bucket. */
 vslam_status vslam_imu_reinit_velocity(vslam_matcher* m, const vslam_imu_input* imu, const double* T_cw_new, double* out);
 /* the same for n_lanes buckets with ONE launch of k_imu_preintegrate_b and ONE of k_reloc_velocity_b; T_cw_new [n_lanes][16],

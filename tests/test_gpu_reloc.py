@@ -3,6 +3,8 @@
 Steps A - C are compared bit for bit through the test tap (vslam_relocalize_debug), the refined pose to 1e-7 as in the
 project's other pose tests.  Crafted frames go through set_keys + vslam_stereo_finalize_arrays (the finalize kernel's 1 %
 nearest-depth cut applies: the tests read the stereo state back and hand exactly that to the restatement)."""
+import hashlib
+import os
 import numpy as np
 import pytest
 import synth
@@ -138,17 +140,22 @@ def test_limits_and_arguments(capi, crafted):
     m, _ = crafted
     g = matching_scene(4, 8, 3)
     load_frame(m, g["kL"], g["dL"], g["kR"], g["dR"], g["best"], g["depth"], g["sad"])
+    texts = []
     with pytest.raises(capi.VslamError) as e:
         m.relocalize(np.zeros((65537, 3)), np.zeros((65537, 32), np.uint8))
     assert e.value.status == capi.ERR_CAPACITY
+    texts.append(str(e.value))
     with pytest.raises(capi.VslamError) as e:
         m.relocalize(g["points"], g["desc"], n_hypotheses=1025)
     assert e.value.status == capi.ERR_INVALID
+    texts.append(str(e.value))
     ge = capi.Extractor(RIG["w"], RIG["h"], 1500, batch=2)
     fresh = capi.Matcher(RIG, ge, 0, ge, 1)                    # no completed stereo match
     with pytest.raises(capi.VslamError) as e:
         fresh.relocalize(g["points"], g["desc"])
     assert e.value.status == capi.ERR_INVALID
+    texts.append(str(e.value))
+    assert not any("lane" in t for t in texts), texts          # the single call is one lane of the batched driver and names none
 
 
 # ---- step C: hypotheses ----------------------------------------------------------------------------------------------------
@@ -222,6 +229,62 @@ def test_points_behind_the_camera_do_not_count(capi, oracle, crafted):
     # without the z test they would all count: their weighted residual under the true pose is far below the bound
     _, val = rr.chi2_values(rec, R, t, RIG, inv_sigma)
     assert (val[behind] < 1e-3).all()
+
+
+# ---- the single call against what it returned before it became the one-lane case of the batched driver ---------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reloc_single.npz")
+# name -> (generator, its arguments): hypothesis_case in mode 0, reloc_p3p_cases.find_case in mode 1, matching_scene (N, nL)
+RECORDED = {"pose_C2": ("pose", 2), "pose_C3": ("pose", 3), "mirror_C65": ("mirror", 65), "pose_C200": ("pose", 200),
+            "p3p_C200": ("p3p", 200), "p3p_C2": ("p3p", 2),
+            "match_0_2049": ("match", 0, 2049), "match_300_0": ("match", 300, 0), "match_1_1": ("match", 1, 1), "match_257_2047": ("match", 257, 2047)}
+FRAME_ARRAYS = ("kL", "dL", "kR", "dR", "best", "depth", "sad", "points", "desc")
+REPORT_INTS = ("success", "n_points", "n_pairs", "best_hypothesis", "best_count", "n_inliers", "n_stereo")
+
+
+def recorded_case(name, m, oracle, inv_sigma):
+    """one case of tests/golden/reloc_single.npz run on matcher m: what make_reloc_single.py stored and what the test compares.
+    ints: the report's integer fields, lm.iterations, lm.inner, whether a pose was returned; f64: the pose (zeros without one),
+    lm.initialError, lm.finalError, lm.lam; sha: a checksum of the frame and the map the generator built"""
+    kind, args = RECORDED[name][0], RECORDED[name][1:]
+    if kind == "match":
+        N, nL = args
+        g = matching_scene(N, nL, 1000 * N + nL)
+        load_frame(m, g["kL"], g["dL"], g["kR"], g["dR"], g["best"], g["depth"], g["sad"])
+        T, rep, pairs = m.relocalize(g["points"], g["desc"], n_hypotheses=4)
+    elif kind == "p3p":
+        import reloc_p3p_cases as pc
+        g, st, _ = pc.find_case(oracle, inv_sigma, C=args[0])
+        load_frame(m, g["kL"], g["dL"], g["kR"], g["dR"], g["best"], g["depth"], g["sad"])
+        T, rep, pairs = m.relocalize(g["points"], g["desc"], mode=1)
+    else:
+        g, _, T, rep, pairs, _ = hypothesis_case(m, oracle, inv_sigma, args[0], mode=kind)
+    dbg = m.relocalize_debug()
+    sha = hashlib.sha256()
+    for f in FRAME_ARRAYS:
+        sha.update(np.ascontiguousarray(g[f]).tobytes())
+    lm = rep["lm"]
+    out = dict(ints=np.array([rep[f] for f in REPORT_INTS] + [lm["iterations"], lm["inner"], int(T is not None)], np.int32),
+               f64=np.concatenate([(T if T is not None else np.zeros((4, 4))).ravel(), [lm["initialError"], lm["finalError"], lm["lam"]]]),
+               pairs=pairs, sha=np.frombuffer(sha.digest(), np.uint8))
+    out.update(dbg)
+    return out
+
+
+@pytest.mark.parametrize("name", list(RECORDED))
+def test_single_call_returns_recorded_results(capi, oracle, crafted, name):
+    """vslam_relocalize against tests/golden/reloc_single.npz: what the call returned on an MI355X at commit 85824ca, the last one
+    where it had its own by-value kernels, its own host loop and the host-built refinement problem (make_reloc_single.py).
+    Integers, pairs, the four tap arrays, the pose and the three LM doubles byte for byte: the bound between the two drivers was
+    1e-12 max(1, |x|) (test_gpu_reloc_batch.py, test_gpu_reloc_p3p.py), the difference seen on every case here was zero
+    (profiles/README.md), so the bytes are held."""
+    m, inv_sigma = crafted
+    got = recorded_case(name, m, oracle, inv_sigma)
+    with np.load(GOLDEN) as z:
+        want = {k: z[name + "/" + k] for k in got}
+    assert np.array_equal(got["sha"], want["sha"]), "the seeded generator of this case no longer builds the recorded inputs"
+    for k in ("ints", "pairs", "d", "key_winner", "counts", "flags", "f64"):
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert got[k].tobytes() == want[k].tobytes(), (k, np.abs(got[k].astype(np.float64) - want[k]).max() if got[k].size else 0)
 
 
 # ---- the whole stage on rendered frames ------------------------------------------------------------------------------------
