@@ -152,9 +152,11 @@ __global__ __launch_bounds__(256) void k_np_match(const NpArgs* __restrict__ tab
 #pragma unroll
     for (int l = 0; l < MAX_LEVELS; l++) S.scalePyr[l] = A.scalePyr[l];
     S.xMult = A.xMult; S.yMult = A.yMult; S.xGrids = A.xGrids; S.yGrids = A.yGrids; S.mode = PROJ_STEREO;
-    unsigned long long l2[2] = {KEY_NONE, KEY_NONE}, r2[2] = {KEY_NONE, KEY_NONE};
-    if (hasL && pLx > 0 && pLy > 0) scan_side<2>(S, 0, md, pLx, pLy, predScale, K.unF, l2);
-    if (hasR && pRx > 0 && pRy > 0) scan_side<2>(S, 1, md, pRx, pRy, predScale, K.unFR, r2);
+    unsigned long long lsel = KEY_NONE, rsel = KEY_NONE;      // lane 0 / 1: best / second key of the side
+    if (hasL && pLx > 0 && pLy > 0) scan_side<2>(S, 0, md, pLx, pLy, predScale, K.unF, lsel);
+    if (hasR && pRx > 0 && pRy > 0) scan_side<2>(S, 1, md, pRx, pRy, predScale, K.unFR, rsel);
+    const unsigned long long l2[2] = {wave_read_u64(lsel, 0), wave_read_u64(lsel, 1)};
+    const unsigned long long r2[2] = {wave_read_u64(rsel, 0), wave_read_u64(rsel, 1)};
     if (lane == 0) {
         const int matchDistLBA = 50;         // include/FeatureMatcher.h:29
         const float ratioLBA = 0.6f;         // :30

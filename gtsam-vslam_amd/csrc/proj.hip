@@ -83,7 +83,7 @@ void launch_proj_cells(hipStream_t s, const ProjArgs& A) {
 
 __device__ __forceinline__ void proj_candidates_body(const ProjArgs& A, const int* __restrict__ matches,
                                                      unsigned long long* __restrict__ topk,
-                                                     unsigned long long* __restrict__ stats) {
+                                                     unsigned long long* __restrict__ stats, int sparse) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (the map point is wave-uniform: scalar loads / SGPRs)
     const int job = blockIdx.x * 4 + wave;      // job = mp * 2 + side
@@ -96,9 +96,7 @@ __device__ __forceinline__ void proj_candidates_body(const ProjArgs& A, const in
     int tests = 0;
     if (job < 2 * M) {
         const int i = job >> 1, side = job & 1;
-        unsigned long long out[PROJ_K];
-#pragma unroll
-        for (int j = 0; j < PROJ_K; j++) out[j] = KEY_NONE;
+        unsigned long long sel = KEY_NONE;          // lane r < PROJ_K: the key of rank r
         const vslam_mappoint_view* mp = A.mpv + i;
         const bool skip = matches[2 * i] >= 0 || matches[2 * i + 1] >= 0;
         const bool inF = side ? (A.mode == PROJ_STEREO && mp->in_frame_r) : mp->in_frame;
@@ -107,14 +105,15 @@ __device__ __forceinline__ void proj_candidates_body(const ProjArgs& A, const in
             load_mp_desc(mp, md);
             const float px = side ? mp->pred_rx : mp->pred_lx, py = side ? mp->pred_ry : mp->pred_ly;
             const int ps = side ? mp->scale_level_r : mp->scale_level_l;
-            tests = scan_side<PROJ_K>(A, side, md, px, py, ps, nullptr, out);
+#ifdef VSLAM_PROJ_HIST
+            int visited = 0;
+            tests = scan_side<PROJ_K>(A, side, md, px, py, ps, nullptr, sel, sparse != 0, &visited);
+            proj_hist_add(visited, tests);
+#else
+            tests = scan_side<PROJ_K>(A, side, md, px, py, ps, nullptr, sel, sparse != 0);
+#endif
         }
-        if (lane < PROJ_K) {
-            unsigned long long v = out[0];
-#pragma unroll
-            for (int j = 1; j < PROJ_K; j++) v = lane == j ? out[j] : v;
-            topk[(size_t)job * PROJ_K + lane] = v;
-        }
+        if (lane < PROJ_K) topk[(size_t)job * PROJ_K + lane] = sel;
     }
     if (lane == 0 && tests) atomicAdd(&sTests, (unsigned int)tests);
     __syncthreads();
@@ -122,20 +121,31 @@ __device__ __forceinline__ void proj_candidates_body(const ProjArgs& A, const in
 }
 
 __global__ __launch_bounds__(256) void k_proj_candidates(ProjArgs A, const int* __restrict__ matches, unsigned long long* __restrict__ topk,
-                                                         unsigned long long* __restrict__ stats) {
-    proj_candidates_body(A, matches, topk, stats);
+                                                         unsigned long long* __restrict__ stats, int sparse) {
+    proj_candidates_body(A, matches, topk, stats, sparse);
 }
 // batched form: blockIdx.y = lane
-__global__ __launch_bounds__(256) void k_proj_candidates_b(const ProjLane* __restrict__ lanes) {
+__global__ __launch_bounds__(256) void k_proj_candidates_b(const ProjLane* __restrict__ lanes, int sparse) {
     const ProjLane& L = *lane_entry(lanes, blockIdx.y);
     if ((int)(blockIdx.x * 4) >= 2 * L.A.M) return;
-    proj_candidates_body(L.A, L.matches, L.topk, L.stats);
+    proj_candidates_body(L.A, L.matches, L.topk, L.stats, sparse);
 }
+
+// VSLAM_PROJ_SELECT=0: every window takes scan_side's general selection (per-lane sorted lists, wave-wide merges) - A/B and
+// tests of both paths in one build (read per launch)
+static int proj_select() {
+    const char* e = getenv("VSLAM_PROJ_SELECT");
+    return (e && e[0] == '0') ? 0 : 1;
+}
+
+// k_proj_resolve's developer switches (read per launch): bit 0 VSLAM_PROJ_SEQUENTIAL (sequential walk only), bit 1 the selection.
+// ONE argument: with a third int the compiler reserved scratch for the SGPR spills of k_proj_resolve (tests/test_abi.py).
+static int proj_resolve_flags() { return (getenv("VSLAM_PROJ_SEQUENTIAL") ? 1 : 0) | (proj_select() << 1); }
 
 void launch_proj_candidates(hipStream_t s, const ProjArgs& A, const int* matches,
                             unsigned long long* topk, unsigned long long* stats) {
     if (A.M <= 0) return;
-    hipLaunchKernelGGL(k_proj_candidates, dim3((2 * A.M + 3) / 4), dim3(256), 0, s, A, matches, topk, stats);
+    hipLaunchKernelGGL(k_proj_candidates, dim3((2 * A.M + 3) / 4), dim3(256), 0, s, A, matches, topk, stats, proj_select());
 }
 
 // The accept rule of the reference scan given the first / second unclaimed key of each side
@@ -191,7 +201,8 @@ __device__ __forceinline__ void lds_order() { asm volatile("s_waitcnt lgkmcnt(0)
 
 __device__ __forceinline__ void proj_resolve_body(const ProjArgs& A, const unsigned long long* __restrict__ topk,
                                                   int* __restrict__ matchedL, int* __restrict__ matchedR,
-                                                  int* __restrict__ matches, int* __restrict__ outp, int forceSeq, int superN) {
+                                                  int* __restrict__ matches, int* __restrict__ outp, int flags, int superN) {
+    const int forceSeq = flags & 1, sparse = (flags >> 1) & 1;      // proj_resolve_flags
     extern __shared__ int claims[];
     int* cl = claims;
     int* cr = claims + A.n[0];
@@ -427,12 +438,12 @@ __device__ __forceinline__ void proj_resolve_body(const ProjArgs& A, const unsig
                         const vslam_mappoint_view* mp = A.mpv + i;
                         uint32_t md[8];
                         load_mp_desc(mp, md);
-                        unsigned long long o2k[2] = {KEY_NONE, KEY_NONE};
+                        unsigned long long o2k = KEY_NONE;      // lane 0 / 1: first / second unclaimed key
                         const float px = s ? mp->pred_rx : mp->pred_lx, py = s ? mp->pred_ry : mp->pred_ly;
                         const int ps = s ? mp->scale_level_r : mp->scale_level_l;
-                        scan_side<2>(A, s, md, px, py, ps, s ? cr : cl, o2k);
-                        b1k[s] = o2k[0];
-                        b2k[s] = o2k[1];
+                        scan_side<2>(A, s, md, px, py, ps, s ? cr : cl, o2k, sparse != 0);
+                        b1k[s] = wave_read_u64(o2k, 0);
+                        b2k[s] = wave_read_u64(o2k, 1);
                     } else {
                         int l1 = -1, l2 = -1;
                         if (fmm) { l1 = __ffs(fmm) - 1; fmm &= fmm - 1; }
@@ -471,13 +482,13 @@ __device__ __forceinline__ void proj_resolve_body(const ProjArgs& A, const unsig
 }
 
 __global__ __launch_bounds__(PROJ_NT) void k_proj_resolve(ProjArgs A, const unsigned long long* __restrict__ topk, int* __restrict__ matchedL,
-                                                     int* __restrict__ matchedR, int* __restrict__ matches, int* __restrict__ outp, int forceSeq, int superN) {
-    proj_resolve_body(A, topk, matchedL, matchedR, matches, outp, forceSeq, superN);
+                                                     int* __restrict__ matchedR, int* __restrict__ matches, int* __restrict__ outp, int flags, int superN) {
+    proj_resolve_body(A, topk, matchedL, matchedR, matches, outp, flags, superN);
 }
 // batched form: blockIdx.x = lane
-__global__ __launch_bounds__(PROJ_NT) void k_proj_resolve_b(const ProjLane* __restrict__ lanes, int forceSeq, int superN) {
+__global__ __launch_bounds__(PROJ_NT) void k_proj_resolve_b(const ProjLane* __restrict__ lanes, int flags, int superN) {
     const ProjLane& L = *lane_entry(lanes, blockIdx.x);
-    proj_resolve_body(L.A, L.topk, L.matchedL, L.matchedR, L.matches, L.out, forceSeq, superN);
+    proj_resolve_body(L.A, L.topk, L.matchedL, L.matchedR, L.matches, L.out, flags, superN);
 }
 
 static size_t proj_resolve_lds(int nL, int nR, int superN) {
@@ -502,7 +513,7 @@ static void proj_attrs() {
 void launch_proj_batch(hipStream_t s, const ProjLane* dLanes, int B, int maxM, int maxL, int maxR, StageTimer* tm, bool buildCells) {
     if (B <= 0 || maxM <= 0) return;
     proj_attrs();
-    const int forceSeq = getenv("VSLAM_PROJ_SEQUENTIAL") ? 1 : 0;
+    const int sparse = proj_select();
     int t = -1;
     if (buildCells) {       // (the refinement pass of a frame matches against the same keys: the first pass's buckets stand)
         t = tm ? tm->begin("proj_cells") : -1;
@@ -510,10 +521,10 @@ void launch_proj_batch(hipStream_t s, const ProjLane* dLanes, int B, int maxM, i
         if (tm) tm->end(t);
     }
     t = tm ? tm->begin("proj_candidates") : -1;
-    hipLaunchKernelGGL(k_proj_candidates_b, dim3((2 * maxM + 3) / 4, B), dim3(256), 0, s, dLanes);
+    hipLaunchKernelGGL(k_proj_candidates_b, dim3((2 * maxM + 3) / 4, B), dim3(256), 0, s, dLanes, sparse);
     if (tm) { tm->end(t); t = tm->begin("proj_resolve"); }
     const int sp = proj_super(maxL, maxR);
-    hipLaunchKernelGGL(k_proj_resolve_b, dim3(B), dim3(PROJ_NT), proj_resolve_lds(maxL, maxR, sp), s, dLanes, forceSeq, sp);
+    hipLaunchKernelGGL(k_proj_resolve_b, dim3(B), dim3(PROJ_NT), proj_resolve_lds(maxL, maxR, sp), s, dLanes, proj_resolve_flags(), sp);
     if (tm) tm->end(t);
 }
 
@@ -522,8 +533,7 @@ void launch_proj_resolve(hipStream_t s, const ProjArgs& A, const unsigned long l
     const int sp = proj_super(A.n[0], A.n[1]);
     const size_t sh = proj_resolve_lds(A.n[0], A.n[1], sp);
     proj_attrs();
-    const int forceSeq = getenv("VSLAM_PROJ_SEQUENTIAL") ? 1 : 0;     // A/B and fallback testing (read per launch)
-    hipLaunchKernelGGL(k_proj_resolve, dim3(1), dim3(PROJ_NT), sh, s, A, topk, matchedL, matchedR, matches, out, forceSeq, sp);
+    hipLaunchKernelGGL(k_proj_resolve, dim3(1), dim3(PROJ_NT), sh, s, A, topk, matchedL, matchedR, matches, out, proj_resolve_flags(), sp);
 #ifdef VSLAM_PROJ_STAMPS
     { int o[2]; (void)hipStreamSynchronize(s); (void)hipMemcpy(o, out, sizeof(o), hipMemcpyDeviceToHost); fprintf(stderr, "proj_resolve: matches %d, fixed-point rounds %d (-1 = sequential walk)\n", o[0], o[1]); }
 #endif
@@ -532,6 +542,16 @@ void launch_proj_resolve(hipStream_t s, const ProjArgs& A, const unsigned long l
 }  // namespace vslam
 
 using namespace vslam;
+
+#ifdef VSLAM_PROJ_HIST
+// out[2][66]: jobs of k_proj_candidates(_b) so far by keys visited / Hamming tests (index 65: more than 64)
+extern "C" vslam_status vslam_debug_proj_hist(unsigned long long* out) {
+    if (!out) return VSLAM_ERR_INVALID;
+    VS_HIP(hipDeviceSynchronize());
+    VS_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_projHist), sizeof(unsigned long long) * 2 * 66));
+    return VSLAM_OK;
+}
+#endif
 
 vslam_status vslam_matcher::ensure_proj_cap(int M) {
     if (M <= projCap && d_matchedL && d_projOut) return VSLAM_OK;
@@ -761,7 +781,7 @@ vslam_status vslam_matcher::match_radius_window(const void* lastKeys, int nLast,
     proj_attrs();
     if (lanes[0].A.cellStart[0])
         hipLaunchKernelGGL(k_proj_cells_b, dim3(1, nTargets), dim3(PROJ_CELLS_NT), (size_t)PROJ_MAX_CELLS * sizeof(int), stream, dLanes);
-    hipLaunchKernelGGL(k_proj_candidates_b, dim3((2 * nLast + 3) / 4, nTargets), dim3(256), 0, stream, dLanes);
+    hipLaunchKernelGGL(k_proj_candidates_b, dim3((2 * nLast + 3) / 4, nTargets), dim3(256), 0, stream, dLanes, proj_select());
     for (int t = 0; t < nTargets; t++)          // in list order, the claim table carried from target to target
         launch_proj_resolve(stream, lanes[t].A, lanes[t].topk, tab, tab, lanes[t].matches, lanes[t].out);
     VS_HIP(hipGetLastError());
