@@ -27,72 +27,17 @@
 #include "dmath.hpp"
 #include "ba_pool.hpp"
 #include "ba_packed.hpp"
+#include "ba_types.hpp"           // argument blocks, control block, launch constants
+#include "ba_order_host.hpp"      // host: ordering, membership, second-pass statistics, reports
+#include "ba_plan.hpp"            // host: launch geometry
 #include <algorithm>
 #include <cmath>
-#include <numeric>
 #include <vector>
-#include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
 
 namespace vslam {
 
-struct BaEdge {
-    int a, b, fa, fb;
-    DPose measured;
-    double r[6], Ja[36], Jb[36];
-    double Haa[36], Hab[36], Hbb[36], ga[6], gb[6];   // Ja^T Ja, Ja^T Jb, Jb^T Jb, Ja^T r, Jb^T r (filled at linearisation)
-};
-
-struct BaDev {
-    int NF, Lp, F, K, NE, n;
-    const int* facKf; const int* facFi; const int* facLp; const int* facLm;
-    const double* facZ; const double* facIs; const uint8_t* facRight;
-    double* facJ;
-    const int* lpStart; const int* lpSlotStart; const int* slotStart; const int* slotFi; const int* lpOrig;
-    DPose* poseCur; DPose* poseTrial; const int* fidx;
-    double* lmCur; double* lmTrial;
-    BaEdge* edges;
-    double* S; double* rhs; double* Spart; double* Sedge; double* dP; double* dL;
-    double* sums; double* partial;
-    int* flags;
-    double fx, fy, cx, cy, b;
-    double* ctl;      // device-side LM state (below)
-    // ---- lambda look-ahead + speculative linearisation (single GPU) --------------------------------------
-    // One "trial" launch evaluates NB candidates lambda, 10 lambda, 100 lambda ... at once (grid dimension y / z /
-    // x of the per-trial kernels); the control step then walks them in order exactly as the sequential policy
-    // would (the outcome of a rejected trial only changes lambda), so the result is bit-identical to NB = 1
-    // while a chain of rejections costs one round instead of NB.
-    // Values live in NB + 1 slots; slot `sel` is current, candidate c writes slot (sel + 1 + c) mod (NB + 1).
-    // With specLin every candidate also linearises at its trial values into its slot's facJ / edge buffers, so
-    // an accepted step needs no linearisation launch of its own.
-    int NB, specLin, cand;
-    // Large problems: the look-ahead is ADAPTIVE - a round evaluates only nAct candidates (control block, CI_NACT): one
-    // while steps are being accepted, all NB after a round that ended in rejections (a rejection chain is then walked in
-    // one round as before).  The sequential policy is replayed unchanged; candidates that are not evaluated cost nothing.
-    int adaptive, nAct;                  // nAct: set by ba_enter
-    double lambda;                       // set by ba_enter: damping of this workgroup's candidate
-    DPose* poseBase; double* lmBase; size_t lmStride;
-    double* facJBase; size_t facJStride; double* SedgeBase; BaEdge* edgesBase;
-    double* facJ2; double* Sedge2; BaEdge* edges2;            // set by ba_enter (slot of the candidate)
-    size_t sysStride, spartStride, partialStride, dLStride;
-    int solveKind;                       // which reduced-camera solve serves this lane (a batch may mix kinds: each kernel skips foreign lanes)
-    double* Lg;                          // k_ba_solve_mfma: the lane's factor storage (null: the launch's argument)
-    double* ctlHost;                     // != null: pinned host mirror of the control block, written by the control step (the host's poll is then a wait, not a copy)
-};
-enum { BA_SOLVE_MFMA64 = 0, BA_SOLVE_WAVE = 1, BA_SOLVE_MFMA = 2, BA_SOLVE_LARGE = 3 };
-
-// The LM policy (GTSAM 4.2) runs on the DEVICE: the control step after each linearisation / trial updates this
-// block, every other kernel starts by checking that it is its turn (state) and picks the current / trial
-// buffers by `sel`.  The host enqueues a few speculative steps at a time and only reads the
-// block back to learn whether the pass has finished - no host round trip per lambda trial.
-enum { CTL_LAMBDA = 0, CTL_ERROR = 1, CTL_CUR = 2, CTL_INIT_ERR = 3, CTL_INTS = 8, CTL_DOUBLES = 16 };
-enum { CI_STATE = 0, CI_SEL = 1, CI_ITER = 2, CI_INNER = 3, CI_MAXIT = 4, CI_FIRST = 5, CI_NACT = 6, CI_ROUNDS = 7 };
-enum { BA_LINEARIZE = 0, BA_TRY = 1, BA_DONE = 2 };
-enum { BA_MAX_NB = 4, SUMS_CAND = 16, FLAG_COUNT = 1, FLAG_FAIL = 4 };   // sums[16 + 2c | 17 + 2c], flags[4 + c] per candidate
+static_assert(BA_MAX_LEVELS == MAX_LEVELS, "BaChi::thr holds one threshold per pyramid level");
+// value slot of candidate c (BaDev: NB + 1 slots, `sel` is current)
 __device__ __forceinline__ int ba_slot(int sel, int c, int NB) {
     const int s = sel + 1 + c;
     return s > NB ? s - (NB + 1) : s;
@@ -119,13 +64,6 @@ __device__ __forceinline__ bool ba_enter(BaDev& D, int state, int c = 0) {
     D.lambda = lam;
     return true;
 }
-
-constexpr int BA_SCHUR_WAVES = 16;         // max landmarks in flight per workgroup (one per wave): the LDS copy of S is
-                                           // zeroed / written out once per group; the host picks 16, 8 or 4 to fit the LDS
-constexpr int BA_LDS_MAX_F = 20;          // (6F)^2 doubles must fit next to the W staging in 160 KB
-// A workgroup gets 160 KB of LDS, static and dynamic together.  The batch's kernels with dynamic LDS have (almost) no static LDS:
-// its plan keeps BA_STATIC_LDS_RESERVE bytes for it, and ba_kernel_attributes checks the code objects against the reserve.
-constexpr int BA_LDS_BYTES = 160 * 1024, BA_STATIC_LDS_RESERVE = 1024, BA_DYN_LDS_MAX = BA_LDS_BYTES - BA_STATIC_LDS_RESERVE;
 
 // whitened residual / Jacobians of one projection factor (cheirality: constant 2*fx residual)
 __device__ __forceinline__ void ba_eval_fac(const BaDev& D, const DPose& T, const double* p, bool right,
@@ -511,7 +449,6 @@ __device__ __forceinline__ void ba_wave_fence() { asm volatile("s_waitcnt lgkmcn
 // lanes idle; a wave can carry 64 / BA_LPL landmarks side by side; `act` = this lane group has a landmark);
 // measured: the back-substitution is faster with two landmarks per wave, the Schur accumulation (longer per-landmark
 // chains of LDS atomics) with one.
-constexpr int BA_LPL_SCHUR = 64, BA_LPL_BACK = 32;
 template <int BA_LPL>
 __device__ __forceinline__ void ba_lm_blocks(const BaDev& D, int lp, bool act, double* W, int* sfi, double* h, int& ns) {
     const int lane = threadIdx.x & (BA_LPL - 1);
@@ -671,11 +608,6 @@ __global__ __launch_bounds__(64 * BA_SCHUR_WAVES) void k_ba_schur(const BaDev* _
 //   Hpp     lane (f, i) owns row i of the factor's Jp^T Jp (upper part) and its gradient entry.
 // One LDS copy of the reduced system per workgroup; the look-ahead candidates are separate workgroups (grid y; candidates beyond the
 // round's nAct leave at once).
-constexpr int BA2_MAX_F = 10;
-__host__ __device__ inline int ba2_stage_doubles(int maxFac, int maxSlots) {
-    const int ints = maxFac + 2 * (maxSlots + 1);
-    return ((maxFac * 20 + 2 * maxSlots * 18 + 10 + (ints + 1) / 2) + 1) & ~1;        // even: rows are copied as double2
-}
 __device__ __forceinline__ double ba2_dpp_xor(double v, int which) {      // lane ^ 1 (which = 0) / lane ^ 2 (which = 1) inside a quad
     const int lo = __double2loint(v), hi = __double2hiint(v);
     int l2, h2;
@@ -747,18 +679,6 @@ __device__ __forceinline__ void ba2_w_row(const Ba2Region& g, const Ba2Roles& R,
     }
 }
 
-// Layout of the workgroup's LDS copy of the system (and of the partial it writes out):
-//   BA2_PACKED     upper 6x6 blocks only, block pitch BA_PACKED_PITCH (ba_packed.hpp) - the production form: 2 095 instead of 3 660
-//                  doubles to zero, flush, write and sum at F = 10, and block bases spread over the LDS banks;
-//   BA2_ROWMAJOR   n x n row-major with pitch n (the form of D.S; k_ba_schur's);  BA2_ROWMAJOR1  the same with LDS pitch n + 1 (the
-//                  bank effect alone; written out with pitch n).  Developer overrides: VSLAM_BA_SCHUR2_LAYOUT = 0 / 1.
-enum { BA2_ROWMAJOR = 0, BA2_ROWMAJOR1 = 1, BA2_PACKED = 2 };
-__host__ __device__ inline int ba2_sys_doubles(int n, int layout) {       // LDS doubles of the system copy (even: the staging regions follow)
-    return layout == BA2_PACKED ? (ba_packed_doubles(n / 6) + 1) & ~1 : layout == BA2_ROWMAJOR1 ? n * (n + 1) + n : n * n + n;
-}
-__host__ __device__ inline int ba2_part_doubles(int n, int layout) {      // doubles of one partial in Spart
-    return layout == BA2_PACKED ? ba_packed_doubles(n / 6) : n * n + n;
-}
 // the block phase: two lanes own one 6x6 block (s1 <= s2), three rows each; 32 blocks per pass.  One base address per lane, the 18
 // atomics at constant offsets from it (PACKED: row pitch 6 - all of them immediates; else the rows are ld apart).
 template <bool PACKED>
@@ -962,21 +882,9 @@ __global__ __launch_bounds__(256) void k_ba_reduce(const BaDev* __restrict__ tab
 // by free keyframes of block rows {a, b, ...} is listed under every window (a, b) of that set).  The window - one copy
 // per lambda candidate - lives in LDS; a landmark adds the 6x6 blocks of its (slot, slot) pairs that fall inside
 // it.  Partial windows are written out once and summed in a fixed order by k_ba_reduce_win.  No fp64 global atomics.
-struct BaWin {
-    int TB, T, TP, tileDoubles, nWin;      // T = 6 TB; tile = T rows of pitch TP = T + 1 (rows 6 apart must not share an
-                                           // LDS bank pair) followed by T right-hand-side entries (diagonal windows)
-    const int* winA; const int* winB;      // [nWin] block row / block column of a window
-    const int* winFirstWg;                 // [nWin + 1] first workgroup (= partial) of each window
-    const int* wgWin; const int* wgBegin; const int* wgEnd;   // [nWg] window and range of winLm of a workgroup
-    const int* winLm;                      // concatenated landmark lists (local landmark index lp)
-    double* part;                          // [nWg][NB][tileDoubles]
-    double* Wg; double* Hg;                // per slot entry: Hpl block (18), per landmark: Hll (6) | bl (3) - k_ba_lm_prep
-};
-
 // Landmark blocks of the current linearisation, once per trial round: a landmark that is seen from several block rows
 // sits in several windows' lists, which then only fetch the W blocks of their own rows / columns (144 B each) instead of
 // rebuilding everything from the landmark's factors.
-constexpr int BA_WIN_HG = 9 + 6 * BA_MAX_NB;      // doubles per landmark: Hll (6) | bl (3) | per candidate the 6 unique entries of (Hll + lambda I)^-1
 __global__ __launch_bounds__(64 * BA_SCHUR_WAVES) void k_ba_lm_prep(const BaDev* __restrict__ tab, BaWin Wn, int maxSlots) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the batch)
     extern __shared__ int smi[];
@@ -1010,7 +918,6 @@ __global__ __launch_bounds__(64 * BA_SCHUR_WAVES) void k_ba_lm_prep(const BaDev*
 // (entry, pair) into one index space, and 6 lanes serve one pair (lane = row i of the 6x6 block: the W row of its own
 // slot, the 18 W entries of the partner slot and Hll | bl come straight from HBM / L2, 6 LDS atomics per candidate).
 // No staging, no per-landmark barriers or fences: the atomics are fire-and-forget until the final flush.
-constexpr int BA_WIN_META = 5 * 64 + 65;       // ints of LDS per wave: lp, seR, nR, seC, nC per entry + prefix
 __global__ __launch_bounds__(64 * BA_SCHUR_WAVES) void k_ba_schur_win(const BaDev* __restrict__ tab, BaWin Wn) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the batch)
     extern __shared__ double sm[];
@@ -1323,7 +1230,6 @@ __global__ __launch_bounds__(1024) void k_ba_solve(const BaDev* __restrict__ tab
 // solved by ONE wave with the matrix in registers: lane i owns row i, pivots and multipliers travel by
 // v_readlane, no LDS round trip or barrier per column.  Right-looking Cholesky (rsqrt pivots as in k_ba_solve),
 // forward substitution, transpose of L through LDS, column-oriented back substitution, pose retraction.
-constexpr int BA_WAVE_N = 60;
 __global__ __launch_bounds__(64) void k_ba_solve_wave(const BaDev* __restrict__ tab) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the batch)
     constexpr int N = BA_WAVE_N;
@@ -1413,7 +1319,6 @@ __global__ __launch_bounds__(64) void k_ba_solve_wave(const BaDev* __restrict__ 
 // thread solves one panel row against it, then every wave updates its tiles with v_mfma_f64_16x16x4 (A and B
 // operands straight from the LDS panel).  L is streamed to global memory column block by column block for the
 // blocked forward / backward substitutions that follow.  Padding rows are identity.
-constexpr int BA_MFMA_N = 256, BA_MFMA_NB = BA_MFMA_N / 16, BA_MFMA_NW = 8, BA_MFMA_SLOTS = 17, BA_MFMA_LD = 17;
 typedef double ba_d4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(64 * BA_MFMA_NW) void k_ba_solve_mfma(const BaDev* __restrict__ tab, double* __restrict__ Lg) {
@@ -1722,7 +1627,6 @@ __global__ __launch_bounds__(64) void k_ba_solve_mfma64(const BaDev* __restrict_
 // rounded up to 64, identity padding) and y live in HBM / L2.  k_ba_chol_back then solves L^T x = y block by block in
 // one workgroup and retracts the trial poses.  (n = 384: 6 + 1 launches, ~0.15 ms, against 1.7 ms for the row-per-thread
 // kernel this replaces.)
-constexpr int CH_B = 64, CH_LD = 65, CH_PLD = 17;
 
 __global__ __launch_bounds__(256) void k_ba_chol_col(const BaDev* __restrict__ tab, double* __restrict__ Lg, double* __restrict__ yG, int N, int J, int* __restrict__ failFlag) {
     BaDev D = *lane_entry(tab, blockIdx.z);      // per-lane argument block (grid z = problem of the batch)
@@ -2013,11 +1917,6 @@ __global__ __launch_bounds__(64 * BA_SCHUR_WAVES) void k_ba_back(const BaDev* __
 }
 
 // chi2 re-check (src/OptimizationBA.cpp:787-871): pair-parallel
-struct BaChi {
-    int NP; const int* pairKf; const int* pairLm; const uint8_t* pairFlags; const float* pairUv; const int* pairOct;
-    const uint8_t* kfLocal; const uint8_t* kfPresent; const uint8_t* lmPresent; const DPose* pose; const double* lm;
-    float thr[MAX_LEVELS]; double fx, fy, cx, cy, b; uint8_t* wrong;
-};
 __device__ __forceinline__ bool ba_outlier(const BaChi& C, const double* pc, float ou, float ov, int oct, bool right) {
     const double x = right ? pc[0] - C.b : pc[0], y = pc[1], z = pc[2];
     if (z <= 0) return true;
@@ -2103,12 +2002,6 @@ __global__ __launch_bounds__(256) void k_ba_init_slots(int nPose, const double* 
 }
 
 // ---- batch-only kernels: the steps the one-problem path drives from the host, per lane of a batch (grid y = lane) ----------
-struct BaLaneAux {
-    BaChi C;                                        // chi2 re-check (C.pose / C.lm: taken from the lane's current value slot)
-    int NF; const int* facPair; double* facIs;      // k_ba_mask
-    int nPose, nLm; const double* pose0; const double* lm0;     // k_ba_init_slots over the lane's NB + 1 slots
-    double* outPose; double* outLm;                 // final values, gathered for one download
-};
 // (the lane's BaChi block stays in the constant-addressed table - thr[oct] is indexed there: a by-value copy of the struct put its
 //  threshold array in scratch, 192 bytes per lane)
 __device__ __forceinline__ bool ba_outlier_at(const BaChi& C, const double* pc, float ou, float ov, int oct, bool right) {
@@ -2452,9 +2345,8 @@ static thread_local void (*g_baRelease)() = nullptr;      // frees the calling t
 
 // Pinned host arena with a device mirror: the per-pass index / measurement arrays are written straight into
 // pinned memory and travel in ONE copy.
-struct PinnedArena {
-    uint8_t* h = nullptr; uint8_t* d = nullptr;
-    size_t cap = 0, used = 0;
+struct PinnedArena : BaArenaView {
+    uint8_t* d = nullptr;
     hipError_t ensure(size_t bytes, hipStream_t s) {
         if (bytes <= cap) return hipSuccess;
         hipError_t e = hipStreamSynchronize(s);
@@ -2467,19 +2359,8 @@ struct PinnedArena {
         if (e != hipSuccess) return e;
         return hipMalloc((void**)&d, cap);
     }
-    void reset() { used = 0; }
-    template <class T> T* take(size_t count) {
-        used = (used + 255) & ~(size_t)255;
-        T* p = (T*)(h + used);
-        used += std::max<size_t>(count, 1) * sizeof(T);
-        return used <= cap ? p : nullptr;
-    }
     template <class T> T* dev(T* hostPtr) const { return (T*)(d + ((uint8_t*)hostPtr - h)); }
     hipError_t upload(hipStream_t s) const { return hipMemcpyAsync(d, h, used, hipMemcpyHostToDevice, s); }
-};
-struct BaHostTmp {
-    std::vector<uint8_t> kfPresent, lmPresent;
-    std::vector<int> cnt, fidx, lpOf, order, fill, key, src, ns;
 };
 
 // vslam_local_ba_set_lookahead (-1: environment / default).  Like the timing switch and the workspace these belong to
@@ -2489,8 +2370,54 @@ static bool ba_use_mfma() {
     static const bool envOff = getenv("VSLAM_BA_NO_MFMA") != nullptr;      // process-wide default; vslam_local_ba_set_solver overrides it per thread
     return g_baSolver < 0 ? !envOff : g_baSolver == 0;
 }
+// lambda look-ahead (see BaDev): candidates per trial round and speculative linearisation - the thread's setting, else the environment
+struct BaLmKnobs { int NB; bool specLin; };
+static BaLmKnobs ba_lm_knobs() {
+    static const int nbEnv = [] { const char* e = getenv("VSLAM_BA_LOOKAHEAD"); return e ? std::max(1, std::min((int)BA_MAX_NB, atoi(e))) : (int)BA_MAX_NB; }();
+    static const bool specEnv = !getenv("VSLAM_BA_NO_SPECLIN");
+    return {g_baLookahead > 0 ? std::min(g_baLookahead, (int)BA_MAX_NB) : nbEnv, g_baSpecLin >= 0 ? g_baSpecLin != 0 : specEnv};
+}
+static int ba_adaptive_env() { const char* e = getenv("VSLAM_BA_ADAPTIVE"); return e ? atoi(e) : -1; }      // -1: the caller's default
 
-struct HostFac { int pair, kf, lm, fi, lp; bool right; double z[2], is; };
+// the device of a call: there is one, `device` names one (ba_select_device: and it becomes the calling thread's current device)
+static vslam_status ba_check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    return device < 0 || device >= ndev ? VSLAM_ERR_INVALID : VSLAM_OK;
+}
+static vslam_status ba_select_device(int device) {
+    VS_CHECK(ba_check_device(device));
+    VS_HIP(hipSetDevice(device));
+    return VSLAM_OK;
+}
+
+// The fields of a problem's argument block that both entry points fill alike: the pass's arrays in the arena, the value slots and
+// work buffers of the lane.  The caller adds what is its own: partial / Spart (+ strides), solveKind, Lg, ctlHost.
+struct BaLaneBufs { int K, L; DPose* poseS; double *lmS, *facJ, *S, *Sedge, *dP, *dL, *sums; int* flags; };
+static void ba_fill_dev(BaDev& D, const BaPassHost& H, const PinnedArena& A, const BaLaneBufs& B, const vslam_rig& rig, int NB, bool specLin, bool adaptive) {
+    const int n = H.n;
+    D.NF = H.NF; D.Lp = H.Lp; D.F = H.F; D.K = B.K; D.NE = H.NE; D.n = n;
+    D.facKf = A.dev(H.h_facKf); D.facFi = A.dev(H.h_facFi); D.facLp = A.dev(H.h_facLp); D.facLm = A.dev(H.h_facLm);
+    D.facZ = A.dev(H.h_facZ); D.facIs = A.dev(H.h_facIs); D.facRight = A.dev(H.h_facRight); D.facJ = B.facJ;
+    D.lpStart = A.dev(H.h_lpStart); D.lpSlotStart = A.dev(H.h_lpSlotStart); D.slotStart = A.dev(H.h_slotStart); D.slotFi = A.dev(H.h_slotFi);
+    D.lpOrig = A.dev(H.h_lpOrig); D.poseCur = B.poseS; D.poseTrial = B.poseS + B.K; D.fidx = A.dev(H.h_fidx);
+    D.lmCur = B.lmS; D.lmTrial = B.lmS + (size_t)3 * B.L; D.edges = A.dev(H.h_edges);
+    D.S = B.S; D.rhs = B.S + (size_t)n * n; D.Sedge = B.Sedge; D.dP = B.dP; D.dL = B.dL; D.sums = B.sums; D.flags = B.flags;
+    D.fx = rig.fx; D.fy = rig.fy; D.cx = rig.cx; D.cy = rig.cy; D.b = (double)rig.baseline;
+    D.ctl = A.dev(H.h_ctl);
+    D.NB = NB; D.specLin = specLin ? 1 : 0; D.adaptive = adaptive ? 1 : 0;
+    D.poseBase = B.poseS; D.lmBase = B.lmS; D.lmStride = (size_t)3 * B.L;
+    D.facJBase = B.facJ; D.facJStride = (size_t)20 * H.NF; D.SedgeBase = B.Sedge; D.edgesBase = A.dev(H.h_edges);
+    D.sysStride = (size_t)n * n + 2 * n + 8; D.dLStride = (size_t)3 * H.Lp;
+}
+// chi2 arguments: the problem's pair arrays (device addresses), the pass's membership arrays, thresholds 7.815 * sigmaFactor, the rig
+struct BaPairArrays { const int* kf; const int* lm; const int* oct; const uint8_t* flags; const float* uv; const uint8_t* kfLocal; };
+static void ba_fill_chi(BaChi& C, const vslam_ba_problem* P, const BaPairArrays& a, const uint8_t* kfPresent, const uint8_t* lmPresent, uint8_t* wrong) {
+    C.NP = P->n_pairs; C.pairKf = a.kf; C.pairLm = a.lm; C.pairFlags = a.flags; C.pairUv = a.uv;
+    C.pairOct = a.oct; C.kfLocal = a.kfLocal; C.kfPresent = kfPresent; C.lmPresent = lmPresent; C.wrong = wrong;
+    for (int l = 0; l < P->n_levels; l++) C.thr[l] = (float)((double)7.815f * (double)P->sigma_factor[l]);
+    C.fx = P->rig.fx; C.fy = P->rig.fy; C.cx = P->rig.cx; C.cy = P->rig.cy; C.b = (double)P->rig.baseline;
+}
 
 }  // namespace
 
@@ -2498,8 +2425,6 @@ void vslam::thread_release() {
     if (g_baRelease) { g_baRelease(); g_baRelease = nullptr; }
     thread_pool_release();
 }
-
-#define BA_UP(dst, vec) VS_HIP(hipMemcpyAsync((dst).p, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, stream))
 
 #ifdef VSLAM_HOST_STAMPS
 #include <chrono>
@@ -2516,190 +2441,6 @@ static int bhs_slot(const char* name) { for (int i = 0; i < 16 && g_bhsName[i]; 
 #define BHS(name) do { const auto t_ = std::chrono::steady_clock::now(); g_bhsNs[bhs_slot(name)] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - bhs_t).count(); bhs_t = t_; } while (0)
 #define BHS2(name) do {} while (0)
 #endif
-
-// Host side of ONE LM pass of one problem: the factor list ordered by (landmark, free index, pair, side), the slot table, the
-// BetweenFactor chain, graph membership - written straight into a pinned arena (device mirror: one upload).  Shared by the
-// one-problem path (ba_run) and the batched one (ba_run_batch).
-static void ba_init_ctl(double* h_ctl, int ps, int nAct) {
-    for (int i = 0; i < CTL_DOUBLES; i++) h_ctl[i] = 0;
-    h_ctl[CTL_LAMBDA] = 1e-5;
-    int* ci = (int*)(h_ctl + CTL_INTS);
-    ci[CI_STATE] = BA_LINEARIZE; ci[CI_SEL] = 0; ci[CI_ITER] = 0; ci[CI_INNER] = 0; ci[CI_MAXIT] = ps == 0 ? 5 : 10; ci[CI_FIRST] = 1;
-    ci[CI_NACT] = nAct;
-}
-struct BaPassHost {
-    int NF = 0, F = 0, n = 0, Lp = 0, NE = 0, maxSlots = 1, nSlotEntries = 0, maxFac = 1;
-    long long sumK2 = 0;
-    double* h_ctl = nullptr; BaDev* h_D = nullptr;
-    int *h_facKf = nullptr, *h_facFi = nullptr, *h_facLp = nullptr, *h_facLm = nullptr, *h_facPair = nullptr;
-    double *h_facZ = nullptr, *h_facIs = nullptr; uint8_t* h_facRight = nullptr;
-    int *h_lpStart = nullptr, *h_lpSlotStart = nullptr, *h_lpOrig = nullptr, *h_slotStart = nullptr, *h_slotFi = nullptr, *h_fidx = nullptr;
-    BaEdge* h_edges = nullptr; uint8_t *h_kfPresent = nullptr, *h_lmPresent = nullptr;
-
-    // membership, free set, landmark shard, factor counts
-    // Large problems (the C5 window: 1.2 M pairs) split the pair scans over the pool by LANDMARK RANGE: every worker reads all pairs
-    // and handles those whose landmark falls in its range - no atomics, the pair order inside a landmark is kept.
-    static int par_ranges(const BaPool* pool, int NP, int L) { return (pool && !pool->workers.empty() && NP >= 200000) ? std::min((int)pool->workers.size() + 1, std::max(1, L / 4096)) : 1; }
-    void count(const vslam_ba_problem* P, const uint8_t* wrong, int rank, int world, BaHostTmp& T, BaPool* pool = nullptr) {
-        const int K = P->n_kf, L = P->n_lm, NP = P->n_pairs;
-        T.kfPresent.assign(K, 0); T.lmPresent.assign(L, 0); T.cnt.assign((size_t)L + 1, 0);
-        NF = 0;
-        const int nr = par_ranges(pool, NP, L);
-        std::vector<long long> nfPart(nr, 0);
-        std::vector<std::vector<uint8_t>> kfPart(nr > 1 ? nr : 0);
-        auto scan = [&](int r) {
-            const int l0 = (int)((long long)L * r / nr), l1 = (int)((long long)L * (r + 1) / nr);
-            uint8_t* kfp = nr > 1 ? (kfPart[r].assign(K, 0), kfPart[r].data()) : T.kfPresent.data();
-            long long nf = 0;
-            for (int p = 0; p < NP; p++) {
-                const int l = P->pair_lm[p];
-                if (l < l0 || l >= l1 || wrong[p]) continue;
-                const int fl = P->pair_flags[p] & 3;
-                if (!fl) continue;
-                kfp[P->pair_kf[p]] = 1; T.lmPresent[l] = 1;             // graph membership is global
-                if (l % world != rank) continue;                           // landmark shard of this rank
-                const int c = (fl & 1) + (fl >> 1);
-                T.cnt[l] += c; nf += c;
-            }
-            nfPart[r] = nf;
-        };
-        if (nr > 1) pool->run(nr, scan); else scan(0);
-        for (int r = 0; r < nr; r++) { NF += (int)nfPart[r]; if (nr > 1) for (int k = 0; k < K; k++) T.kfPresent[k] |= kfPart[r][k]; }
-        T.lpOf.assign(L, -1);
-        Lp = 0;
-        for (int l = 0; l < L; l++) if (T.lmPresent[l] && l % world == rank) T.lpOf[l] = Lp++;
-        free_set_and_edges(P, rank, T);
-    }
-    // free keyframes and the BetweenFactor chain from T.kfPresent (shared by the host and the device ordering)
-    void free_set_and_edges(const vslam_ba_problem* P, int rank, BaHostTmp& T) {
-        const int K = P->n_kf;
-        T.fidx.assign(K, -1);
-        F = 0;
-        for (int k = 0; k < K; k++) if (T.kfPresent[k] && !P->kf_fixed[k]) T.fidx[k] = F++;
-        n = 6 * F;
-        // edges: id-consecutive keyframes of this pass's graph (src/OptimizationBA.cpp:750-768)
-        T.order.clear();
-        for (int k = 0; k < K; k++) if (T.kfPresent[k]) T.order.push_back(k);
-        std::sort(T.order.begin(), T.order.end(), [&](int a, int b) { return P->kf_id[a] < P->kf_id[b]; });
-        // the BetweenFactor chain is counted once (rank 0); S is summed over ranks
-        NE = rank == 0 ? std::max((int)T.order.size() - 1, 0) : 0;
-    }
-    size_t arena_bytes(int K, int L, int edgeSlots) const {
-        return 8192 + (size_t)NF * 56 + ((size_t)NF + Lp + 2) * 8 + ((size_t)Lp + 2) * 12 + (size_t)K * 8 + L +
-               (size_t)edgeSlots * NE * sizeof(BaEdge) + 26 * 256 + sizeof(BaDev);
-    }
-    bool take(PinnedArena& A, int K, int L, int edgeSlots) {
-        h_ctl = A.take<double>(CTL_DOUBLES);
-        h_D = A.take<BaDev>(1);                     // the kernels' argument block (a one-entry lane table)
-        h_facKf = A.take<int>(NF); h_facFi = A.take<int>(NF); h_facLp = A.take<int>(NF); h_facLm = A.take<int>(NF);
-        h_facZ = A.take<double>((size_t)2 * NF); h_facIs = A.take<double>(NF);
-        h_facRight = A.take<uint8_t>(NF);
-        h_facPair = A.take<int>(NF);
-        h_lpStart = A.take<int>(Lp + 1); h_lpSlotStart = A.take<int>(Lp + 1); h_lpOrig = A.take<int>(Lp);
-        h_slotStart = A.take<int>((size_t)NF + Lp + 1); h_slotFi = A.take<int>((size_t)NF + Lp + 1);
-        h_fidx = A.take<int>(K);
-        h_edges = A.take<BaEdge>((size_t)edgeSlots * NE);
-        h_kfPresent = A.take<uint8_t>(K); h_lmPresent = A.take<uint8_t>(L);
-        return h_lmPresent != nullptr;
-    }
-    // bucket by landmark (counting sort, pair order preserved), order each short bucket by free index, emit the arrays
-    void fill(const vslam_ba_problem* P, const uint8_t* wrong, int rank, int world, BaHostTmp& T, const DPose* pose0, BaPool* pool, int edgeSlots) {
-        const int L = P->n_lm, NP = P->n_pairs;
-        for (int l = 0; l < L; l++) if (T.lpOf[l] >= 0) { h_lpOrig[T.lpOf[l]] = l; }
-        {
-            int run = 0;
-            for (int lp = 0; lp < Lp; lp++) { h_lpStart[lp] = run; run += T.cnt[h_lpOrig[lp]]; }
-            h_lpStart[Lp] = run;
-        }
-        T.fill.assign(h_lpStart, h_lpStart + Lp);
-        T.key.resize(NF); T.src.resize(NF);
-        {
-            const int nr = par_ranges(pool, NP, L);
-            auto scatter = [&](int r) {
-                const int l0 = (int)((long long)L * r / nr), l1 = (int)((long long)L * (r + 1) / nr);
-                for (int p = 0; p < NP; p++) {
-                    const int l = P->pair_lm[p];
-                    if (l < l0 || l >= l1 || wrong[p] || l % world != rank) continue;
-                    const int lp = T.lpOf[l];
-                    const int fi = T.fidx[P->pair_kf[p]];
-                    for (int side = 0; side < 2; side++) {
-                        if (!((P->pair_flags[p] >> side) & 1)) continue;
-                        const int pos = T.fill[lp]++;
-                        T.key[pos] = fi; T.src[pos] = 2 * p + side;
-                    }
-                }
-            };
-            if (nr > 1) pool->run(nr, scatter); else scatter(0);
-        }
-        // landmark ranges in parallel: (1) order each bucket by free index and count its slots, (2) after the slot prefix,
-        // write the factor arrays and the slot table.
-        // Slot table: inside a landmark the factors of fixed keyframes (fi = -1) come first, then one
-        // "slot" per free keyframe (its left and/or right factor).  Padded layout: per landmark the slot
-        // starts followed by an end sentinel, so slot s spans [slotStart[s0+s], slotStart[s0+s+1]).
-        T.ns.resize(Lp);
-        const int nChunk = pool ? std::max(1, std::min(32, Lp / 64)) : 1;
-        auto chunk = [&](int c, int& a0, int& a1) { a0 = (int)((long long)Lp * c / nChunk); a1 = (int)((long long)Lp * (c + 1) / nChunk); };
-        auto run_chunks = [&](const std::function<void(int)>& fn) { if (pool && nChunk > 1) pool->run(nChunk, fn); else for (int c = 0; c < nChunk; c++) fn(c); };
-        run_chunks([&](int c) {
-            int a0, a1;
-            chunk(c, a0, a1);
-            for (int lp = a0; lp < a1; lp++) {
-                const int f0 = h_lpStart[lp], f1 = h_lpStart[lp + 1];
-                for (int i = f0 + 1; i < f1; i++) {          // stable insertion sort by free index (buckets are ~10 long)
-                    const int k = T.key[i], v = T.src[i];
-                    int j = i - 1;
-                    while (j >= f0 && T.key[j] > k) { T.key[j + 1] = T.key[j]; T.src[j + 1] = T.src[j]; j--; }
-                    T.key[j + 1] = k; T.src[j + 1] = v;
-                }
-                int lastFi = -2, ns = 0;
-                for (int f = f0; f < f1; f++) { const int fi = T.key[f]; if (fi >= 0 && fi != lastFi) { lastFi = fi; ns++; } }
-                T.ns[lp] = ns;
-            }
-        });
-        maxSlots = 1; nSlotEntries = 0; sumK2 = 0; maxFac = 1;
-        for (int lp = 0; lp < Lp; lp++) {
-            h_lpSlotStart[lp] = nSlotEntries;
-            maxFac = std::max(maxFac, h_lpStart[lp + 1] - h_lpStart[lp]);
-            nSlotEntries += T.ns[lp] + 1;
-            maxSlots = std::max(maxSlots, T.ns[lp]);
-            sumK2 += (long long)T.ns[lp] * T.ns[lp];
-        }
-        run_chunks([&](int c) {
-            int a0, a1;
-            chunk(c, a0, a1);
-            for (int lp = a0; lp < a1; lp++) {
-                const int f0 = h_lpStart[lp], f1 = h_lpStart[lp + 1];
-                int se = h_lpSlotStart[lp], lastFi = -2;
-                for (int f = f0; f < f1; f++) {
-                    const int fi = T.key[f], p = T.src[f] >> 1, side = T.src[f] & 1;
-                    if (fi >= 0 && fi != lastFi) { h_slotStart[se] = f; h_slotFi[se] = fi; se++; lastFi = fi; }
-                    h_facKf[f] = P->pair_kf[p]; h_facFi[f] = fi; h_facLp[f] = lp; h_facLm[f] = P->pair_lm[p];
-                    h_facZ[2 * (size_t)f] = P->pair_uv[4 * (size_t)p + 2 * side]; h_facZ[2 * (size_t)f + 1] = P->pair_uv[4 * (size_t)p + 2 * side + 1];
-                    h_facIs[f] = 1.0 / (1.0 / (double)P->inv_sigma_factor[P->pair_octave[2 * p + side]]);
-                    h_facRight[f] = (uint8_t)side;
-                    h_facPair[f] = p;
-                }
-                h_slotStart[se] = f1; h_slotFi[se] = -1;     // end sentinel
-            }
-        });
-        h_lpSlotStart[Lp] = nSlotEntries;
-        for (int l = 0; l < L; l++) h_lmPresent[l] = T.lmPresent[l];
-        fill_small(P, T, pose0, edgeSlots);
-    }
-    // the host-written small arrays: free index, membership of the keyframes, BetweenFactor edges
-    void fill_small(const vslam_ba_problem* P, BaHostTmp& T, const DPose* pose0, int edgeSlots) {
-        const int K = P->n_kf;
-        for (int k = 0; k < K; k++) { h_fidx[k] = T.fidx[k]; h_kfPresent[k] = T.kfPresent[k]; }
-        for (int i = 0; i < NE; i++) {
-            BaEdge e{};
-            e.a = T.order[i]; e.b = T.order[i + 1]; e.fa = T.fidx[e.a]; e.fb = T.fidx[e.b];
-            DPose ai;
-            pose_inverse(pose0[e.a], ai);
-            pose_compose(ai, pose0[e.b], e.measured);
-            for (int sl = 0; sl < edgeSlots; sl++) h_edges[(size_t)sl * NE + i] = e;
-        }
-    }
-};
 
 // hipFuncSetAttribute is PROCESS-global state: set once, to the largest dynamic LDS size any call may ask for (a per-call,
 // problem-dependent value written by several mapping threads while others launch the same kernel is a race on the runtime's
@@ -2735,29 +2476,13 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
     auto bhs_t = std::chrono::steady_clock::now();
     g_bhsCalls++;
 #endif
-    if (!P || !R || P->n_kf < 1 || P->n_lm < 0 || P->n_pairs < 0 || P->n_levels < 1 || P->n_levels > MAX_LEVELS ||
-        !P->kf_pose_wc || !P->kf_id || !P->kf_fixed || !P->kf_local || !P->sigma_factor || !P->inv_sigma_factor ||
-        !R->kf_pose_wc || !R->lm_xyz || !R->pair_wrong ||
-        (P->n_lm > 0 && !P->lm_xyz) ||
-        (P->n_pairs > 0 && (!P->pair_kf || !P->pair_lm || !P->pair_flags || !P->pair_uv || !P->pair_octave))) {
-        set_error("vslam_local_ba: invalid problem");
-        return VSLAM_ERR_INVALID;
-    }
+    if (!ba_check_args(P, R)) { set_error("vslam_local_ba: invalid problem"); return VSLAM_ERR_INVALID; }
     const int rank = comm ? comm->rank : 0, world = comm ? comm->world : 1;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
+    VS_CHECK(ba_select_device(device));
     const int K = P->n_kf, L = P->n_lm, NP = P->n_pairs;
-    auto pairs_in_range = [&](int p0, int p1) {
-        for (int p = p0; p < p1; p++)
-            if (P->pair_kf[p] < 0 || P->pair_kf[p] >= K || P->pair_lm[p] < 0 || P->pair_lm[p] >= L ||
-                P->pair_octave[2 * p] < 0 || P->pair_octave[2 * p] >= P->n_levels || P->pair_octave[2 * p + 1] < 0 ||
-                P->pair_octave[2 * p + 1] >= P->n_levels) return false;
-        return true;
-    };
     // (the index check of a large problem - 1.2 M pairs: ~1 ms on one core - runs on the workspace's pool, below)
-    if (NP < 200000 && !pairs_in_range(0, NP)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
+    const bool pooledCheck = NP >= BaHostTune{}.parPairs;
+    if (!pooledCheck && !ba_check_pairs(P)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
 
 #ifndef VSLAM_HOST_STAMPS
     BHS("s_check");
@@ -2813,12 +2538,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             ws->pool.start(nt);
         }
     }
-    if (NP >= 200000) {
-        const int nr = (int)ws->pool.workers.size() + 1;
-        std::vector<uint8_t> ok(nr, 1);
-        ws->pool.run(nr, [&](int r) { ok[r] = pairs_in_range((int)((long long)NP * r / nr), (int)((long long)NP * (r + 1) / nr)) ? 1 : 0; });
-        for (int r = 0; r < nr; r++) if (!ok[r]) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
-    }
+    if (pooledCheck && !ba_check_pairs(P, &ws->pool)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
     if ((size_t)P->n_pairs > ws->wrongCap) {
         if (ws->h_wrong) hipHostFree(ws->h_wrong);
         ws->wrongCap = 2 * (size_t)P->n_pairs + 4096;
@@ -2849,14 +2569,10 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
 
     std::vector<DPose> pose0(K);
     for (int k = 0; k < K; k++) pose_from_rm16(P->kf_pose_wc + 16 * (size_t)k, pose0[k]);
-    // lambda look-ahead (see BaDev): candidates per trial round; the sharded path keeps the plain sequential scheme
-    static const int nbEnv = [] { const char* e = getenv("VSLAM_BA_LOOKAHEAD"); return e ? std::max(1, std::min((int)BA_MAX_NB, atoi(e))) : (int)BA_MAX_NB; }();
-    static const bool specEnv = !getenv("VSLAM_BA_NO_SPECLIN");
-    const int nbSet = g_baLookahead, specSet = g_baSpecLin;
-    // (the landmark-sharded path runs the same scheme: every rank evaluates the same candidates, the NB partial systems
+    // (the landmark-sharded path runs the same look-ahead scheme: every rank evaluates the same candidates, the NB partial systems
     // travel in one all-reduce, the control step walks them identically on every rank)
-    const int NB = nbSet > 0 ? std::min(nbSet, (int)BA_MAX_NB) : nbEnv, nSlots = NB + 1;
-    const bool specLin = specSet >= 0 ? specSet != 0 : specEnv;
+    const int NB = ba_lm_knobs().NB, nSlots = NB + 1;
+    const bool specLin = ba_lm_knobs().specLin;
     // the call's constant inputs (initial poses / landmarks, the pair arrays, kf_local) travel in ONE copy through a pinned
     // staging block into one device block (they used to be eight pageable copies)
     VS_HIP(d_poseS.alloc((size_t)nSlots * K));
@@ -2916,7 +2632,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
     double* lmOut = (double*)(ws->h_out + (((size_t)K * sizeof(DPose) + 63) & ~(size_t)63));
     bool resultFetched = false;
     double* lmFinal = p_lm0;
-    const int nCU = 256;
+    const int nCU = BA_NCU;
     auto& A = ws->arena;
     auto& T = ws->tmp;
 
@@ -2971,6 +2687,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             H.count(P, wrong.data(), rank, world, T, &ws->pool);
         BHS("count");
         const int NF = H.NF, F = H.F, n = H.n, Lp = H.Lp, NE = H.NE;
+        if (F > BA_MAX_FREE_KF) { set_error("local BA: more than 170 free keyframes is not supported"); return VSLAM_ERR_CAPACITY; }      // (before anything is sized by F)
         VS_HIP(A.ensure(H.arena_bytes(K, L, specLin ? nSlots : 1), stream));
         A.reset();
         if (!H.take(A, K, L, specLin ? nSlots : 1)) { set_error("local BA: upload arena too small"); return VSLAM_ERR_CAPACITY; }
@@ -3007,17 +2724,14 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             H.fill(P, wrong.data(), rank, world, T, pose0.data(), &ws->pool, specLin ? nSlots : 1);
         BHS("fill");
         double* const h_ctl = H.h_ctl; BaDev* const h_D = H.h_D;
-        int* const h_facKf = H.h_facKf; int* const h_facFi = H.h_facFi; int* const h_facLp = H.h_facLp; int* const h_facLm = H.h_facLm;
-        double* const h_facZ = H.h_facZ; double* const h_facIs = H.h_facIs; uint8_t* const h_facRight = H.h_facRight; int* const h_facPair = H.h_facPair;
-        int* const h_lpStart = H.h_lpStart; int* const h_lpSlotStart = H.h_lpSlotStart; int* const h_lpOrig = H.h_lpOrig;
-        int* const h_slotStart = H.h_slotStart; int* const h_slotFi = H.h_slotFi; int* const h_fidx = H.h_fidx;
+        int* const h_lpSlotStart = H.h_lpSlotStart; int* const h_slotFi = H.h_slotFi;
         BaEdge* const h_edges = H.h_edges; uint8_t* const h_kfPresent = H.h_kfPresent; uint8_t* const h_lmPresent = H.h_lmPresent;
         const int maxSlots = H.maxSlots, nSlotEntries = H.nSlotEntries;
         const long long sumK2 = H.sumK2;
         // ---- LM control block (GTSAM 4.2 policy; k_ba_ctl) ---------------------------------------------
         const double relTol = 1e-5, absTol = 1e-5;
         // adaptive look-ahead for large problems (every candidate costs a full Schur / back-substitution / evaluation pass)
-        const int adaptEnv = [] { const char* e = getenv("VSLAM_BA_ADAPTIVE"); return e ? atoi(e) : -1; }();
+        const int adaptEnv = ba_adaptive_env();
         const bool adaptive = NB > 1 && (adaptEnv >= 0 ? adaptEnv != 0 : NF > 200000);
         auto init_ctl = [&](int ps) { ba_init_ctl(h_ctl, ps, adaptive ? 1 : NB); };
         init_ctl(pass);
@@ -3037,74 +2751,33 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
         VS_HIP(d_dP.alloc((size_t)NB * n)); VS_HIP(d_dL.alloc((size_t)NB * 3 * Lp));
         VS_HIP(d_S.alloc(sysStride * NB));         // per candidate: S | rhs | scratch contiguous (one all-reduce buffer)
         VS_HIP(d_Sedge.alloc(seDoubles * (specLin ? nSlots : 1)));
-        {
+        auto init_slots = [&] {      // every value slot starts from the caller's values
             const int nPose = K * (int)(sizeof(DPose) / sizeof(double)), nLm = 3 * L;
             hipLaunchKernelGGL(k_ba_init_slots, dim3((std::max(nPose, nLm) + 255) / 256, nSlots), dim3(256), 0, stream,
                                nPose, (const double*)p_pose0, (double*)d_poseS.p, nLm, p_lm0, d_lmS.p);
-        }
+        };
+        init_slots();
 
         BaDev D{};
-        D.NF = NF; D.Lp = Lp; D.F = F; D.K = K; D.NE = NE; D.n = n;
-        D.facKf = A.dev(h_facKf); D.facFi = A.dev(h_facFi); D.facLp = A.dev(h_facLp); D.facLm = A.dev(h_facLm);
-        D.facZ = A.dev(h_facZ); D.facIs = A.dev(h_facIs); D.facRight = A.dev(h_facRight); D.facJ = d_facJ.p;
-        D.lpStart = A.dev(h_lpStart); D.lpSlotStart = A.dev(h_lpSlotStart); D.slotStart = A.dev(h_slotStart); D.slotFi = A.dev(h_slotFi);
-        D.lpOrig = A.dev(h_lpOrig); D.poseCur = d_poseS.p; D.poseTrial = d_poseS.p + K; D.fidx = A.dev(h_fidx);
-        D.lmCur = d_lmS.p; D.lmTrial = d_lmS.p + (size_t)3 * L; D.edges = A.dev(h_edges);
-        D.S = d_S.p; D.rhs = d_S.p + (size_t)n * n; D.Sedge = d_Sedge.p; D.dP = d_dP.p; D.dL = d_dL.p; D.sums = d_sums.p; D.flags = d_flags.p;
-        D.fx = P->rig.fx; D.fy = P->rig.fy; D.cx = P->rig.cx; D.cy = P->rig.cy; D.b = (double)P->rig.baseline;
-        D.ctl = A.dev(h_ctl);
-        D.NB = NB; D.specLin = specLin ? 1 : 0; D.adaptive = adaptive ? 1 : 0;
-        D.poseBase = d_poseS.p; D.lmBase = d_lmS.p; D.lmStride = (size_t)3 * L;
-        D.facJBase = d_facJ.p; D.facJStride = (size_t)20 * NF; D.SedgeBase = d_Sedge.p; D.edgesBase = A.dev(h_edges);
-        D.sysStride = sysStride; D.dLStride = (size_t)3 * Lp;
+        ba_fill_dev(D, H, A, BaLaneBufs{K, L, d_poseS.p, d_lmS.p, d_facJ.p, d_S.p, d_Sedge.p, d_dP.p, d_dL.p, d_sums.p, d_flags.p}, P->rig, NB, specLin, adaptive);
 
-        const int obsBlocks = std::max(1, std::min((NF + 255) / 256, 4 * nCU));
-        const bool ldsS = F <= BA_LDS_MAX_F;
+        // ---- launch geometry (ba_plan.hpp); the environment caps the waves per workgroup of the landmark kernels ------------
+        static const BaSingleKnobs envKnobs = {getenv("VSLAM_BA_SCHUR_WAVES") ? std::max(2, std::min(BA_SCHUR_WAVES, atoi(getenv("VSLAM_BA_SCHUR_WAVES")))) : BA_SCHUR_WAVES,
+                                               getenv("VSLAM_BA_BACK_WAVES") ? std::max(1, atoi(getenv("VSLAM_BA_BACK_WAVES"))) : 64, 0, !getenv("VSLAM_BA_NO_SHARED_W")};
+        BaSingleKnobs knobs = envKnobs;
+        if (const char* e = getenv("VSLAM_BA_WINDOW_TB")) knobs.windowTB = std::max(1, std::min(32, atoi(e)));
+        const bool useMfma = ba_use_mfma();
+        const BaSinglePlan plan = ba_single_plan(BaSingleShape{NF, Lp, F, NE, maxSlots, NB, useMfma, devOrder}, knobs);
+        if (plan.why) { set_error("%s", plan.why); return VSLAM_ERR_CAPACITY; }
         const size_t sysDoubles = (size_t)n * n + n;
-        // waves per workgroup of the landmark kernels.  VSLAM_BA_SCHUR_WAVES / VSLAM_BA_BACK_WAVES cap them: a 16-wave workgroup
-        // with ~100 KB of LDS is the fastest form on an idle GPU, but it must find a whole CU's worth of free wave slots and LDS
-        // when the lockstep groups' wide kernels fill the chip; slimmer workgroups slot in between them.
-        static const int schurWavesCap = getenv("VSLAM_BA_SCHUR_WAVES") ? std::max(2, std::min(BA_SCHUR_WAVES, atoi(getenv("VSLAM_BA_SCHUR_WAVES")))) : BA_SCHUR_WAVES;
-        int schurWaves = schurWavesCap;
-        constexpr int SCHUR_LPW = 64 / BA_LPL_SCHUR, BACK_LPW = 64 / BA_LPL_BACK;      // landmarks per wave
-        // (nw waves = nw * LPW landmark units per workgroup)
-        auto stage_lds = [&](int nw) { return (size_t)nw * SCHUR_LPW * 2 * maxSlots * 18 * sizeof(double) + (size_t)nw * SCHUR_LPW * maxSlots * sizeof(int) + 16; };
-        auto schur_lds = [&](int nw, int copies) { return copies * sysDoubles * sizeof(double) + stage_lds(nw); };
-        // one workgroup for all candidates (W blocks built once) when NB copies of the system fit LDS with >= 8 waves
-        static const bool sharedEnv = !getenv("VSLAM_BA_NO_SHARED_W");
-        int sharedW = 0;
+        const bool ldsS = plan.ldsS;
         BaWin Wn{};
         int nWinWg = 0;
-        size_t schurLds = 0;
-        if (ldsS) {
-            if (NB > 1 && sharedEnv) {
-                for (int nw : {16, 12, 8, 6, 4, 2})
-                    if (nw <= schurWavesCap && schur_lds(nw, NB) <= 150 * 1024) { sharedW = 1; schurWaves = nw; break; }
-            }
-            if (!sharedW) while (schurWaves > 2 && schur_lds(schurWaves, 1) > 150 * 1024) schurWaves /= 2;
-            schurLds = schur_lds(schurWaves, sharedW ? NB : 1);
-        } else if (n > 0) {
-            // ---- windowed accumulation: tile size, work lists -------------------------------------------------
-            // TB keyframes per block row: the largest tile whose NB copies leave room for >= 8 waves of staging
-            const size_t metaB = (size_t)BA_SCHUR_WAVES * BA_WIN_META * sizeof(int) + 16;
-            int TB = 4;
-            for (int tb : {32, 24, 16, 12, 8, 6, 4}) {
-                const size_t tileB = ((size_t)6 * tb * (6 * tb + 1) + 6 * tb) * sizeof(double) * NB;
-                if (tileB + metaB <= 150 * 1024) { TB = tb; break; }
-            }
-            if (const char* e = getenv("VSLAM_BA_WINDOW_TB")) TB = std::max(1, std::min(32, atoi(e)));
-            if (devOrder && (F + TB - 1) / TB > 64) TB = (F + 63) / 64;      // (k_win_lists keeps a landmark's block rows in a 64-bit mask)
-            const int nBR = (F + TB - 1) / TB, nWin = nBR * (nBR + 1) / 2;
-            Wn.TB = TB; Wn.T = 6 * TB; Wn.TP = Wn.T + 1; Wn.tileDoubles = Wn.T * Wn.TP + Wn.T; Wn.nWin = nWin;
-            schurWaves = BA_SCHUR_WAVES;
-            schurLds = (size_t)Wn.tileDoubles * sizeof(double) * NB + metaB;
-            if (schurLds > 160 * 1024) { set_error("local BA: window tile does not fit LDS"); return VSLAM_ERR_CAPACITY; }
-            auto win_of = [nBR](int a, int b2) { return a * nBR - a * (a - 1) / 2 + (b2 - a); };     // a <= b2
-            std::vector<int> winA(nWin), winB(nWin), winCnt((size_t)nWin + 1, 0);
-            for (int a2 = 0; a2 < nBR; a2++) for (int b2 = a2; b2 < nBR; b2++) { winA[win_of(a2, b2)] = a2; winB[win_of(a2, b2)] = b2; }
-            // Per landmark the distinct block rows of its slots (sorted by free index); every pair (i <= j) of them is one entry of
-            // window (row_i, row_j).  Landmark chunks run on the pool: each counts its entries per window, a prefix over (window,
-            // chunk) gives every chunk its own segment of every window's list - the same order as one sequential sweep.
+        if (!ldsS) {
+            // ---- windowed accumulation: tile, work lists (host ordering: ba_window_lists_host; device ordering: k_win_*) ---
+            const int TB = plan.win.TB, nBR = plan.win.nBR, nWin = plan.win.nWin;
+            Wn.TB = TB; Wn.T = plan.win.T; Wn.TP = plan.win.TP; Wn.tileDoubles = plan.win.tileDoubles; Wn.nWin = nWin;
+            const int* devWinCnt = nullptr;
             BaWinOrd Q{};
             if (devOrder) {
                 // device ordering: the slot table is on the device - count per (window, 256-landmark block), prefix, and (below, once
@@ -3125,71 +2798,13 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
                 VS_HIP(hipGetLastError());
                 VS_HIP(hipMemcpyAsync(ws->h_ordScal, Q.winCnt, need, hipMemcpyDeviceToHost, stream));
                 VS_HIP(vslam::stream_wait_blocking(stream));
-                const int* hc = (const int*)ws->h_ordScal;
-                for (int w = 0; w <= nWin; w++) winCnt[w] = hc[w];
+                devWinCnt = (const int*)ws->h_ordScal;
             }
-            const int nCh = devOrder ? 0 : (!ws->pool.workers.empty() && Lp >= 16384) ? std::min(32, Lp / 2048) : 1;
-            std::vector<int> chCnt((size_t)nCh * nWin, 0);
-            auto lm_rows = [&](int lp, int* rows) {
-                int nr = 0, last = -1;
-                for (int se = h_lpSlotStart[lp]; se < h_lpSlotStart[lp + 1] - 1; se++) {
-                    const int br = h_slotFi[se] / TB;
-                    if (br != last) { rows[nr++] = br; last = br; }
-                }
-                return nr;
-            };
-            auto ch_range = [&](int c, int& a0, int& a1) { a0 = (int)((long long)Lp * c / nCh); a1 = (int)((long long)Lp * (c + 1) / nCh); };
-            auto count_chunk = [&](int c) {
-                int a0, a1, rows[64];
-                ch_range(c, a0, a1);
-                int* cnt = &chCnt[(size_t)c * nWin];
-                for (int lp = a0; lp < a1; lp++) {
-                    const int nr = lm_rows(lp, rows);
-                    for (int i = 0; i < nr; i++) for (int j = i; j < nr; j++) cnt[win_of(rows[i], rows[j])]++;
-                }
-            };
-            if (nCh > 1) ws->pool.run(nCh, count_chunk); else if (nCh == 1) count_chunk(0);
-            std::vector<int> chOff((size_t)nCh * nWin);
-            if (!devOrder) {
-                int run = 0;
-                for (int w = 0; w < nWin; w++) {
-                    winCnt[w] = run;
-                    for (int c = 0; c < nCh; c++) { chOff[(size_t)c * nWin + w] = run; run += chCnt[(size_t)c * nWin + w]; }
-                }
-                winCnt[nWin] = run;
-            }
-            const int total = winCnt[nWin];
-            std::vector<int> winLm(devOrder ? (size_t)0 : (size_t)std::max(total, 1));
-            auto fill_chunk = [&](int c) {
-                int a0, a1, rows[64];
-                ch_range(c, a0, a1);
-                int* off = &chOff[(size_t)c * nWin];
-                for (int lp = a0; lp < a1; lp++) {
-                    const int nr = lm_rows(lp, rows);
-                    for (int i = 0; i < nr; i++) for (int j = i; j < nr; j++) winLm[off[win_of(rows[i], rows[j])]++] = lp;
-                }
-            };
-            if (nCh > 1) ws->pool.run(nCh, fill_chunk); else if (nCh == 1) fill_chunk(0);
-            // workgroups: a window's list is cut into chunks of >= 256 entries, ~2 workgroups per CU overall
-            const int chunk = std::max(256, (total + 2 * nCU - 1) / (2 * nCU));
-            std::vector<int> wgWin, wgBegin, wgEnd, winFirst((size_t)nWin + 1, 0);
-            for (int w = 0; w < nWin; w++) {
-                winFirst[w] = (int)wgWin.size();
-                for (int i0 = winCnt[w]; i0 < winCnt[w + 1]; i0 += chunk) { wgWin.push_back(w); wgBegin.push_back(i0); wgEnd.push_back(std::min(i0 + chunk, winCnt[w + 1])); }
-            }
-            winFirst[nWin] = (int)wgWin.size();
-            nWinWg = (int)wgWin.size();
-            // one device buffer: winA | winB | winFirst | wgWin | wgBegin | wgEnd | winLm
-            const size_t nInts = (size_t)2 * nWin + (nWin + 1) + (size_t)3 * std::max(nWinWg, 1) + std::max(total, 1);
-            std::vector<int> pack;
-            pack.reserve(nInts);
-            pack.insert(pack.end(), winA.begin(), winA.end()); pack.insert(pack.end(), winB.begin(), winB.end());
-            pack.insert(pack.end(), winFirst.begin(), winFirst.end());
-            const size_t oWg = pack.size();
-            pack.insert(pack.end(), wgWin.begin(), wgWin.end()); pack.resize(oWg + std::max(nWinWg, 1));
-            pack.insert(pack.end(), wgBegin.begin(), wgBegin.end()); pack.resize(oWg + 2 * (size_t)std::max(nWinWg, 1));
-            pack.insert(pack.end(), wgEnd.begin(), wgEnd.end()); pack.resize(oWg + 3 * (size_t)std::max(nWinWg, 1));
-            pack.insert(pack.end(), winLm.begin(), winLm.end());      // (device ordering: the lists are written in place by the fill kernel below)
+            const BaWinLists WL = ba_window_lists_host(Lp, h_lpSlotStart, h_slotFi, TB, nBR, &ws->pool, nCU, devWinCnt);
+            const std::vector<int>& pack = WL.pack;
+            const size_t oWg = WL.oWg, nInts = WL.nInts;
+            const int total = WL.total;
+            nWinWg = WL.nWinWg;
             VS_HIP(d_win.alloc(nInts));
             VS_HIP(hipMemcpyAsync(d_win.p, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, stream));
             if (devOrder && Q.nBlk > 0 && total > 0) {
@@ -3208,48 +2823,26 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             // the lower block triangle is never written (nor read by a solver): keep it at zero for the all-reduce
             VS_HIP(hipMemsetAsync(d_S.p, 0, sysStride * NB * sizeof(double), stream));
         }
-        const int schurUnits = schurWaves * SCHUR_LPW;
-        const int lmBlocks = std::max(1, std::min((Lp + schurUnits - 1) / schurUnits, nCU));
-        int backWaves = BA_SCHUR_WAVES / BACK_LPW;
-        { static const int cap = getenv("VSLAM_BA_BACK_WAVES") ? std::max(1, atoi(getenv("VSLAM_BA_BACK_WAVES"))) : 64; backWaves = std::min(backWaves, cap); }
-        auto back_lds = [&](int nw) { return (size_t)nw * BACK_LPW * maxSlots * 18 * sizeof(double) + (size_t)nw * BACK_LPW * maxSlots * sizeof(int) + 16; };
-        while (backWaves > 1 && back_lds(backWaves) > 150 * 1024) backWaves /= 2;
-        const int backBlocks = std::max(1, std::min((Lp + backWaves * BACK_LPW - 1) / (backWaves * BACK_LPW), nCU));
-        D.partialStride = (size_t)2 * obsBlocks + 2 * (size_t)std::max(NE, 1);
+        D.partialStride = (size_t)2 * plan.obsBlocks + 2 * (size_t)std::max(NE, 1);
         VS_HIP(d_partial.alloc(D.partialStride * NB));
         D.partial = d_partial.p;
-        D.spartStride = sysDoubles * lmBlocks;
+        D.spartStride = sysDoubles * plan.lmBlocks;
         if (ldsS) { VS_HIP(d_Spart.alloc(D.spartStride * NB)); D.Spart = d_Spart.p; }
-        const size_t backLds = back_lds(backWaves);
-        const int sharedBack = (NB > 1 && sharedEnv) ? 1 : 0;
-        const int ldA = ((n + 31) / 32) * 32 + 1;     // row stride = 1 (mod 32) doubles: conflict-free row-per-lane access
-        const size_t solveLdsBytes = ((size_t)n * ldA + n + 8) * sizeof(double);
-        const bool solveLds = solveLdsBytes <= 150 * 1024;
 #ifndef VSLAM_HOST_STAMPS
         BHS("u_alloc");
 #endif
-        if (n > 1024) { set_error("local BA: more than 170 free keyframes is not supported"); return VSLAM_ERR_CAPACITY; }
-        if (schurLds > 160 * 1024) { set_error("local BA: landmark with too many views for the LDS staging"); return VSLAM_ERR_CAPACITY; }
         VS_CHECK(ba_kernel_attributes());
-        const size_t mfmaLds = ((size_t)BA_MFMA_N * BA_MFMA_LD + 16 + BA_MFMA_N) * sizeof(double);
-        const bool useMfma = ba_use_mfma();
-        if (n > BA_WAVE_N && n <= BA_MFMA_N && useMfma) {
-            VS_HIP(d_Lg.alloc((size_t)BA_MFMA_N * BA_MFMA_N * NB));
-        }
+        if (plan.solveKind == BA_SOLVE_MFMA) VS_HIP(d_Lg.alloc((size_t)BA_MFMA_N * BA_MFMA_N * NB));
         // larger systems: block-column MFMA Cholesky (k_ba_chol_col / k_ba_chol_back)
-        const bool useChol = n > BA_MFMA_N && useMfma;
-        const int cholN = vslam::align_up(std::max(n, 1), CH_B);
-        const size_t cholColLds = ((size_t)2 * CH_B * CH_LD + (size_t)CH_B * CH_PLD + 3 * CH_B) * sizeof(double);
-        const size_t cholBackLds = ((size_t)CH_B * CH_LD + cholN + 4 * CH_B) * sizeof(double);
-        if (useChol) {
-            VS_HIP(d_Lg.alloc((size_t)cholN * cholN * NB));
-            VS_HIP(d_cholY.alloc((size_t)cholN * NB));
+        if (plan.useChol) {
+            VS_HIP(d_Lg.alloc((size_t)plan.cholN * plan.cholN * NB));
+            VS_HIP(d_cholY.alloc((size_t)plan.cholN * NB));
             if (!d_cholFail.p) { VS_HIP(d_cholFail.alloc(BA_MAX_NB)); VS_HIP(hipMemsetAsync(d_cholFail.p, 0, BA_MAX_NB * sizeof(int), stream)); }
         }
 #ifndef VSLAM_HOST_STAMPS
         BHS("u_attr");
 #endif
-        D.solveKind = (n <= 64 && useMfma) ? BA_SOLVE_MFMA64 : n <= BA_WAVE_N ? BA_SOLVE_WAVE : (n <= BA_MFMA_N && useMfma) ? BA_SOLVE_MFMA : BA_SOLVE_LARGE;
+        D.solveKind = plan.solveKind;
         *h_D = D;
         const BaDev* const dD = A.dev(h_D);
         VS_HIP(hipMemcpyAsync((void*)dD, h_D, sizeof(BaDev), hipMemcpyHostToDevice, stream));
@@ -3257,12 +2850,11 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
 
         // ---- LM: speculative steps, the device decides (k_ba_ctl) -----------------------------------
         auto run_lm = [&](int ps, long long nfStat, long long lpStat, long long k2Stat) -> vslam_status {
-        (void)poseOut; (void)lmOut;
         // One step = [linearise if the state asks for it] + one lambda trial.  Kernels that are not due
         // return at once, so the host may enqueue a few steps ahead and only then look at the state.
         const int fuseCtl = comm ? 0 : 1;
-        const int facBlocks = (NF ? obsBlocks : 0) + std::max(NE, 1);
-        const int nObs = NF ? obsBlocks : 0;
+        const int facBlocks = (NF ? plan.obsBlocks : 0) + std::max(NE, 1);
+        const int nObs = NF ? plan.obsBlocks : 0;
         VS_HIP(hipMemsetAsync(d_Sedge.p, 0, ((size_t)n * n + n) * sizeof(double), stream));     // first linearisation; later ones: see k_ba_factors
         auto step = [&](bool first) -> vslam_status {
             int t = -1;
@@ -3278,33 +2870,33 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             }
             t = g_baTimer.begin("ba_schur");
             if (n > 0) {
-                if (ldsS) hipLaunchKernelGGL(k_ba_schur, dim3(lmBlocks, sharedW ? 1 : NB), dim3(64 * schurWaves), schurLds, stream, dD, maxSlots, sharedW);
+                if (ldsS) hipLaunchKernelGGL(k_ba_schur, dim3(plan.lmBlocks, plan.sharedW ? 1 : NB), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, maxSlots, plan.sharedW);
                 else if (nWinWg) {
                     hipLaunchKernelGGL(k_ba_lm_prep, dim3(std::max(1, std::min((Lp + BA_SCHUR_WAVES - 1) / BA_SCHUR_WAVES, 4 * nCU))), dim3(64 * BA_SCHUR_WAVES),
                                        (size_t)BA_SCHUR_WAVES * maxSlots * sizeof(int), stream, dD, Wn, maxSlots);
-                    hipLaunchKernelGGL(k_ba_schur_win, dim3(nWinWg), dim3(64 * schurWaves), schurLds, stream, dD, Wn);
+                    hipLaunchKernelGGL(k_ba_schur_win, dim3(nWinWg), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, Wn);
                 }
             }
             g_baTimer.end(t);
             t = g_baTimer.begin("ba_solve");
             if (n > 0) {     // sum of the partial systems + BetweenFactor blocks
-                if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, lmBlocks, 0);
+                if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, plan.lmBlocks, 0);
                 else hipLaunchKernelGGL(k_ba_reduce_win, dim3(Wn.nWin, NB), dim3(256), 0, stream, dD, Wn);
             }
             // the NB candidates' systems are contiguous (sysStride apart): one all-reduce for all of them
             if (comm && n > 0) { const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, d_S.p, sysStride * (NB - 1) + (size_t)n * n + n, stream)); g_baTimer.end(tc); }
-            if (n <= 64 && useMfma) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB), dim3(64), 0, stream, dD);
-            else if (n <= BA_WAVE_N) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB), dim3(64), 0, stream, dD);
-            else if (n <= BA_MFMA_N && useMfma) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB), dim3(64 * BA_MFMA_NW), mfmaLds, stream, dD, d_Lg.p);
-            else if (useChol) {
-                for (int J = 0; J < cholN / CH_B; J++)
-                    hipLaunchKernelGGL(k_ba_chol_col, dim3(cholN / CH_B - J, NB), dim3(256), cholColLds, stream, dD, d_Lg.p, d_cholY.p, cholN, J, d_cholFail.p);
-                hipLaunchKernelGGL(k_ba_chol_back, dim3(NB), dim3(256), cholBackLds, stream, dD, (const double*)d_Lg.p, (const double*)d_cholY.p, cholN, d_cholFail.p);
+            if (D.solveKind == BA_SOLVE_MFMA64) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB), dim3(64), 0, stream, dD);
+            else if (D.solveKind == BA_SOLVE_WAVE) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB), dim3(64), 0, stream, dD);
+            else if (D.solveKind == BA_SOLVE_MFMA) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB), dim3(64 * BA_MFMA_NW), plan.mfmaLds, stream, dD, d_Lg.p);
+            else if (plan.useChol) {
+                for (int J = 0; J < plan.cholN / CH_B; J++)
+                    hipLaunchKernelGGL(k_ba_chol_col, dim3(plan.cholN / CH_B - J, NB), dim3(256), plan.cholColLds, stream, dD, d_Lg.p, d_cholY.p, plan.cholN, J, d_cholFail.p);
+                hipLaunchKernelGGL(k_ba_chol_back, dim3(NB), dim3(256), plan.cholBackLds, stream, dD, (const double*)d_Lg.p, (const double*)d_cholY.p, plan.cholN, d_cholFail.p);
             } else hipLaunchKernelGGL(k_ba_solve, dim3(NB), dim3(std::max(64, vslam::align_up(n, 64))),
-                                    solveLds ? solveLdsBytes : 64, stream, dD, solveLds ? 1 : 0, solveLds ? ldA : n);
+                                    plan.solveLds ? plan.solveLdsBytes : 64, stream, dD, plan.solveLds ? 1 : 0, plan.solveLds ? plan.ldA : n);
             g_baTimer.end(t);
             t = g_baTimer.begin("ba_back");
-            if (Lp) hipLaunchKernelGGL(k_ba_back, dim3(backBlocks, sharedBack ? 1 : NB), dim3(64 * backWaves), backLds, stream, dD, maxSlots, sharedBack);
+            if (Lp) hipLaunchKernelGGL(k_ba_back, dim3(plan.backBlocks, plan.sharedBack ? 1 : NB), dim3(64 * plan.backWaves), plan.backLds, stream, dD, maxSlots, plan.sharedBack);
             g_baTimer.end(t);
             t = g_baTimer.begin("ba_eval");
             hipLaunchKernelGGL(k_ba_factors<1>, dim3(facBlocks, NB), dim3(256), 0, stream, dD, nObs, fuseCtl, relTol, absTol);
@@ -3329,13 +2921,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             if (enq > 400) { set_error("local BA: LM did not terminate"); return VSLAM_ERR_INVALID; }
         }
         D.poseCur = d_poseS.p + (size_t)co[CI_SEL] * K; D.lmCur = d_lmS.p + (size_t)co[CI_SEL] * 3 * L;
-        R->report[ps].iterations = co[CI_ITER];
-        R->report[ps].inner_iterations = co[CI_INNER];
-        R->report[ps].initial_error = h_ctlOut[CTL_INIT_ERR];
-        R->report[ps].final_error = h_ctlOut[CTL_ERROR];
-        R->report[ps].lambda = h_ctlOut[CTL_LAMBDA];
-        R->n_residuals = nfStat; R->n_landmarks = lpStat; R->n_free_kf = F; R->sum_k2 = k2Stat;
-        R->rounds = (ps == 0 ? 0 : R->rounds) + co[CI_ROUNDS];
+        ba_write_report(R, ps, h_ctlOut, F, nfStat, lpStat, k2Stat);
 
         if (comm) {
             // every rank needs all landmarks for the chi2 pass and the result: exchange the shard updates
@@ -3357,11 +2943,8 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
         BHS("lm");
         // ---- chi2 re-check with the optimised values ---------------------------------------------
         BaChi C{};
-        C.NP = NP; C.pairKf = p_pairKf; C.pairLm = p_pairLm; C.pairFlags = p_pairFlags; C.pairUv = p_pairUv;
-        C.pairOct = p_pairOct; C.kfLocal = p_kfLocal; C.kfPresent = A.dev(h_kfPresent); C.lmPresent = A.dev(h_lmPresent);
-        C.pose = D.poseCur; C.lm = D.lmCur; C.wrong = d_wrong.p;
-        for (int l = 0; l < P->n_levels; l++) C.thr[l] = (float)((double)7.815f * (double)P->sigma_factor[l]);
-        C.fx = D.fx; C.fy = D.fy; C.cx = D.cx; C.cy = D.cy; C.b = D.b;
+        ba_fill_chi(C, P, BaPairArrays{p_pairKf, p_pairLm, p_pairOct, p_pairFlags, p_pairUv, p_kfLocal}, A.dev(h_kfPresent), A.dev(h_lmPresent), d_wrong.p);
+        C.pose = D.poseCur; C.lm = D.lmCur;
         int t = g_baTimer.begin("ba_chi2");
         if (NP) hipLaunchKernelGGL(k_ba_chi2, dim3((NP + 255) / 256), dim3(256), 0, stream, C);
         g_baTimer.end(t);
@@ -3387,8 +2970,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
             // membership / statistics of the second graph from the chi2 flags
             // (large problems: by landmark range on the pool, as BaPassHost::count - every worker reads all pairs and handles its range;
             //  with the device ordering: the same kernels again, now with the chi2 flags - membership, counts, and the masked slot statistics)
-            std::vector<uint8_t> kfP2(K, 0), lmP2(devOrder ? 0 : L, 0);
-            long long NF2 = 0, Lp2dev = 0, k2dev = 0;
+            BaSecondPass S2;
             if (devOrder) {
                 const size_t zInts = (size_t)L + K + ((size_t)L + 3) / 4;
                 VS_HIP(hipMemsetAsync(ws->d_ord1.p, 0, zInts * sizeof(int), stream));
@@ -3401,68 +2983,23 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
                 VS_HIP(hipMemcpyAsync(ws->h_ordScal, O.scal, ORD_SCAL * sizeof(long long), hipMemcpyDeviceToHost, stream));
                 VS_HIP(hipMemcpyAsync(h_kfPres, O.kfPres, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, stream));
                 VS_HIP(vslam::stream_wait_blocking(stream));
-                for (int k = 0; k < K; k++) kfP2[k] = h_kfPres[k] ? 1 : 0;
-                NF2 = ws->h_ordScal[ORD_NF]; Lp2dev = ws->h_ordScal[ORD_LP]; k2dev = ws->h_ordScal[ORD_K2_MASKED];
-            } else {
-                const int nr = BaPassHost::par_ranges(&ws->pool, NP, L);
-                std::vector<long long> nfPart(nr, 0);
-                std::vector<std::vector<uint8_t>> kfPart(nr > 1 ? nr : 0);
-                auto scan = [&](int r) {
-                    const int l0 = (int)((long long)L * r / nr), l1 = (int)((long long)L * (r + 1) / nr);
-                    uint8_t* kfp = nr > 1 ? (kfPart[r].assign(K, 0), kfPart[r].data()) : kfP2.data();
-                    long long nf = 0;
-                    for (int p = 0; p < NP; p++) {
-                        const int l = P->pair_lm[p];
-                        if (l < l0 || l >= l1 || wrong[p]) continue;
-                        const int fl = P->pair_flags[p] & 3;
-                        if (!fl) continue;
-                        kfp[P->pair_kf[p]] = 1; lmP2[l] = 1;
-                        if (l % world == rank) nf += (fl & 1) + (fl >> 1);      // (statistics are per shard, summed in run_lm)
-                    }
-                    nfPart[r] = nf;
-                };
-                if (nr > 1) ws->pool.run(nr, scan); else scan(0);
-                for (int r = 0; r < nr; r++) { NF2 += nfPart[r]; if (nr > 1) for (int k = 0; k < K; k++) kfP2[k] |= kfPart[r][k]; }
-            }
-            bool same = true;
-            for (int k = 0; k < K; k++) if (kfP2[k] != T.kfPresent[k]) { same = false; break; }
-            if (same) {       // same keyframes => same free set, same BetweenFactor chain; landmarks may only drop out
-                long long Lp2 = Lp2dev, k2 = k2dev;
-                if (!devOrder) {
-                    const int nc = (!ws->pool.workers.empty() && Lp >= 16384) ? std::min(32, Lp / 2048) : 1;
-                    std::vector<long long> k2Part(nc, 0), lpPart(nc, 0);
-                    auto part = [&](int c) {
-                        long long kk = 0, ll = 0;
-                        for (int l = (int)((long long)L * c / nc), l1 = (int)((long long)L * (c + 1) / nc); l < l1; l++) if (l % world == rank) ll += lmP2[l];
-                        for (int lp = (int)((long long)Lp * c / nc), lp1 = (int)((long long)Lp * (c + 1) / nc); lp < lp1; lp++) {
-                            int ns = 0, last = -2;
-                            for (int f = h_lpStart[lp]; f < h_lpStart[lp + 1]; f++) {
-                                if (wrong[h_facPair[f]]) continue;
-                                const int fi = h_facFi[f];
-                                if (fi >= 0 && fi != last) { last = fi; ns++; }
-                            }
-                            kk += (long long)ns * ns;
-                        }
-                        k2Part[c] = kk; lpPart[c] = ll;
-                    };
-                    if (nc > 1) ws->pool.run(nc, part); else part(0);
-                    for (int c = 0; c < nc; c++) { k2 += k2Part[c]; Lp2 += lpPart[c]; }
-                }
+                S2.kfP2.resize(K);
+                for (int k = 0; k < K; k++) S2.kfP2[k] = h_kfPres[k] ? 1 : 0;
+                S2.NF2 = ws->h_ordScal[ORD_NF]; S2.Lp2 = ws->h_ordScal[ORD_LP]; S2.k2 = ws->h_ordScal[ORD_K2_MASKED];
+                S2.same = S2.kfP2 == T.kfPresent;
+            } else H.second_pass(P, wrong.data(), rank, world, T, &ws->pool, S2);
+            if (S2.same) {       // same keyframes => same free set, same BetweenFactor chain; landmarks may only drop out
                 BHS("p2stats");
-                for (int k = 0; k < K; k++) h_kfPresent[k] = kfP2[k];
-                if (!devOrder) for (int l = 0; l < L; l++) h_lmPresent[l] = lmP2[l];
+                for (int k = 0; k < K; k++) h_kfPresent[k] = S2.kfP2[k];
+                if (!devOrder) for (int l = 0; l < L; l++) h_lmPresent[l] = S2.lmP2[l];
                 init_ctl(1);
                 VS_HIP(hipMemcpyAsync(A.dev(h_kfPresent), h_kfPresent, K, hipMemcpyHostToDevice, stream));
                 if (devOrder) VS_HIP(hipMemcpyAsync(A.dev(h_lmPresent), O.lmPres, (size_t)L, hipMemcpyDeviceToDevice, stream));
                 else if (L) VS_HIP(hipMemcpyAsync(A.dev(h_lmPresent), h_lmPresent, L, hipMemcpyHostToDevice, stream));
                 VS_HIP(hipMemcpyAsync(A.dev(h_ctl), h_ctl, CTL_DOUBLES * sizeof(double), hipMemcpyHostToDevice, stream));
-                if (NF) hipLaunchKernelGGL(k_ba_mask, dim3((NF + 255) / 256), dim3(256), 0, stream, NF, A.dev(h_facPair), d_wrong.p, A.dev(h_facIs));
-                {
-                    const int nPose = K * (int)(sizeof(DPose) / sizeof(double)), nLm = 3 * L;
-                    hipLaunchKernelGGL(k_ba_init_slots, dim3((std::max(nPose, nLm) + 255) / 256, nSlots), dim3(256), 0, stream,
-                                       nPose, (const double*)p_pose0, (double*)d_poseS.p, nLm, p_lm0, d_lmS.p);
-                }
-                VS_CHECK(run_lm(1, NF2, Lp2, k2));
+                if (NF) hipLaunchKernelGGL(k_ba_mask, dim3((NF + 255) / 256), dim3(256), 0, stream, NF, A.dev(H.h_facPair), d_wrong.p, A.dev(H.h_facIs));
+                init_slots();
+                VS_CHECK(run_lm(1, S2.NF2, S2.Lp2, S2.k2));
                 break;
             }
         }
@@ -3475,9 +3012,7 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
         if (L) VS_HIP(hipMemcpyAsync(lmOut, lmFinal, (size_t)3 * L * sizeof(double), hipMemcpyDeviceToHost, stream));
         VS_HIP(hipStreamSynchronize(stream));
     }
-    for (int k = 0; k < K; k++) pose_to_rm16(poseOut[k], R->kf_pose_wc + 16 * (size_t)k);
-    if (L) memcpy(R->lm_xyz, lmOut, (size_t)3 * L * sizeof(double));
-    if (NP) memcpy(R->pair_wrong, wrong.data(), NP);
+    ba_write_result(R, poseOut, lmOut, wrong.data(), K, L, NP);
     return VSLAM_OK;
 }
 
@@ -3493,7 +3028,6 @@ static std::atomic<long long> g_bbsNs[12], g_bbsCalls{0}, g_bbsPolls{0};
 static const char* g_bbsName[12] = {"check+count", "arena fill", "tables+upload", "lm pass 1", "chi2 1", "second-pass prep", "lm pass 2", "chi2 2 + fetch", "results", nullptr, nullptr, nullptr};
 
 // ---- launch plan of the batch: a pure function of the cohort's shape (no device calls; exported as vslam_local_ba_batch_plan) -----
-struct BaPlanKnobs { bool schur2, back2, sharedW; int s2Waves, b2Waves, schurWaves, lmBlocks, s2Layout; };
 static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the environment (none set: the production plan)
     static const bool s2Env = !(getenv("VSLAM_BA_SCHUR2") && atoi(getenv("VSLAM_BA_SCHUR2")) == 0);
     static const bool b2Env = !(getenv("VSLAM_BA_BACK2") && atoi(getenv("VSLAM_BA_BACK2")) == 0);
@@ -3510,75 +3044,6 @@ static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the enviro
     k.s2Layout = getenv("VSLAM_BA_SCHUR2_LAYOUT") ? std::max(0, std::min((int)BA2_PACKED, atoi(getenv("VSLAM_BA_SCHUR2_LAYOUT")))) : (int)BA2_PACKED;
     return k;
 }
-static inline int ba_batch_solve_kind(int n, bool useMfma) { return (n <= 64 && useMfma) ? BA_SOLVE_MFMA64 : n <= BA_WAVE_N ? BA_SOLVE_WAVE : BA_SOLVE_MFMA; }
-// problems outside the batched class (the LDS solve lives in the one-problem path; empty graphs; another rig)
-static inline bool ba_batch_single(const vslam_ba_lane_shape& s, bool useMfma) {
-    return s.own_rig || s.n_free_kf > BA_LDS_MAX_F || s.n_free_kf <= 0 || s.n_factors <= 0 || s.n_pairs <= 0 || (!useMfma && 6 * s.n_free_kf > BA_WAVE_N);
-}
-static void ba_batch_plan(const vslam_ba_batch_shape& S, const BaPlanKnobs& kn, vslam_ba_batch_plan& p) {
-    p = vslam_ba_batch_plan{};
-    const int NB = std::max(1, std::min((int)BA_MAX_NB, (int)S.lookahead));
-    const bool useMfma = S.solver == 0;
-    p.status = VSLAM_OK; p.lookahead = NB;
-    int maxSlots = 1, maxFac = 1, fMax = 0, lpMax = 0, NL = 0;
-    for (int i = 0; i < S.n_lanes; i++) {
-        const vslam_ba_lane_shape& s = S.lanes[i];
-        if (ba_batch_single(s, useMfma)) { p.n_single++; continue; }
-        NL++;
-        maxSlots = std::max(maxSlots, (int)s.max_slots); maxFac = std::max(maxFac, (int)s.max_factors);
-        fMax = std::max(fMax, (int)s.n_free_kf); lpMax = std::max(lpMax, (int)s.n_points);
-        p.solve_kinds |= 1 << ba_batch_solve_kind(6 * s.n_free_kf, useMfma);
-    }
-    p.n_batch = NL; p.f_max = fMax; p.max_slots = maxSlots; p.max_factors = maxFac; p.lp_max = lpMax;
-    if (NL == 0) { p.solve_kinds = 0; return; }
-    const int nCU = 256, nMax = 6 * fMax;
-    const size_t sysMax = (size_t)nMax * nMax + nMax;
-    // k_ba_schur: a wave per landmark, W staging by slots; one workgroup for all lambda candidates (sharedW) when NB copies of the
-    // system fit next to the staging
-    constexpr int SCHUR_LPW = 64 / BA_LPL_SCHUR, BACK_LPW = 64 / BA_LPL_BACK;
-    auto stage_lds = [&](int nw) { return (size_t)nw * SCHUR_LPW * 2 * maxSlots * 18 * sizeof(double) + (size_t)nw * SCHUR_LPW * maxSlots * sizeof(int) + 16; };
-    auto schur_lds = [&](int nw, int copies) { return copies * sysMax * sizeof(double) + stage_lds(nw); };
-    int sharedW = 0, schurWaves = BA_SCHUR_WAVES;
-    if (NB > 1 && kn.sharedW) for (int nw : {16, 12, 8, 6, 4, 2}) if (schur_lds(nw, NB) <= 150 * 1024) { sharedW = 1; schurWaves = nw; break; }
-    if (!sharedW) { if (kn.schurWaves) schurWaves = kn.schurWaves; while (schurWaves > 2 && schur_lds(schurWaves, 1) > 150 * 1024) schurWaves /= 2; }
-    const size_t schurLds = schur_lds(schurWaves, sharedW ? NB : 1);
-    const int schurUnits = schurWaves * SCHUR_LPW;
-    int lmBlocks = std::max(1, std::min((lpMax + schurUnits - 1) / schurUnits, kn.lmBlocks ? kn.lmBlocks : std::max(16, 2 * nCU / NL)));
-    // k_ba_schur2 (tracker windows): one LDS copy of the system + a staging region per landmark-wave
-    const size_t s2StageB = (size_t)ba2_stage_doubles(maxFac, maxSlots) * sizeof(double);
-    int s2Waves = std::max(2, std::min(16, kn.s2Waves));
-    while (s2Waves > 2 && sysMax * sizeof(double) + s2Waves * s2StageB > 156 * 1024) s2Waves /= 2;
-    const size_t s2Lds = sysMax * sizeof(double) + (size_t)s2Waves * s2StageB;
-    const bool useSchur2 = kn.schur2 && fMax <= BA2_MAX_F && maxSlots <= BA2_MAX_F && s2Lds <= 156 * 1024;
-    // (the kernel is a latency chain per landmark-wave: every workgroup of the cohort resident at once - one per CU at this LDS size -,
-    //  each wave walks a few landmarks)
-    if (useSchur2) lmBlocks = std::max(1, std::min((lpMax + 2 * s2Waves - 1) / (2 * s2Waves), kn.lmBlocks ? kn.lmBlocks : std::max(4, (16 / s2Waves) * nCU / NL)));
-    // k_ba_back2 holds b2Waves staging regions and no system: that k_ba_schur2 fits does not make it fit (4 regions of a landmark with
-    // ~120-200 stereo views exceed 160 KB where 2 regions + the system do not), so it halves its own waves until the launch fits
-    int b2Waves = std::max(1, std::min(8, kn.b2Waves));
-    while (b2Waves > 1 && (size_t)b2Waves * s2StageB > BA_DYN_LDS_MAX) b2Waves /= 2;
-    const size_t b2Lds = (size_t)b2Waves * s2StageB;
-    const bool useBack2 = useSchur2 && kn.back2 && b2Lds <= BA_DYN_LDS_MAX;
-    int backWaves = BA_SCHUR_WAVES / BACK_LPW;
-    auto back_lds = [&](int nw) { return (size_t)nw * BACK_LPW * maxSlots * 18 * sizeof(double) + (size_t)nw * BACK_LPW * maxSlots * sizeof(int) + 16; };
-    while (backWaves > 1 && back_lds(backWaves) > 150 * 1024) backWaves /= 2;
-    p.schur_kernel = useSchur2 ? VSLAM_BA_KERNEL_SCHUR2 : VSLAM_BA_KERNEL_SCHUR;
-    p.schur_waves = useSchur2 ? s2Waves : schurWaves;
-    p.schur_shared_w = useSchur2 ? 0 : sharedW;
-    p.schur_blocks = lmBlocks;
-    // (the rules above keep computing with the row-major size: the plans per shape stay; only the LDS asked for follows the layout)
-    p.schur_lds = (int)(useSchur2 ? (size_t)ba2_sys_doubles(nMax, kn.s2Layout) * sizeof(double) + (size_t)s2Waves * s2StageB : schurLds);
-    p.back_kernel = useBack2 ? VSLAM_BA_KERNEL_BACK2 : VSLAM_BA_KERNEL_BACK;
-    if (useBack2) {
-        p.back_waves = b2Waves; p.back_shared = 1; p.back_lds = (int)b2Lds;
-        p.back_blocks = std::max(1, std::min((lpMax + 2 * b2Waves - 1) / (2 * b2Waves), std::max(8, (16 / b2Waves) * nCU / NL)));
-    } else {
-        p.back_waves = backWaves; p.back_shared = NB > 1 ? 1 : 0; p.back_lds = (int)back_lds(backWaves);
-        p.back_blocks = std::max(1, std::min((lpMax + backWaves * BACK_LPW - 1) / (backWaves * BACK_LPW), std::max(16, 2 * nCU / NL)));
-    }
-    p.solve_lds = (p.solve_kinds & (1 << BA_SOLVE_MFMA)) ? (int)(((size_t)BA_MFMA_N * BA_MFMA_LD + 16 + BA_MFMA_N) * sizeof(double)) : 0;
-    if (p.schur_lds > BA_DYN_LDS_MAX || p.back_lds > BA_DYN_LDS_MAX || p.solve_lds > BA_DYN_LDS_MAX) p.status = VSLAM_ERR_CAPACITY;
-}
 thread_local vslam_ba_batch_plan g_baLastPlan{};
 
 static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_result* const* Rs, int N, int device) {
@@ -3588,10 +3053,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     auto bbs_t = std::chrono::steady_clock::now();
     g_bbsCalls++;
     auto BBS = [&](int k) { const auto t_ = std::chrono::steady_clock::now(); g_bbsNs[k] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - bbs_t).count(); bbs_t = t_; };
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
-    VS_HIP(hipSetDevice(device));
+    VS_CHECK(ba_select_device(device));
     struct BatchWs {
         hipStream_t stream = nullptr; int device = -1;
         PinnedArena arena;
@@ -3621,13 +3083,12 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     hipStream_t stream = W.stream;
     g_baTimer.reset(); g_baTimer.stream = stream; g_baTimer.multi = true;
 
-    static const int nbEnv = [] { const char* e = getenv("VSLAM_BA_LOOKAHEAD"); return e ? std::max(1, std::min((int)BA_MAX_NB, atoi(e))) : (int)BA_MAX_NB; }();
-    const int NB = g_baLookahead > 0 ? std::min(g_baLookahead, (int)BA_MAX_NB) : nbEnv, nSlots = NB + 1;
+    const int NB = ba_lm_knobs().NB, nSlots = NB + 1;
     const bool useMfma = ba_use_mfma();
     const double relTol = 1e-5, absTol = 1e-5;
     // adaptive look-ahead (BaDev::adaptive): a round evaluates ONE lambda candidate while steps are being accepted and all NB only
     // after a rejection - the same LM trajectory; in a batch the cost of a round is the candidates it evaluates (throughput, not latency)
-    static const int adaptEnv = [] { const char* e = getenv("VSLAM_BA_ADAPTIVE"); return e ? atoi(e) : -1; }();
+    static const int adaptEnv = ba_adaptive_env();
     const bool adaptive = NB > 1 && (adaptEnv >= 0 ? adaptEnv != 0 : true);
 
     struct Lane {
@@ -3640,7 +3101,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         DPose* d_poseS; double *d_lmS, *d_facJ, *d_dP, *d_dL, *d_S, *d_Sedge, *d_partial, *d_Spart, *d_sums, *d_Lg; int* d_flags; uint8_t* d_wrong;
         double *d_outPose, *d_outLm;
         size_t oWrong, oOut;          // offsets in the landing area
-        long long NF2 = 0, Lp2 = 0, k2 = 0;
+        BaSecondPass S2;
         bool pass2 = false;
     };
     std::vector<Lane> lanes(N);
@@ -3654,18 +3115,10 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     for (int i = 0; i < N; i++) {
         Lane& q = lanes[i];
         const vslam_ba_problem* P = Ps[i]; vslam_ba_result* R = Rs[i];
-        if (!P || !R || P->n_kf < 1 || P->n_lm < 0 || P->n_pairs < 0 || P->n_levels < 1 || P->n_levels > MAX_LEVELS ||
-            !P->kf_pose_wc || !P->kf_id || !P->kf_fixed || !P->kf_local || !P->sigma_factor || !P->inv_sigma_factor ||
-            !R->kf_pose_wc || !R->lm_xyz || !R->pair_wrong || (P->n_lm > 0 && !P->lm_xyz) ||
-            (P->n_pairs > 0 && (!P->pair_kf || !P->pair_lm || !P->pair_flags || !P->pair_uv || !P->pair_octave))) {
-            set_error("vslam_local_ba_batch: invalid problem %d", i);
-            return VSLAM_ERR_INVALID;
-        }
+        const int bad = ba_check_problem(P, R);
+        if (bad == BA_PROBLEM_INVALID) { set_error("vslam_local_ba_batch: invalid problem %d", i); return VSLAM_ERR_INVALID; }
+        if (bad) { set_error("vslam_local_ba_batch: pair index out of range (problem %d)", i); return VSLAM_ERR_INVALID; }
         q.P = P; q.R = R; q.K = P->n_kf; q.L = P->n_lm; q.NP = P->n_pairs;
-        for (int p = 0; p < q.NP; p++)
-            if (P->pair_kf[p] < 0 || P->pair_kf[p] >= q.K || P->pair_lm[p] < 0 || P->pair_lm[p] >= q.L ||
-                P->pair_octave[2 * p] < 0 || P->pair_octave[2 * p] >= P->n_levels || P->pair_octave[2 * p + 1] < 0 ||
-                P->pair_octave[2 * p + 1] >= P->n_levels) { set_error("vslam_local_ba_batch: pair index out of range (problem %d)", i); return VSLAM_ERR_INVALID; }
         // (the rig is the lane's own - BaDev / BaChi2 carry fx, fy, cx, cy, b per lane, the host fill reads its own problem: the lanes of a
         //  fleet's cohort have different cameras and stay on the batched path; only another pyramid depth runs on its own)
         q.ownRig = P->n_levels != Ps[0]->n_levels;
@@ -3744,7 +3197,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     plan_cohort();
     const vslam_ba_batch_plan& plan = g_baLastPlan;
     if (plan.status != VSLAM_OK) { set_error("local BA batch: landmark with too many views for the LDS staging"); return VSLAM_ERR_CAPACITY; }
-    const int nCU = 256;
+    const int nCU = BA_NCU;
     const int obsBlocks = std::max(1, std::min((nfMax + 255) / 256, std::max(16, 2 * nCU / NL)));
     const int facBlocks = obsBlocks + std::max(neMax, 1);
     const size_t sysMax = (size_t)nMax * nMax + nMax;
@@ -3808,31 +3261,16 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         q.d_outLm = (double*)(W.h_back + q.oOut + (o.outLm - o.outPose));
         BaDev D{};
         const int n = H.n, K = q.K, L = q.L;
-        D.NF = H.NF; D.Lp = H.Lp; D.F = H.F; D.K = K; D.NE = H.NE; D.n = n;
-        D.facKf = A.dev(H.h_facKf); D.facFi = A.dev(H.h_facFi); D.facLp = A.dev(H.h_facLp); D.facLm = A.dev(H.h_facLm);
-        D.facZ = A.dev(H.h_facZ); D.facIs = A.dev(H.h_facIs); D.facRight = A.dev(H.h_facRight); D.facJ = q.d_facJ;
-        D.lpStart = A.dev(H.h_lpStart); D.lpSlotStart = A.dev(H.h_lpSlotStart); D.slotStart = A.dev(H.h_slotStart); D.slotFi = A.dev(H.h_slotFi);
-        D.lpOrig = A.dev(H.h_lpOrig); D.poseCur = q.d_poseS; D.poseTrial = q.d_poseS + K; D.fidx = A.dev(H.h_fidx);
-        D.lmCur = q.d_lmS; D.lmTrial = q.d_lmS + (size_t)3 * L; D.edges = A.dev(H.h_edges);
-        D.S = q.d_S; D.rhs = q.d_S + (size_t)n * n; D.Sedge = q.d_Sedge; D.dP = q.d_dP; D.dL = q.d_dL; D.sums = q.d_sums; D.flags = q.d_flags;
-        D.fx = P->rig.fx; D.fy = P->rig.fy; D.cx = P->rig.cx; D.cy = P->rig.cy; D.b = (double)P->rig.baseline;
-        D.ctl = A.dev(H.h_ctl);
-        D.NB = NB; D.specLin = 1; D.adaptive = adaptive ? 1 : 0;
-        D.poseBase = q.d_poseS; D.lmBase = q.d_lmS; D.lmStride = (size_t)3 * L;
-        D.facJBase = q.d_facJ; D.facJStride = (size_t)20 * H.NF; D.SedgeBase = q.d_Sedge; D.edgesBase = A.dev(H.h_edges);
-        D.sysStride = (size_t)n * n + 2 * n + 8; D.dLStride = (size_t)3 * H.Lp;
+        ba_fill_dev(D, H, A, BaLaneBufs{K, L, q.d_poseS, q.d_lmS, q.d_facJ, q.d_S, q.d_Sedge, q.d_dP, q.d_dL, q.d_sums, q.d_flags}, P->rig, NB, true, adaptive);
         D.partialStride = (size_t)2 * obsBlocks + 2 * (size_t)std::max(H.NE, 1); D.partial = q.d_partial;
         D.spartStride = part_doubles(n) * lmBlocks; D.Spart = q.d_Spart;
-        D.solveKind = ba_batch_solve_kind(n, useMfma);
+        D.solveKind = ba_solve_kind(n, useMfma);
         D.Lg = q.d_Lg;
         D.ctlHost = (double*)(W.h_back + oBackCtl) + (size_t)CTL_DOUBLES * a;
         *H.h_D = D;
         BaLaneAux X{};
-        X.C.NP = q.NP; X.C.pairKf = A.dev(q.h_pairKf); X.C.pairLm = A.dev(q.h_pairLm); X.C.pairFlags = A.dev(q.h_pairFlags); X.C.pairUv = A.dev(q.h_pairUv);
-        X.C.pairOct = A.dev(q.h_pairOct); X.C.kfLocal = A.dev(q.h_kfLocal); X.C.kfPresent = A.dev(H.h_kfPresent); X.C.lmPresent = A.dev(H.h_lmPresent);
-        X.C.wrong = q.d_wrong;
-        for (int l = 0; l < P->n_levels; l++) X.C.thr[l] = (float)((double)7.815f * (double)P->sigma_factor[l]);
-        X.C.fx = D.fx; X.C.fy = D.fy; X.C.cx = D.cx; X.C.cy = D.cy; X.C.b = D.b;
+        ba_fill_chi(X.C, P, BaPairArrays{A.dev(q.h_pairKf), A.dev(q.h_pairLm), A.dev(q.h_pairOct), A.dev(q.h_pairFlags), A.dev(q.h_pairUv), A.dev(q.h_kfLocal)},
+                    A.dev(H.h_kfPresent), A.dev(H.h_lmPresent), q.d_wrong);
         X.NF = H.NF; X.facPair = A.dev(H.h_facPair); X.facIs = A.dev(H.h_facIs);
         X.nPose = K * (int)(sizeof(DPose) / sizeof(double)); X.nLm = 3 * L; X.pose0 = (const double*)A.dev(q.h_pose0); X.lm0 = A.dev(q.h_lm0);
         X.outPose = q.d_outPose; X.outLm = q.d_outLm;
@@ -3921,15 +3359,8 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         for (int a = 0; a < NL; a++) {
             Lane& q = lanes[act[a]];
             if (ps == 1 && !q.pass2) continue;
-            const double* c = b_ctl + (size_t)CTL_DOUBLES * a;
-            const int* ci = (const int*)(c + CTL_INTS);
-            vslam_ba_result* R = q.R;
-            R->report[ps].iterations = ci[CI_ITER]; R->report[ps].inner_iterations = ci[CI_INNER];
-            R->report[ps].initial_error = c[CTL_INIT_ERR]; R->report[ps].final_error = c[CTL_ERROR]; R->report[ps].lambda = c[CTL_LAMBDA];
-            R->n_free_kf = q.H.F;
-            R->rounds = (ps == 0 ? 0 : R->rounds) + ci[CI_ROUNDS];
-            if (ps == 0) { R->n_residuals = q.H.NF; R->n_landmarks = q.H.Lp; R->sum_k2 = q.H.sumK2; }
-            else { R->n_residuals = q.NF2; R->n_landmarks = q.Lp2; R->sum_k2 = q.k2; }
+            if (ps == 0) ba_write_report(q.R, 0, b_ctl + (size_t)CTL_DOUBLES * a, q.H.F, q.H.NF, q.H.Lp, q.H.sumK2);
+            else ba_write_report(q.R, 1, b_ctl + (size_t)CTL_DOUBLES * a, q.H.F, q.S2.NF2, q.S2.Lp2, q.S2.k2);
         }
     };
     const int chiBlocks = std::max(1, (std::max(npMax, valMax) + 255) / 256);
@@ -3957,32 +3388,11 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         const BaPassHost& H = q.H;
         memcpy(q.wrong.data(), W.h_back + q.oWrong, q.NP);
         if (q.R->pair_wrong_pass1) memcpy(q.R->pair_wrong_pass1, q.wrong.data(), q.NP);
-        std::vector<uint8_t> kfP2(q.K, 0), lmP2(std::max(q.L, 1), 0);
-        long long NF2 = 0;
-        for (int p = 0; p < q.NP; p++) {
-            if (q.wrong[p]) continue;
-            const int fl = P->pair_flags[p] & 3;
-            if (!fl) continue;
-            kfP2[P->pair_kf[p]] = 1; lmP2[P->pair_lm[p]] = 1; NF2 += (fl & 1) + (fl >> 1);
-        }
-        bool same = g_baMask != 0;
-        for (int k = 0; k < q.K && same; k++) if (kfP2[k] != q.T.kfPresent[k]) same = false;
-        int* ci = (int*)(H.h_ctl + CTL_INTS);
-        if (!same) { q.pass2 = false; ci[CI_STATE] = BA_DONE; ci[CI_FIRST] = 0; return; }      // (stays out of the second round)
-        long long Lp2 = 0, k2 = 0;
-        for (int l = 0; l < q.L; l++) Lp2 += lmP2[l];
-        for (int lp = 0; lp < H.Lp; lp++) {
-            int ns = 0, last = -2;
-            for (int f = H.h_lpStart[lp]; f < H.h_lpStart[lp + 1]; f++) {
-                if (q.wrong[H.h_facPair[f]]) continue;
-                const int fi = H.h_facFi[f];
-                if (fi >= 0 && fi != last) { last = fi; ns++; }
-            }
-            k2 += (long long)ns * ns;
-        }
-        q.NF2 = NF2; q.Lp2 = Lp2; q.k2 = k2; q.pass2 = true;
-        for (int k = 0; k < q.K; k++) H.h_kfPresent[k] = kfP2[k];
-        for (int l = 0; l < q.L; l++) H.h_lmPresent[l] = lmP2[l];
+        H.second_pass(P, q.wrong.data(), 0, 1, q.T, nullptr, q.S2);
+        q.pass2 = g_baMask != 0 && q.S2.same;
+        if (!q.pass2) { int* ci = (int*)(H.h_ctl + CTL_INTS); ci[CI_STATE] = BA_DONE; ci[CI_FIRST] = 0; return; }      // (stays out of the second round)
+        for (int k = 0; k < q.K; k++) H.h_kfPresent[k] = q.S2.kfP2[k];
+        for (int l = 0; l < q.L; l++) H.h_lmPresent[l] = q.S2.lmP2[l];
         ba_init_ctl(H.h_ctl, 1, adaptive ? 1 : NB);
     });
     for (int a = 0; a < NL; a++) if (!lanes[act[a]].pass2) redo.push_back(act[a]);
@@ -4004,9 +3414,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         if (!q.pass2) continue;
         const DPose* po = (const DPose*)(W.h_back + q.oOut);
         const double* lo = (const double*)(W.h_back + q.oOut + (((size_t)q.K * sizeof(DPose) + 255) & ~(size_t)255));
-        for (int k = 0; k < q.K; k++) pose_to_rm16(po[k], q.R->kf_pose_wc + 16 * (size_t)k);
-        if (q.L) memcpy(q.R->lm_xyz, lo, (size_t)3 * q.L * sizeof(double));
-        if (q.NP) memcpy(q.R->pair_wrong, W.h_back + q.oWrong, q.NP);
+        ba_write_result(q.R, po, lo, W.h_back + q.oWrong, q.K, q.L, q.NP);
     }
     BBS(8);
     for (int i : redo) VS_CHECK(ba_run(Ps[i], Rs[i], device, nullptr));
@@ -4217,9 +3625,7 @@ vslam_status vslam_ba_refresh_depth(const vslam_rig* rig, int32_t n_kf, const do
     }
     for (int p = 0; p < n_pairs; p++)
         if (pair_kf[p] < 0 || pair_kf[p] >= n_kf || pair_lm[p] < 0 || pair_lm[p] >= n_lm) { set_error("vslam_ba_refresh_depth: pair index out of range"); return VSLAM_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    VS_CHECK(ba_check_device(device));
     if (n_pairs == 0) return VSLAM_OK;
     return vslam::refresh_depth_sync(nullptr, vslam::refresh_close_th(*rig), n_kf, kf_pose_wc, n_lm, lm_xyz, lm_outlier, n_pairs, pair_kf, pair_lm,
                                      pair_wrong, cur_depth, device, depth_out, close_out, updated_out);
@@ -4247,9 +3653,7 @@ vslam_status vslam_ba_refresh_depth_merged(const vslam_rig* rigs, const int32_t*
     }
     for (int p = 0; p < n_pairs; p++)
         if (pair_kf[p] < 0 || pair_kf[p] >= n_kf || pair_lm[p] < 0 || pair_lm[p] >= n_lm) { set_error("vslam_ba_refresh_depth_merged: pair index out of range"); return VSLAM_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return VSLAM_ERR_INVALID;
+    VS_CHECK(ba_check_device(device));
     if (n_pairs == 0) return VSLAM_OK;
     vslam::RefreshTicket tk{};
     vslam_status st = VSLAM_ERR_CAPACITY;
