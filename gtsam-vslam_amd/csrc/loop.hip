@@ -1,7 +1,9 @@
 // Loop closing of a stereo session (no reference counterpart; vslam_hip.h): the relocalisation
 // stage asked on the part of the map the tracker has left behind, a pose graph over the keyframes solved by
-// vslam_pose_graph_optimize, and the commit that hands the old copy of the place back to the tracker.
+// vslam_pose_graph_optimize, and the commit that hands the old copy of the place back to the tracker.  vslam_system_fuse_loop (item 26)
+// then makes one map point of each landmark the two visits both triangulated.
 #include "system.hpp"
+#include "fuse_host.hpp"
 #include <set>
 
 using namespace vslam;
@@ -248,7 +250,127 @@ vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_r
     return loop_apply(rep->kf_loop, T_corr, P, rep);
 }
 
+// The duplicate map points of a revisited place (vslam_hip.h): B = the non-outlier map points created up to latestKF - min_kf_gap,
+// A = those created since, vslam_fuse_search under the current camera, the commit of fuse_host.hpp.  mapMutex is held from the sets
+// to the commit: nothing may touch the map between them.
+vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
+    static const char* const fn = "vslam_system_fuse_loop";
+    if (!rep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check(fn));
+    vslam_fuse_loop_params P = prm ? *prm : vslam_fuse_loop_params{};
+    const vslam_fuse_params& S = P.search;
+    if (P.min_kf_gap < 0 || S.max_hamming < 0 || !(S.radius >= 0) || !(S.depth_ratio >= 0) || !std::isfinite(S.radius) || !std::isfinite(S.depth_ratio)) {
+        set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID;
+    }
+    if (S.depth_ratio > 0 && S.depth_ratio < 1) { set_error("%s: depth_ratio %g lies inside (0, 1)", fn, (double)S.depth_ratio); return VSLAM_ERR_INVALID; }
+    if (P.min_kf_gap == 0) P.min_kf_gap = 20;
+    *rep = vslam_fuse_loop_report{};
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    VS_HIP(hipSetDevice(cfg.device));
+    std::lock_guard<std::mutex> lk(mapMutex);
+    if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
+        VS_CHECK(change_poses_lca(endLBAIdx));
+        LBADone = false;
+    }
+    std::vector<int> idA, idB;
+    const long long newest = (long long)latestKF - P.min_kf_gap;
+    for (int m = 0; m < (int)mapPoints.size(); m++) {
+        if (mpOutlier[m]) continue;
+        (mapPoints[m].kdx <= newest ? idB : idA).push_back(m);
+    }
+    if (idA.size() > 65536) idA.erase(idA.begin(), idA.end() - 65536);
+    if (idB.size() > 65536) idB.erase(idB.begin(), idB.end() - 65536);
+    const int nA = (int)idA.size(), nB = (int)idB.size();
+    rep->n_a = nA; rep->n_b = nB;
+    fusedPairs.clear();
+    std::vector<double> xyz(3 * (size_t)(nA + nB) + 1);
+    std::vector<uint8_t> desc(32 * (size_t)(nA + nB) + 1);
+    auto fill = [&](const std::vector<int>& ids, size_t at) {
+        for (size_t j = 0; j < ids.size(); j++) {
+            const SysMP& mp = mapPoints[ids[j]];
+            for (int c = 0; c < 3; c++) xyz[3 * (at + j) + c] = mp.wp[c];
+            memcpy(&desc[32 * (at + j)], mp.desc, 32);
+        }
+    };
+    fill(idA, 0); fill(idB, (size_t)nA);
+    std::vector<int> match(std::max(nA, 1), -1), best(4 * (size_t)std::max(nA, 1), 0);
+    VS_CHECK(vslam_fuse_search(camPoseInv.data(), cfg.rig.fx, cfg.rig.fy, cfg.rig.cx, cfg.rig.cy, cfg.rig.width, cfg.rig.height,
+                               xyz.data(), desc.data(), nA, xyz.data() + 3 * (size_t)nA, desc.data() + 32 * (size_t)nA, nB,
+                               &P.search, cfg.device, match.data(), best.data(), &rep->search));
+    std::vector<std::pair<int, int>> pairs;                // ascending a: idA is in creation order
+    for (int j = 0; j < nA; j++) if (match[j] >= 0) pairs.push_back({idA[j], idB[match[j]]});
+    rep->n_active_after = (int)active.size();
+    if (pairs.empty()) return VSLAM_OK;
+    const vslam_fuse::CommitCounts c = vslam_fuse::merge_observations(pairs, mapPoints, keyFrames, mpOutlier, mpInFrame);
+    for (int k : c.refresh) calc_connections(keyFrames[k]);
+    vslam_fuse::merge_active(pairs, mapPoints.size(), active, mpInFrame);
+    lastMatches.clear(); lastOutliers.clear();
+    for (const auto& pr : pairs) { fusedPairs.push_back(pr.first); fusedPairs.push_back(pr.second); }
+    rep->n_fused = c.nFused; rep->n_obs_moved = c.nMoved; rep->n_obs_dropped = c.nDropped;
+    rep->n_keyframes_touched = (int)c.touched.size();
+    rep->n_active_after = (int)active.size();
+    return VSLAM_OK;
+}
+
 extern "C" {
+
+vslam_status vslam_system_fuse_loop(vslam_system* s, const vslam_fuse_loop_params* params, vslam_fuse_loop_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->fuse_loop(params, report);
+}
+
+vslam_status vslam_system_map_point_descriptors(vslam_system* s, int32_t cap, int32_t* n_out, uint8_t* desc) {
+    if (!s || !n_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    const int n = (int)s->mapPoints.size();
+    *n_out = n;
+    if (n > cap) return VSLAM_ERR_CAPACITY;
+    if (desc) for (int i = 0; i < n; i++) memcpy(desc + 32 * (size_t)i, s->mapPoints[i].desc, 32);
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system_map_point_observations(vslam_system* s, int32_t cap_points, int32_t cap_obs, int32_t* n_out, int32_t* n_obs_out,
+                                                 int32_t* offsets, int32_t* triples) {
+    if (!s || !n_out || !n_obs_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    const int n = (int)s->mapPoints.size();
+    long long nObs = 0;
+    for (const SysMP& mp : s->mapPoints) nObs += (long long)mp.kfm.size();
+    *n_out = n; *n_obs_out = (int32_t)nObs;
+    if (!offsets && !triples) return VSLAM_OK;
+    if (n > cap_points || nObs > cap_obs || !offsets || !triples) return VSLAM_ERR_CAPACITY;
+    int q = 0;
+    for (int i = 0; i < n; i++) {
+        offsets[i] = q;
+        for (const KfMatch& o : s->mapPoints[i].kfm) { triples[3 * q] = o.kf; triples[3 * q + 1] = o.l; triples[3 * q + 2] = o.r; q++; }
+    }
+    offsets[n] = q;
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system_keyframe_points(vslam_system* s, int32_t kf, int32_t cap_l, int32_t cap_r, int32_t* n_l_out, int32_t* n_r_out,
+                                          int32_t* lmp_l, int32_t* lmp_r) {
+    if (!s || !n_l_out || !n_r_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    if (kf < 0 || kf >= (int)s->keyFrames.size()) { set_error("vslam_system_keyframe_points: keyframe %d of %d", kf, (int)s->keyFrames.size()); return VSLAM_ERR_INVALID; }
+    const SysKF& K = s->keyFrames[kf];
+    *n_l_out = (int)K.lmpL.size(); *n_r_out = (int)K.lmpR.size();
+    if (!lmp_l && !lmp_r) return VSLAM_OK;
+    if ((int)K.lmpL.size() > cap_l || (int)K.lmpR.size() > cap_r || !lmp_l || !lmp_r) return VSLAM_ERR_CAPACITY;
+    std::copy(K.lmpL.begin(), K.lmpL.end(), lmp_l);
+    std::copy(K.lmpR.begin(), K.lmpR.end(), lmp_r);
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system_fused_pairs(vslam_system* s, int32_t cap, int32_t* n_out, int32_t* pairs) {
+    if (!s || !n_out) return VSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    const int n = (int)s->fusedPairs.size() / 2;
+    *n_out = n;
+    if (n > cap) return VSLAM_ERR_CAPACITY;
+    if (pairs) std::copy(s->fusedPairs.begin(), s->fusedPairs.end(), pairs);
+    return VSLAM_OK;
+}
 
 vslam_status vslam_system_correct_loop(vslam_system* s, int32_t kf_loop, const double* T_wc_corrected, const vslam_loop_params* params,
                                        vslam_loop_report* report) {

@@ -316,6 +316,10 @@ struct vslam_system {
     vslam_status loop_check_close(const char* fn) const;
     vslam_status correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep);
     vslam_status close_loop(const vslam_loop_params* prm, vslam_loop_report* rep);
+    // the duplicate map points of a revisited place become one: the two sets, vslam_fuse_search under
+    // the current camera, the commit of fuse_host.hpp.  fusedPairs: the (absorbed, kept) pairs of the last call (test tap)
+    std::vector<int> fusedPairs;
+    vslam_status fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

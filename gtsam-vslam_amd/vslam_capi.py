@@ -421,6 +421,95 @@ def pose_graph_timings():
     return {names[i].decode(): float(ms[i]) for i in range(n.value)}
 
 
+class FuseParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("depth_ratio", C.c_float), ("max_hamming", C.c_int32)]
+
+
+class FuseReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_visible_a", "n_visible_b", "n_proposals", "n_pairs")]
+
+
+class FuseLane(C.Structure):
+    _fields_ = [("T_cw", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("w", C.c_int32), ("h", C.c_int32), ("a_xyz", C.c_void_p), ("a_desc", C.c_void_p), ("n_a", C.c_int32),
+                ("b_xyz", C.c_void_p), ("b_desc", C.c_void_p), ("n_b", C.c_int32), ("match", C.c_void_p), ("best", C.c_void_p)]
+
+
+class FuseLoopParams(C.Structure):
+    _fields_ = [("search", FuseParams), ("min_kf_gap", C.c_int32)]
+
+
+class FuseLoopReport(C.Structure):
+    _fields_ = [("busy", C.c_int32), ("n_a", C.c_int32), ("n_b", C.c_int32), ("search", FuseReport)] + \
+               [(n, C.c_int32) for n in ("n_fused", "n_obs_moved", "n_obs_dropped", "n_keyframes_touched", "n_active_after")]
+
+
+def _fuse_report_dict(rep):
+    return {f[0]: getattr(rep, f[0]) for f in FuseReport._fields_}
+
+
+def _fuse_arrays(T_cw, xyz_a, desc_a, xyz_b, desc_b):
+    T = np.ascontiguousarray(T_cw, np.float64).reshape(4, 4)
+    xa = np.ascontiguousarray(xyz_a, np.float64).reshape(-1, 3); da = np.ascontiguousarray(desc_a, np.uint8).reshape(-1, 32)
+    xb = np.ascontiguousarray(xyz_b, np.float64).reshape(-1, 3); db = np.ascontiguousarray(desc_b, np.uint8).reshape(-1, 32)
+    assert len(xa) == len(da) and len(xb) == len(db)
+    return T, xa, da, xb, db
+
+
+def fuse_search(T_cw, K, size, xyz_a, desc_a, xyz_b, desc_b, radius=0.0, depth_ratio=0.0, max_hamming=0, device=0, fill=None):
+    """vslam_fuse_search: T_cw (4, 4) camera <- world, K = (fx, fy, cx, cy), size = (w, h), the two sets.  Returns (match (nA),
+    best (nA, 4), report dict).  fill: an int32 value the outputs and the report are pre-filled with (a refused or idle call
+    leaves it there; default -1 / 0 / 0)."""
+    T, xa, da, xb, db = _fuse_arrays(T_cw, xyz_a, desc_a, xyz_b, desc_b)
+    nA = len(xa)
+    match = np.full(max(nA, 1), -1 if fill is None else fill, np.int32)
+    best = np.full((max(nA, 1), 4), 0 if fill is None else fill, np.int32)
+    rep = FuseReport(*([0 if fill is None else fill] * 4))
+    prm = FuseParams(float(radius), float(depth_ratio), int(max_hamming))
+    _chk(lib().vslam_fuse_search(_p(T), C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), int(size[0]), int(size[1]),
+                                 _p(xa), _p(da), nA, _p(xb), _p(db), len(xb), C.byref(prm), int(device), _p(match), _p(best), C.byref(rep)))
+    return match[:nA], best[:nA], _fuse_report_dict(rep)
+
+
+def fuse_search_batch(lanes, radius=0.0, depth_ratio=0.0, max_hamming=0, device=0, fill=None):
+    """vslam_fuse_search_batch: lanes = [(T_cw, K, size, xyz_a, desc_a, xyz_b, desc_b) or None (an idle lane), ...], one parameter
+    set for all.  Returns [(match, best, report dict), ...]; an idle lane's arrays are empty and its report holds the fill."""
+    B = len(lanes)
+    tab = (FuseLane * max(B, 1))()
+    reps = (FuseReport * max(B, 1))()
+    f = 0 if fill is None else fill
+    for g in range(B):
+        reps[g] = FuseReport(f, f, f, f)
+    keep, outs = [], []
+    for g, ln in enumerate(lanes):
+        if ln is None:
+            outs.append((np.zeros(0, np.int32), np.zeros((0, 4), np.int32)))
+            continue
+        T, xa, da, xb, db = _fuse_arrays(ln[0], *ln[3:7])
+        nA = len(xa)
+        match = np.full(max(nA, 1), -1 if fill is None else fill, np.int32)
+        best = np.full((max(nA, 1), 4), f, np.int32)
+        keep.append((T, xa, da, xb, db))
+        outs.append((match[:nA], best[:nA]))
+        K, size = ln[1], ln[2]
+        tab[g] = FuseLane(T.ctypes.data, K[0], K[1], K[2], K[3], int(size[0]), int(size[1]), xa.ctypes.data, da.ctypes.data, nA,
+                          xb.ctypes.data, db.ctypes.data, len(xb), match.ctypes.data, best.ctypes.data)
+    prm = FuseParams(float(radius), float(depth_ratio), int(max_hamming))
+    _chk(lib().vslam_fuse_search_batch(tab, B, C.byref(prm), int(device), reps))
+    return [(outs[g][0], outs[g][1], _fuse_report_dict(reps[g])) for g in range(B)]
+
+
+def fuse_set_timing(on):
+    _chk(lib().vslam_fuse_set_timing(int(bool(on))))
+
+
+def fuse_timings():
+    """stage -> device ms of this thread's last fuse_search / fuse_search_batch (after fuse_set_timing(True))"""
+    names = (C.c_char_p * 4)(); ms = (C.c_float * 4)(); n = C.c_int32()
+    _chk(lib().vslam_fuse_timings(names, ms, 4, C.byref(n)))
+    return {names[i].decode(): float(ms[i]) for i in range(n.value)}
+
+
 class LoopParams(C.Structure):
     _fields_ = [("reloc", RelocParams), ("pgo", PgoParams), ("min_kf_gap", C.c_int32), ("covis_min", C.c_int32),
                 ("loop_weight", C.c_double), ("detect_only", C.c_int32)]
@@ -1348,6 +1437,53 @@ class System:
         prm = self._loop_params(params)
         _chk(self.L.vslam_system_close_loop(self.h_sys, C.byref(prm), C.byref(rep)))
         return _loop_report_dict(rep)
+
+    def fuse_loop(self, **params):
+        """vslam_system_fuse_loop: the duplicate map points of the place the camera sees become one.  params: radius, depth_ratio,
+        max_hamming, min_kf_gap.  Returns the report dict (busy: nothing was done)."""
+        prm = FuseLoopParams()
+        for k, v in params.items():
+            if k == "min_kf_gap":
+                prm.min_kf_gap = int(v)
+            elif k == "max_hamming":
+                prm.search.max_hamming = int(v)
+            else:
+                setattr(prm.search, k, float(v))     # radius, depth_ratio
+        rep = FuseLoopReport()
+        _chk(self.L.vslam_system_fuse_loop(self.h_sys, C.byref(prm), C.byref(rep)))
+        d = {f[0]: getattr(rep, f[0]) for f in FuseLoopReport._fields_ if f[0] != "search"}
+        d["search"] = _fuse_report_dict(rep.search)
+        return d
+
+    def map_point_descriptors(self):
+        """test tap: (n, 32) descriptor bytes of every map point, creation order"""
+        n = C.c_int32(); d = np.zeros((max(self.counts()["map_points"], 1), 32), np.uint8)
+        _chk(self.L.vslam_system_map_point_descriptors(self.h_sys, len(d), C.byref(n), _p(d)))
+        return d[:n.value].copy()
+
+    def map_point_observations(self):
+        """test tap: (offsets (n + 1), triples (n_obs, 3) of (keyframe, left index, right index)) over every map point"""
+        n = C.c_int32(); m = C.c_int32()
+        _chk(self.L.vslam_system_map_point_observations(self.h_sys, 0, 0, C.byref(n), C.byref(m), None, None))
+        off = np.zeros(n.value + 1, np.int32); tr = np.zeros((max(m.value, 1), 3), np.int32)
+        _chk(self.L.vslam_system_map_point_observations(self.h_sys, n.value, len(tr), C.byref(n), C.byref(m), _p(off), _p(tr)))
+        return off, tr[:m.value].copy()
+
+    def keyframe_points(self, kf):
+        """test tap: (localMapPoints, localMapPointsR) of keyframe kf as map-point indices, -1 for none"""
+        nl = C.c_int32(); nr = C.c_int32()
+        _chk(self.L.vslam_system_keyframe_points(self.h_sys, int(kf), 0, 0, C.byref(nl), C.byref(nr), None, None))
+        a = np.zeros(max(nl.value, 1), np.int32); b = np.zeros(max(nr.value, 1), np.int32)
+        _chk(self.L.vslam_system_keyframe_points(self.h_sys, int(kf), len(a), len(b), C.byref(nl), C.byref(nr), _p(a), _p(b)))
+        return a[:nl.value].copy(), b[:nr.value].copy()
+
+    def fused_pairs(self):
+        """test tap: (n, 2) (absorbed, kept) map-point indices of the last fuse_loop call"""
+        n = C.c_int32()
+        self.L.vslam_system_fused_pairs(self.h_sys, 0, C.byref(n), None)
+        pr = np.zeros((max(n.value, 1), 2), np.int32)
+        _chk(self.L.vslam_system_fused_pairs(self.h_sys, len(pr), C.byref(n), _p(pr)))
+        return pr[:n.value].copy()
 
     def active_points(self):
         """test tap: activeMapPoints as map-point indices"""

@@ -504,6 +504,76 @@ vslam_status vslam_pose_graph_set_timing(int32_t on);
 vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
 
 /* ---------------------------------------------------------------------------
+ * Duplicate search between two copies of a place (no reference counterpart: the reference closes no loops; DESIGN.md section 6
+ * item 26, restated in numpy by tests/fuse_ref.py; csrc/fuse.hip).  Set A is the new copy (it will be absorbed), set B the old
+ * one (it is kept): world positions (fp64 [3]) and 256-bit descriptors (32 bytes) of up to 65536 points each.  Both are
+ * projected into ONE camera, T_cw (camera <- world, row-major 4x4, rigid) with the intrinsics fx, fy, cx, cy and the image
+ * size w x h, and every A point looks for its twin among the B points that land beside it.  THE RULES:
+ *   1 projection  Xc[i] = (R[i][0] X[0] + R[i][1] X[1] + R[i][2] X[2]) + t[i] in fp64, no contraction.  Visible iff z > 0 and,
+ *                 with invZ = 1.0 / z, u = fx * x * invZ + cx, v = fy * y * invZ + cy, not (u < 0 || v < 0 || u >= w || v >= h).
+ *                 A visible point's record is ((float)u, (float)v, (float)z); an invisible point's record is (NaN, NaN, -1.f).
+ *   2 gate        in float, no contraction: du = ua - ub, dv = va - vb; the pair passes iff du * du + dv * dv <= radius * radius
+ *                 and zb <= depth_ratio * za and za <= depth_ratio * zb.  A comparison with NaN is false, so an invisible record
+ *                 passes against nothing at any depth_ratio, without a visibility branch: an invisible A point proposes
+ *                 nothing, an invisible B point is proposed to by nobody.  (z = -1 alone fails the depth compares against every
+ *                 visible point, but two such records would pass each other at depth_ratio = 1: hence the NaN.)
+ *   3 best target every visible A point a scans the B points in ascending index: d1 = the smallest 256-bit Hamming distance
+ *                 among the gated ones, b1 = the lowest index attaining it, d2 = the smallest distance among the OTHER gated
+ *                 points (257: none), n_gated = their number.  a proposes b1 iff n_gated > 0 and d1 <= max_hamming.  No ratio
+ *                 test (inside a few pixels there are too few candidates for one to mean anything).
+ *   4 one to one  B point b goes to the proposer with the smallest (d1 << 32 | a): a 64-bit integer atomicMin (deterministic, no
+ *                 floating-point atomics).  A proposer that loses stays unmatched; it gets no second choice.
+ *   5 outputs     match [n_a]: the B index or -1; best [n_a][4] = (d1, b1, d2, n_gated), (257, -1, 257, 0) for a point that
+ *                 gated nothing; the report below.
+ * Kernels, all with a per-lane argument table and the lane as a grid dimension: k_fuse_project_b (a thread per point of either
+ * set: the 16-byte record), k_fuse_match_b (a thread per A point, B staged through LDS in tiles of 1024 targets, record and
+ * descriptor together; the gate first, eight targets per wave vote, and a target's descriptor is read and counted only when some
+ * lane of the wave passed its gate - wave-uniform, so results cannot depend on it; VSLAM_FUSE_SKIP=0, a developer switch read per call, counts every
+ * target), k_fuse_resolve_b (a thread per A point reads the winner back; one workgroup per lane counts).  One upload, one launch
+ * per stage for all lanes, one download, one wait, on the calling thread's device pool.  vslam_fuse_search is its own argument
+ * checks and then the ONE-LANE CASE of the batched call: the same host function, the same kernels - a lane's bytes are the
+ * single call's by construction, whatever the order and company of the lanes.
+ * A lane with n_a = 0 or n_b = 0 is idle for the search: match entries, if any, are -1, best rows (257, -1, 257, 0), the report
+ * counts what is visible.  A lane with both zero is not read and not written at all.
+ * VSLAM_ERR_INVALID, nothing launched, every output and report as the caller left it (the batch names the lane): NULL arrays,
+ * lanes < 1, a negative count, a non-finite pose / coordinate / intrinsic / parameter, w or h < 1, a negative parameter,
+ * depth_ratio inside (0, 1).  VSLAM_ERR_CAPACITY, likewise: n_a or n_b > 65536, lanes > 256, more than 1048576 points over all
+ * lanes.
+ * ------------------------------------------------------------------------- */
+typedef struct vslam_fuse_params {    /* a zero field takes the default in brackets (NULL = all defaults) */
+    float radius;                     /* [4.0]  pixels */
+    float depth_ratio;                /* [1.25] the larger depth over the smaller, at most */
+    int32_t max_hamming;              /* [50]   vslam_relocalize's acceptance distance */
+} vslam_fuse_params;
+
+typedef struct vslam_fuse_report {
+    int32_t n_visible_a, n_visible_b; /* points of either set inside the image */
+    int32_t n_proposals;              /* A points that proposed a target */
+    int32_t n_pairs;                  /* A points that won theirs */
+} vslam_fuse_report;
+
+typedef struct vslam_fuse_lane {      /* one lane; n_a == 0 and n_b == 0: idle lane (nothing read, nothing written) */
+    const double* T_cw;               /* [16] */
+    double fx, fy, cx, cy;
+    int32_t w, h;
+    const double* a_xyz; const uint8_t* a_desc; int32_t n_a;      /* [n_a][3], [n_a][32] */
+    const double* b_xyz; const uint8_t* b_desc; int32_t n_b;
+    int32_t* match;                   /* [n_a] */
+    int32_t* best;                    /* [n_a][4] */
+} vslam_fuse_lane;
+
+vslam_status vslam_fuse_search_batch(const vslam_fuse_lane* lanes, int32_t n_lanes, const vslam_fuse_params* params, int32_t device,
+                                     vslam_fuse_report* reports /* [n_lanes] */);
+vslam_status vslam_fuse_search(const double* T_cw, double fx, double fy, double cx, double cy, int32_t w, int32_t h,
+                               const double* a_xyz, const uint8_t* a_desc, int32_t n_a,
+                               const double* b_xyz, const uint8_t* b_desc, int32_t n_b,
+                               const vslam_fuse_params* params, int32_t device, int32_t* match, int32_t* best, vslam_fuse_report* report);
+/* measurement hook of tools/fuse_rate.py, not part of the supported surface: device time (HIP events) of each stage of the
+ * calling thread's last search - fuse_project, fuse_match, fuse_resolve; off by default; thread-local state. */
+vslam_status vslam_fuse_set_timing(int32_t on);
+vslam_status vslam_fuse_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
+
+/* ---------------------------------------------------------------------------
  * Local bundle adjustment — replaces the numerical core of LocalMapper::localBA
  * (include/OptimizationBA.h:75, src/OptimizationBA.cpp:543-873): GenericProjectionFactor
  * (left, and right with the stereo extrinsics) per observation, BetweenFactor<Pose3>
@@ -1067,6 +1137,57 @@ vslam_status vslam_system_close_loop(vslam_system* sys, const vslam_loop_params*
 vslam_status vslam_system_active_points(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* index);
 vslam_status vslam_system_covisibility(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* triples);
 vslam_status vslam_system_map_point_keyframes(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* first_observer, int32_t* creator);
+
+/* vslam_system_fuse_loop: the duplicate map points of a revisited place become one.  A call of its
+ * own, made BETWEEN tracked frames, normally right after a vslam_system_close_loop / _correct_loop whose report has
+ * corrected = 1: the map then holds every revisited landmark twice, one copy triangulated on the first visit, one since the
+ * return, and nothing connects them.
+ * Sets, over the map points that are not outliers, in creation order: B (kept) = created by a keyframe (MapPoint::kdx) <=
+ * latestKF - min_kf_gap, A (absorbed) = created later; each the most recent 65536.  vslam_fuse_search pairs them under the
+ * current camera (camPoseInv, the session's rig and image size): only what the camera sees is fused - the place being revisited.
+ * The commit, on the caller's timeline under the map's mutex, pairs (a, b) in ascending a:
+ *   for every observation o = (kf, l, r) of a, in kFMatches order:
+ *     b is not observed by kf:  o is appended to b's kFMatches; localMapPoints[l] = b, unMatchedF[l] = b.kdx (l >= 0), likewise
+ *                               localMapPointsR / unMatchedFR (r >= 0)                                       [an observation moved]
+ *     otherwise:                the keyframe's connection to a is erased as KeyFrame::eraseMPConnection does (-1 in the same four
+ *                               tables)                                                                    [an observation dropped]
+ *   a's kFMatches is cleared, a becomes an outlier and leaves the frame (inFrame = 0); b.lastObsKF = max of the two.
+ *   b's position, descriptor, scale distances, kdx and idx are untouched (the old copy hangs on the keyframes the solve held
+ *   fixed or moved least); no descriptor is re-selected.
+ * Every keyframe whose tables changed (n_keyframes_touched) gets calcConnections again, and so does every keyframe that observes
+ * a kept point - its weights towards the keyframes the point was moved into have grown although its own tables stand - all in
+ * ascending keyframe number: the next local BA window can span the loop, from either end.  activeMapPoints becomes the old list without the absorbed points, order kept, then the kept points not yet in
+ * it in ascending index; every kept point's inFrame = 1.  Iff at least one pair was committed the last frame's match tables are
+ * cleared (the rule of the loop correction's commit).  With zero pairs the call changes nothing: the following frames track bit
+ * for bit as without it.  A finished local BA whose changePosesLCA has not run yet is propagated first, as the next frame would.
+ * report->busy = 1, VSLAM_OK, nothing changed: as for the loop calls.  VSLAM_ERR_INVALID, nothing changed: mono sessions,
+ * use_imu = 1 sessions, no tracked frame yet, a negative or non-finite parameter, depth_ratio inside (0, 1). */
+typedef struct vslam_fuse_loop_params {   /* a zero field takes the default in brackets (NULL = all defaults) */
+    vslam_fuse_params search;
+    int32_t min_kf_gap;                   /* [20] */
+} vslam_fuse_loop_params;
+
+typedef struct vslam_fuse_loop_report {
+    int32_t busy;                         /* 1: a mapping pass is in flight, nothing was done */
+    int32_t n_a, n_b;                     /* sizes of the two sets */
+    vslam_fuse_report search;
+    int32_t n_fused;                      /* pairs committed (= search.n_pairs) */
+    int32_t n_obs_moved, n_obs_dropped;
+    int32_t n_keyframes_touched;
+    int32_t n_active_after;
+} vslam_fuse_loop_report;
+
+vslam_status vslam_system_fuse_loop(vslam_system* sys, const vslam_fuse_loop_params* params, vslam_fuse_loop_report* report);
+/* test taps: descriptors (n x 32 bytes) of every map point in creation order; the observations of every map point as
+ * offsets [n + 1] into (keyframe, left index, right index) triples, kFMatches order (triples may be NULL: n_obs_out only);
+ * localMapPoints / localMapPointsR of one keyframe as map-point indices (-1: none); the (absorbed, kept) map-point pairs of the
+ * last vslam_system_fuse_loop call, ascending absorbed index */
+vslam_status vslam_system_map_point_descriptors(vslam_system* sys, int32_t cap, int32_t* n_out, uint8_t* desc);
+vslam_status vslam_system_map_point_observations(vslam_system* sys, int32_t cap_points, int32_t cap_obs, int32_t* n_out, int32_t* n_obs_out,
+                                                 int32_t* offsets, int32_t* triples);
+vslam_status vslam_system_keyframe_points(vslam_system* sys, int32_t kf, int32_t cap_l, int32_t cap_r, int32_t* n_l_out, int32_t* n_r_out,
+                                          int32_t* lmp_l, int32_t* lmp_r);
+vslam_status vslam_system_fused_pairs(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* pairs);
 /* test tap: the IMU state of a session; any pointer may be NULL */
 vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
 /* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with
