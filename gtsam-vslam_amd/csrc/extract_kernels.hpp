@@ -86,6 +86,19 @@ void upload_pattern();
 constexpr int SSC_NMAX_LDS = 16384;      // candidates of one level whose sort arrays the LDS instantiation holds
 constexpr int SSC_NMAX = 65535;          // ... the HBM instantiation (16-bit index field of the sort key)
 constexpr int SSC_PICKW_G = 2048;        // words of a probe's pick bitmask in the HBM instantiation (SSC_NMAX / 32)
+// LDS size classes of the LDS instantiation: a task holds its CU through LDS, so a level is given the smallest form it fits
+constexpr int SSC_NMAX_MID = 8704;       // two workgroups per CU (80 KB each, static LDS included)
+constexpr int SSC_NMAX_SMALL = 6144;     // the 67 KB form, two workgroups per CU
+constexpr int SSC_NMAX_TINY = 3072;      // the 34 KB form, four workgroups per CU
+// the instantiation k_ssc<M> that takes a level of n candidates: 0 = LDS, 16 384; 1 = HBM scratch; 2 = LDS, 6 144;
+// 3 = LDS, SSC_NMAX_MID; 4 = LDS, 3 072.  classes (VSLAM_SSC_CLASSES, default 3): bit 0 = class 3 exists, bit 1 = class 4 exists;
+// 0: only 0 / 1 / 2, the mapping before 3 and 4 existed
+__host__ __device__ static inline int ssc_class(int n, int forceGlobal, int classes = 3) {
+    if (forceGlobal || n > SSC_NMAX_LDS) return 1;
+    if (n > ((classes & 1) ? SSC_NMAX_MID : SSC_NMAX_SMALL)) return 0;
+    if (n > SSC_NMAX_SMALL) return 3;
+    return ((classes & 2) && n <= SSC_NMAX_TINY) ? 4 : 2;
+}
 struct SscArgs {
     const uint32_t* cand; int candCap; const int* levelCount;      // gather output (HBM)
     int nLevels, nimg;
@@ -97,6 +110,7 @@ struct SscArgs {
     // the level's candidate offset, pick bitmasks per (task, probe)
     uint32_t* aG; uint32_t* sortedG; uint32_t* picksG;
     int forceGlobal;        // tests: every level goes through the HBM instantiation
+    int classes;            // VSLAM_SSC_CLASSES: 3 = all LDS classes, 0 = 16 384 / 6 144 only (for measurements against the four)
     int* taskCount;         // [nimg * nLevels]
     int* flags;             // per image: [2 img] error bits of the suppression, [2 img + 1] capacity overflow
 };

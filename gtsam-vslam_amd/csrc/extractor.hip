@@ -261,6 +261,7 @@ vslam_status vslam_extractor::init(const vslam_fe_params* p, int w, int h, int b
     VS_HIP(hipHostGetDevicePointer((void**)&d_counts, h_counts, 0));
     memset(h_counts, 0, (size_t)nimg * 3 * sizeof(int));
     if (const char* e = getenv("VSLAM_SSC_FORCE_GLOBAL")) sscForceGlobal = atoi(e) != 0;
+    if (const char* e = getenv("VSLAM_SSC_CLASSES")) sscClasses = atoi(e) & 3;
     return VSLAM_OK;
 }
 
@@ -491,7 +492,7 @@ vslam_status vslam_extractor::enqueue_ssc() {
     }
     S.gridG = d_sscGrid; S.gridOff = d_sscGridOff;
     S.tmp = d_sscTmp; S.aG = d_sscTmp + (size_t)nimg * candCap; S.sortedG = d_sscTmp + (size_t)2 * nimg * candCap;
-    S.picksG = d_sscPicks; S.forceGlobal = sscForceGlobal ? 1 : 0;
+    S.picksG = d_sscPicks; S.forceGlobal = sscForceGlobal ? 1 : 0; S.classes = sscClasses;
     S.taskCount = d_taskCount; S.flags = d_sscFlags;
     launch_ssc(stream, S, d_kept, keptCap, d_keptOff, d_counts);
     return VSLAM_OK;

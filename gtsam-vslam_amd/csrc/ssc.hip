@@ -18,10 +18,11 @@
 //      covers the 5x5 cells around it), marks them.  The search is speculated three probes deep (7 waves evaluate
 //      both outcomes of the next probes), the decision logic replays the reference loop on the cached counts.
 //
-// Three instantiations of the same code (SscCfg below; 512-thread tasks): k_ssc<0> keeps the sort arrays of a level in LDS (<= 16 384 candidates:
-// every level of the 752x480 / 1241x376 rigs and of a 1920x1200 frame); k_ssc<true> keeps them in HBM scratch
-// (up to 65 535 candidates per level, the width of the index field).  Each (image, level) task is taken by exactly
-// one of them; the other returns at once.  There is no host path.
+// Five instantiations of the same code (SscCfg below; 512-thread tasks): k_ssc<0> keeps the sort arrays of a level in LDS (<= 16 384 candidates:
+// every level of the 752x480 / 1241x376 rigs and of a 1920x1200 frame); k_ssc<3>, <2>, <4> are the same form with the LDS of
+// a level of at most 8 704 / 6 144 / 3 072 candidates (two, two and four tasks per CU); k_ssc<1> keeps the arrays in HBM
+// scratch (up to 65 535 candidates per level, the width of the index field).  Each (image, level) task is taken by exactly
+// one of them (ssc_class); the others return at once.  There is no host path.
 #include "extract_kernels.hpp"
 #include <mutex>
 
@@ -31,14 +32,32 @@ constexpr int SSC_NT = 512, SSC_NW = SSC_NT / 64;       // 8 waves
 constexpr int SSC_NPROBE = 8;                           // speculative probes per round (waves 0..6 are used: a depth-3 tree)
 constexpr int SSC_COOP_MIN = 2048;                      // longer segments: block-cooperative partition (VSLAM_SSC_COOP_MIN; 192 corridor images: 1024 -> 917 us, 2048 -> 882, 4096 -> 877, 512 -> 1023)
 constexpr int SSC_ARENA_WORDS = 20 * 1024;              // 80 KB of cover-grid bits (10 KB per speculating wave)
-constexpr int SSC_NMAX_SMALL = 6144;                    // levels up to this size: the 67 KB form, two workgroups per CU
+constexpr int SSC_LONGMAX = 64;                         // segment-list entries reserved for the segments longer than SSC_COOP_MIN
 
-// M = 0: sort arrays in LDS (<= SSC_NMAX_LDS candidates), M = 1: in HBM scratch, M = 2: in LDS, small level (<= SSC_NMAX_SMALL:
-// half the LDS and <= 64 VGPRs, so that two tasks share a CU - the tasks are latency-bound chains)
+// M = 0: sort arrays in LDS (<= SSC_NMAX_LDS candidates), M = 1: in HBM scratch, M = 2 / 3 / 4: in LDS, smaller levels (<= SSC_NMAX_SMALL /
+// _MID / _TINY: a fraction of the LDS and <= 64 VGPRs, so that two / two / four tasks share a CU - the tasks are latency-bound chains).
+// SEGMAX: entries of one segment list.  The segments of a tree level are disjoint and longer than 16, so at most NMAX / 17 exist at
+// once, beside the SSC_LONGMAX reserved entries (ssc_lds_ok).  ARENA: words of cover-grid bits, an eighth per speculating wave.
 template <int M> struct SscCfg;
 template <> struct SscCfg<0> { static constexpr int NMAX = SSC_NMAX_LDS, SEGMAX = 1088, PICKW = SSC_NMAX_LDS / 32, ARENA = SSC_ARENA_WORDS; };
 template <> struct SscCfg<1> { static constexpr int NMAX = SSC_NMAX, SEGMAX = 4096, PICKW = SSC_PICKW_G, ARENA = SSC_ARENA_WORDS; };
 template <> struct SscCfg<2> { static constexpr int NMAX = SSC_NMAX_SMALL, SEGMAX = 1088, PICKW = SSC_NMAX_SMALL / 32, ARENA = 10 * 1024; };
+template <> struct SscCfg<3> { static constexpr int NMAX = SSC_NMAX_MID, SEGMAX = 576, PICKW = SSC_NMAX_MID / 32, ARENA = 10 * 1024; };
+template <> struct SscCfg<4> { static constexpr int NMAX = SSC_NMAX_TINY, SEGMAX = 256, PICKW = SSC_NMAX_TINY / 32, ARENA = 4 * 1024; };
+// words behind the two sort arrays of an LDS instantiation: the two segment lists, and after the sort the [SSC_NW][256] histogram
+template <int M> constexpr int ssc_seg_words() { return 4 * SscCfg<M>::SEGMAX > SSC_NW * 256 ? 4 * SscCfg<M>::SEGMAX : SSC_NW * 256; }
+template <int M> constexpr size_t ssc_lds_bytes() {
+    return M == 1 ? ((size_t)4 * SscCfg<M>::SEGMAX + (size_t)SscCfg<M>::ARENA) * 4 : ((size_t)2 * SscCfg<M>::NMAX + (size_t)ssc_seg_words<M>()) * 4;
+}
+template <int M> struct SscCheck {
+    using C = SscCfg<M>;
+    static_assert(C::SEGMAX - SSC_LONGMAX >= C::NMAX / 17, "every short segment of a tree level needs a list entry");
+    static_assert(C::PICKW * 32 >= ((C::NMAX + 63) & ~63), "a probe's pick words cover whole 64-candidate steps");
+    static_assert(C::ARENA % SSC_NPROBE == 0 && (M == 1 || C::ARENA / SSC_NPROBE > C::PICKW), "a probing wave's slice holds its pick words and a grid");
+    static_assert(M == 1 || C::NMAX + ssc_seg_words<M>() >= C::ARENA, "arena must fit a | seg");
+    static constexpr bool ok = true;
+};
+static_assert(SscCheck<0>::ok && SscCheck<1>::ok && SscCheck<2>::ok && SscCheck<3>::ok && SscCheck<4>::ok, "k_ssc classes");
 
 // ordering of a wave's own accesses to the sort arrays: LDS traffic of a wave is processed in order (lgkmcnt);
 // the HBM instantiation also waits for its vector-memory operations
@@ -121,7 +140,6 @@ __device__ __forceinline__ int ssc_eval(const uint32_t* sc, int n, int width, in
 // segment list entry: word 0 = first | last << 16 (last <= 65 535), word 1 = remaining introsort depth.
 // A level's list has two parts: [0, SSC_LONGMAX) the segments longer than SSC_COOP_MIN (count cntN[2]; at most
 // 65 535 / 1 025 of them exist at once), [SSC_LONGMAX, ...) the others (count cntN[0]).
-constexpr int SSC_LONGMAX = 64;
 __device__ int g_sscCoopMin = SSC_COOP_MIN;      // (a device variable so that VSLAM_SSC_COOP_MIN can move the threshold for measurements)
 __device__ __forceinline__ void ssc_push(uint32_t* segN, int* cntN, int segMax, int f, int e, int depth, int* sFail) {
     if (e - f > g_sscCoopMin) {
@@ -336,8 +354,8 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     using C = SscCfg<M>;
     constexpr bool G = M == 1;
     extern __shared__ uint32_t lds[];
-    // LDS instantiation:  [sorted = Lp | Rp : NMAX u32] [a : NMAX u32] [seg : 2 x SEGMAX x 2 u32]; after the sort the
-    //                     cover-grid arena reuses a | seg (80 KB), the counting-sort histogram the seg lists (16 KB)
+    // LDS instantiations: [sorted = Lp | Rp : NMAX u32] [a : NMAX u32] [seg : 2 x SEGMAX x 2 u32, at least SSC_NW x 256]; after the
+    //                     sort the cover-grid arena reuses a | seg (ARENA words), the counting-sort histogram the seg lists (8 KB)
     // HBM instantiation:  [seg : 2 x SEGMAX x 2 u32] [arena]; a / sorted live in the task's HBM scratch
     const int img = blockIdx.x % A.nimg, l = blockIdx.x / A.nimg;
     const int task = img * A.nLevels + l;
@@ -345,8 +363,7 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     int coff = 0;
     for (int q = 0; q < l; q++) coff += lc[q];
     const int n = lc[l];
-    const int mode = (A.forceGlobal || n > SSC_NMAX_LDS) ? 1 : (n > SSC_NMAX_SMALL ? 0 : 2);
-    if (mode != M) return;                               // another instantiation's task
+    if (ssc_class(n, A.forceGlobal, A.classes) != M) return;                              // another instantiation's task
     uint32_t* sortedU = G ? A.sortedG + (size_t)img * A.candCap + coff : lds;
     uint32_t* a = G ? A.aG + (size_t)img * A.candCap + coff : lds + C::NMAX;
     uint16_t* Lp = (uint16_t*)sortedU;
@@ -530,6 +547,7 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         if (G) return picksG + (size_t)(slot < 0 ? SSC_NPROBE - 1 : slot) * SSC_PICKW_G;
         return slot < 0 ? arena + C::ARENA - PICKW_L : arena + slot * SLICE + SLICE - PICKW_L;
     };
+    int lastEval = -1;                                   // the latest round that evaluated probes
     for (int round = 0; round < 64; round++) {
         if (tid == 0) {
             // replay the reference loop on the cached counts
@@ -571,6 +589,7 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         if (sDone) break;
         const int ns = nSched;
         const bool solo = sSolo != 0;
+        if (ns > 0) lastEval = round;
         int cnt = -2;
         bool fits = true;
         uint32_t* picks = picks_of(solo ? -1 : wave);
@@ -582,7 +601,7 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         }
         __syncthreads();
         if (wave < ns && lane == 0) {
-            if (fits) { const int q = atomicAdd(&nCache, 1); if (q < 64) { cacheW[q] = sched[wave]; cacheC[q] = cnt; cacheSlot[q] = solo ? -1 : wave; } else sFail = 8; }
+            if (fits) { const int q = atomicAdd(&nCache, 1); if (q < 64) { cacheW[q] = sched[wave]; cacheC[q] = cnt; cacheSlot[q] = (round << 4) | (solo ? 15 : wave); } else sFail = 8; }
             else if (wave == 0) { if (solo) sFail = 16; else sSolo = 1; }       // the needed probe needs the whole arena
         }
         __syncthreads();
@@ -600,15 +619,18 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     if (tid == 0) { st[4] = n; st[5] = nCache; st[6] = sFinal; }
 #endif
     if (!sDone) { if (tid == 0) { atomicOr(&A.flags[2 * img], 32); *taskCount = 0; } return; }
-    // emit the picks of the last evaluated width (lastPicked of the reference loop).  That probe always belongs to
-    // the latest round, so its pick bitmask is still in its wave's slot: prefix over the words, one thread per word.
+    // emit the picks of the last evaluated width (lastPicked of the reference loop).  A probe of the latest round still has its
+    // pick bitmask in its wave's slot: prefix over the words, one thread per word.  (cacheSlot: round << 4 | slot, 15 = solo)
     int total = 0;
     if (sFinal >= 0) {
-        int slot = -1;
-        for (int q = 0; q < nCache; q++) if (cacheW[q] == sFinal) { slot = cacheSlot[q]; total = cacheC[q]; }
+        int slot = -1, evalRound = -1;
+        for (int q = 0; q < nCache; q++) if (cacheW[q] == sFinal) { slot = cacheSlot[q] & 15; evalRound = cacheSlot[q] >> 4; total = cacheC[q]; }
+        if (slot == 15) slot = -1;
         const uint32_t* picks = picks_of(slot);
-        if (total > kmax) {
-            // the search ended on a "too many" probe (width == prevWidth / low > high): its scan was cut short, redo it in full
+        if (total > kmax || evalRound != lastEval) {
+            // the search ended on a "too many" probe (width == prevWidth / low > high): its scan was cut short, redo it in full.
+            // The same for a probe cached by an earlier round (a speculated child of a probe that then needed the solo form): a
+            // solo probe's grid spans the other waves' slices and their pick words.
             __syncthreads();
             if (wave == 0) {
                 uint32_t* pk = picks_of(-1);
@@ -627,11 +649,12 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         if (wave == 0) {                                 // exclusive prefix of the per-word pick counts
             int run = 0;
             for (int base = 0; base < nWords; base += 64) {
-                const int v = pre[base + lane];
+                const bool in = base + lane < C::PICKW;      // (PICKW of the 8 704 / 3 072 classes is no multiple of 64)
+                const int v = in ? pre[base + lane] : 0;
                 int incl = v;
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-                pre[base + lane] = run + incl - v;
+                if (in) pre[base + lane] = run + incl - v;
                 run += __shfl(incl, 63);
             }
         }
@@ -672,11 +695,7 @@ __global__ __launch_bounds__(256) void k_ssc_pack(SscArgs A, uint32_t* __restric
 }
 
 void launch_ssc(hipStream_t s, const SscArgs& A, uint32_t* kept, int keptCap, int* keptOff, int* hostCounts) {
-    const size_t ldsL = ((size_t)2 * SscCfg<0>::NMAX + (size_t)4 * SscCfg<0>::SEGMAX) * 4;
-    const size_t ldsS = ((size_t)2 * SscCfg<2>::NMAX + (size_t)4 * SscCfg<2>::SEGMAX) * 4;
-    const size_t ldsG = ((size_t)4 * SscCfg<1>::SEGMAX + (size_t)SscCfg<1>::ARENA) * 4;
-    static_assert((size_t)SscCfg<0>::NMAX + 4 * SscCfg<0>::SEGMAX >= (size_t)SscCfg<0>::ARENA, "arena must fit a | seg");
-    static_assert((size_t)SscCfg<2>::NMAX + 4 * SscCfg<2>::SEGMAX >= (size_t)SscCfg<2>::ARENA, "arena must fit a | seg");
+    const size_t ldsL = ssc_lds_bytes<0>(), ldsG = ssc_lds_bytes<1>(), ldsS = ssc_lds_bytes<2>(), ldsM = ssc_lds_bytes<3>(), ldsT = ssc_lds_bytes<4>();
     static std::once_flag attr;
     std::call_once(attr, [&] {
         if (const char* e = getenv("VSLAM_SSC_COOP_MIN")) {
@@ -686,13 +705,24 @@ void launch_ssc(hipStream_t s, const SscArgs& A, uint32_t* kept, int keptCap, in
         (void)hipFuncSetAttribute((const void*)k_ssc<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsL);
         (void)hipFuncSetAttribute((const void*)k_ssc<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsS);
         (void)hipFuncSetAttribute((const void*)k_ssc<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsG);
+        (void)hipFuncSetAttribute((const void*)k_ssc<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsM);
+        (void)hipFuncSetAttribute((const void*)k_ssc<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsT);
     });
-    // every (image, level) task is taken by exactly one of the three; the workgroups of the other two return at once
+    // every (image, level) task is taken by exactly one of the instantiations; the workgroups of the others return at once
     // (the three instantiations side by side on extra streams, and the blur beside FAST / the suppression, were measured in the full
     //  run: no gain - the other lockstep group fills whatever a latency-bound kernel leaves idle - and removed again)
-    hipLaunchKernelGGL(k_ssc<2>, dim3(A.nimg * A.nLevels), dim3(SSC_NT), ldsS, s, A);
-    hipLaunchKernelGGL(k_ssc<0>, dim3(A.nimg * A.nLevels), dim3(SSC_NT), ldsL, s, A);
-    hipLaunchKernelGGL(k_ssc<1>, dim3(A.nimg * A.nLevels), dim3(SSC_NT), ldsG, s, A);
+    const dim3 grid(A.nimg * A.nLevels);
+    if (A.classes) {                                     // largest class first
+        hipLaunchKernelGGL(k_ssc<1>, grid, dim3(SSC_NT), ldsG, s, A);
+        hipLaunchKernelGGL(k_ssc<0>, grid, dim3(SSC_NT), ldsL, s, A);
+        if (A.classes & 1) hipLaunchKernelGGL(k_ssc<3>, grid, dim3(SSC_NT), ldsM, s, A);
+        hipLaunchKernelGGL(k_ssc<2>, grid, dim3(SSC_NT), ldsS, s, A);
+        if (A.classes & 2) hipLaunchKernelGGL(k_ssc<4>, grid, dim3(SSC_NT), ldsT, s, A);
+    } else {                                             // VSLAM_SSC_CLASSES=0: the launches as they were with two LDS classes
+        hipLaunchKernelGGL(k_ssc<2>, grid, dim3(SSC_NT), ldsS, s, A);
+        hipLaunchKernelGGL(k_ssc<0>, grid, dim3(SSC_NT), ldsL, s, A);
+        hipLaunchKernelGGL(k_ssc<1>, grid, dim3(SSC_NT), ldsG, s, A);
+    }
     hipLaunchKernelGGL(k_ssc_pack, dim3(A.nimg), dim3(256), 0, s, A, kept, keptCap, keptOff, hostCounts);
 }
 
