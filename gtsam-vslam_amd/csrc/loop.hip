@@ -1,9 +1,11 @@
 // Loop closing of a stereo session (no reference counterpart; vslam_hip.h): the relocalisation
 // stage asked on the part of the map the tracker has left behind, a pose graph over the keyframes solved by
 // vslam_pose_graph_optimize, and the commit that hands the old copy of the place back to the tracker.  vslam_system_fuse_loop (item 26)
-// then makes one map point of each landmark the two visits both triangulated.
+// then makes one map point of each landmark the two visits both triangulated; vslam_system_global_ba (item 27) runs one bundle
+// adjustment over the whole map.
 #include "system.hpp"
 #include "fuse_host.hpp"
+#include <array>
 #include <set>
 
 using namespace vslam;
@@ -311,6 +313,203 @@ vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fu
     rep->n_active_after = (int)active.size();
     return VSLAM_OK;
 }
+
+// ---- vslam_system_global_ba (vslam_hip.h) ------------------------------------------------------
+vslam_status vslam_system::gba_check(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const {
+    VS_CHECK(loop_check(fn));
+    P = prm ? *prm : vslam_system_gba_params{};
+    if (P.gba.max_iterations < 0 || !(P.gba.lambda0 >= 0.0) || !std::isfinite(P.gba.lambda0) || !(P.edge_weight >= 0.0) || !std::isfinite(P.edge_weight)) {
+        set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID;
+    }
+    return VSLAM_OK;
+}
+
+// A map point whose observation rays never open wider than this at the current values carries no factor: its depth is not
+// observable, and a Levenberg-Marquardt pass walks it towards infinity.  0.9998 (1.15 degrees) is the usual triangulation bound.
+// On the corridor walk after close_loop + fuse_loop it holds back 101 of 801 points with two or more factors, among them three
+// at 500 - 700 m and one seen at the same pixel from the first keyframe and from the one that came back to it; without the
+// guard those four move by 5e3 .. 3e10 m in twenty trials while the cost falls by 1e-3, with it no point moves by more than 0.53 m.
+constexpr double GBA_MIN_PARALLAX_COS = 0.9998;
+
+// steps 1 - 4 (mapMutex held): every keyframe, every map point that is not an outlier, ba_collect's pair flags, the sequential edges
+vslam_status vslam_system::gba_flatten(double edgeWeight, GbaFlat& F) {
+    if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
+        VS_CHECK(change_poses_lca(endLBAIdx));
+        LBADone = false;
+    }
+    const int K = (int)keyFrames.size();
+    F.kfPose.resize((size_t)K * 16); F.kfId.resize(K); F.kfFixed.resize(K); F.kfLocal.assign(K, 1);
+    for (int k = 0; k < K; k++) {
+        const SysKF& kf = keyFrames[k];
+        memcpy(&F.kfPose[16 * (size_t)k], kf.pose.data(), 16 * sizeof(double));
+        F.kfId[k] = kf.numb; F.kfFixed[k] = (k == 0 || kf.fixed) ? 1 : 0;
+    }
+    std::vector<std::array<double, 3>> rays;
+    F.allMps.clear(); F.pk.clear(); F.pl.clear(); F.pf.clear(); F.puv.clear(); F.poct.clear(); F.pobj.clear();
+    for (int m = 0; m < (int)mapPoints.size(); m++) if (!mpOutlier[m]) F.allMps.push_back(m);
+    const int Lm = (int)F.allMps.size();
+    F.mpOut.assign(std::max(Lm, 1), 0);
+    F.lm.resize((size_t)std::max(Lm, 1) * 3);
+    for (int i = 0; i < Lm; i++) {
+        const int m = F.allMps[i];
+        const SysMP& mp = mapPoints[m];
+        for (int c = 0; c < 3; c++) F.lm[3 * (size_t)i + c] = mp.wp[c];
+        if (mp.kfm.empty() || (!mpInFrame[m] && (int)mp.kfm.size() < 3)) { F.mpOut[i] = 1; continue; }      // (no factor; an outlier at the commit)
+        const size_t q0 = F.pk.size();
+        for (const KfMatch& o : mp.kfm) {
+            if (o.kf < 0 || o.kf >= K) continue;
+            const SysKeys& keys = keyFrames[o.kf].keys;
+            int flags;
+            if (o.l >= 0) flags = (keys.close[o.l] && o.r >= 0) ? 3 : 1;
+            else if (o.r >= 0) flags = 2;
+            else continue;
+            F.pk.push_back(o.kf); F.pl.push_back(i); F.pf.push_back((uint8_t)flags);
+            F.puv.push_back(o.l >= 0 ? keys.kL[o.l].x : 0.f); F.puv.push_back(o.l >= 0 ? keys.kL[o.l].y : 0.f);
+            F.puv.push_back(o.r >= 0 ? keys.kR[o.r].x : 0.f); F.puv.push_back(o.r >= 0 ? keys.kR[o.r].y : 0.f);
+            F.poct.push_back(o.l >= 0 ? keys.kL[o.l].octave : 0); F.poct.push_back(o.r >= 0 ? keys.kR[o.r].octave : 0);
+            F.pobj.push_back({o.kf, m, o.l, o.r});
+        }
+        // the parallax guard: unit rays from the observing camera centres (the right camera's for a right factor) to the point
+        rays.clear();
+        for (size_t q = q0; q < F.pk.size(); q++) {
+            const M4& T = keyFrames[F.pk[q]].pose;
+            for (int side = 0; side < 2; side++) {
+                if (!((F.pf[q] >> side) & 1)) continue;
+                const double b = side ? (double)cfg.rig.baseline : 0.0;
+                const double d[3] = {mp.wp[0] - (T[3] + T[0] * b), mp.wp[1] - (T[7] + T[4] * b), mp.wp[2] - (T[11] + T[8] * b)};
+                const double nrm = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+                rays.push_back({d[0] / nrm, d[1] / nrm, d[2] / nrm});
+            }
+        }
+        double minCos = 1.0;
+        for (size_t a = 0; a < rays.size(); a++)
+            for (size_t c = 0; c < a; c++) minCos = std::min(minCos, rays[a][0] * rays[c][0] + rays[a][1] * rays[c][1] + rays[a][2] * rays[c][2]);
+        if (rays.size() >= 2 && !(minCos <= GBA_MIN_PARALLAX_COS)) for (size_t q = q0; q < F.pk.size(); q++) F.pf[q] = 0;
+    }
+    F.edges.clear();
+    if (edgeWeight > 0.0)
+        for (int k = 0; k < K; k++) {
+            const int p = keyFrames[k].prevKF;
+            if (p < 0) continue;
+            vslam_pgo_edge e{};
+            e.i = p; e.j = k; e.w_rot = e.w_trans = edgeWeight;
+            const M4 Z = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
+            memcpy(e.Z, Z.data(), 16 * sizeof(double));
+            F.edges.push_back(e);
+        }
+    const int NP = (int)F.pk.size();
+    vslam_ba_problem& P = F.P;
+    P = vslam_ba_problem{};
+    P.rig = cfg.rig; P.n_levels = nLev; P.sigma_factor = sigmaF.data(); P.inv_sigma_factor = invSigmaF.data();
+    P.n_kf = K; P.kf_pose_wc = F.kfPose.data(); P.kf_id = F.kfId.data(); P.kf_fixed = F.kfFixed.data(); P.kf_local = F.kfLocal.data();
+    P.n_lm = Lm; P.lm_xyz = F.lm.data(); P.n_pairs = NP; P.pair_kf = F.pk.data(); P.pair_lm = F.pl.data(); P.pair_flags = F.pf.data();
+    P.pair_uv = F.puv.data(); P.pair_octave = F.poct.data();
+    F.kfOut.assign((size_t)K * 16, 0.0); F.lmOut.assign((size_t)std::max(Lm, 1) * 3, 0.0); F.wrong.assign(std::max(NP, 1), 0);
+    return VSLAM_OK;
+}
+
+// step 6 (mapMutex held): the write-back of ba_commit_a on the whole map; upd: the map points whose position was stored
+void vslam_system::gba_commit(GbaFlat& F, vslam_system_gba_report* rep, std::vector<int>& upd) {
+    const int K = (int)F.kfFixed.size(), Lm = (int)F.allMps.size(), NP = (int)F.pk.size();
+    std::vector<int> nFac(std::max(Lm, 1), 0);
+    for (int q = 0; q < NP; q++) nFac[F.pl[q]] += (F.pf[q] & 1) + ((F.pf[q] >> 1) & 1);
+    int nWrong = 0, nOut = 0;
+    for (int q = 0; q < NP; q++) {
+        if (!F.wrong[q]) continue;
+        nWrong++;
+        SysKF& c = keyFrames[F.pobj[q].kf];
+        SysMP& mp = mapPoints[F.pobj[q].mp];
+        const int e = mp.find(F.pobj[q].kf);
+        if (e < 0) continue;
+        const int l = mp.kfm[e].l, r = mp.kfm[e].r;
+        if (l >= 0) { c.lmpL[l] = -1; c.unF[l] = -1; }              // KeyFrame::eraseMPConnection
+        if (r >= 0) { c.lmpR[r] = -1; c.unFR[r] = -1; }
+        mp.kfm.erase(mp.kfm.begin() + e);                            // MapPoint::eraseKFConnection
+    }
+    for (int k = 0; k < K; k++) if (!F.kfFixed[k]) keyFrames[k].setPose(m4_from(&F.kfOut[16 * (size_t)k]));      // (an isolated keyframe's bytes are its own)
+    upd.clear();
+    for (int i = 0; i < Lm; i++) {
+        const int m = F.allMps[i];
+        SysMP& mp = mapPoints[m];
+        if (F.mpOut[i] || (!mpInFrame[m] && (int)mp.kfm.size() < 3)) { mpOutlier[m] = 1; nOut++; }
+        else if (nFac[i] >= 2) { for (int c = 0; c < 3; c++) mp.wp[c] = F.lmOut[3 * (size_t)i + c]; upd.push_back(m); }
+    }
+    rep->n_wrong = nWrong; rep->n_outliers = nOut;
+}
+
+vslam_status vslam_system::global_ba(const vslam_system_gba_params* prm, vslam_system_gba_report* rep) {
+    static const char* const fn = "vslam_system_global_ba";
+    if (!rep) return VSLAM_ERR_INVALID;
+    vslam_system_gba_params P;
+    VS_CHECK(gba_check(fn, prm, P));
+    *rep = vslam_system_gba_report{};
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    if (keyFrames.size() < 2) return VSLAM_OK;
+    VS_HIP(hipSetDevice(cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        GbaFlat F;
+        VS_CHECK(gba_flatten(P.edge_weight, F));
+        rep->n_keyframes = F.P.n_kf; rep->n_landmarks = F.P.n_lm; rep->n_pairs = F.P.n_pairs; rep->n_edges = (int)F.edges.size();
+        vslam_gba_result R{};
+        R.kf_pose_wc = F.kfOut.data(); R.lm_xyz = F.lmOut.data(); R.pair_wrong = F.wrong.data();
+        VS_CHECK(vslam_global_ba(&F.P, F.edges.empty() ? nullptr : F.edges.data(), (int)F.edges.size(), &P.gba, cfg.device, &R));
+        rep->gba = R.report;
+        std::vector<int> upd;
+        gba_commit(F, rep, upd);
+        VS_CHECK(ba_request_refresh(upd));
+        for (int k = 0; k < (int)keyFrames.size(); k++) {
+            const int p = keyFrames[k].prevKF;
+            if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
+        }
+        lca_finish(latestKF);
+    }
+    vslam_loop_report lr{};
+    VS_CHECK(loop_activate(&lr));
+    rep->n_active_after = lr.n_active_after;
+    rep->success = 1;
+    return VSLAM_OK;
+}
+
+extern "C" {
+
+vslam_status vslam_system_global_ba(vslam_system* s, const vslam_system_gba_params* params, vslam_system_gba_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->global_ba(params, report);
+}
+
+vslam_status vslam_system_global_ba_problem(vslam_system* s, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                            uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                            int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                            vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor) {
+    static const char* const fn = "vslam_system_global_ba_problem";
+    if (!s || !sizes) return VSLAM_ERR_INVALID;
+    vslam_system_gba_params prm{};
+    prm.edge_weight = edge_weight;
+    vslam_system_gba_params P;
+    VS_CHECK(s->gba_check(fn, &prm, P));
+    if (s->loop_busy()) { set_error("%s: a mapping pass is in flight", fn); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(s->cfg.device));
+    std::lock_guard<std::mutex> lk(s->mapMutex);
+    vslam_system::GbaFlat F;
+    VS_CHECK(s->gba_flatten(P.edge_weight, F));
+    const int K = F.P.n_kf, Lm = F.P.n_lm, NP = F.P.n_pairs, M = (int)F.edges.size(), nLev = F.P.n_levels;
+    sizes[0] = K; sizes[1] = Lm; sizes[2] = NP; sizes[3] = M; sizes[4] = nLev;
+    if (!arrays) return VSLAM_OK;
+    if (!kf_pose_wc || !kf_fixed || !kf_local || !lm_xyz || !lm_index || !pair_kf || !pair_lm || !pair_flags || !pair_uv || !pair_octave || !edges ||
+        !sigma_factor || !inv_sigma_factor) { set_error("%s: NULL array", fn); return VSLAM_ERR_INVALID; }
+    memcpy(kf_pose_wc, F.kfPose.data(), (size_t)K * 128); memcpy(kf_fixed, F.kfFixed.data(), K); memcpy(kf_local, F.kfLocal.data(), K);
+    if (Lm) { memcpy(lm_xyz, F.lm.data(), (size_t)Lm * 24); memcpy(lm_index, F.allMps.data(), (size_t)Lm * 4); }
+    if (NP) {
+        memcpy(pair_kf, F.pk.data(), (size_t)NP * 4); memcpy(pair_lm, F.pl.data(), (size_t)NP * 4); memcpy(pair_flags, F.pf.data(), NP);
+        memcpy(pair_uv, F.puv.data(), (size_t)NP * 16); memcpy(pair_octave, F.poct.data(), (size_t)NP * 8);
+    }
+    if (M) memcpy(edges, F.edges.data(), (size_t)M * sizeof(vslam_pgo_edge));
+    memcpy(sigma_factor, s->sigmaF.data(), (size_t)nLev * 4); memcpy(inv_sigma_factor, s->invSigmaF.data(), (size_t)nLev * 4);
+    return VSLAM_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

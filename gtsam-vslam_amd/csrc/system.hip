@@ -1315,6 +1315,11 @@ vslam_status vslam_system::ba_commit_a(MapPass& p) {
         else if (presentLm[m]) { for (int c = 0; c < 3; c++) mp.wp[c] = J.lmOut[3 * m + c]; upd.push_back(allMps[m]); }
     }
     p.nWrong = nWrong; p.nOut = nOut;
+    return ba_request_refresh(upd);
+}
+
+// the write-back's requests for the map points `upd` whose position changed (shared by the local and the global BA's commit)
+vslam_status vslam_system::ba_request_refresh(const std::vector<int>& upd) {
     // MapPoint::updatePos (src/Map.cpp:212-234): depth / close refresh of every observing keyframe (k_ba_refresh_depth),
     // then calcDescriptor - both as requests
     if (!upd.empty()) {

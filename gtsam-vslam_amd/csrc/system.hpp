@@ -320,6 +320,21 @@ struct vslam_system {
     // the current camera, the commit of fuse_host.hpp.  fusedPairs: the (absorbed, kept) pairs of the last call (test tap)
     std::vector<int> fusedPairs;
     vslam_status fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep);
+    // one vslam_global_ba over the whole map: the flattened problem (mapMutex held), the call, the commit
+    struct GbaFlat {
+        std::vector<double> kfPose, lm, kfOut, lmOut;
+        std::vector<uint8_t> kfFixed, kfLocal, mpOut, pf, wrong;
+        std::vector<int64_t> kfId;
+        std::vector<int> allMps, pk, pl, poct;
+        std::vector<float> puv;
+        std::vector<BaJob::Pair> pobj;
+        std::vector<vslam_pgo_edge> edges;
+        vslam_ba_problem P{};
+    };
+    vslam_status gba_check(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const;
+    vslam_status gba_flatten(double edgeWeight, GbaFlat& F);
+    void gba_commit(GbaFlat& F, vslam_system_gba_report* rep, std::vector<int>& upd);
+    vslam_status global_ba(const vslam_system_gba_params* prm, vslam_system_gba_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);
@@ -374,6 +389,7 @@ struct vslam_system {
     void ba_collect(MapPass& p);
     vslam_status ba_device(MapPass& p);
     vslam_status ba_commit_a(MapPass& p);
+    vslam_status ba_request_refresh(const std::vector<int>& upd);      // updatePos' depth / close refresh and calcDescriptor, as requests
     void ba_commit_b(MapPass& p);
     vslam_status submit_job(int stage);
     vslam_status wait_job();

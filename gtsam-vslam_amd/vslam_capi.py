@@ -686,6 +686,62 @@ def local_ba_batch(rig, sigma_factor, inv_sigma_factor, probs, device=0):
     return [b[2]["read"]() for b in built]
 
 
+class GbaParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("lambda0", C.c_double)]
+
+
+class GbaReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("iterations", "accepted", "rejected", "n_free", "n_isolated", "n_present", "n_thin",
+                                          "n_factors", "half_bandwidth", "reserved")] + \
+               [(n, C.c_double) for n in ("initial_cost", "final_cost", "final_lambda")]
+
+
+class GbaResult(C.Structure):
+    _fields_ = [("kf_pose_wc", C.c_void_p), ("lm_xyz", C.c_void_p), ("pair_wrong", C.c_void_p), ("report", GbaReport)]
+
+
+class SystemGbaParams(C.Structure):
+    _fields_ = [("gba", GbaParams), ("edge_weight", C.c_double)]
+
+
+class SystemGbaReport(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("busy", "success", "n_keyframes", "n_landmarks", "n_pairs", "n_edges", "n_wrong", "n_outliers",
+                                          "n_active_after", "reserved")] + [("gba", GbaReport)]
+
+
+def _gba_report_dict(rep):
+    return {f[0]: getattr(rep, f[0]) for f in GbaReport._fields_ if f[0] != "reserved"}
+
+
+def global_ba(rig, sigma_factor, inv_sigma_factor, prob, edges=None, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_global_ba on a flattened problem dict (the keys local_ba takes; kf_id may be missing: it is not used) with optional
+    relative-pose edges as pgo_edges takes them (or its array).  Returns dict(kf_pose, lm, pair_wrong, report)."""
+    if "kf_id" not in prob:
+        prob = dict(prob, kf_id=np.arange(len(prob["kf_pose"]), dtype=np.int64))
+    P, _, keep = ba_problem_structs(rig, sigma_factor, inv_sigma_factor, prob)
+    m = 0 if edges is None else len(edges)
+    ea = None if m == 0 else (edges if isinstance(edges, np.ndarray) else pgo_edges(edges))
+    n_kf, n_lm, n_pairs = P.n_kf, P.n_lm, P.n_pairs
+    kfOut = np.zeros((max(n_kf, 1), 4, 4)); lmOut = np.zeros((max(n_lm, 1), 3)); wrong = np.zeros(max(n_pairs, 1), np.uint8)
+    R = GbaResult()
+    R.kf_pose_wc, R.lm_xyz, R.pair_wrong = _p(kfOut), _p(lmOut), _p(wrong)
+    prm = GbaParams(int(max_iterations), float(lambda0))
+    _chk(lib().vslam_global_ba(C.byref(P), None if ea is None else _p(ea), m, C.byref(prm), int(device), C.byref(R)))
+    del keep
+    return dict(kf_pose=kfOut[:n_kf], lm=lmOut[:n_lm], pair_wrong=wrong[:n_pairs], report=_gba_report_dict(R.report))
+
+
+def global_ba_set_timing(on):
+    _chk(lib().vslam_global_ba_set_timing(int(bool(on))))
+
+
+def global_ba_timings():
+    """kernel group -> device ms of this thread's last global_ba (after global_ba_set_timing(True))"""
+    names = (C.c_char_p * 8)(); ms = (C.c_float * 8)(); n = C.c_int32()
+    _chk(lib().vslam_global_ba_timings(names, ms, 8, C.byref(n)))
+    return {names[i].decode(): float(ms[i]) for i in range(n.value)}
+
+
 class BaLaneShape(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("n_free_kf", "n_points", "n_factors", "n_edges", "n_pairs", "max_slots", "max_factors", "own_rig")]
 
@@ -1307,6 +1363,7 @@ class System:
             if "velocity" in imu:
                 cfg.velocity_init = (C.c_double * 3)(*imu["velocity"])
         self.w, self.h = rig["w"], rig["h"]
+        self.rig = dict(rig)
         self.h_sys = C.c_void_p()
         _chk(self.L.vslam_system_create(C.byref(cfg), C.byref(self.h_sys)))
 
@@ -1484,6 +1541,37 @@ class System:
         pr = np.zeros((max(n.value, 1), 2), np.int32)
         _chk(self.L.vslam_system_fused_pairs(self.h_sys, len(pr), C.byref(n), _p(pr)))
         return pr[:n.value].copy()
+
+    def global_ba(self, edge_weight=0.0, max_iterations=0, lambda0=0.0):
+        """vslam_system_global_ba: one global bundle adjustment over the whole map.  Returns the report dict (busy: nothing was
+        done; success 0: fewer than two keyframes)."""
+        prm = SystemGbaParams(GbaParams(int(max_iterations), float(lambda0)), float(edge_weight))
+        rep = SystemGbaReport()
+        _chk(self.L.vslam_system_global_ba(self.h_sys, C.byref(prm), C.byref(rep)))
+        d = {f[0]: getattr(rep, f[0]) for f in SystemGbaReport._fields_ if f[0] not in ("gba", "reserved")}
+        d["gba"] = _gba_report_dict(rep.gba)
+        return d
+
+    def global_ba_problem(self, edge_weight=0.0):
+        """test tap: (problem dict as global_ba takes it, plus lm_index, sigma_factor and inv_sigma_factor; edges array) that
+        Session.global_ba would build now"""
+        sz = (C.c_int32 * 5)()
+        call = self.L.vslam_system_global_ba_problem
+        _chk(call(self.h_sys, C.c_double(edge_weight), 0, sz, *([None] * 13)))
+        K, Lm, NP, M, nLev = (int(v) for v in sz)
+        z = lambda shape, dt: np.zeros(shape, dt)
+        kf, fx, lc = z((max(K, 1), 4, 4), np.float64), z(max(K, 1), np.uint8), z(max(K, 1), np.uint8)
+        lm, li = z((max(Lm, 1), 3), np.float64), z(max(Lm, 1), np.int32)
+        pk, pl, pf = z(max(NP, 1), np.int32), z(max(NP, 1), np.int32), z(max(NP, 1), np.uint8)
+        uv, oc = z((max(NP, 1), 4), np.float32), z((max(NP, 1), 2), np.int32)
+        ed, sf, isf = z(max(M, 1), PGO_EDGE_DTYPE), z(max(nLev, 1), np.float32), z(max(nLev, 1), np.float32)
+        sz2 = (C.c_int32 * 5)()
+        _chk(call(self.h_sys, C.c_double(edge_weight), 1, sz2, _p(kf), _p(fx), _p(lc), _p(lm), _p(li), _p(pk), _p(pl), _p(pf), _p(uv), _p(oc),
+                  _p(ed), _p(sf), _p(isf)))
+        assert list(sz2) == list(sz)
+        prob = dict(rig=self.rig, kf_pose=kf[:K], kf_fixed=fx[:K], kf_local=lc[:K], lm=lm[:Lm], lm_index=li[:Lm], pair_kf=pk[:NP], pair_lm=pl[:NP],
+                    pair_flags=pf[:NP], pair_uv=uv[:NP], pair_oct=oc[:NP], sigma_factor=sf[:nLev], inv_sigma_factor=isf[:nLev])
+        return prob, ed[:M]
 
     def active_points(self):
         """test tap: activeMapPoints as map-point indices"""

@@ -504,6 +504,77 @@ vslam_status vslam_pose_graph_set_timing(int32_t on);
 vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
 
 /* ---------------------------------------------------------------------------
+ * Global bundle adjustment (no reference counterpart: the reference closes no loops; DESIGN.md section 6 item 27, restated in
+ * numpy by tests/gba_ref.py, which is the authority; csrc/gba.hip, csrc/gba_host.hpp).  Every keyframe and landmark of a
+ * flattened problem (vslam_ba_problem, declared with the local BA below) in ONE Levenberg-Marquardt pass, without the local BA's
+ * cap of 170 free keyframes: the landmarks are eliminated onto the keyframes and the reduced camera system is solved by the
+ * pose-graph solve's block-banded Cholesky after its reordering.  THE RULES:
+ *   factors     every set bit of pair_flags is one two-row factor (bit 0 the left camera, bit 1 the right one, displaced by the
+ *               baseline), whitened by 1 / sigma, sigma = 1 / inv_sigma_factor[octave].  kf_id is not used: there is no
+ *               implicit between-factor chain.  Relative-pose terms are the caller's `edges`, with the residual, weights and
+ *               Jacobians of vslam_pose_graph_optimize.
+ *   unknowns    poses by the pose-graph retraction T [Exp(a), b; 0, 1], landmarks additive.
+ *   cost        sum of the whitened r^2 over the factors + the pose-graph cost of the edges (no 1/2).
+ *   presence    a landmark is PRESENT iff it has at least two factors.  A thin landmark contributes nothing, comes back bit
+ *               for bit and is counted (n_thin).  A keyframe is FREE iff it is not fixed and has a factor on a present
+ *               landmark or an edge; other non-fixed keyframes are isolated, come back bit for bit and are counted.
+ *   gauge       two free keyframes are connected iff they share a present landmark or an edge; a component that shares no
+ *               present landmark and no edge with a fixed keyframe is refused (VSLAM_ERR_INVALID), as the pose-graph call
+ *               refuses a free gauge.  All keyframes fixed is legal: structure only, the landmarks are still optimised.
+ *   LM          one pass with the schedule of vslam_pose_graph_optimize (accept: lambda / 3, floor 1e-12; reject: 4 lambda;
+ *               stop at lambda > 1e8, a relative decrease < 1e-10, |delta|_inf < 1e-12 over poses and landmarks, or
+ *               max_iterations accepted trials; an initial cost <= 1e-20 returns at once).  Damping is lambda diag(H) on the
+ *               pose AND the landmark diagonal, applied before the elimination.  A trial is rejected when a pivot of a
+ *               landmark's damped 3x3 block or of the band is not positive, when its cost is not finite, or when a factor
+ *               has z <= 0.
+ *   flags       after the pass pair_wrong is the local BA's chi2 rule (squared pixel error > (float)(7.815f * sigma_factor
+ *               [octave]) or z <= 0; left, then right) over the pairs of kf_local keyframes on present landmarks; other pairs
+ *               get 0.  The call removes nothing itself: for a second pass clear the flagged pairs' flags and call again.
+ * VSLAM_ERR_INVALID, nothing launched, nothing written: NULL arrays, n_kf < 1, an index out of range, an edge with i == j, a
+ * non-finite value, a negative weight or parameter, an octave outside the tables, a free gauge, a factor on a present landmark
+ * with z <= 0 at the initial values (the message names the pair).
+ * VSLAM_ERR_CAPACITY, likewise, checked before anything is sized: n_kf > 16384, n_edges > 262144, n_pairs > 2097152,
+ * n_lm > 1048576, the squares of the present landmarks' free-keyframe pair counts summing to more than 16777216 (the bound of
+ * the block lists' length), a band of (b + 1) * n_free > 262144 blocks.
+ * Per trial: linearise (only after an accepted trial), the landmarks' damped blocks, W and Y = W Hll^-1 per pair, the reduced
+ * system GATHERED per block of the band over lists built once on the host (no floating-point atomics: two calls on the same
+ * input return the same bytes), band copy, factor and solve (pgo_band_chol_walk), landmark back-substitution, retraction, cost,
+ * fixed-order sum and the accept / reject rule on a device control block.  The host waits once per trial, for one int; every
+ * buffer comes from the calling thread's block cache.
+ * ------------------------------------------------------------------------- */
+struct vslam_ba_problem;
+typedef struct vslam_gba_params {     /* a zero field takes the default in brackets (NULL = all defaults) */
+    int32_t max_iterations;   /* [20]   accepted trials */
+    double lambda0;           /* [1e-4] */
+} vslam_gba_params;
+
+typedef struct vslam_gba_report {
+    int32_t iterations;       /* trials = accepted + rejected */
+    int32_t accepted, rejected;
+    int32_t n_free, n_isolated;           /* keyframes */
+    int32_t n_present, n_thin;            /* landmarks */
+    int32_t n_factors;                    /* two-row factors on present landmarks */
+    int32_t half_bandwidth;               /* b, in blocks, after the reordering */
+    int32_t reserved;
+    double initial_cost, final_cost, final_lambda;
+} vslam_gba_report;
+
+typedef struct vslam_gba_result {
+    double* kf_pose_wc;       /* n_kf x 16 (may be the problem's array) */
+    double* lm_xyz;           /* n_lm x 3  (may be the problem's array) */
+    uint8_t* pair_wrong;      /* n_pairs */
+    vslam_gba_report report;
+} vslam_gba_result;
+
+vslam_status vslam_global_ba(const struct vslam_ba_problem* problem, const vslam_pgo_edge* edges, int32_t n_edges,
+                             const vslam_gba_params* params, int32_t device, vslam_gba_result* result);
+/* measurement hook of tools/gba_rate.py, in the form of the pose-graph one: device time (HIP events) per kernel group of the
+ * calling thread's last vslam_global_ba - gba_linearize, gba_landmarks, gba_assemble, gba_band_chol, gba_back, gba_cost,
+ * gba_chi2; off by default; thread-local state. */
+vslam_status vslam_global_ba_set_timing(int32_t on);
+vslam_status vslam_global_ba_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
+
+/* ---------------------------------------------------------------------------
  * Duplicate search between two copies of a place (no reference counterpart: the reference closes no loops; DESIGN.md section 6
  * item 26, restated in numpy by tests/fuse_ref.py; csrc/fuse.hip).  Set A is the new copy (it will be absorbed), set B the old
  * one (it is kept): world positions (fp64 [3]) and 256-bit descriptors (32 bytes) of up to 65536 points each.  Both are
@@ -1188,6 +1259,54 @@ vslam_status vslam_system_map_point_observations(vslam_system* sys, int32_t cap_
 vslam_status vslam_system_keyframe_points(vslam_system* sys, int32_t kf, int32_t cap_l, int32_t cap_r, int32_t* n_l_out, int32_t* n_r_out,
                                           int32_t* lmp_l, int32_t* lmp_r);
 vslam_status vslam_system_fused_pairs(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* pairs);
+
+/* vslam_system_global_ba: one vslam_global_ba over the whole map of a stereo session - what makes
+ * reprojection error, not relative-pose error, decide where the keyframes and the fused points of a closed loop end up.
+ * Refusals (VSLAM_ERR_INVALID, nothing changed): mono and IMU sessions, with the messages of the loop calls; a negative or
+ * non-finite parameter.  report->busy = 1, VSLAM_OK, nothing changed: a local_mapping = 2 session with a mapping pass in flight.
+ * A session with fewer than two keyframes: success = 0, nothing changed.  Otherwise, under the map's lock:
+ *   1 a finished local BA is propagated first, as the next frame would
+ *   2 ALL keyframes are flattened: keyframe 0 and every `fixed` one are fixed, all are kf_local
+ *   3 all non-outlier map points with the pair flags of the local BA's collection (left: 1, left + right of a `close` key: 3,
+ *     right only: 2); a point that is out of frame with fewer than three observations carries no pair
+ *     PARALLAX GUARD: a point whose observation rays (from the observing camera centres, the right camera's for a right factor,
+ *     at the current values) never open wider than acos(0.9998) = 1.15 degrees gets flags 0 on all its pairs: its depth is not
+ *     observable, one pass would walk it towards infinity.  It stays where it is, as a thin landmark does
+ *   4 sequential edges (prevKF -> keyframe, the current relative pose) at weight edge_weight on rotation and translation; 0: none
+ *   5 vslam_global_ba with `gba`
+ *   6 commit, the local BA's write-back: wrong pairs are erased from the map point and from the keyframe's tables, poses of
+ *     non-fixed keyframes and positions of present points are stored, a point flagged in 3 or left out of frame with fewer than
+ *     three observations becomes an outlier, the depth / close refresh and the descriptor selection of the moved points are served
+ *   7 refPose of every keyframe re-derived, the camera re-anchored on the latest keyframe, the active set rebuilt by
+ *     relocalisation's rule (as vslam_system_correct_loop ends)
+ * A refusal of vslam_global_ba (a free gauge, a point behind a keyframe) is returned as it is, with nothing changed.
+ * Not for lanes of a vslam_batch, not called from vslam_system_close_loop or vslam_system_fuse_loop: the caller decides when. */
+typedef struct vslam_system_gba_params {  /* a zero field takes the default in brackets (NULL = all defaults) */
+    vslam_gba_params gba;
+    double edge_weight;                   /* [0: no edges] */
+} vslam_system_gba_params;
+
+typedef struct vslam_system_gba_report {
+    int32_t busy;                         /* 1: a mapping pass is in flight, nothing was done */
+    int32_t success;                      /* 1: the solve ran and was committed */
+    int32_t n_keyframes, n_landmarks, n_pairs, n_edges;      /* the flattened problem */
+    int32_t n_wrong;                      /* pairs erased */
+    int32_t n_outliers;                   /* map points that became outliers */
+    int32_t n_active_after;
+    int32_t reserved;
+    vslam_gba_report gba;
+} vslam_system_gba_report;
+
+vslam_status vslam_system_global_ba(vslam_system* sys, const vslam_system_gba_params* params, vslam_system_gba_report* report);
+/* test tap: the flattened problem the call would build now (steps 1 - 4; step 1 is carried out).  sizes [5] = n_kf, n_lm,
+ * n_pairs, n_edges, n_levels, always written; with arrays == 0 nothing else is.  Otherwise every array is written, each at least
+ * as long as its size says: kf_pose_wc [n_kf][16], kf_fixed, kf_local, lm_xyz [n_lm][3], lm_index [n_lm] (map-point index),
+ * pair_kf, pair_lm, pair_flags, pair_uv [n_pairs][4], pair_octave [n_pairs][2], edges [n_edges], sigma_factor and
+ * inv_sigma_factor [n_levels].  The same refusals as the call; busy: VSLAM_ERR_INVALID. */
+vslam_status vslam_system_global_ba_problem(vslam_system* sys, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                            uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                            int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                            vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor);
 /* test tap: the IMU state of a session; any pointer may be NULL */
 vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
 /* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with

@@ -1,0 +1,125 @@
+"""Time of one vslam_global_ba call on out-and-back corridors of 200, 1 000 and 2 000 keyframes at the bench workload's density.
+
+The camera walks 0.3 m per keyframe along x, looking sideways (+z) at landmarks 2 - 5 m away, and returns beside its own track.
+Every keyframe of the way out starts 50 landmarks that it and its next two keyframes see (about 100 landmarks per keyframe); the
+first view of a landmark is a left + right pair, the others are left only, and every third landmark is seen again, the same way,
+by the three keyframes of the way back that stand beside them: about 5 factors per landmark.  Keyframe 0 is fixed; measurements
+carry 0.3 px of noise (times 1.2^octave), the start is the truth disturbed by 0.004 rad / 0.01 m per keyframe and 0.01 m per point.
+Every call uploads the problem, runs the LM loop and downloads the result, as a caller's call does.
+Reported per size: the wall-clock time of a call - two warm-up calls, then `reps` repetitions of `calls` calls, median and range
+over the repetitions; the half-bandwidth b after the reordering, the trials, the costs; from one more call with the library's
+HIP-event timing on, the device time per kernel group; microseconds of the factorisation group per block column and trial.
+Then one problem both bundle adjustments can run, 150 free keyframes of the same corridor: vslam_local_ba (two passes, dense
+reduced system) and vslam_global_ba side by side, with the time per LM trial of each.  Numbers only, no bar.
+usage: python tools/gba_rate.py [out.json] [calls] [reps]"""
+import json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("gtsam-vslam_amd", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+import numpy as np
+import gba_ref as gr
+import pgo_ref as pr
+import vslam_capi as vc
+
+SIZES = (200, 1000, 2000)
+PER_KF = 50
+
+
+def corridor(n_free, seed=1):
+    rng = np.random.default_rng(seed)
+    K = n_free + 1
+    half = n_free // 2
+    xs = np.array([0.3 * (k if k <= half else n_free - k) for k in range(K)])
+    truth = np.array([gr.look_z(xs[k], 0.0 if k <= half else 0.06, 0.01 * np.cos(0.3 * k), 0.02 * np.sin(0.2 * k)) for k in range(K)])
+    start_kf = np.repeat(np.arange(half - 1), PER_KF)
+    L = len(start_kf)
+    lm = np.stack([xs[start_kf] + rng.uniform(-0.8, 1.4, L), rng.uniform(-0.8, 0.8, L), rng.uniform(2.0, 5.0, L)], 1)
+    pk, pl, pf = [], [], []
+    for j in range(3):
+        pk.append(start_kf + j); pl.append(np.arange(L)); pf.append(np.full(L, 3 if j == 0 else 1))
+    again = np.flatnonzero(np.arange(L) % 3 == 0)
+    for j in range(3):
+        kb = n_free - (start_kf[again] + j)
+        ok = (kb > half) & (kb < K)
+        pk.append(kb[ok]); pl.append(again[ok]); pf.append(np.full(int(ok.sum()), 3 if j == 0 else 1))
+    pk, pl, pf = np.concatenate(pk), np.concatenate(pl), np.concatenate(pf)
+    order = np.lexsort((pk, pl))
+    pk, pl, pf = pk[order], pl[order], pf[order]
+    fx, fy, cx, cy, bl = gr.camera(gr.RIG)
+    R, t = truth[pk, :3, :3], truth[pk, :3, 3]
+    q = np.einsum("nji,nj->ni", R, lm[pl] - t)
+    octv = np.clip(np.round(np.log(q[:, 2] / 2.0) / np.log(1.2)), 0, 7).astype(np.int32)
+    uv = np.stack([fx * q[:, 0] / q[:, 2] + cx, fy * q[:, 1] / q[:, 2] + cy, fx * (q[:, 0] - bl) / q[:, 2] + cx, fy * q[:, 1] / q[:, 2] + cy], 1)
+    uv += rng.normal(0, 0.3, uv.shape) * gr.SCALE[octv][:, None]
+    start = truth.copy()
+    for k in range(1, K):
+        start[k] = truth[k] @ pr.random_pose(rng, 0.004, 0.01)
+    fixed = np.zeros(K, np.uint8)
+    fixed[0] = 1
+    return dict(rig=gr.RIG, kf_pose=start, kf_id=np.arange(K, dtype=np.int64), kf_fixed=fixed, kf_local=np.ones(K, np.uint8),
+                lm=lm + rng.normal(0, 0.01, lm.shape), pair_kf=pk.astype(np.int32), pair_lm=pl.astype(np.int32), pair_flags=pf.astype(np.uint8),
+                pair_uv=uv.astype(np.float32), pair_oct=np.stack([octv, octv], 1).astype(np.int32))
+
+
+def timed(fn, calls, reps):
+    for _ in range(2):
+        fn()
+    per = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        per.append(1e3 * (time.perf_counter() - t0) / calls)
+    return dict(median=float(np.median(per)), min=float(min(per)), max=float(max(per)))
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "gba_rate.json")
+    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    res = dict(protocol="2 warm-up calls, %d repetitions of %d calls, host clock around calls that end in a device synchronise; kernel groups "
+                        "from HIP events of one more call" % (reps, calls), sizes={})
+    gba = lambda prob: vc.global_ba(prob["rig"], gr.SIGMA, gr.INV_SIGMA, prob)
+    for n in SIZES:
+        prob = corridor(n)
+        got = gba(prob)
+        rep = got["report"]
+        ms = timed(lambda: gba(prob), calls, reps)
+        vc.global_ba_set_timing(True)
+        gba(prob)
+        groups = vc.global_ba_timings()
+        vc.global_ba_set_timing(False)
+        row = dict(keyframes=n + 1, landmarks=len(prob["lm"]), pairs=len(prob["pair_kf"]), factors=rep["n_factors"],
+                   landmarks_per_keyframe=len(prob["pair_kf"]) / (n + 1), factors_per_landmark=rep["n_factors"] / max(rep["n_present"], 1),
+                   ms_per_call=ms, kernel_group_ms=groups, half_bandwidth=rep["half_bandwidth"], lm_trials=rep["iterations"],
+                   accepted=rep["accepted"], rejected=rep["rejected"], initial_cost=rep["initial_cost"], final_cost=rep["final_cost"],
+                   us_band_chol_per_column_and_trial=1e3 * groups.get("gba_band_chol", 0.0) / (rep["n_free"] * max(rep["iterations"], 1)))
+        print(n, json.dumps(row), flush=True)
+        res["sizes"][str(n)] = row
+    # one problem both calls can run
+    prob = corridor(150, seed=2)
+    side = {}
+    g = gba(prob)
+    side["global_ba"] = dict(ms_per_call=timed(lambda: gba(prob), calls, reps), trials=g["report"]["iterations"], half_bandwidth=g["report"]["half_bandwidth"],
+                             initial_cost=g["report"]["initial_cost"], final_cost=g["report"]["final_cost"])
+    side["global_ba"]["ms_per_trial"] = side["global_ba"]["ms_per_call"]["median"] / max(g["report"]["iterations"], 1)
+    try:
+        lba = lambda: vc.local_ba(prob["rig"], gr.SIGMA, gr.INV_SIGMA, prob)
+        l = lba()
+        trials = sum(r["inner"] for r in l["reports"])
+        side["local_ba"] = dict(ms_per_call=timed(lba, calls, reps), trials=trials, lm_iterations=[r["iterations"] for r in l["reports"]],
+                                final_error_x2=[2 * r["finalError"] for r in l["reports"]], free_kf=int(l["free_kf"]),
+                                max_pose_difference_to_global=float(np.abs(l["kf_pose"] - g["kf_pose"]).max()))
+        side["local_ba"]["ms_per_trial"] = side["local_ba"]["ms_per_call"]["median"] / max(trials, 1)
+    except vc.VslamError as e:
+        side["local_ba"] = dict(error=str(e))
+    res["side_by_side_150_free_keyframes"] = dict(keyframes=151, landmarks=len(prob["lm"]), pairs=len(prob["pair_kf"]), **side,
+                                                  note="the local BA adds between factors along kf_id and runs two passes of 5 + 10 iterations at "
+                                                       "tolerance 1e-5; the global BA runs one pass to a relative decrease of 1e-10: the results differ by design")
+    print(json.dumps(res["side_by_side_150_free_keyframes"]), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
