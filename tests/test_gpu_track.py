@@ -31,14 +31,18 @@ def oracle_init_map(rig, ex, kL, dL, st, T_wc):
     return xyz, dL[idx].copy(), msd
 
 
-def oracle_track(oracle, rig, ex, keys, st, mp, T_wc_pred, frame_number, imu=None):
+def oracle_track(oracle, rig, ex, keys, st, mp, T_wc_pred, frame_number, imu=None, outlier=None):
+    """outlier: MapPoint::isOutlier per map point (removeOutOfFrameMPs drops those before the visibility test)"""
     kL, dL, kR, dR = keys
     xyz, desc, msd = mp
     log_scale = np.float32(np.log(np.float64(np.float32(1.2))))
     T_cw = rigid_inv(T_wc_pred)
     uL, vL, lL, visL = oracle.world_to_frame(rig, T_cw, False, xyz, msd, log_scale)
     uR, vR, lR, visR = oracle.world_to_frame(rig, T_cw, True, xyz, msd, log_scale)
-    act = np.nonzero(visL & visR)[0]
+    keep = visL & visR
+    if outlier is not None:
+        keep = keep & ~np.asarray(outlier, bool)
+    act = np.nonzero(keep)[0]
     M = len(act)
     mps = np.zeros(M, oracle.MPV_DTYPE)
     mps["desc"] = desc[act]
@@ -106,7 +110,7 @@ def oracle_track(oracle, rig, ex, keys, st, mp, T_wc_pred, frame_number, imu=Non
     _, mL, mR, mt, _ = oracle.match_projection(ex, rig, mps, kL, dL, kR, dR, state["rightIdxs"], state["leftIdxs"], mL, mR, mt, 4.0)
     r = solve(est, mt, outl, state)
     return dict(T_cw=r["T_cw"], nIn=r["nIn"], nStereo=r["nStereo"], matches=r["matches"], outliers=r["outliers"],
-                act=act, rounds=rounds, iters=iters + r["iterations"], state=state, vel=r.get("vel"), bias=r.get("bias"))
+                act=act, rounds=rounds, last_radius=rad, iters=iters + r["iterations"], state=state, vel=r.get("vel"), bias=r.get("bias"))
 
 
 @pytest.mark.parametrize("f0,f1,frame_number", [(4, 5, 7), (8, 10, 1), (2, 3, 3)])
