@@ -9,6 +9,7 @@
 // Compiled with -ffp-contract=off: float expressions round exactly as written.
 #include "extract_kernels.hpp"
 #include "../../include/vslam_orb_pattern.h"
+#include "orient_math.hpp"
 #include <cfloat>
 
 namespace vslam {
@@ -875,53 +876,8 @@ void launch_blur(hipStream_t s, const uint8_t* pyr, uint8_t* blur, const PyrDesc
 // merge their nibbles into descriptor bytes.  Keypoints are written in the reference
 // output order (level-major, SSC order) with pt scaled AFTER the descriptor (:523-524).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float fast_atan2_deg(float y, float x) {
-    const float scale = (float)(180 / 3.1415926535897932384626433832795);
-    const float p1 = 0.9997878412794807f * scale;
-    const float p3 = -0.3258083974640975f * scale;
-    const float p5 = 0.1555786518463281f * scale;
-    const float p7 = -0.04432655554792128f * scale;
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + (float)DBL_EPSILON);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + (float)DBL_EPSILON);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a;
-}
-
-// float(cos(double(x))), float(sin(double(x))) for x in [0, ~2 pi]: Cody-Waite reduction by pi/2 (k <= 4, so k * pio2_1
-// is exact and the difference is exact) and the fdlibm kernel polynomials (< 1 ulp in double).  Replaces the library
-// cos() + sin() calls (two separate range reductions, ~4x the instructions); wave-uniform work.
-__device__ __forceinline__ void sincos_deg_range(float xf, float& s_out, float& c_out) {
-    const double x = (double)xf;
-    const double kd = rint(x * 6.36619772367581382433e-01);
-    const int k = (int)kd;
-    double r = fma(-kd, 1.57079632673412561417e+00, x);
-    r = fma(-kd, 6.07710050650619224932e-11, r);
-    const double z = r * r;
-    double ps = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    ps = fma(z, ps, 2.75573137070700676789e-06);
-    ps = fma(z, ps, -1.98412698298579493134e-04);
-    ps = fma(z, ps, 8.33333333332248946124e-03);
-    const double sn = fma(z * r, fma(z, ps, -1.66666666666666324348e-01), r);
-    double pc = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    pc = fma(z, pc, -2.75573143513906633035e-07);
-    pc = fma(z, pc, 2.48015872894767294178e-05);
-    pc = fma(z, pc, -1.38888888888741095749e-03);
-    pc = fma(z, pc, 4.16666666666666019037e-02);
-    const double cs = 1.0 - fma(0.5, z, -(z * (z * pc)));
-    const double sq = (k & 1) ? cs : sn, cq = (k & 1) ? sn : cs;
-    s_out = (float)((k & 2) ? -sq : sq);
-    c_out = (float)(((k + 1) & 2) ? -cq : cq);
-}
+// fast_atan2_deg (the cv::fastAtan2 polynomial) and sincos_deg_range (float(cos(double)), float(sin(double))) live in
+// orient_math.hpp, which a host compiler can include too.
 
 // Moments: lane = (half, u): lanes 0..30 walk the rows v = 0..15 of column u = lane - 15, lanes 32..62 the rows
 // -1..-15; a row's loads are contiguous bytes.  m10 = sum_u u * (column sum), m01 = sum v * I: integer sums, order-free.
@@ -1018,8 +974,8 @@ __global__ __launch_bounds__(256) void k_orient_desc(
 
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
     const float ang = angle * factorPI;
-    // correctly-rounded float cos/sin through double (matches libm's cosf/sinf on every input the parity tests cover;
-    // see DESIGN.md "float trig")
+    // float(cos(double)), float(sin(double)): the chosen route, equal to libm's double cos / sin at every float angle (census: DESIGN.md section 6
+    // item 5; libm's cosf / sinf differ from it at 1.5 M angles, at 96 of them by a whole pattern offset)
     float a, b;
     sincos_deg_range(ang, b, a);
     const uint8_t* pb = (const uint8_t*)patch + 19 * (OD_DW * 4) + 19 + xoff;      // the keypoint's own pixel

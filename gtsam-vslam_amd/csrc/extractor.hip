@@ -549,6 +549,7 @@ vslam_status vslam_extractor::run() {
     VS_HIP(hipEventRecord(evDone, stream));
     countsPending = true;          // totals / flags are read (after evDone) by wait_counts()
     ran = true;
+    pyramidsBuilt = true;
     return VSLAM_OK;
 }
 
@@ -771,6 +772,53 @@ vslam_status vslam_extractor_ssc_level(vslam_extractor* ex, int32_t level, const
         out[k].size = (float)ex->scaledPatchSize[level]; out[k].angle = -1.f;
         out[k].response = (float)cand_s(kept[k]); out[k].octave = level; out[k].class_id = -1;
     }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_extractor_describe(vslam_extractor* ex, int32_t i, int32_t level, const vslam_keypoint* kps, int32_t n,
+                                      vslam_keypoint* out_kps, uint8_t* out_desc, int32_t cap, int32_t* n_out) {
+    if (!ex || !n_out || i < 0 || i >= ex->nimg || level < 0 || level >= ex->nLevels || n < 0 || (n > 0 && (!kps || !out_kps || !out_desc))) {
+        set_error("describe: bad argument");
+        return VSLAM_ERR_INVALID;
+    }
+    if (!ex->pyramidsBuilt) { set_error("describe: the extractor has not run (no pyramid, no blurred pyramid)"); return VSLAM_ERR_INVALID; }
+    if (n > ex->keptCap) { set_error("describe: %d keypoints > capacity %d", n, ex->keptCap); return VSLAM_ERR_CAPACITY; }
+    if (n > cap) { set_error("describe: cap %d < %d keypoints", cap, n); return VSLAM_ERR_CAPACITY; }
+    // k_orient_desc reads the 39 x 39 patch around a keypoint without a bounds test: the extractor's own keypoints lie at
+    // least 19 px (>= edge_threshold) inside their level, and so must these
+    const int w = ex->P.w[level], h = ex->P.h[level];
+    std::vector<uint32_t> pk((size_t)std::max(n, 1));
+    for (int k = 0; k < n; k++) {
+        const float fx = kps[k].x, fy = kps[k].y, fr = kps[k].response;
+        if (!(fx >= 19.f && fx <= (float)(w - 20) && fy >= 19.f && fy <= (float)(h - 20)) || fx != (float)(int)fx || fy != (float)(int)fy) {
+            set_error("describe: keypoint %d at (%g, %g) outside 19 <= x <= %d, 19 <= y <= %d of level %d (or not integer-valued)",
+                      k, (double)fx, (double)fy, w - 20, h - 20, level);
+            return VSLAM_ERR_INVALID;
+        }
+        if (!(fr >= 0.f && fr <= 255.f) || fr != (float)(int)fr) {
+            set_error("describe: keypoint %d has response %g outside 0..255", k, (double)fr);
+            return VSLAM_ERR_INVALID;
+        }
+        pk[k] = pack_cand((int)fx, (int)fy, (int)fr);
+    }
+    VS_HIP(hipSetDevice(ex->device));
+    VS_CHECK(ex->wait_counts());
+    ex->wait_consumers();
+    // the kept list of image i: n keypoints, all of `level`; every other image: none
+    std::vector<int> koff((size_t)ex->nimg * (MAX_LEVELS + 1), 0);
+    for (int l = level + 1; l <= MAX_LEVELS; l++) koff[(size_t)i * (MAX_LEVELS + 1) + l] = n;
+    VS_HIP(hipMemcpyAsync(ex->d_keptOff, koff.data(), koff.size() * sizeof(int), hipMemcpyHostToDevice, ex->stream));
+    if (n) VS_HIP(hipMemcpyAsync(ex->d_kept + (size_t)i * ex->keptCap, pk.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ex->stream));
+    launch_orient_desc(ex->stream, ex->d_pyr, ex->d_blur, ex->P, ex->T, ex->d_kept, ex->d_keptOff, ex->keptCap, ex->discRows, ex->d_kps,
+                       ex->d_desc, ex->keptCap, n, ex->nimg);
+    VS_HIP(hipGetLastError());
+    if (n) {
+        VS_HIP(hipMemcpyAsync(out_kps, ex->d_kps + (size_t)i * ex->keptCap, (size_t)n * sizeof(vslam_keypoint), hipMemcpyDeviceToHost, ex->stream));
+        VS_HIP(hipMemcpyAsync(out_desc, ex->d_desc + (size_t)i * ex->keptCap * 32, (size_t)n * 32, hipMemcpyDeviceToHost, ex->stream));
+    }
+    VS_HIP(hipStreamSynchronize(ex->stream));      // (also: the host vectors above were read)
+    ex->ran = false;                 // the extractor's frame outputs no longer describe an image
+    *n_out = n;
     return VSLAM_OK;
 }
 

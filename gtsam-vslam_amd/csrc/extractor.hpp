@@ -55,6 +55,7 @@ struct vslam_extractor {
     vslam_status enable_double_output();
     std::vector<int> nKept;           // per image, after the last run (valid after wait_counts())
     bool ran = false;
+    bool pyramidsBuilt = false;       // a run() has built the pyramid and its blurred copy (what the describe test tap reads)
     // SSC (FeatureExtractor::ssc) runs in k_ssc, on the device only: picks, per-task counts, flags, and the per-image
     // totals / flags mirrored into mapped host memory
     uint32_t* d_sscTmp = nullptr;     // picks | (HBM instantiation) sort keys | stopper lists / sorted candidates

@@ -166,6 +166,16 @@ class Extractor:
         _chk(self.L.vslam_extractor_ssc_level(self.h, level, _p(cand), len(cand), _p(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def describe(self, idx, level, kps):
+        """k_orient_desc alone on caller-supplied keypoints of one level of image `idx` (level coordinates in x / y, response
+        0..255), after a run() on the current images (test tap) -> (keypoints, descriptors)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE)
+        out = np.zeros(max(len(kps), 1), KP_DTYPE)
+        desc = np.zeros((max(len(kps), 1), 32), np.uint8)
+        n = C.c_int32()
+        _chk(self.L.vslam_extractor_describe(self.h, idx, level, _p(kps), len(kps), _p(out), _p(desc), len(out), C.byref(n)))
+        return out[:n.value].copy(), desc[:n.value].copy()
+
     def timings(self):
         names = (C.c_char_p * 32)()
         ms = (C.c_float * 32)()

@@ -130,6 +130,17 @@ vslam_status vslam_extractor_candidates(vslam_extractor* ex, int32_t image_index
 vslam_status vslam_extractor_ssc_level(vslam_extractor* ex, int32_t level, const vslam_keypoint* cand, int32_t n,
                                        vslam_keypoint* out, int32_t cap, int32_t* n_out);
 
+/* test tap: orientation + descriptor (k_orient_desc alone, the kernel a frame runs) of caller-supplied keypoints of
+ * pyramid level `level` of image `image_index`, on the pyramid and the blurred pyramid that the last
+ * vslam_extractor_run() built.  kps[k].x / .y: integer-valued LEVEL coordinates with 19 <= x <= w_level - 20 and
+ * 19 <= y <= h_level - 20 (the extractor's own guarantee; the kernel reads the patch unchecked), .response integer-valued
+ * 0..255; the other fields are ignored.  Writes n keypoints (angle, size, octave, x / y scaled to level 0 as a frame's)
+ * and n x 32 descriptor bytes.  VSLAM_ERR_INVALID before the first run and for a keypoint outside these ranges (nothing
+ * is launched, vslam_last_error() names the keypoint), VSLAM_ERR_CAPACITY for more keypoints than an image can keep or
+ * than `cap`.  Invalidates the extractor's last frame. */
+vslam_status vslam_extractor_describe(vslam_extractor* ex, int32_t image_index, int32_t level, const vslam_keypoint* kps,
+                                      int32_t n, vslam_keypoint* out_kps, uint8_t* out_desc, int32_t cap, int32_t* n_out);
+
 /* per-kernel device time of the last run, in milliseconds (HIP events on the
  * extractor's stream).  names/ms hold up to cap entries; n_out = entries written. */
 vslam_status vslam_extractor_timings(const vslam_extractor* ex, const char** names, float* ms,

@@ -151,11 +151,13 @@ def fast_atan2(y, x):
     return float(lib().vo_fast_atan2(C.c_float(y), C.c_float(x)))
 
 
-def orb_descriptor(kp, img):
+def orb_descriptor(kp, img, trig="double"):
+    """trig: "double" = float(cos(double(angle))), the oracle's route; "float" = cosf / sinf of the host libm (tests only)"""
+    assert trig in ("double", "float")
     img = np.ascontiguousarray(img, np.uint8)
     kp = np.ascontiguousarray(kp, KP_DTYPE)
     d = np.zeros(32, np.uint8)
-    lib().vo_orb_descriptor(_p(kp), _p(img), img.shape[1], img.shape[0], _p(d))
+    lib().vo_orb_descriptor(_p(kp), _p(img), img.shape[1], img.shape[0], _p(d), int(trig == "float"))
     return d
 
 

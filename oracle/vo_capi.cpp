@@ -91,10 +91,11 @@ float vo_orientation(void* h, const uint8_t* img, int w, int hgt, float px, floa
     memcpy(s.d.data(), img, (size_t)w * hgt);
     return e->computeOrientation(s, px, py);
 }
-void vo_orb_descriptor(const KeyPoint* kp, const uint8_t* img, int w, int hgt, uint8_t* desc32) {
+// floatTrig: cosf / sinf of the host libm instead of float(cos(double)), float(sin(double)) (tests only)
+void vo_orb_descriptor(const KeyPoint* kp, const uint8_t* img, int w, int hgt, uint8_t* desc32, int floatTrig) {
     Image s(w, hgt);
     memcpy(s.d.data(), img, (size_t)w * hgt);
-    orbDescriptor(*kp, s, desc32);
+    orbDescriptor(*kp, s, desc32, floatTrig != 0);
 }
 int vo_ssc(void* h, const KeyPoint* in, int n, int numRet, float tol, int cols, int rows,
            KeyPoint* out) {

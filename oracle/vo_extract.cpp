@@ -474,12 +474,17 @@ void gaussianBlur7(const Image& src, Image& dst) {
     }
 }
 
-// computeOrbDescriptor: src/FeatureExtractor.cpp:267-305.  cos/sin taken as the
-// float overloads; the rotated offsets are float expressions rounded half-even.
-void orbDescriptor(const KeyPoint& kpt, const Image& img, uint8_t* desc) {
+// computeOrbDescriptor: src/FeatureExtractor.cpp:267-305.  The reference writes (float)cos(angle) on a float, unqualified,
+// inside its namespace and without `using namespace std`: with the C library's <math.h> declarations alone in the global
+// namespace that is cos(double), and its result rounded to float is ONE defined value; cosf is whatever the installed libm
+// returns (DESIGN.md deviation 5 has the census of where the two part).  The double route is the oracle's; floatTrig keeps
+// the other one reachable for tests.  The rotated offsets are float expressions rounded half-even.
+void orbDescriptor(const KeyPoint& kpt, const Image& img, uint8_t* desc, bool floatTrig) {
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
     float angle = (float)kpt.angle * factorPI;
-    float a = cosf(angle), b = sinf(angle);
+    float a, b;
+    if (floatTrig) { a = cosf(angle); b = sinf(angle); }
+    else { a = (float)std::cos((double)angle); b = (float)std::sin((double)angle); }
     const int step = img.w;
     const uint8_t* center = &img.d[(size_t)cvRoundF(kpt.y) * step + cvRoundF(kpt.x)];
     const signed char* pat = VSLAM_ORB_PATTERN;

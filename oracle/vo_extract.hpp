@@ -37,6 +37,6 @@ int fastCornerScore(const uint8_t* ptr, const int pixel[25], int threshold);
 float fastAtan2(float y, float x);                                      // cv::fastAtan2
 void gaussianKernel7Sigma2(int k[7]);                                   // 8.8 fixed-point taps
 void gaussianBlur7(const Image& src, Image& dst);                       // cv::GaussianBlur 7x7 s=2
-void orbDescriptor(const KeyPoint& kpt, const Image& img, uint8_t* desc);
+void orbDescriptor(const KeyPoint& kpt, const Image& img, uint8_t* desc, bool floatTrig = false);
 
 }  // namespace vo

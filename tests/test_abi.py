@@ -17,6 +17,7 @@ def test_library_exports_every_declared_symbol(capi):
     lib = ctypes.CDLL(capi.LIB_PATH)
     syms = declared_symbols()
     assert len(syms) >= 10
+    assert "vslam_extractor_describe" in syms and "vslam_extractor_ssc_level" in syms      # the extractor's test taps
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
 
