@@ -30,8 +30,14 @@
 #include "ba_types.hpp"           // argument blocks, control block, launch constants
 #include "ba_order_host.hpp"      // host: ordering, membership, second-pass statistics, reports
 #include "ba_plan.hpp"            // host: launch geometry
+#include "grow_buf.hpp"           // host: the grow-only buffers of the workspaces
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cmath>
+#include <memory>
+#include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace vslam {
@@ -2066,302 +2072,74 @@ __global__ __launch_bounds__(256) void k_ba_init_slots_b(const BaDev* __restrict
 }
 
 
-// ---- factor ordering on the device (large problems: the 100 k-landmark window) --------------------------------------------------
-// BaPassHost::count / fill as kernels over the raw pair arrays, which are on the device anyway (the chi2 kernel reads them).  The
-// factor order is (landmark, free index, pair, side): a TOTAL order - the bucket of a landmark is filled in arrival order (atomics)
-// and every factor then finds its place by counting the entries of its bucket that precede it, so the result does not depend on the
-// arrival order and equals the host's stable counting sort + insertion sort entry for entry.
-struct BaOrd {
-    int NP, L, K, world, rank;
-    const int* pairKf; const int* pairLm; const uint8_t* pairFlags; const uint8_t* wrong; const float* pairUv; const int* pairOct;
-    int* cnt; int* lpOf; int* tLpOrig; int* tLpStart; int* kfPres; uint8_t* lmPres; long long* scal;      // phase 1 (sized by L, K)
-    const int* fidx; int* fillc; int* ns; int* key; int* src; int* key2; int* src2;                        // phase 2 (sized by NF, Lp)
-    int* facKf; int* facFi; int* facLp; int* facLm; int* facPair; double* facZ; double* facIs; uint8_t* facRight;
-    int* lpStart; int* lpSlotStart; int* lpOrig; int* slotStart; int* slotFi;
-    float invSigma[MAX_LEVELS];
-};
-enum { ORD_LP = 0, ORD_NF = 1, ORD_NSLOT = 2, ORD_MAXSLOTS = 3, ORD_MAXFAC = 4, ORD_SUMK2 = 5, ORD_K2_MASKED = 6, ORD_SCAL = 8 };
-
-__global__ __launch_bounds__(256) void k_ord_count(BaOrd O) {
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < O.NP; p += gridDim.x * 256) {
-        if (O.wrong[p]) continue;
-        const int fl = O.pairFlags[p] & 3;
-        if (!fl) continue;
-        const int l = O.pairLm[p];
-        O.kfPres[O.pairKf[p]] = 1; O.lmPres[l] = 1;             // graph membership is global
-        if (l % O.world != O.rank) continue;                      // landmark shard of this rank
-        atomicAdd(&O.cnt[l], (fl & 1) + (fl >> 1));
-    }
-}
-// One workgroup walks an array in tiles of 1024 consecutive elements (coalesced): exclusive prefix of two ints per element = carry of the
-// tiles before + prefix of the waves before (LDS) + the wave's own inclusive scan (shuffles).  Two barriers per tile.
-struct OrdScan {
-    int carryA = 0, carryB = 0;
-    __device__ __forceinline__ void tile(int a, int b, int* sA, int* sB, int& exA, int& exB) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        int ia = a, ib = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int ta = __shfl_up(ia, d), tb = __shfl_up(ib, d);
-            if (lane >= d) { ia += ta; ib += tb; }
-        }
-        if (lane == 63) { sA[wave] = ia; sB[wave] = ib; }
-        __syncthreads();
-        int pa = 0, pb = 0, ta = 0, tb = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) { const int va = sA[w], vb = sB[w]; if (w < wave) { pa += va; pb += vb; } ta += va; tb += vb; }
-        exA = carryA + pa + ia - a; exB = carryB + pb + ib - b;
-        carryA += ta; carryB += tb;
-        __syncthreads();
-    }
-};
-// landmarks of this rank's shard that are in the graph, in index order: lpOf / lpOrig, and the start of every bucket
-__global__ __launch_bounds__(1024) void k_ord_scan_lm(BaOrd O) {
-    __shared__ int sA[16], sB[16];
-    OrdScan sc;
-    constexpr int E = 4;             // consecutive elements per thread and tile
-    for (int base = 0; base < O.L; base += 1024 * E) {
-        const int l0 = base + threadIdx.x * E;
-        bool in[E]; int cn[E];
-        int a = 0, b = 0;
-#pragma unroll
-        for (int j = 0; j < E; j++) {
-            const int l = l0 + j;
-            in[j] = l < O.L && O.lmPres[l] && l % O.world == O.rank;
-            cn[j] = in[j] ? O.cnt[l] : 0;
-            a += in[j] ? 1 : 0; b += cn[j];
-        }
-        int ea, eb;
-        sc.tile(a, b, sA, sB, ea, eb);
-#pragma unroll
-        for (int j = 0; j < E; j++) {
-            const int l = l0 + j;
-            if (l >= O.L) break;
-            if (in[j]) { O.lpOf[l] = ea; O.tLpOrig[ea] = l; O.tLpStart[ea] = eb; ea++; eb += cn[j]; }
-            else O.lpOf[l] = -1;
-        }
-    }
-    if (threadIdx.x == 0) { O.tLpStart[sc.carryA] = sc.carryB; O.scal[ORD_LP] = sc.carryA; O.scal[ORD_NF] = sc.carryB; O.scal[ORD_K2_MASKED] = 0; }
-}
-__global__ __launch_bounds__(256) void k_ord_scatter(BaOrd O) {
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < O.NP; p += gridDim.x * 256) {
-        if (O.wrong[p]) continue;
-        const int l = O.pairLm[p];
-        if (l % O.world != O.rank) continue;
-        const int fl = O.pairFlags[p] & 3;
-        if (!fl) continue;
-        const int lp = O.lpOf[l], fi = O.fidx[O.pairKf[p]];
-        const int c = (fl & 1) + (fl >> 1);
-        int pos = O.tLpStart[lp] + atomicAdd(&O.fillc[lp], c);
-        for (int side = 0; side < 2; side++) {
-            if (!((fl >> side) & 1)) continue;
-            O.key[pos] = fi; O.src[pos] = 2 * p + side; O.facLp[pos] = lp;
-            pos++;
-        }
-    }
-}
-// every factor finds its place inside its landmark's bucket: the number of entries (fi, 2 pair + side) that precede it
-__global__ __launch_bounds__(256) void k_ord_rank(BaOrd O, int NF) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= NF) return;
-    const int lp = O.facLp[f], f0 = O.tLpStart[lp], f1 = O.tLpStart[lp + 1];
-    const int k = O.key[f], v = O.src[f];
-    int r = 0;
-    for (int g = f0; g < f1; g++) { const int kg = O.key[g], vg = O.src[g]; r += (kg < k || (kg == k && vg < v)) ? 1 : 0; }
-    O.key2[f0 + r] = k; O.src2[f0 + r] = v;
-}
-__global__ __launch_bounds__(256) void k_ord_ns(BaOrd O, int Lp) {
-    const int lp = blockIdx.x * 256 + threadIdx.x;
-    if (lp >= Lp) return;
-    int last = -2, ns = 0;
-    for (int f = O.tLpStart[lp]; f < O.tLpStart[lp + 1]; f++) { const int fi = O.key2[f]; if (fi >= 0 && fi != last) { last = fi; ns++; } }
-    O.ns[lp] = ns;
-}
-// slot-table prefix (per landmark its slots + an end sentinel), the statistics of the pass, and the landmark arrays into their final place
-__global__ __launch_bounds__(1024) void k_ord_scan_slots(BaOrd O, int Lp) {
-    __shared__ int sA[16], sB[16];
-    __shared__ int rA[1024], rB[1024];
-    __shared__ long long rK[1024];
-    const int tid = threadIdx.x;
-    OrdScan sc;
-    int mx = 0, mf = 0;
-    long long k2 = 0;
-    constexpr int E = 4;
-    for (int base = 0; base < Lp; base += 1024 * E) {
-        const int lp0 = base + tid * E;
-        int nsv[E];
-        int a = 0;
-#pragma unroll
-        for (int j = 0; j < E; j++) {
-            const int lp = lp0 + j;
-            nsv[j] = 0;
-            if (lp < Lp) {
-                const int ns = O.ns[lp], f0 = O.tLpStart[lp], nf = O.tLpStart[lp + 1] - f0;
-                nsv[j] = ns + 1; a += ns + 1; mx = max(mx, ns); mf = max(mf, nf); k2 += (long long)ns * ns;
-                O.lpStart[lp] = f0; O.lpOrig[lp] = O.tLpOrig[lp];
-            }
-        }
-        int ea, eb;
-        sc.tile(a, 0, sA, sB, ea, eb);
-#pragma unroll
-        for (int j = 0; j < E; j++) { const int lp = lp0 + j; if (lp < Lp) { O.lpSlotStart[lp] = ea; ea += nsv[j]; } }
-    }
-    rA[tid] = mx; rB[tid] = mf; rK[tid] = k2;
-    __syncthreads();
-    for (int d = 512; d >= 1; d >>= 1) {
-        if (tid < d) { rA[tid] = max(rA[tid], rA[tid + d]); rB[tid] = max(rB[tid], rB[tid + d]); rK[tid] += rK[tid + d]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        O.lpSlotStart[Lp] = sc.carryA; O.lpStart[Lp] = O.tLpStart[Lp]; O.scal[ORD_NSLOT] = sc.carryA;
-        O.scal[ORD_MAXSLOTS] = max(rA[0], 1); O.scal[ORD_MAXFAC] = max(rB[0], 1); O.scal[ORD_SUMK2] = rK[0];
-    }
-}
-// statistics of the masked second pass: sum over the landmarks of (free keyframes still observing it)^2 with the rejected pairs left out
-__global__ __launch_bounds__(256) void k_ord_k2_masked(BaOrd O, int Lp) {
-    __shared__ long long sK[4];
-    const int lp = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long k2 = 0;
-    if (lp < Lp) {
-        int last = -2, ns = 0;
-        for (int f = O.lpStart[lp]; f < O.lpStart[lp + 1]; f++) {
-            if (O.wrong[O.facPair[f]]) continue;
-            const int fi = O.facFi[f];
-            if (fi >= 0 && fi != last) { last = fi; ns++; }
-        }
-        k2 = (long long)ns * ns;
-    }
-    for (int d = 32; d >= 1; d >>= 1) k2 += __shfl_xor(k2, d);
-    if (lane == 0) sK[wave] = k2;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd((unsigned long long*)&O.scal[ORD_K2_MASKED], (unsigned long long)(sK[0] + sK[1] + sK[2] + sK[3]));
-}
-__global__ __launch_bounds__(256) void k_ord_emit_fac(BaOrd O, int NF) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= NF) return;
-    const int fi = O.key2[f], sv = O.src2[f], p = sv >> 1, side = sv & 1;
-    O.facKf[f] = O.pairKf[p]; O.facFi[f] = fi; O.facLm[f] = O.pairLm[p];
-    O.facZ[2 * (size_t)f] = (double)O.pairUv[4 * (size_t)p + 2 * side]; O.facZ[2 * (size_t)f + 1] = (double)O.pairUv[4 * (size_t)p + 2 * side + 1];
-    O.facIs[f] = 1.0 / (1.0 / (double)O.invSigma[O.pairOct[2 * p + side]]);
-    O.facRight[f] = (uint8_t)side;
-    O.facPair[f] = p;
-}
-__global__ __launch_bounds__(256) void k_ord_emit_slots(BaOrd O, int Lp) {
-    const int lp = blockIdx.x * 256 + threadIdx.x;
-    if (lp >= Lp) return;
-    const int f0 = O.tLpStart[lp], f1 = O.tLpStart[lp + 1];
-    int se = O.lpSlotStart[lp], last = -2;
-    for (int f = f0; f < f1; f++) {
-        const int fi = O.key2[f];
-        if (fi >= 0 && fi != last) { O.slotStart[se] = f; O.slotFi[se] = fi; se++; last = fi; }
-    }
-    O.slotStart[se] = f1; O.slotFi[se] = -1;     // end sentinel
-}
-
-
-// ---- work lists of the windowed Schur accumulation on the device (same lists as the host sweep in ba_run: per window the landmarks
-// with slots in both of its block rows, ascending) : per 256-landmark block and window a count, a prefix over (window, block), the fill
-struct BaWinOrd {
-    int Lp, TB, nBR, nWin, nBlk;
-    const int* lpSlotStart; const int* slotFi;
-    int* blkCnt; int* blkOff;       // [nWin][nBlk]
-    int* winCnt;                    // [nWin + 1]
-    int* winLm;
-};
-template <int FILL>
-__global__ __launch_bounds__(256) void k_win_lists(BaWinOrd Q) {
-    __shared__ int sWave[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lp = blockIdx.x * 256 + tid;
-    unsigned long long rows = 0;        // block rows (free index / TB) this landmark has slots in: <= 43 for 170 free keyframes
-    if (lp < Q.Lp)
-        for (int se = Q.lpSlotStart[lp]; se < Q.lpSlotStart[lp + 1] - 1; se++) rows |= 1ull << (Q.slotFi[se] / Q.TB);
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    int w = 0;
-    for (int a = 0; a < Q.nBR; a++)
-        for (int b = a; b < Q.nBR; b++, w++) {
-            const bool has = ((rows >> a) & 1ull) && ((rows >> b) & 1ull);
-            const unsigned long long bal = __ballot(has);
-            int* sw = sWave[w & 1];                      // (double-buffered: one barrier per window)
-            if (lane == 0) sw[wave] = __popcll(bal);
-            __syncthreads();
-            int before = 0, total = 0;
-            for (int k = 0; k < 4; k++) { const int c = sw[k]; if (k < wave) before += c; total += c; }
-            if (FILL) { if (has) Q.winLm[Q.blkOff[(size_t)w * Q.nBlk + blockIdx.x] + before + __popcll(bal & lt)] = lp; }
-            else if (tid == 0) Q.blkCnt[(size_t)w * Q.nBlk + blockIdx.x] = total;
-        }
-}
-__global__ __launch_bounds__(1024) void k_win_prefix(BaWinOrd Q) {
-    extern __shared__ int sTot[];       // [nWin] totals, then bases
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int w = wave; w < Q.nWin; w += 16) {
-        int run = 0;
-        for (int base = 0; base < Q.nBlk; base += 64) {
-            const int c = base + lane;
-            const int v = c < Q.nBlk ? Q.blkCnt[(size_t)w * Q.nBlk + c] : 0;
-            int inc = v;
-            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-            if (c < Q.nBlk) Q.blkOff[(size_t)w * Q.nBlk + c] = run + inc - v;
-            run += __shfl(inc, 63);
-        }
-        if (lane == 0) sTot[w] = run;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int w = 0; w < Q.nWin; w++) { const int t = sTot[w]; sTot[w] = run; Q.winCnt[w] = run; run += t; }
-        Q.winCnt[Q.nWin] = run;
-    }
-    __syncthreads();
-    for (int w = wave; w < Q.nWin; w += 16)
-        for (int c = lane; c < Q.nBlk; c += 64) Q.blkOff[(size_t)w * Q.nBlk + c] += sTot[w];
-}
-
 }  // namespace vslam
 
 using namespace vslam;
 
 namespace {
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        // grow with headroom: a mapping thread serves sessions whose windows differ a little from call to call, and every
-        // new maximum used to cost a hipFree (a device-wide synchronisation: it waits for the lockstep groups' kernels) +
-        // hipMalloc - 1.6 ms per local BA on average at 128 sessions
-        // The floor is in BYTES (64 KB) and the headroom a factor of two: a 16-int flag block no longer takes 4 MB, a pose-slot
-        // array no longer 96 MB (the first form floored every buffer at 1 M elements: ~230 MB of HBM per optimizer thread).
-        if (p) hipFree(p);
-        n = std::max<size_t>(2 * count, ((size_t)64 << 10) / sizeof(T));
-        return hipMalloc(&p, n * sizeof(T));
+// ---- the grow-only buffers of the workspaces: GrowBuf (grow_buf.hpp) over device memory and pinned host memory -------------------
+struct DeviceAlloc {
+    static hipError_t alloc(void** p, size_t bytes) {      // (hipMalloc: with the debug poison fill, common.hpp)
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess && *p) { (void)hipFree(*p); *p = nullptr; }      // (the fill failed: no block without success)
+        return e;
     }
+    static void free(void* p) { (void)hipFree(p); }
 };
+struct PinnedAlloc {
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <typename T>
+struct DevBuf : GrowBuf<T, DeviceAlloc> {
+    // grow with headroom (grow_dev): a mapping thread serves sessions whose windows differ a little from call to call, and every
+    // new maximum used to cost a hipFree (a device-wide synchronisation: it waits for the lockstep groups' kernels) +
+    // hipMalloc - 1.6 ms per local BA on average at 128 sessions.
+    // (A request of 0 still gives an empty buffer its floor block: the argument blocks of the kernels carry no null pointers.)
+    hipError_t alloc(size_t count) { return this->ensure(std::max<size_t>(count, 1), grow_dev<T>()); }
+};
+using PinBuf = GrowBuf<uint8_t, PinnedAlloc>;      // (sized in bytes)
+static_assert(sizeof(DevBuf<double>) == sizeof(PinBuf), "release_bufs counts the buffers of a struct by its size");
+// frees the N buffers of a struct that holds nothing else: one that is added to the struct and not named here does not compile
+template <size_t N, class... B>
+void release_bufs(B&... b) {
+    static_assert(sizeof...(B) == N, "every buffer of the struct is released");
+    (b.release(), ...);
+}
 
 thread_local StageTimer g_baTimer;
-static thread_local void (*g_baRelease)() = nullptr;      // frees the calling thread's local-BA workspace
-
 
 // Pinned host arena with a device mirror: the per-pass index / measurement arrays are written straight into
 // pinned memory and travel in ONE copy.
 struct PinnedArena : BaArenaView {
     uint8_t* d = nullptr;
+    PinBuf hostHalf;
+    GrowBuf<uint8_t, DeviceAlloc> devHalf;
     hipError_t ensure(size_t bytes, hipStream_t s) {
         if (bytes <= cap) return hipSuccess;
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        h = nullptr; d = nullptr;
-        cap = 2 * bytes + (64 << 10);       // (re-growing costs a synchronisation + two device-synchronising frees)
-        e = hipHostMalloc((void**)&h, cap, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        return hipMalloc((void**)&d, cap);
+        release();      // (re-growing costs a synchronisation + two device-synchronising frees)
+        e = hostHalf.ensure(bytes, grow_block());
+        if (e == hipSuccess) e = devHalf.ensure(bytes, grow_block());
+        if (e != hipSuccess) { release(); return e; }      // (one half without the other is no arena)
+        h = hostHalf.p; d = devHalf.p; cap = hostHalf.n;
+        return hipSuccess;
     }
+    void release() { hostHalf.release(); devHalf.release(); h = nullptr; d = nullptr; cap = 0; }
     template <class T> T* dev(T* hostPtr) const { return (T*)(d + ((uint8_t*)hostPtr - h)); }
     hipError_t upload(hipStream_t s) const { return hipMemcpyAsync(d, h, used, hipMemcpyHostToDevice, s); }
 };
+
+// the problem's pair arrays (device addresses): what the chi2 kernels and the device ordering read
+struct BaPairArrays { const int* kf; const int* lm; const int* oct; const uint8_t* flags; const float* uv; const uint8_t* kfLocal; };
+
+}  // namespace
+
+#include "ba_order_dev.hpp"       // k_ord_* / k_win_* and their host unit (BaDeviceOrder)
+
+namespace {
 
 // vslam_local_ba_set_lookahead (-1: environment / default).  Like the timing switch and the workspace these belong to
 // the CALLING THREAD (one optimizer thread = one local-BA context): sessions with different settings do not interact.
@@ -2410,8 +2188,7 @@ static void ba_fill_dev(BaDev& D, const BaPassHost& H, const PinnedArena& A, con
     D.facJBase = B.facJ; D.facJStride = (size_t)20 * H.NF; D.SedgeBase = B.Sedge; D.edgesBase = A.dev(H.h_edges);
     D.sysStride = (size_t)n * n + 2 * n + 8; D.dLStride = (size_t)3 * H.Lp;
 }
-// chi2 arguments: the problem's pair arrays (device addresses), the pass's membership arrays, thresholds 7.815 * sigmaFactor, the rig
-struct BaPairArrays { const int* kf; const int* lm; const int* oct; const uint8_t* flags; const float* uv; const uint8_t* kfLocal; };
+// chi2 arguments: the problem's pair arrays, the pass's membership arrays, thresholds 7.815 * sigmaFactor, the rig
 static void ba_fill_chi(BaChi& C, const vslam_ba_problem* P, const BaPairArrays& a, const uint8_t* kfPresent, const uint8_t* lmPresent, uint8_t* wrong) {
     C.NP = P->n_pairs; C.pairKf = a.kf; C.pairLm = a.lm; C.pairFlags = a.flags; C.pairUv = a.uv;
     C.pairOct = a.oct; C.kfLocal = a.kfLocal; C.kfPresent = kfPresent; C.lmPresent = lmPresent; C.wrong = wrong;
@@ -2419,27 +2196,178 @@ static void ba_fill_chi(BaChi& C, const vslam_ba_problem* P, const BaPairArrays&
     C.fx = P->rig.fx; C.fy = P->rig.fy; C.cx = P->rig.cx; C.cy = P->rig.cy; C.b = (double)P->rig.baseline;
 }
 
+// ---- the calling thread's local-BA state ------------------------------------------------------------------------------------------
+// Grow-only device workspace + stream of vslam_local_ba, kept per host thread across calls (one local BA per keyframe:
+// re-allocating ~40 buffers every call cost more than the solve itself).
+struct BaSingleBufs {
+    DevBuf<DPose> d_poseS;
+    DevBuf<double> d_lmS, d_facJ, d_S, d_Spart, d_Sedge, d_dP, d_dL, d_lmDiff, d_sums, d_partial, d_Lg, d_cholY, d_winW, d_winH;
+    DevBuf<int> d_flags, d_win, d_cholFail;
+    DevBuf<uint8_t> d_wrong;
+    DevBuf<uint8_t> d_const; PinBuf h_const;      // the call's constant inputs, one block, and its pinned staging block
+    PinBuf h_wrong;                                // landing area of the chi2 flags
+    PinBuf h_out;                                  // pinned landing area of the result (poses | landmarks)
+    PinBuf h_ctlOut;                               // read-back of the LM control block
+    void release_buffers() {
+        release_bufs<sizeof(BaSingleBufs) / sizeof(PinBuf)>(d_poseS, d_lmS, d_facJ, d_S, d_Spart, d_Sedge, d_dP, d_dL, d_lmDiff, d_sums, d_partial, d_Lg, d_cholY,
+                                                           d_winW, d_winH, d_flags, d_win, d_cholFail, d_wrong, d_const, h_const, h_wrong, h_out, h_ctlOut);
+    }
+};
+struct BaSingleWs : BaSingleBufs {
+    hipStream_t stream = nullptr;
+    int device = -1;
+    PinnedArena arena;
+    BaHostTmp tmp;
+    BaPool pool;
+    vslam_status open(int dev) {
+        device = dev;
+        VS_HIP(vslam::create_side_stream(&stream));
+        VS_HIP(h_ctlOut.ensure(CTL_DOUBLES * sizeof(double), GrowPlus{0}));
+        int nt = 7;      // + the calling thread; VSLAM_BA_HOST_THREADS overrides (0 = none).  (C5-size problems: 52 -> 43 ms per BA with 4 threads, 35 with 8)
+        if (const char* e = getenv("VSLAM_BA_HOST_THREADS")) nt = std::max(0, std::min(15, atoi(e)));
+        pool.start(nt);
+        return VSLAM_OK;
+    }
+    void release() {      // (the owner has made `device` current)
+        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); stream = nullptr; }
+        release_buffers();
+        arena.release();
+    }
+};
+// The same for vslam_local_ba_batch: its own stream, one device block, one landing area.
+struct BaBatchWs {
+    hipStream_t stream = nullptr;
+    int device = -1;
+    PinnedArena arena;
+    DevBuf<uint8_t> d_mem;
+    PinBuf h_back;        // pinned landing area: control blocks | chi2 flags | results
+    BaPool pool;
+    vslam_status open(int dev) {
+        device = dev;
+        VS_HIP(vslam::create_side_stream(&stream));
+        pool.start(2);
+        return VSLAM_OK;
+    }
+    void release() {
+        if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); stream = nullptr; }
+        d_mem.release(); h_back.release();
+        arena.release();
+    }
+};
+// One owner for both workspaces, the device ordering's buffers (on the single workspace's device) and the timer's events.  A
+// workspace is created on the first use of its entry point and again when `device` changes.  Nothing here frees from a destructor
+// (no HIP calls from a thread_local destructor: see DevPool): a short-lived optimizer thread that must not leak its streams, pinned
+// buffers and device memory calls vslam_thread_release(); what is left at thread exit (the pools' threads aside, which are joined)
+// is reclaimed with the process.
+struct BaThread {
+    std::unique_ptr<BaSingleWs> single;
+    std::unique_ptr<BaBatchWs> batch;
+    BaDeviceOrder order;
+    vslam_status single_ws(int device, BaSingleWs** out) { return get(single, device, out); }
+    vslam_status batch_ws(int device, BaBatchWs** out) { return get(batch, device, out); }
+    void release() {
+        drop(single);
+        drop(batch);
+        g_baTimer.destroy();
+    }
+
+private:
+    template <class W>
+    vslam_status get(std::unique_ptr<W>& w, int device, W** out) {
+        if (!w || w->device != device) {
+            drop(w);
+            w.reset(new W());
+            const vslam_status st = w->open(device);
+            if (st != VSLAM_OK) { drop(w); return st; }      // (no half-opened workspace for the next call to find)
+        }
+        *out = w.get();
+        return VSLAM_OK;
+    }
+    template <class W>
+    void drop(std::unique_ptr<W>& w) {
+        if (!w) return;
+        const bool own = std::is_same<W, BaSingleWs>::value;      // the ordering's buffers go with the single workspace
+        if (w->device >= 0 && hipSetDevice(w->device) == hipSuccess) {
+            w->release();
+            if (own) order.release();
+        }
+        if (own) order = BaDeviceOrder{};
+        w.reset();
+    }
+};
+thread_local std::unique_ptr<BaThread> g_baThread;
+static BaThread& ba_thread() {
+    if (!g_baThread) g_baThread.reset(new BaThread());
+    return *g_baThread;
+}
+// frees the calling thread's local-BA state (vslam::thread_release)
+static void ba_thread_release() {
+    if (g_baThread) { g_baThread->release(); g_baThread.reset(); }
+}
+
 }  // namespace
 
 void vslam::thread_release() {
-    if (g_baRelease) { g_baRelease(); g_baRelease = nullptr; }
+    ba_thread_release();
     thread_pool_release();
 }
 
+// ---- host sections: where the wall time of the two entry points goes ------------------------------------------------------------------
+static std::atomic<long long> g_bbsNs[12], g_bbsCalls{0}, g_bbsPolls{0};
+static const char* g_bbsName[12] = {"check+count", "arena fill", "tables+upload", "lm pass 1", "chi2 1", "second-pass prep", "lm pass 2", "chi2 2 + fetch", "results", nullptr, nullptr, nullptr};
+
+// The section marks of ba_run, one object in two forms; VSLAM_HOST_STAMPS (tools/stampbuild.sh) chooses here, once.
+//   fine(name)          a mark only the accumulating form keeps
+//   begin_sections(s)   the call's constants are on their way; the sections below are timed on stream s
+//   section(name)       the end of a section
 #ifdef VSLAM_HOST_STAMPS
-#include <chrono>
+// the stamp build: every section mark synchronises the stream and prints the time since the mark before
 static double bhs_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-#define BHS(name) do { hipStreamSynchronize(stream); const double t_ = bhs_now(); fprintf(stderr, "  ba host: %-12s %8.1f us\n", name, t_ - bhs_t); bhs_t = t_; } while (0)
-#define BHS2(name) do { const double t_ = bhs_now(); fprintf(stderr, "     prep: %-12s %8.1f us\n", name, t_ - bhs_t2); bhs_t2 = t_; } while (0)
+struct BaMarks {
+    const double entry = bhs_now();
+    double t = 0;
+    hipStream_t stream = nullptr;
+    void fine(const char*) {}
+    void begin_sections(hipStream_t s) { stream = s; t = entry; section("entry..const"); }
+    void section(const char* name) {
+        hipStreamSynchronize(stream);
+        const double t_ = bhs_now();
+        fprintf(stderr, "  ba host: %-12s %8.1f us\n", name, t_ - t);
+        t = t_;
+    }
+    static void print() {}
+};
 #else
-// cumulative wall time between the section marks of ba_run (no synchronisation added): VSLAM_BATCH_PHASES diagnostics
-#include <chrono>
-#include <atomic>
-static std::atomic<long long> g_bhsNs[16], g_bhsCalls{0};
-static const char* g_bhsName[16] = {"s_check", "s_ws", "s_alloc", "s_const", "setup", "prep", "u_arena", "u_alloc", "u_attr", "upload", "lm", "chi2", "fetch", nullptr, nullptr, nullptr};
-static int bhs_slot(const char* name) { for (int i = 0; i < 16 && g_bhsName[i]; i++) if (!strcmp(g_bhsName[i], name)) return i; return 15; }
-#define BHS(name) do { const auto t_ = std::chrono::steady_clock::now(); g_bhsNs[bhs_slot(name)] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - bhs_t).count(); bhs_t = t_; } while (0)
-#define BHS2(name) do {} while (0)
+// cumulative wall time between the marks (no synchronisation added): the VSLAM_BATCH_PHASES diagnostics
+static std::atomic<long long> g_bhsNs[20], g_bhsCalls{0};
+static const char* const g_bhsName[20] = {"s_check", "s_ws", "s_alloc", "s_const", "setup", "count", "fill", "prep", "u_arena", "u_alloc", "u_attr", "upload",
+                                          "lm", "p2stats", "chi2", "fetch", nullptr, nullptr, nullptr, nullptr};
+static int bhs_slot(const char* name) { for (int i = 0; i < 20 && g_bhsName[i]; i++) if (!strcmp(g_bhsName[i], name)) return i; return 19; }      // 19: "other"
+struct BaMarks {
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    BaMarks() { g_bhsCalls++; }
+    void fine(const char* name) { section(name); }
+    void begin_sections(hipStream_t) {}
+    void section(const char* name) {
+        const auto t_ = std::chrono::steady_clock::now();
+        g_bhsNs[bhs_slot(name)] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - t).count();
+        t = t_;
+    }
+    // averages per call; the marks do not synchronise, so "lm" holds the polls of both LM loops, "chi2" the re-check + second-pass
+    // preparation + result fetch
+    static void print() {
+        if (const long long nb = g_bbsCalls.load()) {
+            fprintf(stderr, "  vslam_local_ba_batch host sections (us per cohort, %lld cohorts, %.1f polls each):", nb, (double)g_bbsPolls.load() / (double)nb);
+            for (int i = 0; i < 12 && g_bbsName[i]; i++) fprintf(stderr, " %s %.1f |", g_bbsName[i], 1e-3 * (double)g_bbsNs[i].load() / (double)nb);
+            fprintf(stderr, "\n");
+        }
+        const long long n = g_bhsCalls.load();
+        if (!n) return;
+        fprintf(stderr, "  vslam_local_ba host sections (us per call, %lld calls):", n);
+        for (int i = 0; i < 20; i++) if (g_bhsName[i] || g_bhsNs[i].load()) fprintf(stderr, " %s %.1f |", g_bhsName[i] ? g_bhsName[i] : "other", 1e-3 * (double)g_bhsNs[i].load() / (double)n);
+        fprintf(stderr, "\n");
+    }
+};
 #endif
 
 // hipFuncSetAttribute is PROCESS-global state: set once, to the largest dynamic LDS size any call may ask for (a per-call,
@@ -2468,142 +2396,96 @@ static vslam_status ba_kernel_attributes() {
     return VSLAM_OK;
 }
 
-static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int device, const vslam_comm* comm) {
-#ifdef VSLAM_HOST_STAMPS
-    const double bhs_fn0 = bhs_now();
-#endif
-#ifndef VSLAM_HOST_STAMPS
-    auto bhs_t = std::chrono::steady_clock::now();
-    g_bhsCalls++;
-#endif
-    if (!ba_check_args(P, R)) { set_error("vslam_local_ba: invalid problem"); return VSLAM_ERR_INVALID; }
-    const int rank = comm ? comm->rank : 0, world = comm ? comm->world : 1;
-    VS_CHECK(ba_select_device(device));
-    const int K = P->n_kf, L = P->n_lm, NP = P->n_pairs;
-    // (the index check of a large problem - 1.2 M pairs: ~1 ms on one core - runs on the workspace's pool, below)
-    const bool pooledCheck = NP >= BaHostTune{}.parPairs;
-    if (!pooledCheck && !ba_check_pairs(P)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
+namespace {
 
-#ifndef VSLAM_HOST_STAMPS
-    BHS("s_check");
-#endif
-    // grow-only device workspace + stream, kept per host thread across calls (one local BA per keyframe:
-    // re-allocating ~40 buffers every call cost more than the solve itself)
-    struct Workspace {
-        hipStream_t stream = nullptr;
-        int device = -1;
-        DevBuf<DPose> d_poseS;
-        DevBuf<double> d_lmS, d_facJ, d_S, d_Spart, d_Sedge, d_dP, d_dL, d_lmDiff, d_sums, d_partial, d_Lg;
-        DevBuf<int> d_flags, d_win, d_cholFail;
-        DevBuf<double> d_cholY, d_winW, d_winH;
-        DevBuf<uint8_t> d_wrong;
-        DevBuf<int> d_ord1, d_ord2, d_winTmp; long long* h_ordScal = nullptr; size_t ordScalCap = 0;      // device-side factor ordering (large problems)
-        PinnedArena arena;
-        BaHostTmp tmp;
-        BaPool pool;
-        double* h_ctlOut = nullptr;
-        DevBuf<uint8_t> d_const; uint8_t* h_const = nullptr; size_t constCap = 0;      // the call's constant inputs, one block
-        uint8_t* h_wrong = nullptr; size_t wrongCap = 0;
-        uint8_t* h_out = nullptr; size_t outCap = 0;                     // pinned landing area of the result (poses | landmarks)
-        // released when the owning host thread ends (or switches device): a short-lived optimizer thread must not
-        // leak its stream, pinned buffers and pool threads
-        ~Workspace() {}          // (no HIP calls from a thread_local destructor: see DevPool)
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
-            for (void* p : {(void*)d_poseS.p, (void*)d_lmS.p, (void*)d_facJ.p, (void*)d_S.p, (void*)d_Spart.p,
-                            (void*)d_Sedge.p, (void*)d_dP.p, (void*)d_dL.p, (void*)d_lmDiff.p, (void*)d_sums.p, (void*)d_partial.p, (void*)d_Lg.p,
-                            (void*)d_win.p, (void*)d_cholFail.p, (void*)d_cholY.p, (void*)d_winW.p, (void*)d_winH.p, (void*)d_flags.p,
-                            (void*)d_wrong.p, (void*)d_ord1.p, (void*)d_ord2.p, (void*)d_winTmp.p, (void*)arena.d})
-                if (p) hipFree(p);
-            if (h_ordScal) hipHostFree(h_ordScal);
-            if (arena.h) hipHostFree(arena.h);
-            if (h_ctlOut) hipHostFree(h_ctlOut);
-            if (h_const) hipHostFree(h_const);
-            if (d_const.p) hipFree(d_const.p);
-            if (h_wrong) hipHostFree(h_wrong);
-            if (h_out) hipHostFree(h_out);
-        }
-    };
-    static thread_local std::unique_ptr<Workspace> ws;
-    if (!ws || ws->device != device) {
-        if (ws) ws->release();
-        ws.reset(new Workspace()); ws->device = device;
-        g_baRelease = []() { if (ws) { ws->release(); ws.reset(); } g_baTimer.destroy(); };
-        VS_HIP(vslam::create_side_stream(&ws->stream));
-        VS_HIP(hipHostMalloc((void**)&ws->h_ctlOut, CTL_DOUBLES * sizeof(double), hipHostMallocDefault));
-        {
-            int nt = 7;      // + the calling thread; VSLAM_BA_HOST_THREADS overrides (0 = none).  (C5-size problems: 52 -> 43 ms per BA with 4 threads, 35 with 8)
-            if (const char* e = getenv("VSLAM_BA_HOST_THREADS")) nt = std::max(0, std::min(15, atoi(e)));
-            ws->pool.start(nt);
-        }
-    }
-    if (pooledCheck && !ba_check_pairs(P, &ws->pool)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
-    if ((size_t)P->n_pairs > ws->wrongCap) {
-        if (ws->h_wrong) hipHostFree(ws->h_wrong);
-        ws->wrongCap = 2 * (size_t)P->n_pairs + 4096;
-        VS_HIP(hipHostMalloc((void**)&ws->h_wrong, ws->wrongCap, hipHostMallocDefault));
-    }
-    {
-        const size_t need = (size_t)P->n_kf * sizeof(DPose) + 64 + (size_t)3 * P->n_lm * sizeof(double);
-        if (need > ws->outCap) {
-            if (ws->h_out) hipHostFree(ws->h_out);
-            ws->outCap = need + need / 2 + 4096;
-            VS_HIP(hipHostMalloc((void**)&ws->h_out, ws->outCap, hipHostMallocDefault));
-        }
-    }
-#ifndef VSLAM_HOST_STAMPS
-    BHS("s_ws");
-#endif
-    hipStream_t stream = ws->stream;
-    g_baTimer.reset();
-    g_baTimer.stream = stream;
-    g_baTimer.multi = true;
-    auto &d_poseS = ws->d_poseS;
-    auto &d_lmS = ws->d_lmS, &d_facJ = ws->d_facJ, &d_S = ws->d_S, &d_Spart = ws->d_Spart,
-         &d_Sedge = ws->d_Sedge, &d_dP = ws->d_dP, &d_dL = ws->d_dL, &d_lmDiff = ws->d_lmDiff, &d_sums = ws->d_sums, &d_partial = ws->d_partial, &d_Lg = ws->d_Lg,
-         &d_cholY = ws->d_cholY;
-    auto &d_win = ws->d_win, &d_cholFail = ws->d_cholFail;
-    auto &d_flags = ws->d_flags;
-    auto &d_wrong = ws->d_wrong;
-
-    std::vector<DPose> pose0(K);
-    for (int k = 0; k < K; k++) pose_from_rm16(P->kf_pose_wc + 16 * (size_t)k, pose0[k]);
+// ---- one vslam_local_ba call: what its stages share, and the stages in the order run() calls them ---------------------------------
+struct BaCall {
+    const vslam_ba_problem* const P;
+    vslam_ba_result* const R;
+    const vslam_comm* const comm;
+    BaSingleWs& ws;
+    BaDeviceOrder& ord;
+    BaMarks& marks;
+    PinnedArena& A;
+    const hipStream_t stream;
+    const int rank, world, K, L, NP;
     // (the landmark-sharded path runs the same look-ahead scheme: every rank evaluates the same candidates, the NB partial systems
     // travel in one all-reduce, the control step walks them identically on every rank)
-    const int NB = ba_lm_knobs().NB, nSlots = NB + 1;
-    const bool specLin = ba_lm_knobs().specLin;
-    // the call's constant inputs (initial poses / landmarks, the pair arrays, kf_local) travel in ONE copy through a pinned
-    // staging block into one device block (they used to be eight pageable copies)
-    VS_HIP(d_poseS.alloc((size_t)nSlots * K));
-    VS_HIP(d_lmS.alloc((size_t)nSlots * 3 * L));
-    VS_HIP(d_wrong.alloc(NP));
-#ifndef VSLAM_HOST_STAMPS
-    BHS("s_alloc");
-#endif
-    size_t cBytes = 0;
-    auto cOff = [&](size_t bytes) { const size_t at = cBytes; cBytes = (cBytes + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at; };
-    const size_t oPose0 = cOff((size_t)K * sizeof(DPose)), oLm0 = cOff((size_t)3 * L * sizeof(double)), oPairKf = cOff((size_t)NP * 4),
-                 oPairLm = cOff((size_t)NP * 4), oPairOct = cOff((size_t)2 * NP * 4), oPairFlags = cOff((size_t)NP), oPairUv = cOff((size_t)4 * NP * 4),
-                 oKfLocal = cOff((size_t)K);
-    // small problems (a tracker's local window): through the pinned block, one copy.  Large ones (the 100 k-landmark window:
-    // 40 MB of pair arrays): straight from the caller's arrays - staging them would cost a host memcpy of the same size.
-    const bool staged = cBytes <= ((size_t)8 << 20);
-    if (ws->d_const.n < cBytes) VS_HIP(ws->d_const.alloc(cBytes));     // (DevBuf adds its own headroom)
-    if (staged && cBytes > ws->constCap) {
-        VS_HIP(hipStreamSynchronize(stream));
-        if (ws->h_const) hipHostFree(ws->h_const);
-        ws->h_const = nullptr;
-        ws->constCap = 2 * cBytes + (64 << 10);
-        VS_HIP(hipHostMalloc((void**)&ws->h_const, ws->constCap, hipHostMallocDefault));
+    const int NB, nSlots;
+    const bool specLin;
+    static constexpr double relTol = 1e-5, absTol = 1e-5;
+    std::vector<DPose> pose0;
+    std::vector<uint8_t> wrong;           // chi2 flags of the pass before (host copy)
+    // the call's constants in the device block
+    DPose* p_pose0 = nullptr;
+    double* p_lm0 = nullptr;
+    BaPairArrays pairs{};
+    // the values of the last pass on the device, and the pinned landing area of the result
+    DPose* poseFinal = nullptr;
+    double* lmFinal = nullptr;
+    DPose* poseOut = nullptr;
+    double* lmOut = nullptr;
+    bool resultFetched = false;
+    // one pass: its ordering, launch plan and argument block
+    struct Pass {
+        BaPassHost H;
+        bool devOrder = false, adaptive = false;
+        BaSinglePlan plan;
+        BaDev D{};                        // host copy of the argument block; poseCur / lmCur: the pass's final values once it is done
+        const BaDev* dD = nullptr;
+        BaWin Wn{};
+        int nWinWg = 0;
+    } q;
+
+    BaCall(const vslam_ba_problem* P_, vslam_ba_result* R_, const vslam_comm* comm_, BaSingleWs& ws_, BaDeviceOrder& ord_, BaMarks& marks_)
+        : P(P_), R(R_), comm(comm_), ws(ws_), ord(ord_), marks(marks_), A(ws_.arena), stream(ws_.stream), rank(comm_ ? comm_->rank : 0), world(comm_ ? comm_->world : 1),
+          K(P_->n_kf), L(P_->n_lm), NP(P_->n_pairs), NB(ba_lm_knobs().NB), nSlots(NB + 1), specLin(ba_lm_knobs().specLin), pose0(P_->n_kf), wrong(P_->n_pairs, 0) {
+        for (int k = 0; k < K; k++) pose_from_rm16(P->kf_pose_wc + 16 * (size_t)k, pose0[k]);
     }
-    {
-        uint8_t* h = staged ? ws->h_const : nullptr;
-        uint8_t* d = ws->d_const.p;
+    int edge_slots() const { return specLin ? nSlots : 1; }
+
+    vslam_status run() {
+        VS_CHECK(constants());
+        marks.begin_sections(stream);
+        marks.section("setup");
+        for (int pass = 0; pass < 2; pass++) {
+            q = Pass{};
+            VS_CHECK(order(pass));
+            VS_CHECK(arm_and_upload(pass));
+            VS_CHECK(plan_and_buffers());
+            if (!q.plan.ldsS) VS_CHECK(window_lists());
+            VS_CHECK(argument_block());
+            VS_CHECK(run_lm(pass, q.H.NF, q.H.Lp, q.H.sumK2));
+            bool done = false;
+            if (pass == 0) VS_CHECK(masked_second_pass(&done));
+            if (done) break;
+        }
+        return result();
+    }
+
+    // ---- the call's constant inputs (initial poses / landmarks, the pair arrays, kf_local) travel in ONE copy through a pinned
+    // staging block into one device block (they used to be eight pageable copies)
+    vslam_status constants() {
+        VS_HIP(ws.d_poseS.alloc((size_t)nSlots * K));
+        VS_HIP(ws.d_lmS.alloc((size_t)nSlots * 3 * L));
+        VS_HIP(ws.d_wrong.alloc(NP));
+        marks.fine("s_alloc");
+        size_t cBytes = 0;
+        auto cOff = [&](size_t bytes) { const size_t at = cBytes; cBytes = (cBytes + std::max<size_t>(bytes, 8) + 255) & ~(size_t)255; return at; };
+        const size_t oPose0 = cOff((size_t)K * sizeof(DPose)), oLm0 = cOff((size_t)3 * L * sizeof(double)), oPairKf = cOff((size_t)NP * 4),
+                     oPairLm = cOff((size_t)NP * 4), oPairOct = cOff((size_t)2 * NP * 4), oPairFlags = cOff((size_t)NP), oPairUv = cOff((size_t)4 * NP * 4),
+                     oKfLocal = cOff((size_t)K);
+        // small problems (a tracker's local window): through the pinned block, one copy.  Large ones (the 100 k-landmark window:
+        // 40 MB of pair arrays): straight from the caller's arrays - staging them would cost a host memcpy of the same size.
+        const bool staged = cBytes <= ((size_t)8 << 20);
+        if (ws.d_const.n < cBytes) VS_HIP(ws.d_const.alloc(cBytes));     // (DevBuf adds its own headroom)
+        if (staged) VS_HIP(ws.h_const.ensure(cBytes, grow_block(), [&] { return hipStreamSynchronize(stream); }));
+        uint8_t* const h = staged ? ws.h_const.p : nullptr;
+        uint8_t* const dc = ws.d_const.p;
         auto put = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
             if (!bytes) return hipSuccess;
             if (h) { memcpy(h + at, src, bytes); return hipSuccess; }
-            return hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, stream);
+            return hipMemcpyAsync(dc + at, src, bytes, hipMemcpyHostToDevice, stream);
         };
         VS_HIP(put(oPose0, pose0.data(), (size_t)K * sizeof(DPose)));
         VS_HIP(put(oLm0, P->lm_xyz, (size_t)3 * L * sizeof(double)));
@@ -2611,409 +2493,341 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
         VS_HIP(put(oPairOct, P->pair_octave, (size_t)2 * NP * 4)); VS_HIP(put(oPairFlags, P->pair_flags, (size_t)NP));
         VS_HIP(put(oPairUv, P->pair_uv, (size_t)4 * NP * 4));
         VS_HIP(put(oKfLocal, P->kf_local, (size_t)K));
-        if (h) VS_HIP(hipMemcpyAsync(d, h, cBytes, hipMemcpyHostToDevice, stream));
+        if (h) VS_HIP(hipMemcpyAsync(dc, h, cBytes, hipMemcpyHostToDevice, stream));
+        marks.fine("s_const");
+        p_pose0 = (DPose*)(dc + oPose0);
+        p_lm0 = (double*)(dc + oLm0);
+        pairs = BaPairArrays{(const int*)(dc + oPairKf), (const int*)(dc + oPairLm), (const int*)(dc + oPairOct), dc + oPairFlags, (const float*)(dc + oPairUv), dc + oKfLocal};
+        VS_HIP(ws.d_sums.alloc(32));
+        if (!ws.d_flags.p) { VS_HIP(ws.d_flags.alloc(16)); VS_HIP(hipMemsetAsync(ws.d_flags.p, 0, 16 * sizeof(int), stream)); }
+        poseFinal = p_pose0;
+        lmFinal = p_lm0;
+        // pinned landing area of the result (see result())
+        poseOut = (DPose*)ws.h_out.p;
+        lmOut = (double*)(ws.h_out.p + (((size_t)K * sizeof(DPose) + 63) & ~(size_t)63));
+        return VSLAM_OK;
     }
-#ifndef VSLAM_HOST_STAMPS
-    BHS("s_const");
-#endif
-    uint8_t* const dc = ws->d_const.p;
-    DPose* const p_pose0 = (DPose*)(dc + oPose0);
-    double* const p_lm0 = (double*)(dc + oLm0);
-    const int* const p_pairKf = (const int*)(dc + oPairKf); const int* const p_pairLm = (const int*)(dc + oPairLm);
-    const int* const p_pairOct = (const int*)(dc + oPairOct); const uint8_t* const p_pairFlags = dc + oPairFlags;
-    const float* const p_pairUv = (const float*)(dc + oPairUv); const uint8_t* const p_kfLocal = dc + oKfLocal;
-    VS_HIP(d_sums.alloc(32));
-    if (!d_flags.p) { VS_HIP(d_flags.alloc(16)); VS_HIP(hipMemsetAsync(d_flags.p, 0, 16 * sizeof(int), stream)); }
 
-    std::vector<uint8_t> wrong(NP, 0);
-    DPose* poseFinal = p_pose0;
-    // pinned landing area of the result (see the end of this function)
-    DPose* poseOut = (DPose*)ws->h_out;
-    double* lmOut = (double*)(ws->h_out + (((size_t)K * sizeof(DPose) + 63) & ~(size_t)63));
-    bool resultFetched = false;
-    double* lmFinal = p_lm0;
-    const int nCU = BA_NCU;
-    auto& A = ws->arena;
-    auto& T = ws->tmp;
-
-#ifdef VSLAM_HOST_STAMPS
-    hipStreamSynchronize(stream);
-    double bhs_t = bhs_now();
-    fprintf(stderr, "  ba host: %-12s %8.1f us\n", "entry..const", bhs_t - bhs_fn0);
-#endif
-    BHS("setup");
-    for (int pass = 0; pass < 2; pass++) {
-        // ---- host: factor list of this pass, ordered by (landmark, free index, pair, side) -----------
-        // Everything the kernels read is written straight into ONE pinned arena and uploaded with one copy.
-        BaPassHost H;
-        // Large problems order their factors ON THE DEVICE (k_ord_*: the raw pair arrays are there for the chi2 kernel anyway); the host
-        // keeps the free set, the BetweenFactor chain and - for the window lists / the second pass's statistics - read-backs of the
-        // slot table.  VSLAM_BA_DEVICE_ORDER = 0: host ordering always, 2: device ordering for every size (tests).
+    // ---- factor list of this pass, ordered by (landmark, free index, pair, side) -------------------------------------------------
+    // Everything the kernels read is written straight into ONE pinned arena and uploaded with one copy.
+    // Large problems order their factors ON THE DEVICE (BaDeviceOrder: the raw pair arrays are there for the chi2 kernel anyway); the
+    // host keeps the free set and the BetweenFactor chain.  VSLAM_BA_DEVICE_ORDER = 0: host ordering always, 2: device ordering for
+    // every size (tests; read at every pass).
+    vslam_status order(int pass) {
+        BaPassHost& H = q.H;
         const int ordEnv = getenv("VSLAM_BA_DEVICE_ORDER") ? atoi(getenv("VSLAM_BA_DEVICE_ORDER")) : 1;
-        const bool devOrder = NP > 0 && L > 0 && (ordEnv == 2 || (ordEnv == 1 && NP >= 200000));
-        BaOrd O{};
-        if (devOrder) {
-            O.NP = NP; O.L = L; O.K = K; O.world = world; O.rank = rank;
-            O.pairKf = p_pairKf; O.pairLm = p_pairLm; O.pairFlags = p_pairFlags; O.wrong = d_wrong.p; O.pairUv = p_pairUv; O.pairOct = p_pairOct;
-            for (int l = 0; l < P->n_levels; l++) O.invSigma[l] = P->inv_sigma_factor[l];
-            // phase 1 buffers: cnt[L] | kfPres[K] | lmPres bytes[L] (zeroed) | lpOf[L] | tLpOrig[L] | tLpStart[L + 1] | scal
-            const size_t zInts = (size_t)L + K + ((size_t)L + 3) / 4, nInts1 = zInts + (size_t)3 * L + 1 + 2 * ORD_SCAL + 2;
-            VS_HIP(ws->d_ord1.alloc(nInts1));
-            int* w = ws->d_ord1.p;
-            O.cnt = w; O.kfPres = w + L; O.lmPres = (uint8_t*)(w + L + K);
-            O.lpOf = w + zInts; O.tLpOrig = O.lpOf + L; O.tLpStart = O.tLpOrig + L;
-            O.scal = (long long*)(w + ((zInts + (size_t)3 * L + 1 + 1) & ~(size_t)1));
-            const size_t scalBytes = ORD_SCAL * sizeof(long long) + (size_t)K * sizeof(int);
-            if (scalBytes > ws->ordScalCap) {
-                if (ws->h_ordScal) hipHostFree(ws->h_ordScal);
-                ws->ordScalCap = scalBytes + 1024;
-                VS_HIP(hipHostMalloc((void**)&ws->h_ordScal, ws->ordScalCap, hipHostMallocDefault));
-            }
-            VS_HIP(hipMemsetAsync(w, 0, zInts * sizeof(int), stream));
-            if (pass == 0) VS_HIP(hipMemsetAsync(d_wrong.p, 0, NP, stream));      // (later passes: the chi2 kernel's flags)
-            const int pairBlocks = std::max(1, std::min((NP + 255) / 256, 8 * nCU));
-            hipLaunchKernelGGL(k_ord_count, dim3(pairBlocks), dim3(256), 0, stream, O);
-            hipLaunchKernelGGL(k_ord_scan_lm, dim3(1), dim3(1024), 0, stream, O);
-            VS_HIP(hipGetLastError());
-            int* const h_kfPres = (int*)(ws->h_ordScal + ORD_SCAL);
-            VS_HIP(hipMemcpyAsync(ws->h_ordScal, O.scal, ORD_SCAL * sizeof(long long), hipMemcpyDeviceToHost, stream));
-            VS_HIP(hipMemcpyAsync(h_kfPres, O.kfPres, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, stream));
-            VS_HIP(vslam::stream_wait_blocking(stream));
-            H.Lp = (int)ws->h_ordScal[ORD_LP]; H.NF = (int)ws->h_ordScal[ORD_NF];
-            T.kfPresent.assign(K, 0);
-            for (int k = 0; k < K; k++) T.kfPresent[k] = h_kfPres[k] ? 1 : 0;
-            H.free_set_and_edges(P, rank, T);
-        } else
-            H.count(P, wrong.data(), rank, world, T, &ws->pool);
-        BHS("count");
-        const int NF = H.NF, F = H.F, n = H.n, Lp = H.Lp, NE = H.NE;
-        if (F > BA_MAX_FREE_KF) { set_error("local BA: more than 170 free keyframes is not supported"); return VSLAM_ERR_CAPACITY; }      // (before anything is sized by F)
-        VS_HIP(A.ensure(H.arena_bytes(K, L, specLin ? nSlots : 1), stream));
+        q.devOrder = NP > 0 && L > 0 && (ordEnv == 2 || (ordEnv == 1 && NP >= 200000));
+        if (q.devOrder) VS_CHECK(ord.count(P, pairs, ws.d_wrong.p, pass, rank, world, stream, H, ws.tmp));
+        else H.count(P, wrong.data(), rank, world, ws.tmp, &ws.pool);
+        marks.section("count");
+        if (H.F > BA_MAX_FREE_KF) { set_error("local BA: more than 170 free keyframes is not supported"); return VSLAM_ERR_CAPACITY; }      // (before anything is sized by F)
+        VS_HIP(A.ensure(H.arena_bytes(K, L, edge_slots()), stream));
         A.reset();
-        if (!H.take(A, K, L, specLin ? nSlots : 1)) { set_error("local BA: upload arena too small"); return VSLAM_ERR_CAPACITY; }
-        if (devOrder) {
-            H.fill_small(P, T, pose0.data(), specLin ? nSlots : 1);
-            VS_HIP(hipMemcpyAsync(A.dev(H.h_fidx), H.h_fidx, (size_t)K * sizeof(int), hipMemcpyHostToDevice, stream));
-            // phase 2 buffers: fillc[Lp] (zeroed) | ns[Lp] | key | src | key2 | src2 [NF each]
-            VS_HIP(ws->d_ord2.alloc((size_t)2 * std::max(Lp, 1) + (size_t)4 * std::max(NF, 1)));
-            int* w = ws->d_ord2.p;
-            O.fillc = w; O.ns = w + std::max(Lp, 1); O.key = O.ns + std::max(Lp, 1); O.src = O.key + std::max(NF, 1); O.key2 = O.src + std::max(NF, 1); O.src2 = O.key2 + std::max(NF, 1);
-            O.fidx = A.dev(H.h_fidx);
-            O.facKf = A.dev(H.h_facKf); O.facFi = A.dev(H.h_facFi); O.facLp = A.dev(H.h_facLp); O.facLm = A.dev(H.h_facLm); O.facPair = A.dev(H.h_facPair);
-            O.facZ = A.dev(H.h_facZ); O.facIs = A.dev(H.h_facIs); O.facRight = A.dev(H.h_facRight);
-            O.lpStart = A.dev(H.h_lpStart); O.lpSlotStart = A.dev(H.h_lpSlotStart); O.lpOrig = A.dev(H.h_lpOrig);
-            O.slotStart = A.dev(H.h_slotStart); O.slotFi = A.dev(H.h_slotFi);
-            VS_HIP(hipMemsetAsync(O.fillc, 0, (size_t)std::max(Lp, 1) * sizeof(int), stream));
-            const int pairBlocks = std::max(1, std::min((NP + 255) / 256, 8 * nCU));
-            if (NF > 0) {
-                hipLaunchKernelGGL(k_ord_scatter, dim3(pairBlocks), dim3(256), 0, stream, O);
-                hipLaunchKernelGGL(k_ord_rank, dim3((NF + 255) / 256), dim3(256), 0, stream, O, NF);
-            }
-            if (Lp > 0) hipLaunchKernelGGL(k_ord_ns, dim3((Lp + 255) / 256), dim3(256), 0, stream, O, Lp);
-            hipLaunchKernelGGL(k_ord_scan_slots, dim3(1), dim3(1024), 0, stream, O, Lp);
-            if (NF > 0) hipLaunchKernelGGL(k_ord_emit_fac, dim3((NF + 255) / 256), dim3(256), 0, stream, O, NF);
-            if (Lp > 0) hipLaunchKernelGGL(k_ord_emit_slots, dim3((Lp + 255) / 256), dim3(256), 0, stream, O, Lp);
-            VS_HIP(hipGetLastError());
-            VS_HIP(hipMemcpyAsync(A.dev(H.h_lmPresent), O.lmPres, (size_t)L, hipMemcpyDeviceToDevice, stream));
-            VS_HIP(hipMemcpyAsync(ws->h_ordScal, O.scal, ORD_SCAL * sizeof(long long), hipMemcpyDeviceToHost, stream));
-            VS_HIP(vslam::stream_wait_blocking(stream));
-            H.nSlotEntries = (int)ws->h_ordScal[ORD_NSLOT]; H.maxSlots = (int)ws->h_ordScal[ORD_MAXSLOTS]; H.maxFac = (int)ws->h_ordScal[ORD_MAXFAC];
-            H.sumK2 = ws->h_ordScal[ORD_SUMK2];
-            // (nothing of the factor list comes back to the host: the window lists and the second pass's statistics are device work too)
-        } else
-            H.fill(P, wrong.data(), rank, world, T, pose0.data(), &ws->pool, specLin ? nSlots : 1);
-        BHS("fill");
-        double* const h_ctl = H.h_ctl; BaDev* const h_D = H.h_D;
-        int* const h_lpSlotStart = H.h_lpSlotStart; int* const h_slotFi = H.h_slotFi;
-        BaEdge* const h_edges = H.h_edges; uint8_t* const h_kfPresent = H.h_kfPresent; uint8_t* const h_lmPresent = H.h_lmPresent;
-        const int maxSlots = H.maxSlots, nSlotEntries = H.nSlotEntries;
-        const long long sumK2 = H.sumK2;
-        // ---- LM control block (GTSAM 4.2 policy; k_ba_ctl) ---------------------------------------------
-        const double relTol = 1e-5, absTol = 1e-5;
+        if (!H.take(A, K, L, edge_slots())) { set_error("local BA: upload arena too small"); return VSLAM_ERR_CAPACITY; }
+        if (q.devOrder) VS_CHECK(ord.emit(P, pose0.data(), edge_slots(), A, stream, H, ws.tmp));
+        else H.fill(P, wrong.data(), rank, world, ws.tmp, pose0.data(), &ws.pool, edge_slots());
+        marks.section("fill");
+        return VSLAM_OK;
+    }
+
+    // ---- LM control block (GTSAM 4.2 policy; k_ba_ctl) ----------------------------------------------------------------------------
+    void arm_ctl(int ps) { ba_init_ctl(q.H.h_ctl, ps, q.adaptive ? 1 : NB); }
+    vslam_status arm_and_upload(int pass) {
+        const BaPassHost& H = q.H;
         // adaptive look-ahead for large problems (every candidate costs a full Schur / back-substitution / evaluation pass)
         const int adaptEnv = ba_adaptive_env();
-        const bool adaptive = NB > 1 && (adaptEnv >= 0 ? adaptEnv != 0 : NF > 200000);
-        auto init_ctl = [&](int ps) { ba_init_ctl(h_ctl, ps, adaptive ? 1 : NB); };
-        init_ctl(pass);
-        // The arena is complete except for the kernels' argument block (h_D, written after the launch geometry below): its upload
+        q.adaptive = NB > 1 && (adaptEnv >= 0 ? adaptEnv != 0 : H.NF > 200000);
+        arm_ctl(pass);
+        // The arena is complete except for the kernels' argument block (h_D, written after the launch geometry): its upload
         // starts now and runs under the host work that follows (the window lists of a large problem); h_D follows as a copy of its own.
         // (Device ordering: the factor arrays were written in place on the device; only the host-written small pieces travel.)
-        if (devOrder) {
-            VS_HIP(hipMemcpyAsync(A.dev(h_ctl), h_ctl, CTL_DOUBLES * sizeof(double), hipMemcpyHostToDevice, stream));
-            VS_HIP(hipMemcpyAsync(A.dev(h_kfPresent), h_kfPresent, (size_t)K, hipMemcpyHostToDevice, stream));
-            if (NE > 0) VS_HIP(hipMemcpyAsync(A.dev(h_edges), h_edges, (size_t)(specLin ? nSlots : 1) * NE * sizeof(BaEdge), hipMemcpyHostToDevice, stream));
+        if (q.devOrder) {
+            VS_HIP(hipMemcpyAsync(A.dev(H.h_ctl), H.h_ctl, CTL_DOUBLES * sizeof(double), hipMemcpyHostToDevice, stream));
+            VS_HIP(hipMemcpyAsync(A.dev(H.h_kfPresent), H.h_kfPresent, (size_t)K, hipMemcpyHostToDevice, stream));
+            if (H.NE > 0) VS_HIP(hipMemcpyAsync(A.dev(H.h_edges), H.h_edges, (size_t)edge_slots() * H.NE * sizeof(BaEdge), hipMemcpyHostToDevice, stream));
         } else VS_HIP(A.upload(stream));
-        BHS("prep");
+        marks.section("prep");
+        return VSLAM_OK;
+    }
 
-        // ---- device buffers, argument block, then ONE upload ----------------------------------------------
+    void init_slots() {      // every value slot starts from the caller's values
+        const int nPose = K * (int)(sizeof(DPose) / sizeof(double)), nLm = 3 * L;
+        hipLaunchKernelGGL(k_ba_init_slots, dim3((std::max(nPose, nLm) + 255) / 256, nSlots), dim3(256), 0, stream,
+                           nPose, (const double*)p_pose0, (double*)ws.d_poseS.p, nLm, p_lm0, ws.d_lmS.p);
+    }
+    // ---- device buffers sized by the pass, the argument block's common part, the launch geometry -------------------------------
+    vslam_status plan_and_buffers() {
+        const BaPassHost& H = q.H;
+        const int n = H.n, NF = H.NF;
         const size_t sysStride = (size_t)n * n + 2 * n + 8, seDoubles = (size_t)n * n + n;
-        VS_HIP(d_facJ.alloc((size_t)20 * NF * (specLin ? nSlots : 1)));
-        VS_HIP(d_dP.alloc((size_t)NB * n)); VS_HIP(d_dL.alloc((size_t)NB * 3 * Lp));
-        VS_HIP(d_S.alloc(sysStride * NB));         // per candidate: S | rhs | scratch contiguous (one all-reduce buffer)
-        VS_HIP(d_Sedge.alloc(seDoubles * (specLin ? nSlots : 1)));
-        auto init_slots = [&] {      // every value slot starts from the caller's values
-            const int nPose = K * (int)(sizeof(DPose) / sizeof(double)), nLm = 3 * L;
-            hipLaunchKernelGGL(k_ba_init_slots, dim3((std::max(nPose, nLm) + 255) / 256, nSlots), dim3(256), 0, stream,
-                               nPose, (const double*)p_pose0, (double*)d_poseS.p, nLm, p_lm0, d_lmS.p);
-        };
+        VS_HIP(ws.d_facJ.alloc((size_t)20 * NF * edge_slots()));
+        VS_HIP(ws.d_dP.alloc((size_t)NB * n)); VS_HIP(ws.d_dL.alloc((size_t)NB * 3 * H.Lp));
+        VS_HIP(ws.d_S.alloc(sysStride * NB));         // per candidate: S | rhs | scratch contiguous (one all-reduce buffer)
+        VS_HIP(ws.d_Sedge.alloc(seDoubles * edge_slots()));
         init_slots();
-
-        BaDev D{};
-        ba_fill_dev(D, H, A, BaLaneBufs{K, L, d_poseS.p, d_lmS.p, d_facJ.p, d_S.p, d_Sedge.p, d_dP.p, d_dL.p, d_sums.p, d_flags.p}, P->rig, NB, specLin, adaptive);
-
-        // ---- launch geometry (ba_plan.hpp); the environment caps the waves per workgroup of the landmark kernels ------------
+        ba_fill_dev(q.D, H, A, BaLaneBufs{K, L, ws.d_poseS.p, ws.d_lmS.p, ws.d_facJ.p, ws.d_S.p, ws.d_Sedge.p, ws.d_dP.p, ws.d_dL.p, ws.d_sums.p, ws.d_flags.p},
+                    P->rig, NB, specLin, q.adaptive);
+        // launch geometry (ba_plan.hpp); the environment caps the waves per workgroup of the landmark kernels
         static const BaSingleKnobs envKnobs = {getenv("VSLAM_BA_SCHUR_WAVES") ? std::max(2, std::min(BA_SCHUR_WAVES, atoi(getenv("VSLAM_BA_SCHUR_WAVES")))) : BA_SCHUR_WAVES,
                                                getenv("VSLAM_BA_BACK_WAVES") ? std::max(1, atoi(getenv("VSLAM_BA_BACK_WAVES"))) : 64, 0, !getenv("VSLAM_BA_NO_SHARED_W")};
         BaSingleKnobs knobs = envKnobs;
         if (const char* e = getenv("VSLAM_BA_WINDOW_TB")) knobs.windowTB = std::max(1, std::min(32, atoi(e)));
-        const bool useMfma = ba_use_mfma();
-        const BaSinglePlan plan = ba_single_plan(BaSingleShape{NF, Lp, F, NE, maxSlots, NB, useMfma, devOrder}, knobs);
-        if (plan.why) { set_error("%s", plan.why); return VSLAM_ERR_CAPACITY; }
-        const size_t sysDoubles = (size_t)n * n + n;
-        const bool ldsS = plan.ldsS;
-        BaWin Wn{};
-        int nWinWg = 0;
-        if (!ldsS) {
-            // ---- windowed accumulation: tile, work lists (host ordering: ba_window_lists_host; device ordering: k_win_*) ---
-            const int TB = plan.win.TB, nBR = plan.win.nBR, nWin = plan.win.nWin;
-            Wn.TB = TB; Wn.T = plan.win.T; Wn.TP = plan.win.TP; Wn.tileDoubles = plan.win.tileDoubles; Wn.nWin = nWin;
-            const int* devWinCnt = nullptr;
-            BaWinOrd Q{};
-            if (devOrder) {
-                // device ordering: the slot table is on the device - count per (window, 256-landmark block), prefix, and (below, once
-                // the list buffer has its size) the fill; only the nWin + 1 list starts come back
-                Q.Lp = Lp; Q.TB = TB; Q.nBR = nBR; Q.nWin = nWin; Q.nBlk = (Lp + 255) / 256;
-                Q.lpSlotStart = A.dev(h_lpSlotStart); Q.slotFi = A.dev(h_slotFi);
-                VS_HIP(ws->d_winTmp.alloc((size_t)2 * nWin * std::max(Q.nBlk, 1) + nWin + 1));
-                Q.blkCnt = ws->d_winTmp.p; Q.blkOff = Q.blkCnt + (size_t)nWin * std::max(Q.nBlk, 1); Q.winCnt = Q.blkOff + (size_t)nWin * std::max(Q.nBlk, 1);
-                const size_t need = ((size_t)nWin + 1) * sizeof(int);
-                if (need > ws->ordScalCap) {
-                    VS_HIP(hipStreamSynchronize(stream));
-                    if (ws->h_ordScal) hipHostFree(ws->h_ordScal);
-                    ws->ordScalCap = need + 1024;
-                    VS_HIP(hipHostMalloc((void**)&ws->h_ordScal, ws->ordScalCap, hipHostMallocDefault));
-                }
-                if (Q.nBlk > 0) hipLaunchKernelGGL(k_win_lists<0>, dim3(Q.nBlk), dim3(256), 0, stream, Q);
-                hipLaunchKernelGGL(k_win_prefix, dim3(1), dim3(1024), (size_t)nWin * sizeof(int), stream, Q);
-                VS_HIP(hipGetLastError());
-                VS_HIP(hipMemcpyAsync(ws->h_ordScal, Q.winCnt, need, hipMemcpyDeviceToHost, stream));
-                VS_HIP(vslam::stream_wait_blocking(stream));
-                devWinCnt = (const int*)ws->h_ordScal;
-            }
-            const BaWinLists WL = ba_window_lists_host(Lp, h_lpSlotStart, h_slotFi, TB, nBR, &ws->pool, nCU, devWinCnt);
-            const std::vector<int>& pack = WL.pack;
-            const size_t oWg = WL.oWg, nInts = WL.nInts;
-            const int total = WL.total;
-            nWinWg = WL.nWinWg;
-            VS_HIP(d_win.alloc(nInts));
-            VS_HIP(hipMemcpyAsync(d_win.p, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-            if (devOrder && Q.nBlk > 0 && total > 0) {
-                Q.winLm = d_win.p + oWg + 3 * (size_t)std::max(nWinWg, 1);
-                hipLaunchKernelGGL(k_win_lists<1>, dim3(Q.nBlk), dim3(256), 0, stream, Q);
-                VS_HIP(hipGetLastError());
-            }
-            VS_HIP(hipStreamSynchronize(stream));          // (pack is a local: the copy must have left it)
-            Wn.winA = d_win.p; Wn.winB = d_win.p + nWin; Wn.winFirstWg = d_win.p + 2 * nWin;
-            Wn.wgWin = d_win.p + oWg; Wn.wgBegin = Wn.wgWin + std::max(nWinWg, 1); Wn.wgEnd = Wn.wgBegin + std::max(nWinWg, 1);
-            Wn.winLm = Wn.wgEnd + std::max(nWinWg, 1);
-            VS_HIP(d_Spart.alloc((size_t)std::max(nWinWg, 1) * NB * Wn.tileDoubles));
-            Wn.part = d_Spart.p;
-            VS_HIP(ws->d_winW.alloc((size_t)std::max(nSlotEntries, 1) * 18)); VS_HIP(ws->d_winH.alloc((size_t)std::max(Lp, 1) * BA_WIN_HG));
-            Wn.Wg = ws->d_winW.p; Wn.Hg = ws->d_winH.p;
-            // the lower block triangle is never written (nor read by a solver): keep it at zero for the all-reduce
-            VS_HIP(hipMemsetAsync(d_S.p, 0, sysStride * NB * sizeof(double), stream));
-        }
-        D.partialStride = (size_t)2 * plan.obsBlocks + 2 * (size_t)std::max(NE, 1);
-        VS_HIP(d_partial.alloc(D.partialStride * NB));
-        D.partial = d_partial.p;
+        q.plan = ba_single_plan(BaSingleShape{NF, H.Lp, H.F, H.NE, H.maxSlots, NB, ba_use_mfma(), q.devOrder}, knobs);
+        if (q.plan.why) { set_error("%s", q.plan.why); return VSLAM_ERR_CAPACITY; }
+        return VSLAM_OK;
+    }
+
+    // ---- windowed accumulation: tile, work lists (host ordering: ba_window_lists_host alone; device ordering: counts and fill by k_win_*)
+    vslam_status window_lists() {
+        const BaPassHost& H = q.H;
+        const BaSinglePlan& plan = q.plan;
+        BaWin& Wn = q.Wn;
+        const int TB = plan.win.TB, nBR = plan.win.nBR, nWin = plan.win.nWin, n = H.n, Lp = H.Lp;
+        Wn.TB = TB; Wn.T = plan.win.T; Wn.TP = plan.win.TP; Wn.tileDoubles = plan.win.tileDoubles; Wn.nWin = nWin;
+        const int* devWinCnt = nullptr;
+        if (q.devOrder) VS_CHECK(ord.window_counts(H, A, TB, nBR, nWin, stream, &devWinCnt));
+        const BaWinLists WL = ba_window_lists_host(Lp, H.h_lpSlotStart, H.h_slotFi, TB, nBR, &ws.pool, BA_NCU, devWinCnt);
+        const int nWinWg = q.nWinWg = WL.nWinWg;
+        VS_HIP(ws.d_win.alloc(WL.nInts));
+        int* const dw = ws.d_win.p;
+        VS_HIP(hipMemcpyAsync(dw, WL.pack.data(), WL.pack.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (q.devOrder) VS_CHECK(ord.window_fill(dw + WL.oWg + 3 * (size_t)std::max(nWinWg, 1), WL.total, stream));
+        VS_HIP(hipStreamSynchronize(stream));          // (WL.pack is a local: the copy must have left it)
+        Wn.winA = dw; Wn.winB = dw + nWin; Wn.winFirstWg = dw + 2 * nWin;
+        Wn.wgWin = dw + WL.oWg; Wn.wgBegin = Wn.wgWin + std::max(nWinWg, 1); Wn.wgEnd = Wn.wgBegin + std::max(nWinWg, 1);
+        Wn.winLm = Wn.wgEnd + std::max(nWinWg, 1);
+        VS_HIP(ws.d_Spart.alloc((size_t)std::max(nWinWg, 1) * NB * Wn.tileDoubles));
+        Wn.part = ws.d_Spart.p;
+        VS_HIP(ws.d_winW.alloc((size_t)std::max(H.nSlotEntries, 1) * 18)); VS_HIP(ws.d_winH.alloc((size_t)std::max(Lp, 1) * BA_WIN_HG));
+        Wn.Wg = ws.d_winW.p; Wn.Hg = ws.d_winH.p;
+        // the lower block triangle is never written (nor read by a solver): keep it at zero for the all-reduce
+        VS_HIP(hipMemsetAsync(ws.d_S.p, 0, ((size_t)n * n + 2 * n + 8) * NB * sizeof(double), stream));
+        return VSLAM_OK;
+    }
+
+    // ---- what the plan adds to the argument block, then its upload ------------------------------------------------------------
+    vslam_status argument_block() {
+        const BaPassHost& H = q.H;
+        const BaSinglePlan& plan = q.plan;
+        BaDev& D = q.D;
+        const size_t sysDoubles = (size_t)H.n * H.n + H.n;
+        D.partialStride = (size_t)2 * plan.obsBlocks + 2 * (size_t)std::max(H.NE, 1);
+        VS_HIP(ws.d_partial.alloc(D.partialStride * NB));
+        D.partial = ws.d_partial.p;
         D.spartStride = sysDoubles * plan.lmBlocks;
-        if (ldsS) { VS_HIP(d_Spart.alloc(D.spartStride * NB)); D.Spart = d_Spart.p; }
-#ifndef VSLAM_HOST_STAMPS
-        BHS("u_alloc");
-#endif
+        if (plan.ldsS) { VS_HIP(ws.d_Spart.alloc(D.spartStride * NB)); D.Spart = ws.d_Spart.p; }
+        marks.fine("u_alloc");
         VS_CHECK(ba_kernel_attributes());
-        if (plan.solveKind == BA_SOLVE_MFMA) VS_HIP(d_Lg.alloc((size_t)BA_MFMA_N * BA_MFMA_N * NB));
+        if (plan.solveKind == BA_SOLVE_MFMA) VS_HIP(ws.d_Lg.alloc((size_t)BA_MFMA_N * BA_MFMA_N * NB));
         // larger systems: block-column MFMA Cholesky (k_ba_chol_col / k_ba_chol_back)
         if (plan.useChol) {
-            VS_HIP(d_Lg.alloc((size_t)plan.cholN * plan.cholN * NB));
-            VS_HIP(d_cholY.alloc((size_t)plan.cholN * NB));
-            if (!d_cholFail.p) { VS_HIP(d_cholFail.alloc(BA_MAX_NB)); VS_HIP(hipMemsetAsync(d_cholFail.p, 0, BA_MAX_NB * sizeof(int), stream)); }
+            VS_HIP(ws.d_Lg.alloc((size_t)plan.cholN * plan.cholN * NB));
+            VS_HIP(ws.d_cholY.alloc((size_t)plan.cholN * NB));
+            if (!ws.d_cholFail.p) { VS_HIP(ws.d_cholFail.alloc(BA_MAX_NB)); VS_HIP(hipMemsetAsync(ws.d_cholFail.p, 0, BA_MAX_NB * sizeof(int), stream)); }
         }
-#ifndef VSLAM_HOST_STAMPS
-        BHS("u_attr");
-#endif
+        marks.fine("u_attr");
         D.solveKind = plan.solveKind;
-        *h_D = D;
-        const BaDev* const dD = A.dev(h_D);
-        VS_HIP(hipMemcpyAsync((void*)dD, h_D, sizeof(BaDev), hipMemcpyHostToDevice, stream));
-        BHS("upload");
+        *H.h_D = D;
+        q.dD = A.dev(H.h_D);
+        VS_HIP(hipMemcpyAsync((void*)q.dD, H.h_D, sizeof(BaDev), hipMemcpyHostToDevice, stream));
+        marks.section("upload");
+        return VSLAM_OK;
+    }
 
-        // ---- LM: speculative steps, the device decides (k_ba_ctl) -----------------------------------
-        auto run_lm = [&](int ps, long long nfStat, long long lpStat, long long k2Stat) -> vslam_status {
-        // One step = [linearise if the state asks for it] + one lambda trial.  Kernels that are not due
-        // return at once, so the host may enqueue a few steps ahead and only then look at the state.
+    // ---- LM: speculative steps, the device decides (k_ba_ctl) ------------------------------------------------------------------
+    // One step = [linearise if the state asks for it] + one lambda trial.  Kernels that are not due
+    // return at once, so the host may enqueue a few steps ahead and only then look at the state.
+    vslam_status lm_step(bool first) {
+        const BaPassHost& H = q.H;
+        const BaSinglePlan& plan = q.plan;
+        const BaDev* const dD = q.dD;
+        const BaWin& Wn = q.Wn;
+        const int n = H.n, NF = H.NF, NE = H.NE, Lp = H.Lp, maxSlots = H.maxSlots, nWinWg = q.nWinWg, nCU = BA_NCU;
+        const size_t sysStride = (size_t)n * n + 2 * n + 8, sysDoubles = (size_t)n * n + n;
+        const bool ldsS = plan.ldsS;
         const int fuseCtl = comm ? 0 : 1;
         const int facBlocks = (NF ? plan.obsBlocks : 0) + std::max(NE, 1);
         const int nObs = NF ? plan.obsBlocks : 0;
-        VS_HIP(hipMemsetAsync(d_Sedge.p, 0, ((size_t)n * n + n) * sizeof(double), stream));     // first linearisation; later ones: see k_ba_factors
-        auto step = [&](bool first) -> vslam_status {
-            int t = -1;
-            // with speculative linearisation only the first step of a pass linearises on its own
-            if (first || !specLin) {
-                t = g_baTimer.begin("ba_linearize");
-                hipLaunchKernelGGL(k_ba_factors<0>, dim3(facBlocks), dim3(256), 0, stream, dD, nObs, fuseCtl, relTol, absTol);
-                g_baTimer.end(t);
-            }
-            if (comm) {
-                const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, d_sums.p, 1, stream)); g_baTimer.end(tc);
-                hipLaunchKernelGGL(k_ba_ctl, dim3(1), dim3(256), 0, stream, dD, 0, relTol, absTol);
-            }
-            t = g_baTimer.begin("ba_schur");
-            if (n > 0) {
-                if (ldsS) hipLaunchKernelGGL(k_ba_schur, dim3(plan.lmBlocks, plan.sharedW ? 1 : NB), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, maxSlots, plan.sharedW);
-                else if (nWinWg) {
-                    hipLaunchKernelGGL(k_ba_lm_prep, dim3(std::max(1, std::min((Lp + BA_SCHUR_WAVES - 1) / BA_SCHUR_WAVES, 4 * nCU))), dim3(64 * BA_SCHUR_WAVES),
-                                       (size_t)BA_SCHUR_WAVES * maxSlots * sizeof(int), stream, dD, Wn, maxSlots);
-                    hipLaunchKernelGGL(k_ba_schur_win, dim3(nWinWg), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, Wn);
-                }
-            }
+        int t = -1;
+        // with speculative linearisation only the first step of a pass linearises on its own
+        if (first || !specLin) {
+            t = g_baTimer.begin("ba_linearize");
+            hipLaunchKernelGGL(k_ba_factors<0>, dim3(facBlocks), dim3(256), 0, stream, dD, nObs, fuseCtl, relTol, absTol);
             g_baTimer.end(t);
-            t = g_baTimer.begin("ba_solve");
-            if (n > 0) {     // sum of the partial systems + BetweenFactor blocks
-                if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, plan.lmBlocks, 0);
-                else hipLaunchKernelGGL(k_ba_reduce_win, dim3(Wn.nWin, NB), dim3(256), 0, stream, dD, Wn);
+        }
+        if (comm) {
+            const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, ws.d_sums.p, 1, stream)); g_baTimer.end(tc);
+            hipLaunchKernelGGL(k_ba_ctl, dim3(1), dim3(256), 0, stream, dD, 0, relTol, absTol);
+        }
+        t = g_baTimer.begin("ba_schur");
+        if (n > 0) {
+            if (ldsS) hipLaunchKernelGGL(k_ba_schur, dim3(plan.lmBlocks, plan.sharedW ? 1 : NB), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, maxSlots, plan.sharedW);
+            else if (nWinWg) {
+                hipLaunchKernelGGL(k_ba_lm_prep, dim3(std::max(1, std::min((Lp + BA_SCHUR_WAVES - 1) / BA_SCHUR_WAVES, 4 * nCU))), dim3(64 * BA_SCHUR_WAVES),
+                                   (size_t)BA_SCHUR_WAVES * maxSlots * sizeof(int), stream, dD, Wn, maxSlots);
+                hipLaunchKernelGGL(k_ba_schur_win, dim3(nWinWg), dim3(64 * plan.schurWaves), plan.schurLds, stream, dD, Wn);
             }
-            // the NB candidates' systems are contiguous (sysStride apart): one all-reduce for all of them
-            if (comm && n > 0) { const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, d_S.p, sysStride * (NB - 1) + (size_t)n * n + n, stream)); g_baTimer.end(tc); }
-            if (D.solveKind == BA_SOLVE_MFMA64) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB), dim3(64), 0, stream, dD);
-            else if (D.solveKind == BA_SOLVE_WAVE) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB), dim3(64), 0, stream, dD);
-            else if (D.solveKind == BA_SOLVE_MFMA) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB), dim3(64 * BA_MFMA_NW), plan.mfmaLds, stream, dD, d_Lg.p);
-            else if (plan.useChol) {
-                for (int J = 0; J < plan.cholN / CH_B; J++)
-                    hipLaunchKernelGGL(k_ba_chol_col, dim3(plan.cholN / CH_B - J, NB), dim3(256), plan.cholColLds, stream, dD, d_Lg.p, d_cholY.p, plan.cholN, J, d_cholFail.p);
-                hipLaunchKernelGGL(k_ba_chol_back, dim3(NB), dim3(256), plan.cholBackLds, stream, dD, (const double*)d_Lg.p, (const double*)d_cholY.p, plan.cholN, d_cholFail.p);
-            } else hipLaunchKernelGGL(k_ba_solve, dim3(NB), dim3(std::max(64, vslam::align_up(n, 64))),
-                                    plan.solveLds ? plan.solveLdsBytes : 64, stream, dD, plan.solveLds ? 1 : 0, plan.solveLds ? plan.ldA : n);
-            g_baTimer.end(t);
-            t = g_baTimer.begin("ba_back");
-            if (Lp) hipLaunchKernelGGL(k_ba_back, dim3(plan.backBlocks, plan.sharedBack ? 1 : NB), dim3(64 * plan.backWaves), plan.backLds, stream, dD, maxSlots, plan.sharedBack);
-            g_baTimer.end(t);
-            t = g_baTimer.begin("ba_eval");
-            hipLaunchKernelGGL(k_ba_factors<1>, dim3(facBlocks, NB), dim3(256), 0, stream, dD, nObs, fuseCtl, relTol, absTol);
-            g_baTimer.end(t);
-            if (comm) {
-                const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, d_sums.p + SUMS_CAND, (size_t)2 * NB, stream)); g_baTimer.end(tc);
-                hipLaunchKernelGGL(k_ba_ctl, dim3(1), dim3(256), 0, stream, dD, 1, relTol, absTol);
-            }
-            VS_HIP(hipGetLastError());
-            return VSLAM_OK;
-        };
-        double* h_ctlOut = ws->h_ctlOut;
+        }
+        g_baTimer.end(t);
+        t = g_baTimer.begin("ba_solve");
+        if (n > 0) {     // sum of the partial systems + BetweenFactor blocks
+            if (ldsS) hipLaunchKernelGGL(k_ba_reduce, dim3(((int)sysDoubles + 31) / 32, NB), dim3(256), 0, stream, dD, plan.lmBlocks, 0);
+            else hipLaunchKernelGGL(k_ba_reduce_win, dim3(Wn.nWin, NB), dim3(256), 0, stream, dD, Wn);
+        }
+        // the NB candidates' systems are contiguous (sysStride apart): one all-reduce for all of them
+        if (comm && n > 0) { const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, ws.d_S.p, sysStride * (NB - 1) + (size_t)n * n + n, stream)); g_baTimer.end(tc); }
+        if (q.D.solveKind == BA_SOLVE_MFMA64) hipLaunchKernelGGL(k_ba_solve_mfma64, dim3(NB), dim3(64), 0, stream, dD);
+        else if (q.D.solveKind == BA_SOLVE_WAVE) hipLaunchKernelGGL(k_ba_solve_wave, dim3(NB), dim3(64), 0, stream, dD);
+        else if (q.D.solveKind == BA_SOLVE_MFMA) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(NB), dim3(64 * BA_MFMA_NW), plan.mfmaLds, stream, dD, ws.d_Lg.p);
+        else if (plan.useChol) {
+            for (int J = 0; J < plan.cholN / CH_B; J++)
+                hipLaunchKernelGGL(k_ba_chol_col, dim3(plan.cholN / CH_B - J, NB), dim3(256), plan.cholColLds, stream, dD, ws.d_Lg.p, ws.d_cholY.p, plan.cholN, J, ws.d_cholFail.p);
+            hipLaunchKernelGGL(k_ba_chol_back, dim3(NB), dim3(256), plan.cholBackLds, stream, dD, (const double*)ws.d_Lg.p, (const double*)ws.d_cholY.p, plan.cholN, ws.d_cholFail.p);
+        } else hipLaunchKernelGGL(k_ba_solve, dim3(NB), dim3(std::max(64, vslam::align_up(n, 64))),
+                                plan.solveLds ? plan.solveLdsBytes : 64, stream, dD, plan.solveLds ? 1 : 0, plan.solveLds ? plan.ldA : n);
+        g_baTimer.end(t);
+        t = g_baTimer.begin("ba_back");
+        if (Lp) hipLaunchKernelGGL(k_ba_back, dim3(plan.backBlocks, plan.sharedBack ? 1 : NB), dim3(64 * plan.backWaves), plan.backLds, stream, dD, maxSlots, plan.sharedBack);
+        g_baTimer.end(t);
+        t = g_baTimer.begin("ba_eval");
+        hipLaunchKernelGGL(k_ba_factors<1>, dim3(facBlocks, NB), dim3(256), 0, stream, dD, nObs, fuseCtl, relTol, absTol);
+        g_baTimer.end(t);
+        if (comm) {
+            const int tc = g_baTimer.begin("ba_allreduce"); VS_CHECK(comm_allreduce(comm, ws.d_sums.p + SUMS_CAND, (size_t)2 * NB, stream)); g_baTimer.end(tc);
+            hipLaunchKernelGGL(k_ba_ctl, dim3(1), dim3(256), 0, stream, dD, 1, relTol, absTol);
+        }
+        VS_HIP(hipGetLastError());
+        return VSLAM_OK;
+    }
+    // one pass of LM on the armed control block, its report (with the statistics of the graph it ran on), then the chi2 re-check
+    vslam_status run_lm(int ps, long long nfStat, long long lpStat, long long k2Stat) {
+        BaDev& D = q.D;
+        const int n = q.H.n;
+        VS_HIP(hipMemsetAsync(ws.d_Sedge.p, 0, ((size_t)n * n + n) * sizeof(double), stream));     // first linearisation; later ones: see k_ba_factors
+        double* const h_ctlOut = (double*)ws.h_ctlOut.p;
         const int* co = (const int*)(h_ctlOut + CTL_INTS);
         int enq = 0;
         for (;;) {
             static const int perPoll = getenv("VSLAM_BA_STEPS_PER_POLL") ? std::max(1, atoi(getenv("VSLAM_BA_STEPS_PER_POLL"))) : 4;
-            for (int b = 0; b < perPoll; b++) VS_CHECK(step(enq + b == 0));
+            for (int b = 0; b < perPoll; b++) VS_CHECK(lm_step(enq + b == 0));
             enq += perPoll;
             VS_HIP(hipMemcpyAsync(h_ctlOut, D.ctl, CTL_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
             VS_HIP(vslam::stream_wait_blocking(stream));
             if (co[CI_STATE] == BA_DONE) break;
             if (enq > 400) { set_error("local BA: LM did not terminate"); return VSLAM_ERR_INVALID; }
         }
-        D.poseCur = d_poseS.p + (size_t)co[CI_SEL] * K; D.lmCur = d_lmS.p + (size_t)co[CI_SEL] * 3 * L;
-        ba_write_report(R, ps, h_ctlOut, F, nfStat, lpStat, k2Stat);
-
-        if (comm) {
-            // every rank needs all landmarks for the chi2 pass and the result: exchange the shard updates
-            const int tc = g_baTimer.begin("ba_allreduce");
-            if (L) {
-                VS_HIP(d_lmDiff.alloc((size_t)3 * L));
-                hipLaunchKernelGGL(k_ba_lm_diff, dim3((3 * L + 255) / 256), dim3(256), 0, stream, 3 * L, D.lmCur, p_lm0, d_lmDiff.p, 0);
-                VS_CHECK(comm_allreduce(comm, d_lmDiff.p, (size_t)3 * L, stream));
-                hipLaunchKernelGGL(k_ba_lm_apply, dim3((3 * L + 255) / 256), dim3(256), 0, stream, 3 * L, D.lmCur, p_lm0, d_lmDiff.p);
-            }
-            double st[4] = {(double)nfStat, (double)lpStat, (double)k2Stat, 0.0};
-            VS_HIP(hipMemcpyAsync(d_sums.p + 4, st, sizeof(st), hipMemcpyHostToDevice, stream));
-            VS_CHECK(comm_allreduce(comm, d_sums.p + 4, 3, stream));
-            VS_HIP(hipMemcpyAsync(st, d_sums.p + 4, sizeof(st), hipMemcpyDeviceToHost, stream));
-            VS_HIP(hipStreamSynchronize(stream));
-            R->n_residuals = (int64_t)llround(st[0]); R->n_landmarks = (int64_t)llround(st[1]); R->sum_k2 = (int64_t)llround(st[2]);
-            g_baTimer.end(tc);
+        D.poseCur = ws.d_poseS.p + (size_t)co[CI_SEL] * K; D.lmCur = ws.d_lmS.p + (size_t)co[CI_SEL] * 3 * L;
+        ba_write_report(R, ps, h_ctlOut, q.H.F, nfStat, lpStat, k2Stat);
+        if (comm) VS_CHECK(exchange_shards(nfStat, lpStat, k2Stat));
+        marks.section("lm");
+        return chi2_and_fetch(ps);
+    }
+    // landmark shards: every rank needs all landmarks for the chi2 pass and the result - exchange the shard updates and the statistics
+    vslam_status exchange_shards(long long nfStat, long long lpStat, long long k2Stat) {
+        BaDev& D = q.D;
+        const int tc = g_baTimer.begin("ba_allreduce");
+        if (L) {
+            VS_HIP(ws.d_lmDiff.alloc((size_t)3 * L));
+            hipLaunchKernelGGL(k_ba_lm_diff, dim3((3 * L + 255) / 256), dim3(256), 0, stream, 3 * L, D.lmCur, p_lm0, ws.d_lmDiff.p, 0);
+            VS_CHECK(comm_allreduce(comm, ws.d_lmDiff.p, (size_t)3 * L, stream));
+            hipLaunchKernelGGL(k_ba_lm_apply, dim3((3 * L + 255) / 256), dim3(256), 0, stream, 3 * L, D.lmCur, p_lm0, ws.d_lmDiff.p);
         }
-        BHS("lm");
-        // ---- chi2 re-check with the optimised values ---------------------------------------------
+        double st[4] = {(double)nfStat, (double)lpStat, (double)k2Stat, 0.0};
+        VS_HIP(hipMemcpyAsync(ws.d_sums.p + 4, st, sizeof(st), hipMemcpyHostToDevice, stream));
+        VS_CHECK(comm_allreduce(comm, ws.d_sums.p + 4, 3, stream));
+        VS_HIP(hipMemcpyAsync(st, ws.d_sums.p + 4, sizeof(st), hipMemcpyDeviceToHost, stream));
+        VS_HIP(hipStreamSynchronize(stream));
+        R->n_residuals = (int64_t)llround(st[0]); R->n_landmarks = (int64_t)llround(st[1]); R->sum_k2 = (int64_t)llround(st[2]);
+        g_baTimer.end(tc);
+        return VSLAM_OK;
+    }
+    // ---- chi2 re-check with the optimised values; the flags come back, and behind the last pass's flags its values --------------
+    vslam_status chi2_and_fetch(int ps) {
+        const BaPassHost& H = q.H;
+        const BaDev& D = q.D;
         BaChi C{};
-        ba_fill_chi(C, P, BaPairArrays{p_pairKf, p_pairLm, p_pairOct, p_pairFlags, p_pairUv, p_kfLocal}, A.dev(h_kfPresent), A.dev(h_lmPresent), d_wrong.p);
+        ba_fill_chi(C, P, pairs, A.dev(H.h_kfPresent), A.dev(H.h_lmPresent), ws.d_wrong.p);
         C.pose = D.poseCur; C.lm = D.lmCur;
-        int t = g_baTimer.begin("ba_chi2");
+        const int t = g_baTimer.begin("ba_chi2");
         if (NP) hipLaunchKernelGGL(k_ba_chi2, dim3((NP + 255) / 256), dim3(256), 0, stream, C);
         g_baTimer.end(t);
         VS_HIP(hipGetLastError());
-        if (NP) VS_HIP(hipMemcpyAsync(ws->h_wrong, d_wrong.p, NP, hipMemcpyDeviceToHost, stream));
+        if (NP) VS_HIP(hipMemcpyAsync(ws.h_wrong.p, ws.d_wrong.p, NP, hipMemcpyDeviceToHost, stream));
         if (ps == 1) {      // the second pass is the last one: its values ride behind the flags, one synchronisation for both
             VS_HIP(hipMemcpyAsync(poseOut, D.poseCur, K * sizeof(DPose), hipMemcpyDeviceToHost, stream));
             if (L) VS_HIP(hipMemcpyAsync(lmOut, D.lmCur, (size_t)3 * L * sizeof(double), hipMemcpyDeviceToHost, stream));
             resultFetched = true;
         }
         VS_HIP(hipStreamSynchronize(stream));
-        if (NP) memcpy(wrong.data(), ws->h_wrong, NP);
+        if (NP) memcpy(wrong.data(), ws.h_wrong.p, NP);
         if (ps == 0 && R->pair_wrong_pass1 && NP) memcpy(R->pair_wrong_pass1, wrong.data(), NP);
         poseFinal = D.poseCur;
         lmFinal = D.lmCur;
         return VSLAM_OK;
-        };
-        VS_CHECK(run_lm(pass, NF, Lp, sumK2));
+    }
 
-        // ---- second pass on the first pass's structure (single GPU): mask instead of rebuild ------------------
+    // ---- second pass on the first pass's structure (single GPU): mask instead of rebuild ------------------------------------------
+    // Membership / statistics of the second graph from the chi2 flags (large problems: by landmark range on the pool, as
+    // BaPassHost::count - every worker reads all pairs and handles its range; with the device ordering: the same kernels again).
+    // *done: the second pass has run here; otherwise the caller rebuilds the graph for it.
+    vslam_status masked_second_pass(bool* done) {
         static const bool maskEnv = !getenv("VSLAM_BA_NO_MASK");
-        if (pass == 0 && maskEnv && g_baMask) {
-            // membership / statistics of the second graph from the chi2 flags
-            // (large problems: by landmark range on the pool, as BaPassHost::count - every worker reads all pairs and handles its range;
-            //  with the device ordering: the same kernels again, now with the chi2 flags - membership, counts, and the masked slot statistics)
-            BaSecondPass S2;
-            if (devOrder) {
-                const size_t zInts = (size_t)L + K + ((size_t)L + 3) / 4;
-                VS_HIP(hipMemsetAsync(ws->d_ord1.p, 0, zInts * sizeof(int), stream));
-                const int pairBlocks = std::max(1, std::min((NP + 255) / 256, 8 * nCU));
-                hipLaunchKernelGGL(k_ord_count, dim3(pairBlocks), dim3(256), 0, stream, O);
-                hipLaunchKernelGGL(k_ord_scan_lm, dim3(1), dim3(1024), 0, stream, O);
-                if (Lp > 0) hipLaunchKernelGGL(k_ord_k2_masked, dim3((Lp + 255) / 256), dim3(256), 0, stream, O, Lp);
-                VS_HIP(hipGetLastError());
-                int* const h_kfPres = (int*)(ws->h_ordScal + ORD_SCAL);
-                VS_HIP(hipMemcpyAsync(ws->h_ordScal, O.scal, ORD_SCAL * sizeof(long long), hipMemcpyDeviceToHost, stream));
-                VS_HIP(hipMemcpyAsync(h_kfPres, O.kfPres, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, stream));
-                VS_HIP(vslam::stream_wait_blocking(stream));
-                S2.kfP2.resize(K);
-                for (int k = 0; k < K; k++) S2.kfP2[k] = h_kfPres[k] ? 1 : 0;
-                S2.NF2 = ws->h_ordScal[ORD_NF]; S2.Lp2 = ws->h_ordScal[ORD_LP]; S2.k2 = ws->h_ordScal[ORD_K2_MASKED];
-                S2.same = S2.kfP2 == T.kfPresent;
-            } else H.second_pass(P, wrong.data(), rank, world, T, &ws->pool, S2);
-            if (S2.same) {       // same keyframes => same free set, same BetweenFactor chain; landmarks may only drop out
-                BHS("p2stats");
-                for (int k = 0; k < K; k++) h_kfPresent[k] = S2.kfP2[k];
-                if (!devOrder) for (int l = 0; l < L; l++) h_lmPresent[l] = S2.lmP2[l];
-                init_ctl(1);
-                VS_HIP(hipMemcpyAsync(A.dev(h_kfPresent), h_kfPresent, K, hipMemcpyHostToDevice, stream));
-                if (devOrder) VS_HIP(hipMemcpyAsync(A.dev(h_lmPresent), O.lmPres, (size_t)L, hipMemcpyDeviceToDevice, stream));
-                else if (L) VS_HIP(hipMemcpyAsync(A.dev(h_lmPresent), h_lmPresent, L, hipMemcpyHostToDevice, stream));
-                VS_HIP(hipMemcpyAsync(A.dev(h_ctl), h_ctl, CTL_DOUBLES * sizeof(double), hipMemcpyHostToDevice, stream));
-                if (NF) hipLaunchKernelGGL(k_ba_mask, dim3((NF + 255) / 256), dim3(256), 0, stream, NF, A.dev(H.h_facPair), d_wrong.p, A.dev(H.h_facIs));
-                init_slots();
-                VS_CHECK(run_lm(1, S2.NF2, S2.Lp2, S2.k2));
-                break;
-            }
+        if (!maskEnv || !g_baMask) return VSLAM_OK;
+        const BaPassHost& H = q.H;
+        BaSecondPass S2;
+        if (q.devOrder) VS_CHECK(ord.second_pass(H.Lp, ws.tmp, stream, S2));
+        else H.second_pass(P, wrong.data(), rank, world, ws.tmp, &ws.pool, S2);
+        if (!S2.same) return VSLAM_OK;       // same keyframes => same free set, same BetweenFactor chain; landmarks may only drop out
+        marks.section("p2stats");
+        for (int k = 0; k < K; k++) H.h_kfPresent[k] = S2.kfP2[k];
+        if (!q.devOrder) for (int l = 0; l < L; l++) H.h_lmPresent[l] = S2.lmP2[l];
+        arm_ctl(1);
+        VS_HIP(hipMemcpyAsync(A.dev(H.h_kfPresent), H.h_kfPresent, K, hipMemcpyHostToDevice, stream));
+        if (q.devOrder) VS_HIP(hipMemcpyAsync(A.dev(H.h_lmPresent), ord.lm_present(), (size_t)L, hipMemcpyDeviceToDevice, stream));
+        else if (L) VS_HIP(hipMemcpyAsync(A.dev(H.h_lmPresent), H.h_lmPresent, L, hipMemcpyHostToDevice, stream));
+        VS_HIP(hipMemcpyAsync(A.dev(H.h_ctl), H.h_ctl, CTL_DOUBLES * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (H.NF) hipLaunchKernelGGL(k_ba_mask, dim3((H.NF + 255) / 256), dim3(256), 0, stream, H.NF, A.dev(H.h_facPair), ws.d_wrong.p, A.dev(H.h_facIs));
+        init_slots();
+        VS_CHECK(run_lm(1, S2.NF2, S2.Lp2, S2.k2));
+        *done = true;
+        return VSLAM_OK;
+    }
+
+    // ---- results land in pinned memory (a copy into the caller's pageable arrays is staged and synchronised by the runtime) ------
+    vslam_status result() {
+        marks.section("chi2");
+        marks.section("fetch");
+        if (!resultFetched) {
+            VS_HIP(hipMemcpyAsync(poseOut, poseFinal, K * sizeof(DPose), hipMemcpyDeviceToHost, stream));
+            if (L) VS_HIP(hipMemcpyAsync(lmOut, lmFinal, (size_t)3 * L * sizeof(double), hipMemcpyDeviceToHost, stream));
+            VS_HIP(hipStreamSynchronize(stream));
         }
+        ba_write_result(R, poseOut, lmOut, wrong.data(), K, L, NP);
+        return VSLAM_OK;
     }
-    BHS("chi2");
-    // results land in pinned memory (a copy into the caller's pageable arrays is staged and synchronised by the runtime)
-    BHS("fetch");
-    if (!resultFetched) {
-        VS_HIP(hipMemcpyAsync(poseOut, poseFinal, K * sizeof(DPose), hipMemcpyDeviceToHost, stream));
-        if (L) VS_HIP(hipMemcpyAsync(lmOut, lmFinal, (size_t)3 * L * sizeof(double), hipMemcpyDeviceToHost, stream));
-        VS_HIP(hipStreamSynchronize(stream));
-    }
-    ba_write_result(R, poseOut, lmOut, wrong.data(), K, L, NP);
-    return VSLAM_OK;
+};
+
+}  // namespace
+
+static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int device, const vslam_comm* comm) {
+    BaMarks marks;
+    if (!ba_check_args(P, R)) { set_error("vslam_local_ba: invalid problem"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(ba_select_device(device));
+    // (the index check of a large problem - 1.2 M pairs: ~1 ms on one core - runs on the workspace's pool, below)
+    const bool pooledCheck = P->n_pairs >= BaHostTune{}.parPairs;
+    if (!pooledCheck && !ba_check_pairs(P)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
+    marks.fine("s_check");
+    BaThread& th = ba_thread();
+    BaSingleWs* ws = nullptr;
+    VS_CHECK(th.single_ws(device, &ws));
+    if (pooledCheck && !ba_check_pairs(P, &ws->pool)) { set_error("vslam_local_ba: pair index out of range"); return VSLAM_ERR_INVALID; }
+    VS_HIP(ws->h_wrong.ensure((size_t)P->n_pairs, grow_wrong()));
+    VS_HIP(ws->h_out.ensure((size_t)P->n_kf * sizeof(DPose) + 64 + (size_t)3 * P->n_lm * sizeof(double), grow_out()));
+    marks.fine("s_ws");
+    g_baTimer.reset();
+    g_baTimer.stream = ws->stream;
+    g_baTimer.multi = true;
+    return BaCall(P, R, comm, *ws, th.order, marks).run();
 }
 
 // ---- batched local BA: N independent tracker-window problems, ONE launch per stage for all of them -------------------------------
@@ -3024,8 +2838,6 @@ static vslam_status ba_run(const vslam_ba_problem* P, vslam_ba_result* R, int de
 // chi2 flags; the second pass is re-armed for all lanes together (mask, no rebuild).  Problems outside the tracker-window
 // class (more than BA_LDS_MAX_F free keyframes, empty graphs) and lanes whose second graph loses a keyframe take the
 // one-problem path.
-static std::atomic<long long> g_bbsNs[12], g_bbsCalls{0}, g_bbsPolls{0};
-static const char* g_bbsName[12] = {"check+count", "arena fill", "tables+upload", "lm pass 1", "chi2 1", "second-pass prep", "lm pass 2", "chi2 2 + fetch", "results", nullptr, nullptr, nullptr};
 
 // ---- launch plan of the batch: a pure function of the cohort's shape (no device calls; exported as vslam_local_ba_batch_plan) -----
 static BaPlanKnobs ba_plan_knobs() {      // developer overrides from the environment (none set: the production plan)
@@ -3054,32 +2866,9 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     g_bbsCalls++;
     auto BBS = [&](int k) { const auto t_ = std::chrono::steady_clock::now(); g_bbsNs[k] += std::chrono::duration_cast<std::chrono::nanoseconds>(t_ - bbs_t).count(); bbs_t = t_; };
     VS_CHECK(ba_select_device(device));
-    struct BatchWs {
-        hipStream_t stream = nullptr; int device = -1;
-        PinnedArena arena;
-        DevBuf<uint8_t> d_mem;
-        uint8_t* h_back = nullptr; size_t backCap = 0;        // pinned landing area: control blocks | chi2 flags | results
-        BaPool pool;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
-            if (d_mem.p) hipFree(d_mem.p);
-            if (arena.d) hipFree(arena.d);
-            if (arena.h) hipHostFree(arena.h);
-            if (h_back) hipHostFree(h_back);
-        }
-    };
-    static thread_local std::unique_ptr<BatchWs> bws;
-    static thread_local void (*prevRelease)() = nullptr;
-    if (!bws || bws->device != device) {
-        if (bws) bws->release();
-        bws.reset(new BatchWs()); bws->device = device;
-        VS_HIP(vslam::create_side_stream(&bws->stream));
-        bws->pool.start(2);
-        prevRelease = g_baRelease;
-        g_baRelease = []() { if (bws) { bws->release(); bws.reset(); } if (prevRelease) { auto f = prevRelease; prevRelease = nullptr; f(); } g_baTimer.destroy(); };
-    }
-    BatchWs& W = *bws;
+    BaBatchWs* bws = nullptr;
+    VS_CHECK(ba_thread().batch_ws(device, &bws));
+    BaBatchWs& W = *bws;
     hipStream_t stream = W.stream;
     g_baTimer.reset(); g_baTimer.stream = stream; g_baTimer.multi = true;
 
@@ -3239,12 +3028,8 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     // landing area: [control blocks][flags of all lanes][results of all lanes]
     const size_t oBackCtl = 0, oBackWrong = ((size_t)CTL_DOUBLES * 8 * NL + 255) & ~(size_t)255, oBackOut = oBackWrong + (wrongEnd - wrongBase);
     const size_t backBytes = oBackOut + (outEnd - outBase);
-    if (backBytes > W.backCap) {
-        VS_HIP(hipStreamSynchronize(stream));
-        if (W.h_back) hipHostFree(W.h_back);
-        W.backCap = 2 * backBytes + 4096;
-        VS_HIP(hipHostMalloc((void**)&W.h_back, W.backCap, hipHostMallocDefault));
-    }
+    VS_HIP(W.h_back.ensure(backBytes, grow_back(), [&] { return hipStreamSynchronize(stream); }));
+    uint8_t* const h_back = W.h_back.p;
     // ---- argument tables ------------------------------------------------------------------------------------------------
     for (int a = 0; a < NL; a++) {
         Lane& q = lanes[act[a]];
@@ -3257,8 +3042,8 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         q.d_Lg = o.Lg ? (double*)(dm + o.Lg) : nullptr; q.oWrong = oBackWrong + (o.wrong - wrongBase); q.oOut = oBackOut + (o.outPose - outBase);
         // the chi2 kernel writes its flags and the pass's final values STRAIGHT into the pinned landing area (device-addressable host
         // memory): no download copies behind it - each was a blit launch of its own that queued behind the groups' wide kernels
-        q.d_wrong = W.h_back + q.oWrong; q.d_outPose = (double*)(W.h_back + q.oOut);
-        q.d_outLm = (double*)(W.h_back + q.oOut + (o.outLm - o.outPose));
+        q.d_wrong = h_back + q.oWrong; q.d_outPose = (double*)(h_back + q.oOut);
+        q.d_outLm = (double*)(h_back + q.oOut + (o.outLm - o.outPose));
         BaDev D{};
         const int n = H.n, K = q.K, L = q.L;
         ba_fill_dev(D, H, A, BaLaneBufs{K, L, q.d_poseS, q.d_lmS, q.d_facJ, q.d_S, q.d_Sedge, q.d_dP, q.d_dL, q.d_sums, q.d_flags}, P->rig, NB, true, adaptive);
@@ -3266,7 +3051,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         D.spartStride = part_doubles(n) * lmBlocks; D.Spart = q.d_Spart;
         D.solveKind = ba_solve_kind(n, useMfma);
         D.Lg = q.d_Lg;
-        D.ctlHost = (double*)(W.h_back + oBackCtl) + (size_t)CTL_DOUBLES * a;
+        D.ctlHost = (double*)(h_back + oBackCtl) + (size_t)CTL_DOUBLES * a;
         *H.h_D = D;
         BaLaneAux X{};
         ba_fill_chi(X.C, P, BaPairArrays{A.dev(q.h_pairKf), A.dev(q.h_pairLm), A.dev(q.h_pairOct), A.dev(q.h_pairFlags), A.dev(q.h_pairUv), A.dev(q.h_kfLocal)},
@@ -3312,7 +3097,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         VS_HIP(hipGetLastError());
         return VSLAM_OK;
     };
-    double* const b_ctl = (double*)(W.h_back + oBackCtl);
+    double* const b_ctl = (double*)(h_back + oBackCtl);
     // The host's copy of the lanes' control blocks is written by the control steps themselves (BaDev::ctlHost).  It starts every pass as
     // the ARMED block, so that a poll can only ever see "not done" until a lane's own control step has said otherwise - a block left
     // over from the previous pass (BA_DONE) would end the pass before it began and leave the chi2 kernel with lanes it skips.
@@ -3386,7 +3171,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
         Lane& q = lanes[act[a]];
         const vslam_ba_problem* P = q.P;
         const BaPassHost& H = q.H;
-        memcpy(q.wrong.data(), W.h_back + q.oWrong, q.NP);
+        memcpy(q.wrong.data(), h_back + q.oWrong, q.NP);
         if (q.R->pair_wrong_pass1) memcpy(q.R->pair_wrong_pass1, q.wrong.data(), q.NP);
         H.second_pass(P, q.wrong.data(), 0, 1, q.T, nullptr, q.S2);
         q.pass2 = g_baMask != 0 && q.S2.same;
@@ -3412,9 +3197,9 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
     for (int a = 0; a < NL; a++) {
         Lane& q = lanes[act[a]];
         if (!q.pass2) continue;
-        const DPose* po = (const DPose*)(W.h_back + q.oOut);
-        const double* lo = (const double*)(W.h_back + q.oOut + (((size_t)q.K * sizeof(DPose) + 255) & ~(size_t)255));
-        ba_write_result(q.R, po, lo, W.h_back + q.oWrong, q.K, q.L, q.NP);
+        const DPose* po = (const DPose*)(h_back + q.oOut);
+        const double* lo = (const double*)(h_back + q.oOut + (((size_t)q.K * sizeof(DPose) + 255) & ~(size_t)255));
+        ba_write_result(q.R, po, lo, h_back + q.oWrong, q.K, q.L, q.NP);
     }
     BBS(8);
     for (int i : redo) VS_CHECK(ba_run(Ps[i], Rs[i], device, nullptr));
@@ -3424,20 +3209,7 @@ static vslam_status ba_run_batch(const vslam_ba_problem* const* Ps, vslam_ba_res
 namespace vslam {
 // VSLAM_BATCH_PHASES: where ba_run's wall time goes (averages per call; the marks do not synchronise, so "lm" holds the
 // polls of both LM loops, "chi2" the re-check + second-pass preparation + result fetch)
-void ba_host_profile_print() {
-#ifndef VSLAM_HOST_STAMPS
-    if (const long long nb = g_bbsCalls.load()) {
-        fprintf(stderr, "  vslam_local_ba_batch host sections (us per cohort, %lld cohorts, %.1f polls each):", nb, (double)g_bbsPolls.load() / (double)nb);
-        for (int i = 0; i < 12 && g_bbsName[i]; i++) fprintf(stderr, " %s %.1f |", g_bbsName[i], 1e-3 * (double)g_bbsNs[i].load() / (double)nb);
-        fprintf(stderr, "\n");
-    }
-    const long long n = g_bhsCalls.load();
-    if (!n) return;
-    fprintf(stderr, "  vslam_local_ba host sections (us per call, %lld calls):", n);
-    for (int i = 0; i < 16; i++) if (g_bhsName[i] || g_bhsNs[i].load()) fprintf(stderr, " %s %.1f |", g_bhsName[i] ? g_bhsName[i] : "other", 1e-3 * (double)g_bhsNs[i].load() / (double)n);
-    fprintf(stderr, "\n");
-#endif
-}
+void ba_host_profile_print() { BaMarks::print(); }
 }  // namespace vslam
 
 extern "C" {
