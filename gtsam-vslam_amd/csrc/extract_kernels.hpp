@@ -87,7 +87,7 @@ constexpr int SSC_NMAX_LDS = 16384;      // candidates of one level whose sort a
 constexpr int SSC_NMAX = 65535;          // ... the HBM instantiation (16-bit index field of the sort key)
 constexpr int SSC_PICKW_G = 2048;        // words of a probe's pick bitmask in the HBM instantiation (SSC_NMAX / 32)
 // LDS size classes of the LDS instantiation: a task holds its CU through LDS, so a level is given the smallest form it fits
-constexpr int SSC_NMAX_MID = 8704;       // two workgroups per CU (80 KB each, static LDS included)
+constexpr int SSC_NMAX_MID = 11008;      // two workgroups per CU (compact layout: one stopper array, sorted in place; ssc.hip)
 constexpr int SSC_NMAX_SMALL = 6144;     // the 67 KB form, two workgroups per CU
 constexpr int SSC_NMAX_TINY = 3072;      // the 34 KB form, four workgroups per CU
 // the instantiation k_ssc<M> that takes a level of n candidates: 0 = LDS, 16 384; 1 = HBM scratch; 2 = LDS, 6 144;

@@ -68,7 +68,7 @@ struct vslam_extractor {
     int* d_counts = nullptr;
     int sscHigh[vslam::MAX_LEVELS] = {0}, sscKmin[vslam::MAX_LEVELS] = {0}, sscKmax[vslam::MAX_LEVELS] = {0};
     bool sscForceGlobal = false;      // VSLAM_SSC_FORCE_GLOBAL=1 (tests): every level through the HBM instantiation
-    int sscClasses = 3;               // VSLAM_SSC_CLASSES (measurements): bit 0 = the 8 704 class, bit 1 = the 3 072 class; 0 = neither
+    int sscClasses = 3;               // VSLAM_SSC_CLASSES (measurements): bit 0 = the SSC_NMAX_MID class, bit 1 = the 3 072 class; 0 = neither
     bool countsPending = false;
     vslam_status wait_counts();      // completes a run on the host side (keypoint totals, error flags)
     vslam_status enqueue_ssc();

@@ -20,10 +20,12 @@
 //
 // Five instantiations of the same code (SscCfg below; 512-thread tasks): k_ssc<0> keeps the sort arrays of a level in LDS (<= 16 384 candidates:
 // every level of the 752x480 / 1241x376 rigs and of a 1920x1200 frame); k_ssc<3>, <2>, <4> are the same form with the LDS of
-// a level of at most 8 704 / 6 144 / 3 072 candidates (two, two and four tasks per CU); k_ssc<1> keeps the arrays in HBM
+// a level of at most SSC_NMAX_MID / 6 144 / 3 072 candidates (two, two and four tasks per CU; <3> in the compact layout: one capped
+// stopper array, ssc_stoppers.hpp, and the sorted candidates in the sort keys' place); k_ssc<1> keeps the arrays in HBM
 // scratch (up to 65 535 candidates per level, the width of the index field).  Each (image, level) task is taken by exactly
 // one of them (ssc_class); the others return at once.  There is no host path.
 #include "extract_kernels.hpp"
+#include "ssc_stoppers.hpp"
 #include <mutex>
 
 namespace vslam {
@@ -38,23 +40,30 @@ constexpr int SSC_LONGMAX = 64;                         // segment-list entries 
 // _MID / _TINY: a fraction of the LDS and <= 64 VGPRs, so that two / two / four tasks share a CU - the tasks are latency-bound chains).
 // SEGMAX: entries of one segment list.  The segments of a tree level are disjoint and longer than 16, so at most NMAX / 17 exist at
 // once, beside the SSC_LONGMAX reserved entries (ssc_lds_ok).  ARENA: words of cover-grid bits, an eighth per speculating wave.
+// COMPACT: the two stopper lists share ONE u16 array with a slot per element (ssc_stoppers.hpp), the sorted candidates replace the
+// sort keys in place, and the arena is that stopper array and the segment words: 1.5 NMAX words + the lists instead of 2 NMAX.
 template <int M> struct SscCfg;
-template <> struct SscCfg<0> { static constexpr int NMAX = SSC_NMAX_LDS, SEGMAX = 1088, PICKW = SSC_NMAX_LDS / 32, ARENA = SSC_ARENA_WORDS; };
-template <> struct SscCfg<1> { static constexpr int NMAX = SSC_NMAX, SEGMAX = 4096, PICKW = SSC_PICKW_G, ARENA = SSC_ARENA_WORDS; };
-template <> struct SscCfg<2> { static constexpr int NMAX = SSC_NMAX_SMALL, SEGMAX = 1088, PICKW = SSC_NMAX_SMALL / 32, ARENA = 10 * 1024; };
-template <> struct SscCfg<3> { static constexpr int NMAX = SSC_NMAX_MID, SEGMAX = 576, PICKW = SSC_NMAX_MID / 32, ARENA = 10 * 1024; };
-template <> struct SscCfg<4> { static constexpr int NMAX = SSC_NMAX_TINY, SEGMAX = 256, PICKW = SSC_NMAX_TINY / 32, ARENA = 4 * 1024; };
-// words behind the two sort arrays of an LDS instantiation: the two segment lists, and after the sort the [SSC_NW][256] histogram
+template <> struct SscCfg<0> { static constexpr int NMAX = SSC_NMAX_LDS, SEGMAX = 1088, PICKW = SSC_NMAX_LDS / 32, ARENA = SSC_ARENA_WORDS; static constexpr bool COMPACT = false; };
+template <> struct SscCfg<1> { static constexpr int NMAX = SSC_NMAX, SEGMAX = 4096, PICKW = SSC_PICKW_G, ARENA = SSC_ARENA_WORDS; static constexpr bool COMPACT = false; };
+template <> struct SscCfg<2> { static constexpr int NMAX = SSC_NMAX_SMALL, SEGMAX = 1088, PICKW = SSC_NMAX_SMALL / 32, ARENA = 10 * 1024; static constexpr bool COMPACT = false; };
+template <> struct SscCfg<3> { static constexpr int NMAX = SSC_NMAX_MID, SEGMAX = (SSC_LONGMAX + SSC_NMAX_MID / 17 + 7) & ~7, PICKW = SSC_NMAX_MID / 32, ARENA = SSC_NMAX_MID / 2 + 4 * SEGMAX; static constexpr bool COMPACT = true; };
+template <> struct SscCfg<4> { static constexpr int NMAX = SSC_NMAX_TINY, SEGMAX = 256, PICKW = SSC_NMAX_TINY / 32, ARENA = 4 * 1024; static constexpr bool COMPACT = false; };
+// words behind the sort arrays of an LDS instantiation: the two segment lists, and after the sort the [SSC_NW][256] histogram
 template <int M> constexpr int ssc_seg_words() { return 4 * SscCfg<M>::SEGMAX > SSC_NW * 256 ? 4 * SscCfg<M>::SEGMAX : SSC_NW * 256; }
+// words of the sort arrays: sort keys and the stopper lists (two u16 lists of NMAX entries, or the compact form's one)
+template <int M> constexpr int ssc_sort_words() { return SscCfg<M>::COMPACT ? SscCfg<M>::NMAX + SscCfg<M>::NMAX / 2 : 2 * SscCfg<M>::NMAX; }
 template <int M> constexpr size_t ssc_lds_bytes() {
-    return M == 1 ? ((size_t)4 * SscCfg<M>::SEGMAX + (size_t)SscCfg<M>::ARENA) * 4 : ((size_t)2 * SscCfg<M>::NMAX + (size_t)ssc_seg_words<M>()) * 4;
+    return M == 1 ? ((size_t)4 * SscCfg<M>::SEGMAX + (size_t)SscCfg<M>::ARENA) * 4 : ((size_t)ssc_sort_words<M>() + (size_t)ssc_seg_words<M>()) * 4;
 }
 template <int M> struct SscCheck {
     using C = SscCfg<M>;
     static_assert(C::SEGMAX - SSC_LONGMAX >= C::NMAX / 17, "every short segment of a tree level needs a list entry");
     static_assert(C::PICKW * 32 >= ((C::NMAX + 63) & ~63), "a probe's pick words cover whole 64-candidate steps");
     static_assert(C::ARENA % SSC_NPROBE == 0 && (M == 1 || C::ARENA / SSC_NPROBE > C::PICKW), "a probing wave's slice holds its pick words and a grid");
-    static_assert(M == 1 || C::NMAX + ssc_seg_words<M>() >= C::ARENA, "arena must fit a | seg");
+    static_assert(M == 1 || C::COMPACT || C::NMAX + ssc_seg_words<M>() >= C::ARENA, "arena must fit a | seg");
+    static_assert(!C::COMPACT || (C::NMAX % 2 == 0 && C::NMAX / 2 + ssc_seg_words<M>() >= C::ARENA), "compact: arena must fit stoppers | seg");
+    static_assert(ssc_seg_words<M>() >= SSC_NW * 256, "the counting sort's histogram lies in the segment words");
+    static_assert(C::NMAX <= 65536, "stopper entries and candidate indices are u16");
     static constexpr bool ok = true;
 };
 static_assert(SscCheck<0>::ok && SscCheck<1>::ok && SscCheck<2>::ok && SscCheck<3>::ok && SscCheck<4>::ok, "k_ssc classes");
@@ -220,7 +229,8 @@ __device__ __forceinline__ int ssc_sel_lo(unsigned long long m, int k) {
 // partner of an exchange found through the stopper lists, one bpermute).  Same permutation as the array paths below.
 // A sub-segment that reaches depth 0 while still longer than 16 ends the register walk: the values go back to the
 // array and every unfinished sub-segment is pushed to the next level's list (depth 0 -> heap sort there).
-template <bool G>
+// CP: Lp == Rp is the compact stopper array (ssc_stoppers.hpp), the slice of sub-segment [lo, hi) its own hi - lo slots.
+template <bool G, bool CP>
 __device__ __forceinline__ void ssc_small_segment(uint32_t* a, int f, int e, int depth, uint16_t* Lp, uint16_t* Rp,
                                                   uint32_t* segN, int* cntN, int segMax, int* sFail) {
     const int lane = threadIdx.x & 63, m = e - f;
@@ -255,18 +265,20 @@ __device__ __forceinline__ void ssc_small_segment(uint32_t* a, int f, int e, int
         const int kR = lane == 63 ? 0 : __popcll(mR >> (lane + 1));
         // stopper positions by rank, in the segment's own slice of the stopper lists (left stoppers ascending, right
         // stoppers from the top): the partner of the k-th left stopper is the k-th right stopper from the top
-        if (isL) Lp[f + lo + kL] = (uint16_t)lane;
-        if (isR) Rp[f + lo + kR] = (uint16_t)lane;
+        const int cap = CP ? ssc_stop_cap(lo, hi) : 0;      // (compact: ranks >= cap are not stored and read as crossed)
+        const int iL = CP ? ssc_stop_left(f + lo, kL) : f + lo + kL, iR = CP ? ssc_stop_right(f + hi, kR) : f + lo + kR;
+        if (isL && (!CP || kL < cap)) Lp[iL] = (uint16_t)lane;
+        if (isR && (!CP || kR < cap)) Rp[iR] = (uint16_t)lane;
         ssc_fence<G>();
         int src = lane;
         bool asL = false;
-        if (isL && kL < nR) { const int p = Rp[f + lo + kL]; if (lane < p) { src = p; asL = true; } }
-        if (!asL && isR && kR < nL) { const int p = Lp[f + lo + kR]; if (p < lane) src = p; }
+        if (isL && kL < nR && (!CP || kL < cap)) { const int p = Rp[CP ? ssc_stop_right(f + hi, kL) : f + lo + kL]; if (lane < p) { src = p; asL = true; } }
+        if (!asL && isR && kR < nL && (!CP || kR < cap)) { const int p = Lp[CP ? ssc_stop_left(f + lo, kR) : f + lo + kR]; if (p < lane) src = p; }
         const int K = __popcll(__ballot(asL) & segmask);
         v = __shfl(v, src);
         if (act) {
-            int cut = K >= 1 ? (int)Rp[f + lo + K - 1] : hi;
-            if (K < nL) cut = min(cut, (int)Lp[f + lo + K]);
+            int cut = K >= 1 ? (int)Rp[CP ? ssc_stop_right(f + hi, K - 1) : f + lo + K - 1] : hi;
+            if (CP ? ssc_stop_has_left(K, nL, cap) : K < nL) cut = min(cut, (int)Lp[CP ? ssc_stop_left(f + lo, K) : f + lo + K]);
             d--;
             if (lane < cut) hi = cut; else lo = cut;
         }
@@ -288,7 +300,8 @@ __device__ __forceinline__ void ssc_median_to_first(uint32_t* a, int f, int e) {
 
 // One introsort step (__unguarded_partition_pivot) of segment [f, e) by the WHOLE workgroup; every thread calls it.
 // sW: 2 * SSC_NW + 2 ints of LDS.
-template <bool G>
+// CP: Lp == Rp is the compact stopper array, the segment's slice its own e - f slots (ssc_stoppers.hpp).
+template <bool G, bool CP>
 __device__ __forceinline__ void ssc_partition_coop(uint32_t* a, uint16_t* Lp, uint16_t* Rp, int f, int e, int depth, int* sW,
                                                    uint32_t* segN, int* cntN, int segMax, int* sFail) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -315,32 +328,39 @@ __device__ __forceinline__ void ssc_partition_coop(uint32_t* a, uint16_t* Lp, ui
         nL += l; nR += r;
     }
     const unsigned long long lt = (1ull << lane) - 1ull;
+    const int cap = CP ? ssc_stop_cap(f, e) : 0;
     for (int base = c0; base < c1; base += 64) {
         const int x = base + lane;
         const bool v = x < c1;
         const uint32_t kx = v ? (a[x] >> 16) : 0u;
         const bool isL = v && kx >= pk, isR = v && kx <= pk;
         const unsigned long long bl = __ballot(isL), br = __ballot(isR);
-        if (isL) Lp[f + 1 + offL + __popcll(bl & lt)] = (uint16_t)x;
-        if (isR) Rp[f + 1 + offR + __popcll(br & lt)] = (uint16_t)x;
+        if (CP) {                                        // ranks: left from the bottom, right from the top, below the cap only
+            const int rl = offL + __popcll(bl & lt), rr = nR - 1 - (offR + __popcll(br & lt));
+            if (isL && rl < cap) Lp[ssc_stop_left(f, rl)] = (uint16_t)x;
+            if (isR && rr < cap) Rp[ssc_stop_right(e, rr)] = (uint16_t)x;
+        } else {
+            if (isL) Lp[f + 1 + offL + __popcll(bl & lt)] = (uint16_t)x;
+            if (isR) Rp[f + 1 + offR + __popcll(br & lt)] = (uint16_t)x;
+        }
         offL += __popcll(bl); offR += __popcll(br);
     }
-    const int nPair = min(nL, nR);
+    const int nPair = CP ? ssc_stop_pairs(nL, nR, cap) : min(nL, nR);
     if (tid == 0) sW[2 * SSC_NW] = nPair;
     ssc_fence<G>();
     __syncthreads();
     // K = number of leading pairs that have not crossed (monotone: the first failure ends the run)
     for (int k = tid; k < nPair; k += SSC_NT)
-        if (!(Lp[f + 1 + k] < Rp[f + 1 + nR - 1 - k])) { atomicMin(&sW[2 * SSC_NW], k); break; }
+        if (!(Lp[CP ? ssc_stop_left(f, k) : f + 1 + k] < Rp[CP ? ssc_stop_right(e, k) : f + 1 + nR - 1 - k])) { atomicMin(&sW[2 * SSC_NW], k); break; }
     __syncthreads();
     const int K = sW[2 * SSC_NW];
     for (int k = tid; k < K; k += SSC_NT) {
-        const int xl = Lp[f + 1 + k], xr = Rp[f + 1 + nR - 1 - k];
+        const int xl = Lp[CP ? ssc_stop_left(f, k) : f + 1 + k], xr = Rp[CP ? ssc_stop_right(e, k) : f + 1 + nR - 1 - k];
         const uint32_t t = a[xl]; a[xl] = a[xr]; a[xr] = t;
     }
     if (tid == 0) {
-        int cut = K >= 1 ? (int)Rp[f + 1 + nR - K] : e;
-        if (K < nL) cut = min(cut, (int)Lp[f + 1 + K]);
+        int cut = K >= 1 ? (int)Rp[CP ? ssc_stop_right(e, K - 1) : f + 1 + nR - K] : e;
+        if (CP ? ssc_stop_has_left(K, nL, cap) : K < nL) cut = min(cut, (int)Lp[CP ? ssc_stop_left(f, K) : f + 1 + K]);
         // __introsort_loop(cut, last, depth - 1); last = cut
         if (e - cut > 16) ssc_push(segN, cntN, segMax, cut, e, depth - 1, sFail);
         if (cut - f > 16) ssc_push(segN, cntN, segMax, f, cut, depth - 1, sFail);
@@ -352,10 +372,12 @@ __device__ __forceinline__ void ssc_partition_coop(uint32_t* a, uint16_t* Lp, ui
 template <int M>
 __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     using C = SscCfg<M>;
-    constexpr bool G = M == 1;
+    constexpr bool G = M == 1, CP = C::COMPACT;
     extern __shared__ uint32_t lds[];
     // LDS instantiations: [sorted = Lp | Rp : NMAX u32] [a : NMAX u32] [seg : 2 x SEGMAX x 2 u32, at least SSC_NW x 256]; after the
     //                     sort the cover-grid arena reuses a | seg (ARENA words), the counting-sort histogram the seg lists (8 KB)
+    // compact form:       [a, then sorted : NMAX u32] [stoppers : NMAX u16] [seg]; the counting sort leaves the order as u16 candidate
+    //                     indices in the stopper array and expands them over a; the arena reuses stoppers | seg
     // HBM instantiation:  [seg : 2 x SEGMAX x 2 u32] [arena]; a / sorted live in the task's HBM scratch
     const int img = blockIdx.x % A.nimg, l = blockIdx.x / A.nimg;
     const int task = img * A.nLevels + l;
@@ -365,10 +387,10 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     const int n = lc[l];
     if (ssc_class(n, A.forceGlobal, A.classes) != M) return;                              // another instantiation's task
     uint32_t* sortedU = G ? A.sortedG + (size_t)img * A.candCap + coff : lds;
-    uint32_t* a = G ? A.aG + (size_t)img * A.candCap + coff : lds + C::NMAX;
-    uint16_t* Lp = (uint16_t*)sortedU;
-    uint16_t* Rp = Lp + (G ? n : C::NMAX);
-    uint32_t* seg = G ? lds : lds + 2 * C::NMAX;
+    uint32_t* a = G ? A.aG + (size_t)img * A.candCap + coff : (CP ? lds : lds + C::NMAX);
+    uint16_t* Lp = CP ? (uint16_t*)(lds + C::NMAX) : (uint16_t*)sortedU;
+    uint16_t* Rp = CP ? Lp : Lp + (G ? n : C::NMAX);
+    uint32_t* seg = G ? lds : lds + ssc_sort_words<M>();
     uint32_t* arena = G ? lds + 4 * C::SEGMAX : lds + C::NMAX;
     int* h2 = G ? (int*)arena : (int*)seg;               // [SSC_NW][256]
     __shared__ int hist[256], sCnt[4], sFail, sW[2 * SSC_NW + 2];      // sCnt[list]: short segments, sCnt[2 + list]: long ones
@@ -420,19 +442,59 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         for (int s = 0; s < nlong; s++) {
             const int f = (int)(segL[2 * s] & 0xffffu), e = (int)(segL[2 * s] >> 16), depth = (int)segL[2 * s + 1];
             if (depth == 0) { if (tid == 0) ssc_heapsort<G>(a + f, e - f); continue; }
-            ssc_partition_coop<G>(a, Lp, Rp, f, e, depth, sW, segN, cntN, C::SEGMAX, &sFail);
+            ssc_partition_coop<G, CP>(a, Lp, Rp, f, e, depth, sW, segN, cntN, C::SEGMAX, &sFail);
         }
         for (int s = wave; s < nseg; s += SSC_NW) {
             const uint32_t sfe = (uint32_t)__builtin_amdgcn_readfirstlane((int)segC[2 * s]);          // (LDS words read at a uniform address)
             const int f = (int)(sfe & 0xffffu), e = (int)(sfe >> 16), depth = __builtin_amdgcn_readfirstlane((int)segC[2 * s + 1]);
             if (depth == 0) { if (lane == 0) ssc_heapsort<G>(a + f, e - f); continue; }      // libstdc++ switches to heapsort here
             if (e - f <= 64) {                            // the whole subtree of a short segment, in registers
-                ssc_small_segment<G>(a, f, e, depth, Lp, Rp, segN, cntN, C::SEGMAX, &sFail);
+                ssc_small_segment<G, CP>(a, f, e, depth, Lp, Rp, segN, cntN, C::SEGMAX, &sFail);
                 continue;
             }
             if (lane == 0) ssc_median_to_first(a, f, e);
             ssc_fence<G>();
             const uint32_t pk = a[f] >> 16;
+            if constexpr (CP) {
+                // the same partition on the compact stopper array (ssc_stoppers.hpp): the left stoppers are ranked by a scan from the
+                // left, the right stoppers by a scan from the right, each stored below the cap only; once both lists have reached the
+                // cap nothing further can be stored or asked for
+                const int cap = ssc_stop_cap(f, e);
+                const unsigned long long lt = (1ull << lane) - 1ull;
+                int nL = 0, nR = 0;
+                for (int base = 0; base < e - f - 1; base += 64) {
+                    const int xl = f + 1 + base + lane, xr = e - 1 - base - lane;
+                    const bool isL = xl < e && (a[xl] >> 16) >= pk, isR = xr > f && (a[xr] >> 16) <= pk;
+                    const unsigned long long bl = __ballot(isL), br = __ballot(isR);
+                    const int rl = nL + __popcll(bl & lt), rr = nR + __popcll(br & lt);
+                    if (isL && rl < cap) Lp[ssc_stop_left(f, rl)] = (uint16_t)xl;
+                    if (isR && rr < cap) Lp[ssc_stop_right(e, rr)] = (uint16_t)xr;
+                    nL += __popcll(bl); nR += __popcll(br);
+                    if (nL >= cap && nR >= cap) break;
+                }
+                ssc_fence<G>();
+                const int nPair = ssc_stop_pairs(nL, nR, cap);
+                int K = 0;
+                for (int base = 0; base < nPair; base += 64) {
+                    const int k = base + lane;
+                    const bool ok = k < nPair && Lp[ssc_stop_left(f, k)] < Lp[ssc_stop_right(e, k)];
+                    const unsigned long long bo = __ballot(ok);
+                    K += __popcll(bo);
+                    if (bo != ~0ull) break;
+                }
+                for (int k = lane; k < K; k += 64) {
+                    const int xl = Lp[ssc_stop_left(f, k)], xr = Lp[ssc_stop_right(e, k)];
+                    const uint32_t t = a[xl]; a[xl] = a[xr]; a[xr] = t;
+                }
+                ssc_fence<G>();
+                int cut = K >= 1 ? (int)Lp[ssc_stop_right(e, K - 1)] : e;
+                if (ssc_stop_has_left(K, nL, cap)) cut = min(cut, (int)Lp[ssc_stop_left(f, K)]);
+                if (lane == 0) {
+                    if (e - cut > 16) ssc_push(segN, cntN, C::SEGMAX, cut, e, depth - 1, &sFail);
+                    if (cut - f > 16) ssc_push(segN, cntN, C::SEGMAX, f, cut, depth - 1, &sFail);
+                }
+                continue;
+            }
             // __unguarded_partition(f+1, e, pivot): stoppers from the left (>= pivot) / from the right (<= pivot)
             int nL = 0, nR = 0;
             for (int base = f + 1; base < e; base += 64) {
@@ -518,7 +580,8 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
             same &= __ballot(v);
             if (v) {
                 const int rank = __popcll(same & ((1ull << lane) - 1ull));
-                sortedU[n - 1 - (off[key] + rank)] = cand[e & 0xffffu];
+                if (CP) Lp[n - 1 - (off[key] + rank)] = (uint16_t)(e & 0xffffu);      // (a is still being read: the order first)
+                else sortedU[n - 1 - (off[key] + rank)] = cand[e & 0xffffu];
             }
             ssc_lds_fence();
             if (v && (same >> lane) == 1ull) off[key] += __popcll(same);      // the highest lane of each key group
@@ -527,6 +590,11 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
     }
     ssc_fence<G>();
     __syncthreads();
+    if constexpr (CP) {                                  // the sort keys are done with: the candidates in sorted order, over them
+        for (int i = tid; i < n; i += SSC_NT) sortedU[i] = cand[Lp[i]];
+        ssc_fence<G>();
+        __syncthreads();
+    }
     SSC_STAMP(1);
     const uint32_t* sc = sortedU;                        // candidates in response order (descending, reference tie order)
 
@@ -649,7 +717,7 @@ __global__ __launch_bounds__(SSC_NT, 4) void k_ssc(SscArgs A) {
         if (wave == 0) {                                 // exclusive prefix of the per-word pick counts
             int run = 0;
             for (int base = 0; base < nWords; base += 64) {
-                const bool in = base + lane < C::PICKW;      // (PICKW of the 8 704 / 3 072 classes is no multiple of 64)
+                const bool in = base + lane < C::PICKW;      // (PICKW of the SSC_NMAX_MID / 3 072 classes is no multiple of 64)
                 const int v = in ? pre[base + lane] : 0;
                 int incl = v;
 #pragma unroll
