@@ -192,6 +192,12 @@ struct vslam_batch {
     // correct: vslam_batch_correct_loop (kfLoop [B], T_wc_corrected [B][16]); else vslam_batch_close_loop (both null)
     vslam_status loop(bool correct, const uint8_t* mask, const int32_t* kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm,
                       vslam_loop_report* reps);
+    // what fuse_loop and global_ba refuse, in the order of loop(): the arguments and an IMU batch, (the parameters,) then any masked
+    // lane's loop_check with the lane in the message; nothing has changed when one fails.  *nOn: masked lanes
+    vslam_status followup_check_args(const char* fn, const uint8_t* mask, const void* reps) const;
+    vslam_status followup_check_lanes(const char* fn, const uint8_t* mask, int* nOn) const;
+    vslam_status fuse_loop(const uint8_t* mask, const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* reps);
+    vslam_status global_ba(const uint8_t* mask, const vslam_system_gba_params* prm, vslam_system_gba_report* reps);
     std::vector<uint8_t> rqDescs; std::vector<int> rqStart, rqBest;
     vslam_status step(const uint8_t* const* L, const uint8_t* const* R, int stride, int channels, bool onDevice, const int* frames,
                       const vslam_imu_bucket* imu, const uint8_t* mask, double* T_wc_out, vslam_frame_report* reps,
@@ -1110,6 +1116,111 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
     return VSLAM_OK;
 }
 
+vslam_status vslam_batch::followup_check_args(const char* fn, const uint8_t* mask, const void* reps) const {
+    if (!mask || !reps) { set_error("%s: invalid arguments", fn); return VSLAM_ERR_INVALID; }
+    if (useImu) { set_error("%s: an IMU batch cannot close loops yet (its velocity and gravity frame would have to follow)", fn); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
+vslam_status vslam_batch::followup_check_lanes(const char* fn, const uint8_t* mask, int* nOn) const {
+    char who[96];
+    *nOn = 0;
+    for (int b = 0; b < B; b++) {
+        if (!mask[b]) continue;
+        (*nOn)++;
+        snprintf(who, sizeof who, "%s: lane %d", fn, b);
+        VS_CHECK(sys[b]->loop_check(who));
+    }
+    return VSLAM_OK;
+}
+
+// The duplicate map points of the masked lanes, between two steps: per lane what vslam_system::fuse_loop does to a session, with ONE
+// vslam_fuse_search_batch call for all lanes that reach the search.  Every lane's map is locked from its sets to its commit.  Refusals
+// come first and change nothing in any lane; a busy lane reports busy and is untouched.
+vslam_status vslam_batch::fuse_loop(const uint8_t* mask, const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* reps) {
+    static const char* const fn = "vslam_batch_fuse_loop";
+    int nOn = 0;
+    VS_CHECK(followup_check_args(fn, mask, reps));
+    vslam_fuse_loop_params P;
+    if (!resolve_fuse_loop_params(fn, prm, P)) return VSLAM_ERR_INVALID;
+    VS_CHECK(followup_check_lanes(fn, mask, &nOn));
+    if (!nOn) return VSLAM_OK;
+    VS_HIP(hipSetDevice(device));
+    std::vector<int> run;
+    for (int b = 0; b < B; b++) {
+        if (!mask[b]) continue;
+        reps[b] = vslam_fuse_loop_report{};
+        if (sys[b]->loop_busy()) { reps[b].busy = 1; continue; }
+        run.push_back(b);
+    }
+    const int nr = (int)run.size();
+    if (!nr) return VSLAM_OK;
+    std::vector<vslam_system::FuseSets> F((size_t)nr);
+    std::vector<vslam_fuse_lane> lanes((size_t)nr);
+    std::vector<vslam_fuse_report> sr((size_t)nr);
+    std::vector<std::unique_lock<std::mutex>> locks;           // every lane's map stays as its sets saw it until its commit
+    for (int i = 0; i < nr; i++) {
+        vslam_system* s = sys[run[i]];
+        locks.emplace_back(s->mapMutex);
+        VS_CHECK(s->fuse_sets(P, &reps[run[i]], F[i]));
+        lanes[i] = F[i].lane;
+    }
+    VS_CHECK(vslam_fuse_search_batch(lanes.data(), nr, &P.search, device, sr.data()));
+    for (int i = 0; i < nr; i++) {
+        reps[run[i]].search = sr[i];
+        sys[run[i]]->fuse_commit(F[i], &reps[run[i]]);
+    }
+    return VSLAM_OK;
+}
+
+// One global bundle adjustment per masked lane, between two steps: per lane what vslam_system::global_ba does to a session, with ONE
+// vslam_global_ba_batch call for all lanes that reach the solve (their factorisations' dependency chains run side by side).  Every
+// lane's map is locked from its flattening to its commit.  Refusals come first and change nothing in any lane - a refusal of the
+// batched solve for any lane (a free gauge, a point behind its keyframe) included: it is returned as it is.
+vslam_status vslam_batch::global_ba(const uint8_t* mask, const vslam_system_gba_params* prm, vslam_system_gba_report* reps) {
+    static const char* const fn = "vslam_batch_global_ba";
+    int nOn = 0;
+    VS_CHECK(followup_check_args(fn, mask, reps));
+    vslam_system_gba_params P;
+    if (!resolve_system_gba_params(fn, prm, P)) return VSLAM_ERR_INVALID;
+    VS_CHECK(followup_check_lanes(fn, mask, &nOn));
+    if (!nOn) return VSLAM_OK;
+    VS_HIP(hipSetDevice(device));
+    std::vector<int> run;
+    for (int b = 0; b < B; b++) {
+        if (!mask[b]) continue;
+        reps[b] = vslam_system_gba_report{};
+        if (sys[b]->loop_busy()) { reps[b].busy = 1; continue; }
+        if (sys[b]->keyFrames.size() < 2) continue;
+        run.push_back(b);
+    }
+    const int nr = (int)run.size();
+    if (!nr) return VSLAM_OK;
+    std::vector<vslam_system::GbaFlat> F((size_t)nr);
+    std::vector<vslam_gba_result> R((size_t)nr);
+    std::vector<vslam_gba_lane> lanes((size_t)nr);
+    {
+        std::vector<std::unique_lock<std::mutex>> locks;       // every lane's map stays as its problem saw it until its commit
+        for (int i = 0; i < nr; i++) {
+            vslam_system* s = sys[run[i]];
+            vslam_system_gba_report& r = reps[run[i]];
+            locks.emplace_back(s->mapMutex);
+            VS_CHECK(s->gba_flatten(P.edge_weight, F[i]));
+            r.n_keyframes = F[i].P.n_kf; r.n_landmarks = F[i].P.n_lm; r.n_pairs = F[i].P.n_pairs; r.n_edges = (int)F[i].edges.size();
+            R[i] = vslam_gba_result{};
+            R[i].kf_pose_wc = F[i].kfOut.data(); R[i].lm_xyz = F[i].lmOut.data(); R[i].pair_wrong = F[i].wrong.data();
+            lanes[i] = vslam_gba_lane{&F[i].P, F[i].edges.empty() ? nullptr : F[i].edges.data(), (int32_t)F[i].edges.size(), &R[i]};
+        }
+        VS_CHECK(vslam_global_ba_batch(lanes.data(), nr, &P.gba, device));
+        for (int i = 0; i < nr; i++) {
+            reps[run[i]].gba = R[i].report;
+            VS_CHECK(sys[run[i]]->gba_finish(F[i], &reps[run[i]]));
+        }
+    }
+    for (int i = 0; i < nr; i++) VS_CHECK(sys[run[i]]->gba_activate(&reps[run[i]]));
+    return VSLAM_OK;
+}
+
 // Ends a lane's session and starts a new one in its place, between two steps, on the thread that drives the group.  Nothing on the
 // device is allocated or freed (a device free waits for every group's kernels, and a service whose lanes restart for ever is the steady
 // state): the new session takes over the old one's matcher - same extractor images, stream and result-block slices; its rig and
@@ -1183,6 +1294,16 @@ vslam_status vslam_batch_correct_loop(vslam_batch* b, const uint8_t* lane_mask, 
 vslam_status vslam_batch_close_loop(vslam_batch* b, const uint8_t* lane_mask, const vslam_loop_params* params, vslam_loop_report* reports) {
     if (!b) return VSLAM_ERR_INVALID;
     return b->loop(false, lane_mask, nullptr, nullptr, params, reports);
+}
+
+vslam_status vslam_batch_fuse_loop(vslam_batch* b, const uint8_t* lane_mask, const vslam_fuse_loop_params* params, vslam_fuse_loop_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->fuse_loop(lane_mask, params, reports);
+}
+
+vslam_status vslam_batch_global_ba(vslam_batch* b, const uint8_t* lane_mask, const vslam_system_gba_params* params, vslam_system_gba_report* reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    return b->global_ba(lane_mask, params, reports);
 }
 
 vslam_status vslam_batch_relocalize_imu(vslam_batch* b, const uint8_t* const* left, const uint8_t* const* right, int32_t stride, int32_t on_device,

@@ -17,253 +17,76 @@
 //                         (pgo_lm_decide) on a device control block
 //   k_gba_chi2            a thread per pair: the outlier flags at the final values
 // The host waits once per trial, for one int.
+// vslam_global_ba_batch runs several problems (lanes) at once: every stage has a k_gba_*_b kernel
+// with the lane as a grid dimension, the reduce is one workgroup per lane (k_gba_reduce_b) and the rule one thread per lane
+// (k_gba_decide_b); the host waits once per ROUND (one trial of every active lane).  The bodies of all kernels are in
+// gba_dev.hpp, one function per stage on ONE problem's arrays, called by k_gba_* and k_gba_*_b alike: a lane's bytes are the
+// single call's.  The lane table is packed by gba_pack_host.hpp (no HIP).
 #include "common.hpp"
 #include "dmath.hpp"
 #include "pgo_dev.hpp"
 #include "gba_host.hpp"
+#include "gba_pack_host.hpp"
+#include "gba_dev.hpp"
 #include <cmath>
 
 using namespace vslam;
 
 namespace {
 
-struct GbaCam { double fx, fy, cx, cy, bl; };
-
-// One projection factor: q = R^T (X - t); the right camera sees q - (bl, 0, 0).  r = (projection - measurement) * is.
-// Jp [2][6]: d r / d (a, b) of the pose retraction T [Exp(a), b];  Jl [2][3]: d r / d X.  Returns z > 0.
-template <bool JAC>
-__device__ __forceinline__ bool gba_factor(const double* __restrict__ T, const double* __restrict__ X, const GbaCam& cam, int right,
-                                           double u, double v, double is, double* r, double* Jp, double* Jl) {
-    double R[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = T[k];
-    const double d[3] = {X[0] - T[9], X[1] - T[10], X[2] - T[11]};
-    double q[3];
-    mat3T_vec(R, d, q);
-    const double x = q[0], y = q[1], z = q[2];
-    if (!(z > 0.0)) return false;
-    const double iz = 1.0 / z;
-    const double xx = right ? x - cam.bl : x;
-    r[0] = (cam.fx * xx * iz + cam.cx - u) * is;
-    r[1] = (cam.fy * y * iz + cam.cy - v) * is;
-    if (JAC) {
-        const double al[2][3] = {{cam.fx * iz, 0.0, -cam.fx * xx * iz * iz}, {0.0, cam.fy * iz, -cam.fy * y * iz * iz}};
-        const double S[3][3] = {{0.0, -z, y}, {z, 0.0, -x}, {-y, x, 0.0}};
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                Jp[6 * a + c] = (al[a][0] * S[0][c] + al[a][1] * S[1][c] + al[a][2] * S[2][c]) * is;
-                Jp[6 * a + 3 + c] = -al[a][c] * is;
-                Jl[3 * a + c] = (al[a][0] * R[3 * c] + al[a][1] * R[3 * c + 1] + al[a][2] * R[3 * c + 2]) * is;
-            }
-    }
-    return true;
-}
-
-// the problem's arrays on the device (read-only for the kernels) and the sizes
-struct GbaDev {
-    int K, L, P, M, nf, b, nBlk;
-    GbaCam cam;
-    const PgoEdge* edges;
-    const int* pos;                 // [K]
-    const int* rowStart; const int* inc;
-    const int* pairKf; const int* pairLm; const uint8_t* pairFlags;
-    const float* pairUv;            // [P][4]
-    const double* pairIs;           // [P][2]  whitening factor of the left / right factor
-    const double* pairThr;          // [P][2]  chi2 threshold
-    const uint8_t* kfLocal; const uint8_t* lmPresent;
-    const int* lmStart; const int* lmPairs;
-    const int* blkC; const int* blkD; const int* blkStart; const int* list;
-};
-
-// slot t = 2 p + side.  A slot without a factor (or on a thin landmark) holds zeros and a zero cost term.
+// ---- the kernels of vslam_global_ba: one problem, the bodies of gba_dev.hpp on the call's arrays
 __global__ __launch_bounds__(256) void k_gba_linearize(GbaDev D, const PgoCtl* __restrict__ ctl, int init, const double* __restrict__ P0,
                                                        const double* __restrict__ P1, const double* __restrict__ L0,
                                                        const double* __restrict__ L1, double* __restrict__ Jp, double* __restrict__ Jl,
                                                        double* __restrict__ res, double* __restrict__ cost) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 2 * D.P) return;
-    if (!init && !(ctl->active && (ctl->need_linearize & PGO_NEED_J))) return;
-    const int p = t >> 1, side = t & 1, kf = D.pairKf[p], lm = D.pairLm[p];
-    double r[2] = {0.0, 0.0}, jp[12], jl[6];
-#pragma unroll
-    for (int k = 0; k < 12; k++) jp[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) jl[k] = 0.0;
-    double c = 0.0;
-    if (((D.pairFlags[p] >> side) & 1) && D.lmPresent[lm]) {
-        const double* T = (ctl->cur ? P1 : P0) + (size_t)kf * 12;
-        const double* X = (ctl->cur ? L1 : L0) + (size_t)lm * 3;
-        const bool ok = gba_factor<true>(T, X, D.cam, side, (double)D.pairUv[4 * (size_t)p + 2 * side], (double)D.pairUv[4 * (size_t)p + 2 * side + 1],
-                                         D.pairIs[t], r, jp, jl);
-        c = ok ? r[0] * r[0] + r[1] * r[1] : NAN;
-    }
-#pragma unroll
-    for (int k = 0; k < 12; k++) Jp[(size_t)t * 12 + k] = jp[k];
-#pragma unroll
-    for (int k = 0; k < 6; k++) Jl[(size_t)t * 6 + k] = jl[k];
-    res[(size_t)t * 2] = r[0]; res[(size_t)t * 2 + 1] = r[1];
-    cost[t] = c;
+    gba_linearize_slot(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, init, P0, P1, L0, L1, Jp, Jl, res, cost);
 }
 
-// the trial values are the buffers that are not `cur`; a factor behind its camera makes the sum NaN (a rejected trial)
 __global__ __launch_bounds__(256) void k_gba_cost(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ P0,
                                                   const double* __restrict__ P1, const double* __restrict__ L0,
                                                   const double* __restrict__ L1, double* __restrict__ cost) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 2 * D.P || !ctl->active) return;
-    const int p = t >> 1, side = t & 1, kf = D.pairKf[p], lm = D.pairLm[p];
-    if (!(((D.pairFlags[p] >> side) & 1) && D.lmPresent[lm])) return;
-    const double* T = (ctl->cur ? P0 : P1) + (size_t)kf * 12;
-    const double* X = (ctl->cur ? L0 : L1) + (size_t)lm * 3;
-    double r[2];
-    const bool ok = gba_factor<false>(T, X, D.cam, side, (double)D.pairUv[4 * (size_t)p + 2 * side], (double)D.pairUv[4 * (size_t)p + 2 * side + 1],
-                                      D.pairIs[t], r, nullptr, nullptr);
-    cost[t] = ok ? r[0] * r[0] + r[1] * r[1] : NAN;
+    gba_cost_slot(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, P0, P1, L0, L1, cost);
 }
 
 __global__ __launch_bounds__(256) void k_gba_edge_linearize(GbaDev D, const PgoCtl* __restrict__ ctl, int init, const double* __restrict__ P0,
                                                             const double* __restrict__ P1, double* __restrict__ res, double* __restrict__ Ji,
                                                             double* __restrict__ Jj, double* __restrict__ cost) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= D.M) return;
-    if (!init && !(ctl->active && (ctl->need_linearize & PGO_NEED_J))) return;
-    pgo_linearize_edge(e, D.edges, ctl->cur ? P1 : P0, res, Ji, Jj, cost);
+    gba_edge_linearize_one(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, init, P0, P1, res, Ji, Jj, cost);
 }
 
 __global__ __launch_bounds__(256) void k_gba_edge_cost(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ P0,
                                                        const double* __restrict__ P1, double* __restrict__ cost) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= D.M || !ctl->active) return;
-    pgo_cost_edge(e, D.edges, ctl->cur ? P0 : P1, cost);
+    gba_edge_cost_one(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, P0, P1, cost);
 }
 
-// Hll = sum Jl^T Jl over the landmark's factors, damped by lambda diag(Hll); Hinv [9] by cofactors; gl = sum Jl^T r.
-// A pivot of the damped block that is not positive raises *flag.
 __global__ __launch_bounds__(256) void k_gba_landmark(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ Jl,
                                                       const double* __restrict__ res, double* __restrict__ Hinv, double* __restrict__ gl,
                                                       int* __restrict__ flag) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= D.L || !ctl->active || !D.lmPresent[l]) return;
-    double h00 = 0.0, h01 = 0.0, h02 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-    for (int q = D.lmStart[l]; q < D.lmStart[l + 1]; q++) {
-        const size_t p = (size_t)D.lmPairs[q];
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            const double* j = Jl + (p * 4 + a) * 3;
-            const double j0 = j[0], j1 = j[1], j2 = j[2], r = res[p * 4 + a];
-            h00 += j0 * j0; h01 += j0 * j1; h02 += j0 * j2; h11 += j1 * j1; h12 += j1 * j2; h22 += j2 * j2;
-            g0 += j0 * r; g1 += j1 * r; g2 += j2 * r;
-        }
-    }
-    const double lam = ctl->lambda;
-    h00 += lam * h00; h11 += lam * h11; h22 += lam * h22;
-    // pivots of the LDL^T factorisation
-    const double d0 = h00, l10 = h01 / d0, l20 = h02 / d0;
-    const double d1 = h11 - l10 * h01, u12 = h12 - l20 * h01;
-    const double d2 = h22 - l20 * h02 - (u12 / d1) * u12;
-    if (!(d0 > 0.0) || !(d1 > 0.0) || !(d2 > 0.0) || !(d0 < 1e300) || !(d1 < 1e300) || !(d2 < 1e300)) atomicOr(flag, 1);
-    const double A = h11 * h22 - h12 * h12, B = h02 * h12 - h01 * h22, C = h01 * h12 - h02 * h11;
-    const double id = 1.0 / (h00 * A + h01 * B + h02 * C);
-    double* o = Hinv + (size_t)l * 9;
-    o[0] = A * id; o[1] = B * id; o[2] = C * id;
-    o[3] = B * id; o[4] = (h00 * h22 - h02 * h02) * id; o[5] = (h01 * h02 - h00 * h12) * id;
-    o[6] = C * id; o[7] = (h01 * h02 - h00 * h12) * id; o[8] = (h00 * h11 - h01 * h01) * id;
-    gl[(size_t)l * 3] = g0; gl[(size_t)l * 3 + 1] = g1; gl[(size_t)l * 3 + 2] = g2;
+    gba_landmark_one(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, Jl, res, Hinv, gl, flag);
 }
 
-// W [6][3] = sum Jp^T Jl over the pair's factors, Y = W Hinv
 __global__ __launch_bounds__(256) void k_gba_wy(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ Jp,
                                                 const double* __restrict__ Jl, const double* __restrict__ Hinv, double* __restrict__ W,
                                                 double* __restrict__ Y) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.P || !ctl->active) return;
-    const int lm = D.pairLm[p];
-    if (!(D.pairFlags[p] & 3) || !D.lmPresent[lm] || D.pos[D.pairKf[p]] < 0) return;
-    double w[18];
-#pragma unroll
-    for (int k = 0; k < 18; k++) w[k] = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const double* jp = Jp + ((size_t)p * 4 + a) * 6;
-        const double* jl = Jl + ((size_t)p * 4 + a) * 3;
-        const double l0 = jl[0], l1 = jl[1], l2 = jl[2];
-#pragma unroll
-        for (int i = 0; i < 6; i++) { const double v = jp[i]; w[3 * i] += v * l0; w[3 * i + 1] += v * l1; w[3 * i + 2] += v * l2; }
-    }
-    double hi[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) hi[k] = Hinv[(size_t)lm * 9 + k];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            W[(size_t)p * 18 + 3 * i + j] = w[3 * i + j];
-            Y[(size_t)p * 18 + 3 * i + j] = w[3 * i] * hi[j] + w[3 * i + 1] * hi[3 + j] + w[3 * i + 2] * hi[6 + j];
-        }
+    gba_wy_pair(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, Jp, Jl, Hinv, W, Y);
 }
 
-// the edges' part of column c: every block of the column is written (zero where no edge reaches), diagH and g too
 __global__ __launch_bounds__(64) void k_gba_edge_columns(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ res,
                                                          const double* __restrict__ Ji, const double* __restrict__ Jj,
                                                          double* __restrict__ band, double* __restrict__ diagH, double* __restrict__ g) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    if (c >= D.nf || lane >= 42 || !ctl->active) return;
-    pgo_assemble_column(c, lane, D.nf, D.b, D.pos, D.rowStart, D.inc, D.edges, res, Ji, Jj, band, diagH, g);
+    gba_edge_column(blockIdx.x, threadIdx.x, D, ctl, res, Ji, Jj, band, diagH, g);
 }
 
-// Block i of the landmark lists: H[c + d][c] += sum over its entries (p1 on c + d, p2 on c) of -Y_p1 W_p2^T, and on the diagonal
-// (p1 == p2) the pair's Jp^T Jp; lanes 36 .. 41 of a diagonal block: g_c -= Jp^T r - Y_p gl.  diagH gets the undamped pose
-// diagonal (Jp^T Jp alone).  It runs after k_gba_edge_columns, which wrote the block.
 __global__ __launch_bounds__(64) void k_gba_gather(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ Jp,
                                                    const double* __restrict__ res, const double* __restrict__ W, const double* __restrict__ Y,
                                                    const double* __restrict__ gl, double* __restrict__ band, double* __restrict__ diagH,
                                                    double* __restrict__ g) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= D.nBlk || lane >= 42 || !ctl->active) return;
-    const int c = D.blkC[i], d = D.blkD[i];
-    if (lane >= 36 && d != 0) return;
-    const int r = lane / 6, s = lane % 6;
-    double acc = 0.0, accH = 0.0;
-    for (int k = D.blkStart[i]; k < D.blkStart[i + 1]; k++) {
-        const size_t p1 = (size_t)D.list[2 * (size_t)k], p2 = (size_t)D.list[2 * (size_t)k + 1];
-        if (lane < 36) {
-            const double* y = Y + p1 * 18 + 3 * r;
-            const double* w = W + p2 * 18 + 3 * s;
-            acc -= y[0] * w[0] + y[1] * w[1] + y[2] * w[2];
-            if (d == 0 && p1 == p2) {
-                const double* jp = Jp + p1 * 24;
-                double v = 0.0;
-#pragma unroll
-                for (int a = 0; a < 4; a++) v += jp[6 * a + r] * jp[6 * a + s];
-                acc += v; accH += v;
-            }
-        } else if (p1 == p2) {
-            const double* jp = Jp + p1 * 24;
-            const double* rr = res + p1 * 4;
-            const double* y = Y + p1 * 18 + 3 * s;
-            const double* q = gl + (size_t)D.pairLm[p1] * 3;
-            double v = 0.0;
-#pragma unroll
-            for (int a = 0; a < 4; a++) v += jp[6 * a + s] * rr[a];
-            acc += v - (y[0] * q[0] + y[1] * q[1] + y[2] * q[2]);
-        }
-    }
-    if (lane < 36) {
-        band[((size_t)c * (D.b + 1) + d) * 36 + lane] += acc;
-        if (d == 0 && r == s) diagH[(size_t)c * 6 + r] += accH;
-    } else {
-        g[(size_t)c * 6 + s] -= acc;
-    }
+    gba_gather_block(blockIdx.x, threadIdx.x, D, ctl, Jp, res, W, Y, gl, band, diagH, g);
 }
 
 __global__ __launch_bounds__(256) void k_gba_band_copy(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ bandH,
                                                        const double* __restrict__ g, double* __restrict__ bandL, double* __restrict__ rhs) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)(D.b + 1) * D.nf * 36 || !ctl->active) return;
-    bandL[t] = bandH[t];
-    if (t < (size_t)D.nf * 6) rhs[t] = g[t];
+    gba_band_copy_one((size_t)blockIdx.x * blockDim.x + threadIdx.x, D, ctl, bandH, g, bandL, rhs);
 }
 
 __global__ __launch_bounds__(PGO_CHOL_NT) void k_gba_band_chol(GbaDev D, const PgoCtl* __restrict__ ctl, double* __restrict__ bandL,
@@ -273,38 +96,15 @@ __global__ __launch_bounds__(PGO_CHOL_NT) void k_gba_band_chol(GbaDev D, const P
     pgo_band_chol_walk(D.nf, D.b, ctl->lambda, bandL, diagH, rhs, delta, flag);
 }
 
-// the landmark step dX = Hinv (-gl - sum W_p^T delta_kf(p)) over the landmark's pairs on free keyframes, in list order; the trial
-// landmark; a thin landmark's trial value is its value.  The steps follow the poses' in `delta` (|delta|_inf covers both).
 __global__ __launch_bounds__(256) void k_gba_back(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ W,
                                                   const double* __restrict__ Hinv, const double* __restrict__ gl, double* __restrict__ L0,
                                                   double* __restrict__ L1, double* __restrict__ delta) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= D.L || !ctl->active) return;
-    const double* X = (ctl->cur ? L1 : L0) + (size_t)l * 3;
-    double* Xt = (ctl->cur ? L0 : L1) + (size_t)l * 3;
-    double* dl = delta + (size_t)D.nf * 6 + (size_t)l * 3;
-    if (!D.lmPresent[l]) { Xt[0] = X[0]; Xt[1] = X[1]; Xt[2] = X[2]; dl[0] = dl[1] = dl[2] = 0.0; return; }
-    double t0 = -gl[(size_t)l * 3], t1 = -gl[(size_t)l * 3 + 1], t2 = -gl[(size_t)l * 3 + 2];
-    for (int q = D.lmStart[l]; q < D.lmStart[l + 1]; q++) {
-        const size_t p = (size_t)D.lmPairs[q];
-        const int c = D.pos[D.pairKf[p]];
-        if (c < 0) continue;
-        const double* w = W + p * 18;
-        const double* dp = delta + (size_t)c * 6;
-#pragma unroll
-        for (int i = 0; i < 6; i++) { const double v = dp[i]; t0 -= w[3 * i] * v; t1 -= w[3 * i + 1] * v; t2 -= w[3 * i + 2] * v; }
-    }
-    const double* hi = Hinv + (size_t)l * 9;
-    const double d0 = hi[0] * t0 + hi[1] * t1 + hi[2] * t2, d1 = hi[3] * t0 + hi[4] * t1 + hi[5] * t2, d2 = hi[6] * t0 + hi[7] * t1 + hi[8] * t2;
-    Xt[0] = X[0] + d0; Xt[1] = X[1] + d1; Xt[2] = X[2] + d2;
-    dl[0] = d0; dl[1] = d1; dl[2] = d2;
+    gba_back_one(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, W, Hinv, gl, L0, L1, delta);
 }
 
 __global__ __launch_bounds__(256) void k_gba_retract(GbaDev D, const PgoCtl* __restrict__ ctl, double* __restrict__ P0, double* __restrict__ P1,
                                                      const double* __restrict__ delta) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= D.K || !ctl->active) return;
-    pgo_retract_pose(k, D.pos, ctl->cur ? P1 : P0, delta, ctl->cur ? P0 : P1);
+    gba_retract_one(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, P0, P1, delta);
 }
 
 // One workgroup: the fixed-order sum of the nCost cost terms and |delta|_inf, then thread 0 applies the rule (pgo_lm_decide).
@@ -331,34 +131,191 @@ __global__ __launch_bounds__(PGO_RED_NT) void k_gba_reduce_decide(int init, int 
     *nActive = c.active;
 }
 
-// the local BA's chi2 rule at the final values: pairs of kf_local keyframes on present landmarks, left then right
 __global__ __launch_bounds__(256) void k_gba_chi2(GbaDev D, const PgoCtl* __restrict__ ctl, const double* __restrict__ P0,
                                                   const double* __restrict__ P1, const double* __restrict__ L0, const double* __restrict__ L1,
                                                   uint8_t* __restrict__ wrong) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.P) return;
-    const int kf = D.pairKf[p], lm = D.pairLm[p], fl = D.pairFlags[p] & 3;
-    uint8_t w = 0;
-    if (fl && D.kfLocal[kf] && D.lmPresent[lm]) {
-        const double* T = (ctl->cur ? P1 : P0) + (size_t)kf * 12;
-        const double* X = (ctl->cur ? L1 : L0) + (size_t)lm * 3;
-        const double d[3] = {X[0] - T[9], X[1] - T[10], X[2] - T[11]};
-        double R[9], q[3];
-#pragma unroll
-        for (int k = 0; k < 9; k++) R[k] = T[k];
-        mat3T_vec(R, d, q);
-        const double z = q[2];
-        bool out[2];
-#pragma unroll
-        for (int side = 0; side < 2; side++) {
-            const double x = side ? q[0] - D.cam.bl : q[0];
-            const double px = D.cam.fx * x + D.cam.cx * z, py = D.cam.fy * q[1] + D.cam.cy * z;
-            const double eu = (double)D.pairUv[4 * (size_t)p + 2 * side] - px / z, ev = (double)D.pairUv[4 * (size_t)p + 2 * side + 1] - py / z;
-            out[side] = !(z > 0.0) || (eu * eu + ev * ev) > D.pairThr[2 * (size_t)p + side];
+    gba_chi2_pair(blockIdx.x * blockDim.x + threadIdx.x, D, ctl, P0, P1, L0, L1, wrong);
+}
+
+// ---- the kernels of vslam_global_ba_batch: several problems (lanes) in one launch per stage, blockIdx.y (blockIdx.x of the
+// one-workgroup-per-lane kernels) = lane.  The lanes' arrays are concatenated (gba_pack_host.hpp); `B` and `Wb` hold where the
+// concatenated arrays begin, a lane's table entry where its parts begin in them.  Indices inside a lane's arrays are lane-local,
+// so every body sees one problem's arrays whatever the other lanes are.  A lane that has stopped costs a workgroup one load.
+struct GbaWork {                    // the device's own arrays
+    double *P0, *P1, *L0, *L1;      // both value buffers (P0 and L0 come up with the problem)
+    double *Jp, *Jl, *res, *cost, *eres, *eJi, *eJj, *Hinv, *gl, *W, *Y, *bandH, *bandL, *diagH, *g, *rhs, *delta;
+    uint8_t* wrong;
+};
+
+__device__ __forceinline__ GbaDev gba_lane_dev(const GbaLane* T, const GbaDev& B) {
+    GbaDev D;
+    D.K = T->K; D.L = T->L; D.P = T->P; D.M = T->M; D.nf = T->nf; D.b = T->b; D.nBlk = T->nBlk;
+    D.cam = GbaCam{T->fx, T->fy, T->cx, T->cy, T->bl};
+    const size_t kf0 = (size_t)T->kf0, lm0 = (size_t)T->lm0, p0 = (size_t)T->pair0, ln = (size_t)T->lane;
+    D.edges = B.edges + (size_t)T->edge0;
+    D.pos = B.pos + kf0;
+    D.rowStart = B.rowStart + (size_t)T->free0 + ln; D.inc = B.inc + (size_t)T->inc0;
+    D.pairKf = B.pairKf + p0; D.pairLm = B.pairLm + p0; D.pairFlags = B.pairFlags + p0;
+    D.pairUv = B.pairUv + p0 * 4; D.pairIs = B.pairIs + p0 * 2; D.pairThr = B.pairThr + p0 * 2;
+    D.kfLocal = B.kfLocal + kf0; D.lmPresent = B.lmPresent + lm0;
+    D.lmStart = B.lmStart + lm0 + ln; D.lmPairs = B.lmPairs + (size_t)T->lp0;
+    D.blkC = B.blkC + (size_t)T->blk0; D.blkD = B.blkD + (size_t)T->blk0; D.blkStart = B.blkStart + (size_t)T->blk0 + ln;
+    D.list = B.list + (size_t)T->list0 * 2;
+    return D;
+}
+
+__device__ __forceinline__ GbaWork gba_lane_work(const GbaLane* T, const GbaWork& B) {
+    GbaWork W;
+    const size_t kf0 = (size_t)T->kf0, lm0 = (size_t)T->lm0, p0 = (size_t)T->pair0, e0 = (size_t)T->edge0, f0 = (size_t)T->free0;
+    W.P0 = B.P0 + kf0 * 12; W.P1 = B.P1 + kf0 * 12; W.L0 = B.L0 + lm0 * 3; W.L1 = B.L1 + lm0 * 3;
+    W.Jp = B.Jp + p0 * 24; W.Jl = B.Jl + p0 * 12; W.res = B.res + p0 * 4; W.cost = B.cost + p0 * 2 + e0;
+    W.eres = B.eres + e0 * 6; W.eJi = B.eJi + e0 * 36; W.eJj = B.eJj + e0 * 36;
+    W.Hinv = B.Hinv + lm0 * 9; W.gl = B.gl + lm0 * 3; W.W = B.W + p0 * 18; W.Y = B.Y + p0 * 18;
+    W.bandH = B.bandH + (size_t)T->band0 * 36; W.bandL = B.bandL + (size_t)T->band0 * 36;
+    W.diagH = B.diagH + f0 * 6; W.g = B.g + f0 * 6; W.rhs = B.rhs + f0 * 6; W.delta = B.delta + f0 * 6 + lm0 * 3;
+    W.wrong = B.wrong + p0;
+    return W;
+}
+
+__global__ __launch_bounds__(256) void k_gba_linearize_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, int init, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!init && !C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_linearize_slot(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, init, W.P0, W.P1, W.L0, W.L1, W.Jp, W.Jl, W.res, W.cost);
+}
+
+__global__ __launch_bounds__(256) void k_gba_edge_linearize_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, int init, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!init && !C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_edge_linearize_one(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, init, W.P0, W.P1, W.eres, W.eJi, W.eJj, W.cost + (size_t)2 * T->P);
+}
+
+__global__ __launch_bounds__(256) void k_gba_landmark_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb, int* __restrict__ flagLm) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_landmark_one(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.Jl, W.res, W.Hinv, W.gl, flagLm + blockIdx.y);
+}
+
+__global__ __launch_bounds__(256) void k_gba_wy_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_wy_pair(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.Jp, W.Jl, W.Hinv, W.W, W.Y);
+}
+
+__global__ __launch_bounds__(64) void k_gba_edge_columns_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_edge_column(blockIdx.x, threadIdx.x, gba_lane_dev(T, B), C, W.eres, W.eJi, W.eJj, W.bandH, W.diagH, W.g);
+}
+
+__global__ __launch_bounds__(64) void k_gba_gather_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_gather_block(blockIdx.x, threadIdx.x, gba_lane_dev(T, B), C, W.Jp, W.res, W.W, W.Y, W.gl, W.bandH, W.diagH, W.g);
+}
+
+__global__ __launch_bounds__(256) void k_gba_band_copy_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_band_copy_one((size_t)blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.bandH, W.g, W.bandL, W.rhs);
+}
+
+// one workgroup per lane: the walk on the lane's band with the lane's n_free, b and lambda
+__global__ __launch_bounds__(PGO_CHOL_NT) void k_gba_band_chol_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaWork Wb,
+                                                                 int* __restrict__ flagChol) {
+    const PgoCtl* C = ctl + blockIdx.x;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.x);
+    const GbaWork W = gba_lane_work(T, Wb);
+    pgo_band_chol_walk(T->nf, T->b, C->lambda, W.bandL, W.diagH, W.rhs, W.delta, flagChol + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_gba_back_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_back_one(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.W, W.Hinv, W.gl, W.L0, W.L1, W.delta);
+}
+
+__global__ __launch_bounds__(256) void k_gba_retract_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_retract_one(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.P0, W.P1, W.delta);
+}
+
+__global__ __launch_bounds__(256) void k_gba_cost_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_cost_slot(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.P0, W.P1, W.L0, W.L1, W.cost);
+}
+
+__global__ __launch_bounds__(256) void k_gba_edge_cost_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const PgoCtl* C = ctl + blockIdx.y;
+    if (!C->active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_edge_cost_one(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), C, W.P0, W.P1, W.cost + (size_t)2 * T->P);
+}
+
+// out[2 lane], out[2 lane + 1]: the lane's 2 P + M cost terms summed in the single call's order, and |delta|_inf over its 6 nf + 3 L
+// steps (init: every lane's initial cost, no delta yet)
+__global__ __launch_bounds__(PGO_RED_NT) void k_gba_reduce_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, int init, GbaWork Wb,
+                                                             double* __restrict__ out) {
+    __shared__ double sS[PGO_RED_NT], sM[PGO_RED_NT];
+    if (!init && !ctl[blockIdx.x].active) return;
+    const GbaLane* T = lane_entry(tab, blockIdx.x);
+    const GbaWork W = gba_lane_work(T, Wb);
+    pgo_reduce_sum(threadIdx.x, 2 * T->P + T->M, W.cost, init ? 0 : T->nf * 6 + T->L * 3, W.delta, out + 2 * (size_t)blockIdx.x, sS, sM);
+}
+
+// The accept / reject rule, one thread per lane (what thread 0 of k_gba_reduce_decide does for the single call).
+// *nActive: what the host reads once per round.
+__global__ __launch_bounds__(GBA_MAX_LANES) void k_gba_decide_b(int lanes, int init, int maxIt, const GbaLane* __restrict__ tab,
+                                                                PgoCtl* __restrict__ ctl, const double* __restrict__ out,
+                                                                int* __restrict__ flagChol, int* __restrict__ flagLm, int* __restrict__ nActive) {
+    const int l = threadIdx.x;
+    int act = 0;
+    if (l < lanes) {
+        PgoCtl c = ctl[l];
+        if (init) {
+            c.cost = c.initial_cost = out[2 * l];
+            c.active = (c.cost > 1e-20) && tab[l].hasUnknowns;
+            c.need_linearize = PGO_NEED_H;
+            flagChol[l] = 0; flagLm[l] = 0;
+            ctl[l] = c;
+        } else if (c.active) {
+            pgo_lm_decide(c, out[2 * l], out[2 * l + 1], flagChol[l] | flagLm[l], maxIt);
+            flagLm[l] = 0;
+            ctl[l] = c;
         }
-        w = ((fl & 1) && out[0]) || ((fl & 2) && out[1]);
+        act = c.active;
     }
-    wrong[p] = w;
+    const int cnt = __syncthreads_count(act);
+    if (threadIdx.x == 0) *nActive = cnt;
+}
+
+__global__ __launch_bounds__(256) void k_gba_chi2_b(const GbaLane* __restrict__ tab, const PgoCtl* __restrict__ ctl, GbaDev B, GbaWork Wb) {
+    const GbaLane* T = lane_entry(tab, blockIdx.y);
+    const GbaWork W = gba_lane_work(T, Wb);
+    gba_chi2_pair(blockIdx.x * blockDim.x + threadIdx.x, gba_lane_dev(T, B), ctl + blockIdx.y, W.P0, W.P1, W.L0, W.L1, W.wrong);
 }
 
 thread_local std::vector<std::pair<const char*, float>> g_gbaTimes;
@@ -371,6 +328,114 @@ struct GbaLayout {
 
 inline bool gba_finite(const double* p, size_t n) { for (size_t k = 0; k < n; k++) if (!std::isfinite(p[k])) return false; return true; }
 inline unsigned gba_grid(size_t n) { return (unsigned)((n + 255) / 256); }
+
+// What the host derives from one problem before anything is launched, for the single call and for every lane of the batched one:
+// the plan (gba_host.hpp) and the device forms of poses, edges, whitening factors and chi2 thresholds.  `who` (the entry point,
+// with the lane for a batched call) starts every error text.
+struct GbaPrep {
+    GbaPlan G;
+    std::vector<double> hp, his, hthr;      // poses [K][12]; per factor slot [P][2]
+    std::vector<PgoEdge> he;
+};
+
+vslam_status gba_check_args(const char* who, const vslam_ba_problem& Q, const vslam_pgo_edge* edges, int M, const vslam_gba_result* result) {
+    const int K = Q.n_kf, L = Q.n_lm, P = Q.n_pairs;
+    if (K < 1 || L < 0 || P < 0 || M < 0 || !Q.kf_pose_wc || !Q.kf_fixed || !Q.kf_local || !result->kf_pose_wc || (L > 0 && (!Q.lm_xyz || !result->lm_xyz)) ||
+        (P > 0 && (!Q.pair_kf || !Q.pair_lm || !Q.pair_flags || !Q.pair_uv || !Q.pair_octave || !result->pair_wrong || !Q.sigma_factor || !Q.inv_sigma_factor || Q.n_levels < 1)) ||
+        (M > 0 && !edges)) {
+        set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID;
+    }
+    // the plan's limits come first (the edge ends are copied only after them)
+    static const int32_t none = 0;
+    GbaIndex I;
+    I.n_kf = K; I.kf_fixed = Q.kf_fixed; I.n_lm = L; I.n_pairs = P; I.pair_kf = Q.pair_kf; I.pair_lm = Q.pair_lm; I.pair_flags = Q.pair_flags;
+    I.n_edges = M; I.edge_i = &none; I.edge_j = &none;
+    GbaPlan G;
+    if (const int st = gba_check_sizes(I, G)) { set_error("%s: %s", who, G.err.c_str()); return (vslam_status)st; }
+    return VSLAM_OK;
+}
+
+// (after gba_check_args) host plan: presence, free set, gauge, reordering, lists; then every value is checked and converted
+vslam_status gba_prepare(const char* who, const vslam_ba_problem& Q, const vslam_pgo_edge* edges, int M, GbaPrep& R) {
+    const int K = Q.n_kf, L = Q.n_lm, P = Q.n_pairs;
+    std::vector<int32_t> ei(std::max(M, 1)), ej(std::max(M, 1));
+    GbaIndex I;
+    I.n_kf = K; I.kf_fixed = Q.kf_fixed; I.n_lm = L; I.n_pairs = P; I.pair_kf = Q.pair_kf; I.pair_lm = Q.pair_lm; I.pair_flags = Q.pair_flags;
+    I.n_edges = M; I.edge_i = ei.data(); I.edge_j = ej.data();
+    GbaPlan& G = R.G;
+    for (int e = 0; e < M; e++) { ei[e] = edges[e].i; ej[e] = edges[e].j; }
+    if (const int st = gba_plan(I, G)) { set_error("%s: %s", who, G.err.c_str()); return (vslam_status)st; }
+    if (!gba_finite(Q.kf_pose_wc, (size_t)K * 16) || !gba_finite(Q.lm_xyz, (size_t)L * 3) || !std::isfinite(Q.rig.fx) || !std::isfinite(Q.rig.fy) ||
+        !std::isfinite(Q.rig.cx) || !std::isfinite(Q.rig.cy) || !std::isfinite(Q.rig.baseline)) {
+        set_error("%s: non-finite pose, landmark or camera", who); return VSLAM_ERR_INVALID;
+    }
+    for (int e = 0; e < M; e++) {
+        const vslam_pgo_edge& E = edges[e];
+        if (!gba_finite(E.Z, 16) || !std::isfinite(E.w_rot) || !std::isfinite(E.w_trans)) { set_error("%s: edge %d has a non-finite value", who, e); return VSLAM_ERR_INVALID; }
+        if (E.w_rot < 0 || E.w_trans < 0) { set_error("%s: edge %d has a negative weight", who, e); return VSLAM_ERR_INVALID; }
+    }
+    // device forms: poses [12], whitening and chi2 threshold per factor slot; the initial depth of every present factor
+    std::vector<double>& hp = R.hp; std::vector<double>& his = R.his; std::vector<double>& hthr = R.hthr;
+    hp.assign((size_t)K * 12, 0.0); his.assign((size_t)std::max(P, 1) * 2, 0.0); hthr.assign((size_t)std::max(P, 1) * 2, 0.0);
+    for (int k = 0; k < K; k++)
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) hp[(size_t)k * 12 + 3 * r + c] = Q.kf_pose_wc[(size_t)k * 16 + 4 * r + c]; hp[(size_t)k * 12 + 9 + r] = Q.kf_pose_wc[(size_t)k * 16 + 4 * r + 3]; }
+    for (int p = 0; p < P; p++) {
+        const int fl = Q.pair_flags[p] & 3, lm = Q.pair_lm[p];
+        if (!fl || !G.lmPresent[lm]) continue;
+        for (int side = 0; side < 2; side++) {
+            if (!((fl >> side) & 1)) continue;
+            const int oct = Q.pair_octave[2 * (size_t)p + side];
+            if (oct < 0 || oct >= Q.n_levels) { set_error("%s: pair %d has octave %d of %d levels", who, p, oct, Q.n_levels); return VSLAM_ERR_INVALID; }
+            if (!std::isfinite(Q.pair_uv[4 * (size_t)p + 2 * side]) || !std::isfinite(Q.pair_uv[4 * (size_t)p + 2 * side + 1])) { set_error("%s: pair %d has a non-finite measurement", who, p); return VSLAM_ERR_INVALID; }
+            his[2 * (size_t)p + side] = 1.0 / (1.0 / (double)Q.inv_sigma_factor[oct]);           // sigma = 1 / inv_sigma_factor
+            hthr[2 * (size_t)p + side] = (double)(float)((double)7.815f * (double)Q.sigma_factor[oct]);
+        }
+        const double* T = &hp[(size_t)Q.pair_kf[p] * 12];
+        const double* X = Q.lm_xyz + (size_t)lm * 3;
+        const double z = T[2] * (X[0] - T[9]) + T[5] * (X[1] - T[10]) + T[8] * (X[2] - T[11]);
+        if (!(z > 0.0)) { set_error("%s: pair %d (keyframe %d, landmark %d) is not in front of its camera at the initial values", who, p, Q.pair_kf[p], lm); return VSLAM_ERR_INVALID; }
+    }
+    R.he.assign(std::max(M, 1), PgoEdge{});
+    for (int e = 0; e < M; e++) {
+        PgoEdge& o = R.he[e];
+        o.i = edges[e].i; o.j = edges[e].j; o.wr = edges[e].w_rot; o.wt = edges[e].w_trans;
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o.Rz[3 * r + c] = edges[e].Z[4 * r + c]; o.tz[r] = edges[e].Z[4 * r + 3]; }
+    }
+    return VSLAM_OK;
+}
+
+// The solved values into the caller's arrays (hp [K][12], hl [L][3], hw [P] from the device) and the report.  Fixed and isolated
+// keyframes and thin landmarks are the input's bytes.  The outputs may be the problem's arrays.
+void gba_write_out(const vslam_ba_problem& Q, const GbaPlan& G, const double* hp, const double* hl, const uint8_t* hw, const PgoCtl& ctl, vslam_gba_result* result) {
+    const int K = Q.n_kf, L = Q.n_lm, P = Q.n_pairs;
+    for (int k = 0; k < K; k++) {
+        double* o = result->kf_pose_wc + (size_t)k * 16;
+        const double* in = Q.kf_pose_wc + (size_t)k * 16;
+        if (G.pos[k] < 0) { if (o != in) memcpy(o, in, 128); continue; }
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o[4 * r + c] = hp[(size_t)k * 12 + 3 * r + c]; o[4 * r + 3] = hp[(size_t)k * 12 + 9 + r]; }
+        o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+    }
+    for (int l = 0; l < L; l++) {
+        double* o = result->lm_xyz + (size_t)l * 3;
+        const double* in = G.lmPresent[l] ? hl + (size_t)l * 3 : Q.lm_xyz + (size_t)l * 3;
+        if (o != in) memcpy(o, in, 24);
+    }
+    if (P) memcpy(result->pair_wrong, hw, (size_t)P);
+    vslam_gba_report& R = result->report;
+    R = vslam_gba_report{};
+    R.accepted = ctl.accepted; R.rejected = ctl.rejected; R.iterations = ctl.accepted + ctl.rejected;
+    R.n_free = G.nf; R.n_isolated = G.nIso; R.n_present = G.nPresent; R.n_thin = G.nThin; R.n_factors = G.nFactors; R.half_bandwidth = G.b;
+    R.initial_cost = ctl.initial_cost; R.final_cost = ctl.cost; R.final_lambda = ctl.lambda;
+}
+
+vslam_status gba_check_params(const char* who, const vslam_gba_params* params, int* maxIt, double* lambda0) {
+    *maxIt = params ? params->max_iterations : 0;
+    *lambda0 = params ? params->lambda0 : 0.0;
+    if (*maxIt < 0 || !(*lambda0 >= 0.0) || !std::isfinite(*lambda0)) { set_error("%s: negative or non-finite parameter", who); return VSLAM_ERR_INVALID; }
+    if (*maxIt == 0) *maxIt = 20;
+    if (*lambda0 == 0.0) *lambda0 = 1e-4;
+    return VSLAM_OK;
+}
 
 }  // namespace
 
@@ -393,62 +458,18 @@ extern "C" vslam_status vslam_global_ba(const vslam_ba_problem* problem, const v
     static const char* const who = "vslam_global_ba";
     if (!problem || !result) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
     const vslam_ba_problem& Q = *problem;
-    int maxIt = params ? params->max_iterations : 0;
-    double lambda0 = params ? params->lambda0 : 0.0;
-    if (maxIt < 0 || !(lambda0 >= 0.0) || !std::isfinite(lambda0)) { set_error("%s: negative or non-finite parameter", who); return VSLAM_ERR_INVALID; }
-    if (maxIt == 0) maxIt = 20;
-    if (lambda0 == 0.0) lambda0 = 1e-4;
+    int maxIt = 0;
+    double lambda0 = 0.0;
+    VS_CHECK(gba_check_params(who, params, &maxIt, &lambda0));
     const int K = Q.n_kf, L = Q.n_lm, P = Q.n_pairs, M = n_edges;
-    if (K < 1 || L < 0 || P < 0 || M < 0 || !Q.kf_pose_wc || !Q.kf_fixed || !Q.kf_local || !result->kf_pose_wc || (L > 0 && (!Q.lm_xyz || !result->lm_xyz)) ||
-        (P > 0 && (!Q.pair_kf || !Q.pair_lm || !Q.pair_flags || !Q.pair_uv || !Q.pair_octave || !result->pair_wrong || !Q.sigma_factor || !Q.inv_sigma_factor || Q.n_levels < 1)) ||
-        (M > 0 && !edges)) {
-        set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID;
-    }
-    // host plan: presence, free set, gauge, reordering, lists (its limits come first)
-    std::vector<int32_t> ei(std::max(M, 1)), ej(std::max(M, 1));
-    GbaIndex I;
-    I.n_kf = K; I.kf_fixed = Q.kf_fixed; I.n_lm = L; I.n_pairs = P; I.pair_kf = Q.pair_kf; I.pair_lm = Q.pair_lm; I.pair_flags = Q.pair_flags;
-    I.n_edges = M; I.edge_i = ei.data(); I.edge_j = ej.data();
-    GbaPlan G;
-    if (const int st = gba_check_sizes(I, G)) { set_error("%s: %s", who, G.err.c_str()); return (vslam_status)st; }
-    for (int e = 0; e < M; e++) { ei[e] = edges[e].i; ej[e] = edges[e].j; }
-    if (const int st = gba_plan(I, G)) { set_error("%s: %s", who, G.err.c_str()); return (vslam_status)st; }
-    if (!gba_finite(Q.kf_pose_wc, (size_t)K * 16) || !gba_finite(Q.lm_xyz, (size_t)L * 3) || !std::isfinite(Q.rig.fx) || !std::isfinite(Q.rig.fy) ||
-        !std::isfinite(Q.rig.cx) || !std::isfinite(Q.rig.cy) || !std::isfinite(Q.rig.baseline)) {
-        set_error("%s: non-finite pose, landmark or camera", who); return VSLAM_ERR_INVALID;
-    }
-    for (int e = 0; e < M; e++) {
-        const vslam_pgo_edge& E = edges[e];
-        if (!gba_finite(E.Z, 16) || !std::isfinite(E.w_rot) || !std::isfinite(E.w_trans)) { set_error("%s: edge %d has a non-finite value", who, e); return VSLAM_ERR_INVALID; }
-        if (E.w_rot < 0 || E.w_trans < 0) { set_error("%s: edge %d has a negative weight", who, e); return VSLAM_ERR_INVALID; }
-    }
+    VS_CHECK(gba_check_args(who, Q, edges, M, result));
+    GbaPrep prep;
+    VS_CHECK(gba_prepare(who, Q, edges, M, prep));
+    const GbaPlan& G = prep.G;
+    std::vector<double>& hp = prep.hp;
+    const std::vector<double>& his = prep.his; const std::vector<double>& hthr = prep.hthr;
+    const std::vector<PgoEdge>& he = prep.he;
     const int nf = G.nf, b = G.b;
-    // device forms: poses [12], whitening and chi2 threshold per factor slot; the initial depth of every present factor
-    std::vector<double> hp((size_t)K * 12), his((size_t)std::max(P, 1) * 2, 0.0), hthr((size_t)std::max(P, 1) * 2, 0.0);
-    for (int k = 0; k < K; k++)
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) hp[(size_t)k * 12 + 3 * r + c] = Q.kf_pose_wc[(size_t)k * 16 + 4 * r + c]; hp[(size_t)k * 12 + 9 + r] = Q.kf_pose_wc[(size_t)k * 16 + 4 * r + 3]; }
-    for (int p = 0; p < P; p++) {
-        const int fl = Q.pair_flags[p] & 3, lm = Q.pair_lm[p];
-        if (!fl || !G.lmPresent[lm]) continue;
-        for (int side = 0; side < 2; side++) {
-            if (!((fl >> side) & 1)) continue;
-            const int oct = Q.pair_octave[2 * (size_t)p + side];
-            if (oct < 0 || oct >= Q.n_levels) { set_error("%s: pair %d has octave %d of %d levels", who, p, oct, Q.n_levels); return VSLAM_ERR_INVALID; }
-            if (!std::isfinite(Q.pair_uv[4 * (size_t)p + 2 * side]) || !std::isfinite(Q.pair_uv[4 * (size_t)p + 2 * side + 1])) { set_error("%s: pair %d has a non-finite measurement", who, p); return VSLAM_ERR_INVALID; }
-            his[2 * (size_t)p + side] = 1.0 / (1.0 / (double)Q.inv_sigma_factor[oct]);           // sigma = 1 / inv_sigma_factor
-            hthr[2 * (size_t)p + side] = (double)(float)((double)7.815f * (double)Q.sigma_factor[oct]);
-        }
-        const double* T = &hp[(size_t)Q.pair_kf[p] * 12];
-        const double* X = Q.lm_xyz + (size_t)lm * 3;
-        const double z = T[2] * (X[0] - T[9]) + T[5] * (X[1] - T[10]) + T[8] * (X[2] - T[11]);
-        if (!(z > 0.0)) { set_error("%s: pair %d (keyframe %d, landmark %d) is not in front of its camera at the initial values", who, p, Q.pair_kf[p], lm); return VSLAM_ERR_INVALID; }
-    }
-    std::vector<PgoEdge> he(std::max(M, 1), PgoEdge{});
-    for (int e = 0; e < M; e++) {
-        PgoEdge& o = he[e];
-        o.i = edges[e].i; o.j = edges[e].j; o.wr = edges[e].w_rot; o.wt = edges[e].w_trans;
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o.Rz[3 * r + c] = edges[e].Z[4 * r + c]; o.tz[r] = edges[e].Z[4 * r + 3]; }
-    }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
@@ -570,24 +591,201 @@ extern "C" vslam_status vslam_global_ba(const vslam_ba_problem* problem, const v
         g_gbaTimes.clear();
         for (int q = 0; q < k; q++) g_gbaTimes.push_back({names[q], ms[q]});
     }
-    // nothing is written before the last wait has returned; fixed and isolated keyframes and thin landmarks are the input's bytes
-    for (int k = 0; k < K; k++) {
-        double* o = result->kf_pose_wc + (size_t)k * 16;
-        const double* in = Q.kf_pose_wc + (size_t)k * 16;
-        if (G.pos[k] < 0) { if (o != in) memcpy(o, in, 128); continue; }
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o[4 * r + c] = hp[(size_t)k * 12 + 3 * r + c]; o[4 * r + 3] = hp[(size_t)k * 12 + 9 + r]; }
-        o[12] = o[13] = o[14] = 0.0; o[15] = 1.0;
+    // nothing is written before the last wait has returned
+    gba_write_out(Q, G, hp.data(), hl.data(), hw.data(), ctl, result);
+    return VSLAM_OK;
+}
+
+// Several problems (lanes) at once: one launch per stage for all of them, in the layout of pgo_solve (pgo.hip).  Host work per
+// lane is gba_check_args and gba_prepare, exactly the single call's; the lanes' arrays then go up as ONE block (table, control
+// blocks, the problems' and the plans' arrays) and the device's own arrays are one more block from the thread's cache.  A round is
+// one trial of every active lane and ends with one wait, for a single int (how many lanes are still active).  Nothing is written
+// before the last wait has returned, so a refusal leaves every lane's outputs alone.
+extern "C" vslam_status vslam_global_ba_batch(const vslam_gba_lane* lanes, int32_t n_lanes, const vslam_gba_params* params, int32_t device) {
+    static const char* const who = "vslam_global_ba_batch";
+    if (!lanes || n_lanes < 1) { set_error("%s: invalid arguments", who); return VSLAM_ERR_INVALID; }
+    if (n_lanes > GBA_MAX_LANES) { set_error("%s: %d lanes exceed the limit (%d)", who, n_lanes, GBA_MAX_LANES); return VSLAM_ERR_CAPACITY; }
+    int maxIt = 0;
+    double lambda0 = 0.0;
+    VS_CHECK(gba_check_params(who, params, &maxIt, &lambda0));
+    char lw[96];
+    auto lane_text = [&](int g) { snprintf(lw, sizeof lw, "%s: lane %d", who, g); return lw; };
+    std::vector<int> live;                  // the lanes that hold a problem, in call order: the device's lanes
+    std::vector<GbaLaneShape> shape;
+    for (int g = 0; g < n_lanes; g++) {
+        const vslam_gba_lane& Ln = lanes[g];
+        if (!Ln.problem || Ln.problem->n_kf == 0) continue;
+        if (!Ln.result) { set_error("%s: no result", lane_text(g)); return VSLAM_ERR_INVALID; }
+        VS_CHECK(gba_check_args(lane_text(g), *Ln.problem, Ln.edges, Ln.n_edges, Ln.result));
+        GbaLaneShape S;
+        S.K = Ln.problem->n_kf; S.L = Ln.problem->n_lm; S.P = Ln.problem->n_pairs; S.M = Ln.n_edges;
+        shape.push_back(S);
+        live.push_back(g);
     }
-    for (int l = 0; l < L; l++) {
-        double* o = result->lm_xyz + (size_t)l * 3;
-        const double* in = G.lmPresent[l] ? &hl[(size_t)l * 3] : Q.lm_xyz + (size_t)l * 3;
-        if (o != in) memcpy(o, in, 24);
+    const int nl = (int)live.size();
+    std::string err;
+    if (const int st = gba_pack_check_sizes(shape.data(), nl, &err)) { set_error("%s: %s", who, err.c_str()); return (vslam_status)st; }
+    std::vector<GbaPrep> prep(nl);
+    for (int l = 0; l < nl; l++) {
+        const vslam_gba_lane& Ln = lanes[live[l]];
+        VS_CHECK(gba_prepare(lane_text(live[l]), *Ln.problem, Ln.edges, Ln.n_edges, prep[l]));
+        const GbaPlan& G = prep[l].G;
+        const auto& rig = Ln.problem->rig;
+        GbaLaneShape& S = shape[l];
+        S.nf = G.nf; S.b = G.b; S.nBlk = G.nBlk; S.nInc = G.rowStart[G.nf]; S.nLmPairs = G.lmStart[S.L]; S.nList = G.blkStart.back();
+        S.hasUnknowns = (G.nf > 0 || G.nPresent > 0) ? 1 : 0;
+        S.fx = rig.fx; S.fy = rig.fy; S.cx = rig.cx; S.cy = rig.cy; S.bl = (double)rig.baseline;
     }
-    if (P) memcpy(result->pair_wrong, hw.data(), (size_t)P);
-    vslam_gba_report& R = result->report;
-    R = vslam_gba_report{};
-    R.accepted = ctl.accepted; R.rejected = ctl.rejected; R.iterations = ctl.accepted + ctl.rejected;
-    R.n_free = nf; R.n_isolated = G.nIso; R.n_present = G.nPresent; R.n_thin = G.nThin; R.n_factors = G.nFactors; R.half_bandwidth = b;
-    R.initial_cost = ctl.initial_cost; R.final_cost = ctl.cost; R.final_lambda = ctl.lambda;
+    if (nl == 0) return VSLAM_OK;           // (every lane idle: nothing to solve, nothing written)
+    std::vector<GbaLane> tab;
+    GbaPackSums S;
+    if (const int st = gba_pack(shape.data(), nl, tab, S, &err)) { set_error("%s: %s", who, err.c_str()); return (vslam_status)st; }
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (no CPU fallback)"); return VSLAM_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) { set_error("%s: no device %d", who, device); return VSLAM_ERR_INVALID; }
+    VS_HIP(hipSetDevice(device));
+    DevPool* pool = thread_pool(device);
+    if (!pool) { set_error("no device pool"); return VSLAM_ERR_HIP; }
+    pool->pending.clear();
+    hipStream_t st = pool->stream;
+
+    GbaLayout up, wk;                       // the upload block and the work block
+    const size_t sK = (size_t)S.K, sL = (size_t)S.L, sP = (size_t)S.P, sM = (size_t)S.M, sF = (size_t)S.nf, sB = (size_t)S.band * 36 * 8;
+    const size_t oTab = up.section(nl * sizeof(GbaLane)), oCtl = up.section(nl * sizeof(PgoCtl));
+    const size_t oE = up.section(sM * sizeof(PgoEdge)), oP0 = up.section(sK * 96), oL0 = up.section(sL * 24);
+    const size_t oPos = up.section(sK * 4), oRow = up.section((sF + nl) * 4), oInc = up.section((size_t)S.inc * 4);
+    const size_t oPk = up.section(sP * 4), oPl = up.section(sP * 4), oPf = up.section(sP), oUv = up.section(sP * 16);
+    const size_t oIs = up.section(sP * 16), oThr = up.section(sP * 16), oLoc = up.section(sK), oPres = up.section(sL);
+    const size_t oLs = up.section((sL + nl) * 4), oLp = up.section((size_t)S.lp * 4);
+    const size_t oBc = up.section((size_t)S.blk * 4), oBd = up.section((size_t)S.blk * 4), oBs = up.section(((size_t)S.blk + nl) * 4), oLi = up.section((size_t)S.list * 8);
+    const size_t oP1 = wk.section(sK * 96), oL1 = wk.section(sL * 24);
+    const size_t oJp = wk.section(sP * 24 * 8), oJl = wk.section(sP * 12 * 8), oRes = wk.section(sP * 4 * 8);
+    const size_t oCost = wk.section((sP * 2 + sM) * 8), oERes = wk.section(sM * 48), oEJi = wk.section(sM * 288), oEJj = wk.section(sM * 288);
+    const size_t oHinv = wk.section(sL * 72), oGl = wk.section(sL * 24), oW = wk.section(sP * 144), oY = wk.section(sP * 144);
+    const size_t oBandH = wk.section(sB), oBandL = wk.section(sB), oDiag = wk.section(sF * 48), oG = wk.section(sF * 48), oRhs = wk.section(sF * 48);
+    const size_t oDelta = wk.section(sF * 48 + sL * 24), oOut = wk.section((size_t)nl * 16), oFlagC = wk.section((size_t)nl * 4), oFlagL = wk.section((size_t)nl * 4);
+    const size_t oAct = wk.section(4), oWrong = wk.section(sP);
+    std::vector<uint8_t> hUp(up.bytes, 0);
+    auto put = [&](size_t at, const void* src, size_t n) { if (n) memcpy(hUp.data() + at, src, n); };
+    put(oTab, tab.data(), nl * sizeof(GbaLane));
+    int maxK = 0, maxL = 0, maxP = 0, maxM = 0, maxNf = 0, maxBlk = 0;
+    size_t maxBand = 0;                     // doubles of the largest lane's band
+    for (int l = 0; l < nl; l++) {
+        const vslam_ba_problem& Q = *lanes[live[l]].problem;
+        const GbaPrep& R = prep[l];
+        const GbaPlan& G = R.G;
+        const GbaLane& T = tab[l];
+        const size_t K = T.K, L = T.L, P = T.P, M = T.M, kf0 = T.kf0, lm0 = T.lm0, p0 = T.pair0, f0 = T.free0, b0 = T.blk0;
+        PgoCtl c0{};
+        c0.lambda = lambda0;
+        put(oCtl + l * sizeof(PgoCtl), &c0, sizeof c0);
+        put(oE + (size_t)T.edge0 * sizeof(PgoEdge), R.he.data(), M * sizeof(PgoEdge));
+        put(oP0 + kf0 * 96, R.hp.data(), K * 96); put(oL0 + lm0 * 24, Q.lm_xyz, L * 24);
+        put(oPos + kf0 * 4, G.pos.data(), K * 4); put(oRow + (f0 + l) * 4, G.rowStart.data(), (size_t)(G.nf + 1) * 4);
+        put(oInc + (size_t)T.inc0 * 4, G.inc.data(), (size_t)G.rowStart[G.nf] * 4);
+        put(oPk + p0 * 4, Q.pair_kf, P * 4); put(oPl + p0 * 4, Q.pair_lm, P * 4); put(oPf + p0, Q.pair_flags, P); put(oUv + p0 * 16, Q.pair_uv, P * 16);
+        put(oIs + p0 * 16, R.his.data(), P * 16); put(oThr + p0 * 16, R.hthr.data(), P * 16);
+        put(oLoc + kf0, Q.kf_local, K); put(oPres + lm0, G.lmPresent.data(), L);
+        put(oLs + (lm0 + l) * 4, G.lmStart.data(), (L + 1) * 4); put(oLp + (size_t)T.lp0 * 4, G.lmPairs.data(), (size_t)G.lmStart[L] * 4);
+        put(oBc + b0 * 4, G.blkC.data(), (size_t)G.nBlk * 4); put(oBd + b0 * 4, G.blkD.data(), (size_t)G.nBlk * 4);
+        put(oBs + (b0 + l) * 4, G.blkStart.data(), (size_t)(G.nBlk + 1) * 4);
+        put(oLi + (size_t)T.list0 * 8, G.list.data(), (size_t)G.blkStart.back() * 8);
+        maxK = std::max(maxK, T.K); maxL = std::max(maxL, T.L); maxP = std::max(maxP, T.P); maxM = std::max(maxM, T.M);
+        maxNf = std::max(maxNf, T.nf); maxBlk = std::max(maxBlk, T.nBlk);
+        maxBand = std::max(maxBand, (size_t)(T.b + 1) * T.nf * 36);
+    }
+    PoolBuf<uint8_t> dUp(pool), dWk(pool);
+    VS_HIP(dUp.up(hUp.data(), up.bytes)); VS_HIP(dWk.alloc(wk.bytes));
+    GbaDev B{};                             // where the concatenated arrays begin (the sizes and the camera are the lanes')
+    B.edges = (const PgoEdge*)(dUp.p + oE); B.pos = (const int*)(dUp.p + oPos); B.rowStart = (const int*)(dUp.p + oRow); B.inc = (const int*)(dUp.p + oInc);
+    B.pairKf = (const int*)(dUp.p + oPk); B.pairLm = (const int*)(dUp.p + oPl); B.pairFlags = dUp.p + oPf; B.pairUv = (const float*)(dUp.p + oUv);
+    B.pairIs = (const double*)(dUp.p + oIs); B.pairThr = (const double*)(dUp.p + oThr); B.kfLocal = dUp.p + oLoc; B.lmPresent = dUp.p + oPres;
+    B.lmStart = (const int*)(dUp.p + oLs); B.lmPairs = (const int*)(dUp.p + oLp);
+    B.blkC = (const int*)(dUp.p + oBc); B.blkD = (const int*)(dUp.p + oBd); B.blkStart = (const int*)(dUp.p + oBs); B.list = (const int*)(dUp.p + oLi);
+    const GbaLane* dTab = (const GbaLane*)(dUp.p + oTab);
+    PgoCtl* dCtl = (PgoCtl*)(dUp.p + oCtl);
+    auto W8 = [&](size_t at) { return (double*)(dWk.p + at); };
+    GbaWork Wb{};
+    Wb.P0 = (double*)(dUp.p + oP0); Wb.L0 = (double*)(dUp.p + oL0); Wb.P1 = W8(oP1); Wb.L1 = W8(oL1);
+    Wb.Jp = W8(oJp); Wb.Jl = W8(oJl); Wb.res = W8(oRes); Wb.cost = W8(oCost); Wb.eres = W8(oERes); Wb.eJi = W8(oEJi); Wb.eJj = W8(oEJj);
+    Wb.Hinv = W8(oHinv); Wb.gl = W8(oGl); Wb.W = W8(oW); Wb.Y = W8(oY); Wb.bandH = W8(oBandH); Wb.bandL = W8(oBandL);
+    Wb.diagH = W8(oDiag); Wb.g = W8(oG); Wb.rhs = W8(oRhs); Wb.delta = W8(oDelta); Wb.wrong = dWk.p + oWrong;
+    double* dOut = W8(oOut);
+    int* dFlagC = (int*)(dWk.p + oFlagC); int* dFlagL = (int*)(dWk.p + oFlagL); int* dAct = (int*)(dWk.p + oAct);
+
+    struct TimerOwner { StageTimer t; ~TimerOwner() { t.destroy(); } } timerOwner;      // (the events go on every return path)
+    StageTimer& timer = timerOwner.t;
+    timer.stream = st; timer.multi = true; timer.enabled = g_gbaTimingOn;
+    // grids are sized by the largest lane; a stage no lane has anything for is not launched
+    const dim3 gSlot(gba_grid((size_t)2 * maxP), nl), gEdge(gba_grid(maxM), nl), gLm(gba_grid(maxL), nl), gPair(gba_grid(maxP), nl), gKf(gba_grid(maxK), nl), B256(256);
+    int nActive = 0;
+    auto linearize = [&](int init) {
+        const int t = timer.begin("gba_linearize");
+        if (maxP) hipLaunchKernelGGL(k_gba_linearize_b, gSlot, B256, 0, st, dTab, dCtl, init, B, Wb);
+        if (maxM) hipLaunchKernelGGL(k_gba_edge_linearize_b, gEdge, B256, 0, st, dTab, dCtl, init, B, Wb);
+        timer.end(t);
+    };
+    auto decide = [&](int init, int t) -> vslam_status {        // closes the gba_cost group `t`, then the round's one wait
+        hipLaunchKernelGGL(k_gba_reduce_b, dim3(nl), dim3(PGO_RED_NT), 0, st, dTab, dCtl, init, Wb, dOut);
+        hipLaunchKernelGGL(k_gba_decide_b, dim3(1), dim3(GBA_MAX_LANES), 0, st, nl, init, maxIt, dTab, dCtl, dOut, dFlagC, dFlagL, dAct);
+        timer.end(t);
+        VS_HIP(hipGetLastError());
+        VS_HIP(pool->d2h(&nActive, dAct, sizeof(int)));
+        VS_HIP(pool->sync());
+        return VSLAM_OK;
+    };
+    linearize(1);
+    VS_CHECK(decide(1, timer.begin("gba_cost")));
+    while (nActive > 0) {       // one round
+        linearize(0);
+        int t = timer.begin("gba_landmarks");
+        if (maxL) hipLaunchKernelGGL(k_gba_landmark_b, gLm, B256, 0, st, dTab, dCtl, B, Wb, dFlagL);
+        if (maxP && maxNf) hipLaunchKernelGGL(k_gba_wy_b, gPair, B256, 0, st, dTab, dCtl, B, Wb);
+        timer.end(t);
+        t = timer.begin("gba_assemble");
+        if (maxNf) hipLaunchKernelGGL(k_gba_edge_columns_b, dim3(maxNf, nl), dim3(64), 0, st, dTab, dCtl, B, Wb);
+        if (maxBlk) hipLaunchKernelGGL(k_gba_gather_b, dim3(maxBlk, nl), dim3(64), 0, st, dTab, dCtl, B, Wb);
+        timer.end(t);
+        t = timer.begin("gba_band_chol");
+        if (maxNf) hipLaunchKernelGGL(k_gba_band_copy_b, dim3(gba_grid(maxBand), nl), B256, 0, st, dTab, dCtl, B, Wb);
+        hipLaunchKernelGGL(k_gba_band_chol_b, dim3(nl), dim3(PGO_CHOL_NT), 0, st, dTab, dCtl, Wb, dFlagC);
+        timer.end(t);
+        t = timer.begin("gba_back");
+        if (maxL) hipLaunchKernelGGL(k_gba_back_b, gLm, B256, 0, st, dTab, dCtl, B, Wb);
+        hipLaunchKernelGGL(k_gba_retract_b, gKf, B256, 0, st, dTab, dCtl, B, Wb);
+        timer.end(t);
+        t = timer.begin("gba_cost");
+        if (maxP) hipLaunchKernelGGL(k_gba_cost_b, gSlot, B256, 0, st, dTab, dCtl, B, Wb);
+        if (maxM) hipLaunchKernelGGL(k_gba_edge_cost_b, gEdge, B256, 0, st, dTab, dCtl, B, Wb);
+        VS_CHECK(decide(0, t));
+    }
+    int t = timer.begin("gba_chi2");
+    if (maxP) hipLaunchKernelGGL(k_gba_chi2_b, gPair, B256, 0, st, dTab, dCtl, B, Wb);
+    timer.end(t);
+    VS_HIP(hipGetLastError());
+    std::vector<PgoCtl> ctl(nl);
+    VS_HIP(pool->d2h(ctl.data(), dCtl, nl * sizeof(PgoCtl)));
+    VS_HIP(pool->sync());
+    std::vector<double> hl(std::max<size_t>(sL, 1) * 3);
+    std::vector<uint8_t> hw(std::max<size_t>(sP, 1));
+    for (int l = 0; l < nl; l++) {
+        const GbaLane& T = tab[l];
+        VS_HIP(pool->d2h(prep[l].hp.data(), (ctl[l].cur ? Wb.P1 : Wb.P0) + (size_t)T.kf0 * 12, (size_t)T.K * 96));
+        if (T.L) VS_HIP(pool->d2h(hl.data() + (size_t)T.lm0 * 3, (ctl[l].cur ? Wb.L1 : Wb.L0) + (size_t)T.lm0 * 3, (size_t)T.L * 24));
+    }
+    if (sP) VS_HIP(pool->d2h(hw.data(), Wb.wrong, sP));
+    VS_HIP(pool->sync());
+    if (timer.enabled) {
+        const char* names[8]; float ms[8];
+        const int k = timer.read(names, ms, 8);
+        g_gbaTimes.clear();
+        for (int q = 0; q < k; q++) g_gbaTimes.push_back({names[q], ms[q]});
+    }
+    // nothing is written before the last wait has returned
+    for (int l = 0; l < nl; l++) {
+        const vslam_gba_lane& Ln = lanes[live[l]];
+        gba_write_out(*Ln.problem, prep[l].G, prep[l].hp.data(), hl.data() + (size_t)tab[l].lm0 * 3, hw.data() + tab[l].pair0, ctl[l], Ln.result);
+    }
     return VSLAM_OK;
 }

@@ -2,7 +2,8 @@
 // stage asked on the part of the map the tracker has left behind, a pose graph over the keyframes solved by
 // vslam_pose_graph_optimize, and the commit that hands the old copy of the place back to the tracker.  vslam_system_fuse_loop (item 26)
 // then makes one map point of each landmark the two visits both triangulated; vslam_system_global_ba (item 27) runs one bundle
-// adjustment over the whole map.
+// adjustment over the whole map.  Each of the three calls is a sequence of stages that vslam_batch (batch.hip) runs for its lanes
+// too, with the device work of all lanes in one batched call between them (items 25 and 28).
 #include "system.hpp"
 #include "fuse_host.hpp"
 #include <array>
@@ -253,28 +254,28 @@ vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_r
 }
 
 // The duplicate map points of a revisited place (vslam_hip.h): B = the non-outlier map points created up to latestKF - min_kf_gap,
-// A = those created since, vslam_fuse_search under the current camera, the commit of fuse_host.hpp.  mapMutex is held from the sets
-// to the commit: nothing may touch the map between them.
-vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
-    static const char* const fn = "vslam_system_fuse_loop";
-    if (!rep) return VSLAM_ERR_INVALID;
-    VS_CHECK(loop_check(fn));
-    vslam_fuse_loop_params P = prm ? *prm : vslam_fuse_loop_params{};
+// A = those created since, vslam_fuse_search under the current camera, the commit of fuse_host.hpp.  In stages, shared with
+// vslam_batch_fuse_loop: fuse_check (the refusals), fuse_sets (the two sets and their upload arrays), the search, fuse_commit.
+// mapMutex is held by one holder from fuse_sets to fuse_commit: nothing may touch the map between them.
+bool vslam_sys::resolve_fuse_loop_params(const char* fn, const vslam_fuse_loop_params* prm, vslam_fuse_loop_params& P) {
+    P = prm ? *prm : vslam_fuse_loop_params{};
     const vslam_fuse_params& S = P.search;
     if (P.min_kf_gap < 0 || S.max_hamming < 0 || !(S.radius >= 0) || !(S.depth_ratio >= 0) || !std::isfinite(S.radius) || !std::isfinite(S.depth_ratio)) {
-        set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID;
+        set_error("%s: negative or non-finite parameter", fn); return false;
     }
-    if (S.depth_ratio > 0 && S.depth_ratio < 1) { set_error("%s: depth_ratio %g lies inside (0, 1)", fn, (double)S.depth_ratio); return VSLAM_ERR_INVALID; }
+    if (S.depth_ratio > 0 && S.depth_ratio < 1) { set_error("%s: depth_ratio %g lies inside (0, 1)", fn, (double)S.depth_ratio); return false; }
     if (P.min_kf_gap == 0) P.min_kf_gap = 20;
-    *rep = vslam_fuse_loop_report{};
-    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
-    VS_HIP(hipSetDevice(cfg.device));
-    std::lock_guard<std::mutex> lk(mapMutex);
+    return true;
+}
+
+// stage 1 (mapMutex held): a finished local BA is propagated, then the sets A and B, their positions and descriptors, the lane of the search
+vslam_status vslam_system::fuse_sets(const vslam_fuse_loop_params& P, vslam_fuse_loop_report* rep, FuseSets& F) {
     if (LBADone) {                                         // a finished local BA is propagated first, as the next frame would
         VS_CHECK(change_poses_lca(endLBAIdx));
         LBADone = false;
     }
-    std::vector<int> idA, idB;
+    std::vector<int>& idA = F.idA; std::vector<int>& idB = F.idB;
+    idA.clear(); idB.clear();
     const long long newest = (long long)latestKF - P.min_kf_gap;
     for (int m = 0; m < (int)mapPoints.size(); m++) {
         if (mpOutlier[m]) continue;
@@ -285,8 +286,9 @@ vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fu
     const int nA = (int)idA.size(), nB = (int)idB.size();
     rep->n_a = nA; rep->n_b = nB;
     fusedPairs.clear();
-    std::vector<double> xyz(3 * (size_t)(nA + nB) + 1);
-    std::vector<uint8_t> desc(32 * (size_t)(nA + nB) + 1);
+    std::vector<double>& xyz = F.xyz; std::vector<uint8_t>& desc = F.desc;
+    xyz.assign(3 * (size_t)(nA + nB) + 1, 0.0);
+    desc.assign(32 * (size_t)(nA + nB) + 1, 0);
     auto fill = [&](const std::vector<int>& ids, size_t at) {
         for (size_t j = 0; j < ids.size(); j++) {
             const SysMP& mp = mapPoints[ids[j]];
@@ -295,14 +297,20 @@ vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fu
         }
     };
     fill(idA, 0); fill(idB, (size_t)nA);
-    std::vector<int> match(std::max(nA, 1), -1), best(4 * (size_t)std::max(nA, 1), 0);
-    VS_CHECK(vslam_fuse_search(camPoseInv.data(), cfg.rig.fx, cfg.rig.fy, cfg.rig.cx, cfg.rig.cy, cfg.rig.width, cfg.rig.height,
-                               xyz.data(), desc.data(), nA, xyz.data() + 3 * (size_t)nA, desc.data() + 32 * (size_t)nA, nB,
-                               &P.search, cfg.device, match.data(), best.data(), &rep->search));
+    F.match.assign(std::max(nA, 1), -1); F.best.assign(4 * (size_t)std::max(nA, 1), 0);
+    F.T_cw = camPoseInv;
+    F.lane = vslam_fuse_lane{F.T_cw.data(), cfg.rig.fx, cfg.rig.fy, cfg.rig.cx, cfg.rig.cy, cfg.rig.width, cfg.rig.height,
+                             xyz.data(), desc.data(), nA, xyz.data() + 3 * (size_t)nA, desc.data() + 32 * (size_t)nA, nB, F.match.data(), F.best.data()};
+    return VSLAM_OK;
+}
+
+// stage 3 (mapMutex held): the search's matches into the map
+void vslam_system::fuse_commit(const FuseSets& F, vslam_fuse_loop_report* rep) {
+    const int nA = (int)F.idA.size();
     std::vector<std::pair<int, int>> pairs;                // ascending a: idA is in creation order
-    for (int j = 0; j < nA; j++) if (match[j] >= 0) pairs.push_back({idA[j], idB[match[j]]});
+    for (int j = 0; j < nA; j++) if (F.match[j] >= 0) pairs.push_back({F.idA[j], F.idB[F.match[j]]});
     rep->n_active_after = (int)active.size();
-    if (pairs.empty()) return VSLAM_OK;
+    if (pairs.empty()) return;
     const vslam_fuse::CommitCounts c = vslam_fuse::merge_observations(pairs, mapPoints, keyFrames, mpOutlier, mpInFrame);
     for (int k : c.refresh) calc_connections(keyFrames[k]);
     vslam_fuse::merge_active(pairs, mapPoints.size(), active, mpInFrame);
@@ -311,17 +319,39 @@ vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fu
     rep->n_fused = c.nFused; rep->n_obs_moved = c.nMoved; rep->n_obs_dropped = c.nDropped;
     rep->n_keyframes_touched = (int)c.touched.size();
     rep->n_active_after = (int)active.size();
+}
+
+vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
+    static const char* const fn = "vslam_system_fuse_loop";
+    if (!rep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check(fn));
+    vslam_fuse_loop_params P;
+    if (!resolve_fuse_loop_params(fn, prm, P)) return VSLAM_ERR_INVALID;
+    *rep = vslam_fuse_loop_report{};
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    VS_HIP(hipSetDevice(cfg.device));
+    std::lock_guard<std::mutex> lk(mapMutex);
+    FuseSets F;
+    VS_CHECK(fuse_sets(P, rep, F));
+    const vslam_fuse_lane& Q = F.lane;
+    VS_CHECK(vslam_fuse_search(Q.T_cw, Q.fx, Q.fy, Q.cx, Q.cy, Q.w, Q.h, Q.a_xyz, Q.a_desc, Q.n_a, Q.b_xyz, Q.b_desc, Q.n_b,
+                               &P.search, cfg.device, Q.match, Q.best, &rep->search));
+    fuse_commit(F, rep);
     return VSLAM_OK;
 }
 
 // ---- vslam_system_global_ba (vslam_hip.h) ------------------------------------------------------
-vslam_status vslam_system::gba_check(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const {
-    VS_CHECK(loop_check(fn));
+bool vslam_sys::resolve_system_gba_params(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) {
     P = prm ? *prm : vslam_system_gba_params{};
     if (P.gba.max_iterations < 0 || !(P.gba.lambda0 >= 0.0) || !std::isfinite(P.gba.lambda0) || !(P.edge_weight >= 0.0) || !std::isfinite(P.edge_weight)) {
-        set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID;
+        set_error("%s: negative or non-finite parameter", fn); return false;
     }
-    return VSLAM_OK;
+    return true;
+}
+
+vslam_status vslam_system::gba_check(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const {
+    VS_CHECK(loop_check(fn));
+    return resolve_system_gba_params(fn, prm, P) ? VSLAM_OK : VSLAM_ERR_INVALID;
 }
 
 // A map point whose observation rays never open wider than this at the current values carries no factor: its depth is not
@@ -437,6 +467,30 @@ void vslam_system::gba_commit(GbaFlat& F, vslam_system_gba_report* rep, std::vec
     rep->n_wrong = nWrong; rep->n_outliers = nOut;
 }
 
+// steps 6 and 7 up to the camera (mapMutex held): the commit, the refresh request of the moved points, every refPose, the camera
+vslam_status vslam_system::gba_finish(GbaFlat& F, vslam_system_gba_report* rep) {
+    std::vector<int> upd;
+    gba_commit(F, rep, upd);
+    VS_CHECK(ba_request_refresh(upd));
+    for (int k = 0; k < (int)keyFrames.size(); k++) {
+        const int p = keyFrames[k].prevKF;
+        if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
+    }
+    lca_finish(latestKF);
+    return VSLAM_OK;
+}
+
+// the end of step 7 (takes mapMutex itself): the active set under the new camera pose
+vslam_status vslam_system::gba_activate(vslam_system_gba_report* rep) {
+    vslam_loop_report lr{};
+    VS_CHECK(loop_activate(&lr));
+    rep->n_active_after = lr.n_active_after;
+    rep->success = 1;
+    return VSLAM_OK;
+}
+
+// The stages are shared with vslam_batch_global_ba: gba_check, gba_flatten, the solve, gba_finish, gba_activate.  mapMutex is held by
+// one holder from gba_flatten to gba_finish.
 vslam_status vslam_system::global_ba(const vslam_system_gba_params* prm, vslam_system_gba_report* rep) {
     static const char* const fn = "vslam_system_global_ba";
     if (!rep) return VSLAM_ERR_INVALID;
@@ -455,20 +509,9 @@ vslam_status vslam_system::global_ba(const vslam_system_gba_params* prm, vslam_s
         R.kf_pose_wc = F.kfOut.data(); R.lm_xyz = F.lmOut.data(); R.pair_wrong = F.wrong.data();
         VS_CHECK(vslam_global_ba(&F.P, F.edges.empty() ? nullptr : F.edges.data(), (int)F.edges.size(), &P.gba, cfg.device, &R));
         rep->gba = R.report;
-        std::vector<int> upd;
-        gba_commit(F, rep, upd);
-        VS_CHECK(ba_request_refresh(upd));
-        for (int k = 0; k < (int)keyFrames.size(); k++) {
-            const int p = keyFrames[k].prevKF;
-            if (p >= 0) keyFrames[k].refPose = m4_mul(keyFrames[p].poseInv, keyFrames[k].pose);
-        }
-        lca_finish(latestKF);
+        VS_CHECK(gba_finish(F, rep));
     }
-    vslam_loop_report lr{};
-    VS_CHECK(loop_activate(&lr));
-    rep->n_active_after = lr.n_active_after;
-    rep->success = 1;
-    return VSLAM_OK;
+    return gba_activate(rep);
 }
 
 extern "C" {

@@ -320,6 +320,18 @@ struct vslam_system {
     // the current camera, the commit of fuse_host.hpp.  fusedPairs: the (absorbed, kept) pairs of the last call (test tap)
     std::vector<int> fusedPairs;
     vslam_status fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep);
+    // fuse_loop's stages.  The single call runs them back to back; vslam_batch_fuse_loop runs fuse_sets for every lane, ONE
+    // vslam_fuse_search_batch call, then fuse_commit per lane.  Both are called with mapMutex held (by one holder across both).
+    struct FuseSets {                              // (lane points into the other members: a filled FuseSets is not moved)
+        std::vector<int> idA, idB;                 // map-point indices of the two sets
+        std::vector<double> xyz;                   // [nA + nB][3], A first
+        std::vector<uint8_t> desc;                 // [nA + nB][32]
+        std::vector<int> match, best;              // the search's outputs: [nA], [nA][4]
+        M4 T_cw;
+        vslam_fuse_lane lane{};
+    };
+    vslam_status fuse_sets(const vslam_fuse_loop_params& P, vslam_fuse_loop_report* rep, FuseSets& F);
+    void fuse_commit(const FuseSets& F, vslam_fuse_loop_report* rep);
     // one vslam_global_ba over the whole map: the flattened problem (mapMutex held), the call, the commit
     struct GbaFlat {
         std::vector<double> kfPose, lm, kfOut, lmOut;
@@ -334,6 +346,11 @@ struct vslam_system {
     vslam_status gba_check(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const;
     vslam_status gba_flatten(double edgeWeight, GbaFlat& F);
     void gba_commit(GbaFlat& F, vslam_system_gba_report* rep, std::vector<int>& upd);
+    // global_ba's stages after the solve.  The single call runs gba_check, gba_flatten, vslam_global_ba, gba_finish and gba_activate
+    // back to back; vslam_batch_global_ba runs gba_flatten for every lane, ONE vslam_global_ba_batch call, then gba_finish and
+    // gba_activate per lane.  gba_flatten and gba_finish are called with mapMutex held (by one holder across both).
+    vslam_status gba_finish(GbaFlat& F, vslam_system_gba_report* rep);      // commit, refresh request, every refPose, the camera
+    vslam_status gba_activate(vslam_system_gba_report* rep);                // the active set (takes mapMutex itself); success = 1
     vslam_status global_ba(const vslam_system_gba_params* prm, vslam_system_gba_report* rep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
@@ -404,5 +421,8 @@ namespace vslam_sys {
 // loop.hip, shared with the batched calls of batch.hip: the defaults and ranges of vslam_loop_params (false: out of range); the
 // report's drift fields from the corrected pose
 bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P);
+// vslam_system_fuse_loop's parameters with the defaults in; false with the error text set (fn names the call)
+bool resolve_fuse_loop_params(const char* fn, const vslam_fuse_loop_params* prm, vslam_fuse_loop_params& P);
+bool resolve_system_gba_params(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P);
 void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep);
 }  // namespace vslam_sys

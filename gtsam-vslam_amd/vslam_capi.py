@@ -723,6 +723,18 @@ def _gba_report_dict(rep):
     return {f[0]: getattr(rep, f[0]) for f in GbaReport._fields_ if f[0] != "reserved"}
 
 
+def _system_gba_report_dict(rep):
+    d = {f[0]: getattr(rep, f[0]) for f in SystemGbaReport._fields_ if f[0] not in ("gba", "reserved")}
+    d["gba"] = _gba_report_dict(rep.gba)
+    return d
+
+
+def _fuse_loop_report_dict(rep):
+    d = {f[0]: getattr(rep, f[0]) for f in FuseLoopReport._fields_ if f[0] != "search"}
+    d["search"] = _fuse_report_dict(rep.search)
+    return d
+
+
 def global_ba(rig, sigma_factor, inv_sigma_factor, prob, edges=None, max_iterations=0, lambda0=0.0, device=0):
     """vslam_global_ba on a flattened problem dict (the keys local_ba takes; kf_id may be missing: it is not used) with optional
     relative-pose edges as pgo_edges takes them (or its array).  Returns dict(kf_pose, lm, pair_wrong, report)."""
@@ -741,12 +753,58 @@ def global_ba(rig, sigma_factor, inv_sigma_factor, prob, edges=None, max_iterati
     return dict(kf_pose=kfOut[:n_kf], lm=lmOut[:n_lm], pair_wrong=wrong[:n_pairs], report=_gba_report_dict(R.report))
 
 
+class GbaLane(C.Structure):
+    _fields_ = [("problem", C.POINTER(BaProblem)), ("edges", C.c_void_p), ("n_edges", C.c_int32), ("result", C.POINTER(GbaResult))]
+
+
+def global_ba_batch(lanes, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_global_ba_batch: lanes = [None (an idle lane) or dict(rig, sigma_factor, inv_sigma_factor, prob, edges=None,
+    out=None, in_place=False), ...], one parameter set for all.  prob and edges are what global_ba takes.  out: dict(kf_pose
+    (K, 4, 4) float64, lm (L, 3) float64, pair_wrong (P) uint8) of the caller's own C-contiguous arrays for the call to write into
+    (default: fresh arrays); in_place: the result arrays are the problem's own (its kf_pose and lm must be C-contiguous float64
+    arrays, which are then overwritten).  Returns [None or dict(kf_pose, lm, pair_wrong, report), ...]."""
+    B = len(lanes)
+    tab = (GbaLane * max(B, 1))()
+    keep, outs = [], [None] * B
+    for g, ln in enumerate(lanes):
+        if ln is None:
+            continue
+        prob = ln["prob"]
+        if "kf_id" not in prob:
+            prob = dict(prob, kf_id=np.arange(len(prob["kf_pose"]), dtype=np.int64))
+        P, _, kp = ba_problem_structs(ln["rig"], ln["sigma_factor"], ln["inv_sigma_factor"], prob)
+        edges = ln.get("edges")
+        m = 0 if edges is None else len(edges)
+        ea = None if m == 0 else (edges if isinstance(edges, np.ndarray) else pgo_edges(edges))
+        n_kf, n_lm, n_pairs = P.n_kf, P.n_lm, P.n_pairs
+        if ln.get("in_place"):
+            kfOut, lmOut = kp["arrays"][0], kp["arrays"][4]
+            assert kfOut.ctypes.data == np.asarray(prob["kf_pose"]).ctypes.data and (n_lm == 0 or lmOut.ctypes.data == np.asarray(prob["lm"]).ctypes.data)
+            kfOut = kfOut.reshape(-1, 4, 4)
+            wrong = np.zeros(max(n_pairs, 1), np.uint8)
+        elif ln.get("out") is not None:
+            kfOut, lmOut, wrong = ln["out"]["kf_pose"], ln["out"]["lm"], ln["out"]["pair_wrong"]
+            for a, dt, n in ((kfOut, np.float64, n_kf * 16), (lmOut, np.float64, n_lm * 3), (wrong, np.uint8, n_pairs)):
+                assert a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size >= n
+        else:
+            kfOut = np.zeros((max(n_kf, 1), 4, 4)); lmOut = np.zeros((max(n_lm, 1), 3)); wrong = np.zeros(max(n_pairs, 1), np.uint8)
+        R = GbaResult()
+        R.kf_pose_wc, R.lm_xyz, R.pair_wrong = _p(kfOut), _p(lmOut), _p(wrong)
+        keep.append((P, R, kp, ea))
+        outs[g] = (R, kfOut[:n_kf], lmOut[:n_lm], wrong[:n_pairs])
+        tab[g] = GbaLane(C.pointer(P), None if ea is None else ea.ctypes.data, m, C.pointer(R))
+    prm = GbaParams(int(max_iterations), float(lambda0))
+    _chk(lib().vslam_global_ba_batch(tab, B, C.byref(prm), int(device)))
+    return [None if o is None else dict(kf_pose=o[1], lm=o[2], pair_wrong=o[3], report=_gba_report_dict(o[0].report)) for o in outs]
+
+
 def global_ba_set_timing(on):
     _chk(lib().vslam_global_ba_set_timing(int(bool(on))))
 
 
 def global_ba_timings():
-    """kernel group -> device ms of this thread's last global_ba (after global_ba_set_timing(True))"""
+    """kernel group -> device ms of this thread's last global_ba or global_ba_batch (after global_ba_set_timing(True)); a batched
+    call's figures cover all its lanes"""
     names = (C.c_char_p * 8)(); ms = (C.c_float * 8)(); n = C.c_int32()
     _chk(lib().vslam_global_ba_timings(names, ms, 8, C.byref(n)))
     return {names[i].decode(): float(ms[i]) for i in range(n.value)}
@@ -1508,6 +1566,13 @@ class System:
     def fuse_loop(self, **params):
         """vslam_system_fuse_loop: the duplicate map points of the place the camera sees become one.  params: radius, depth_ratio,
         max_hamming, min_kf_gap.  Returns the report dict (busy: nothing was done)."""
+        prm = self._fuse_loop_params(params)
+        rep = FuseLoopReport()
+        _chk(self.L.vslam_system_fuse_loop(self.h_sys, C.byref(prm), C.byref(rep)))
+        return _fuse_loop_report_dict(rep)
+
+    @staticmethod
+    def _fuse_loop_params(params):
         prm = FuseLoopParams()
         for k, v in params.items():
             if k == "min_kf_gap":
@@ -1516,11 +1581,7 @@ class System:
                 prm.search.max_hamming = int(v)
             else:
                 setattr(prm.search, k, float(v))     # radius, depth_ratio
-        rep = FuseLoopReport()
-        _chk(self.L.vslam_system_fuse_loop(self.h_sys, C.byref(prm), C.byref(rep)))
-        d = {f[0]: getattr(rep, f[0]) for f in FuseLoopReport._fields_ if f[0] != "search"}
-        d["search"] = _fuse_report_dict(rep.search)
-        return d
+        return prm
 
     def map_point_descriptors(self):
         """test tap: (n, 32) descriptor bytes of every map point, creation order"""
@@ -1558,9 +1619,7 @@ class System:
         prm = SystemGbaParams(GbaParams(int(max_iterations), float(lambda0)), float(edge_weight))
         rep = SystemGbaReport()
         _chk(self.L.vslam_system_global_ba(self.h_sys, C.byref(prm), C.byref(rep)))
-        d = {f[0]: getattr(rep, f[0]) for f in SystemGbaReport._fields_ if f[0] not in ("gba", "reserved")}
-        d["gba"] = _gba_report_dict(rep.gba)
-        return d
+        return _system_gba_report_dict(rep)
 
     def global_ba_problem(self, edge_weight=0.0):
         """test tap: (problem dict as global_ba takes it, plus lm_index, sigma_factor and inv_sigma_factor; edges array) that
@@ -1883,9 +1942,10 @@ def _report_dict(rep):
 class _BorrowedSystem(System):
     """a lane's vslam_system (owned by the batch): the read-out methods of System"""
 
-    def __init__(self, L, handle):      # noqa: super().__init__ creates a session; this one is borrowed
+    def __init__(self, L, handle, rig=None):      # noqa: super().__init__ creates a session; this one is borrowed
         self.L = L
         self.h_sys = C.c_void_p(handle)
+        self.rig = rig                  # (global_ba_problem hands it on)
 
     def close(self):
         self.h_sys = C.c_void_p()
@@ -2106,6 +2166,24 @@ class Batch:
         _chk(self.L.vslam_batch_correct_loop(self.h_b, _p(mk), _p(kf), _p(T), C.byref(prm), reps))
         return [_loop_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
 
+    def fuse_loop(self, mask=None, **params):
+        """vslam_batch_fuse_loop: per masked lane (None: all) what System.fuse_loop does, the searches of all lanes in one batched
+        call.  params as System.fuse_loop.  Returns the per-lane report dicts (None for lanes outside the mask)."""
+        mk = self._loop_mask(mask)
+        reps = (FuseLoopReport * self.lanes)()
+        prm = System._fuse_loop_params(params)
+        _chk(self.L.vslam_batch_fuse_loop(self.h_b, _p(mk), C.byref(prm), reps))
+        return [_fuse_loop_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
+
+    def global_ba(self, mask=None, edge_weight=0.0, max_iterations=0, lambda0=0.0):
+        """vslam_batch_global_ba: per masked lane (None: all) what System.global_ba does, the solves of all lanes in one batched
+        call.  Returns the per-lane report dicts (None for lanes outside the mask)."""
+        mk = self._loop_mask(mask)
+        reps = (SystemGbaReport * self.lanes)()
+        prm = SystemGbaParams(GbaParams(int(max_iterations), float(lambda0)), float(edge_weight))
+        _chk(self.L.vslam_batch_global_ba(self.h_b, _p(mk), C.byref(prm), reps))
+        return [_system_gba_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
+
     def relocalize_debug(self, lane):
         """Matcher.relocalize_debug of lane `lane`: its part of the last relocalize call (test tap)"""
         return _reloc_debug(lambda *a: self.L.vslam_batch_relocalize_debug(self.h_b, int(lane), *a))
@@ -2124,7 +2202,7 @@ class Batch:
         return bk
 
     def system(self, lane):
-        return _BorrowedSystem(self.L, self.L.vslam_batch_system(self.h_b, lane))
+        return _BorrowedSystem(self.L, self.L.vslam_batch_system(self.h_b, lane), self.rigs[lane])
 
     def wait_mapping(self):
         _chk(self.L.vslam_batch_wait_mapping(self.h_b))

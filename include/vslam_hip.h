@@ -579,9 +579,31 @@ typedef struct vslam_gba_result {
 
 vslam_status vslam_global_ba(const struct vslam_ba_problem* problem, const vslam_pgo_edge* edges, int32_t n_edges,
                              const vslam_gba_params* params, int32_t device, vslam_gba_result* result);
+/* vslam_global_ba_batch: several problems (lanes) at once, one launch per stage for all of them (csrc/gba.hip, the layout of
+ * vslam_pose_graph_optimize_batch).  THE RULE: a lane's poses, landmarks, pair_wrong and report are, byte for byte, what
+ * vslam_global_ba returns for that problem alone with the same params; the order and company of the lanes do not matter.  The
+ * kernels of both calls run the same __device__ bodies (csrc/gba_dev.hpp) - the batched ones on a lane's part of concatenated
+ * arrays, with the lane as a grid dimension, the lane's own camera (lanes may have different rigs) and the lane's own
+ * Levenberg-Marquardt state and pivot flags.  A ROUND is one trial of every active lane: linearise, landmarks, W / Y, the
+ * edges' columns and the gather (grids sized by the largest lane), band copy, the factorisation (k_gba_band_chol_b: one
+ * workgroup per lane, so the lanes' dependency chains run side by side), back-substitution, retraction, cost, the per-lane
+ * fixed-order sum (k_gba_reduce_b) and the rule (k_gba_decide_b: a thread per lane).  A lane that has stopped costs its
+ * workgroups one load.  The host waits once per round, for one int: the number of lanes still active.  No floating-point atomics.
+ * VSLAM_ERR_INVALID, nothing launched, no lane written: n_lanes < 1, NULL lanes, a lane with a problem and no result, a bad
+ * parameter, or any lane the single call would refuse as invalid (the error text names the lane).
+ * VSLAM_ERR_CAPACITY, likewise: a lane beyond the single call's limits; n_lanes > 1024; in all lanes together more than 262144
+ * keyframes, 1048576 edges, 8388608 pairs, 4194304 landmarks, 1048576 band blocks (b + 1) * n_free or 67108864 block-list
+ * entries (every offset of the lane table is an element count that fits int32). */
+typedef struct vslam_gba_lane {            /* one lane; problem == NULL or problem->n_kf == 0: idle lane, nothing read or written */
+    const struct vslam_ba_problem* problem;
+    const vslam_pgo_edge* edges; int32_t n_edges;
+    vslam_gba_result* result;              /* as for vslam_global_ba; its arrays may be the problem's */
+} vslam_gba_lane;
+vslam_status vslam_global_ba_batch(const vslam_gba_lane* lanes, int32_t n_lanes, const vslam_gba_params* params, int32_t device);
 /* measurement hook of tools/gba_rate.py, in the form of the pose-graph one: device time (HIP events) per kernel group of the
- * calling thread's last vslam_global_ba - gba_linearize, gba_landmarks, gba_assemble, gba_band_chol, gba_back, gba_cost,
- * gba_chi2; off by default; thread-local state. */
+ * calling thread's last vslam_global_ba or vslam_global_ba_batch (a batched call's figures are those of all its lanes
+ * together) - gba_linearize, gba_landmarks, gba_assemble, gba_band_chol, gba_back, gba_cost, gba_chi2; off by default;
+ * thread-local state. */
 vslam_status vslam_global_ba_set_timing(int32_t on);
 vslam_status vslam_global_ba_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
 
@@ -1291,7 +1313,8 @@ vslam_status vslam_system_fused_pairs(vslam_system* sys, int32_t cap, int32_t* n
  *   7 refPose of every keyframe re-derived, the camera re-anchored on the latest keyframe, the active set rebuilt by
  *     relocalisation's rule (as vslam_system_correct_loop ends)
  * A refusal of vslam_global_ba (a free gauge, a point behind a keyframe) is returned as it is, with nothing changed.
- * Not for lanes of a vslam_batch, not called from vslam_system_close_loop or vslam_system_fuse_loop: the caller decides when. */
+ * Lanes of a vslam_batch have vslam_batch_global_ba (one batched solve for all of them); vslam_fleet lanes have neither yet.
+ * Not called from vslam_system_close_loop or vslam_system_fuse_loop: the caller decides when. */
 typedef struct vslam_system_gba_params {  /* a zero field takes the default in brackets (NULL = all defaults) */
     vslam_gba_params gba;
     double edge_weight;                   /* [0: no edges] */
@@ -1524,6 +1547,27 @@ vslam_status vslam_batch_correct_loop(vslam_batch* batch, const uint8_t* lane_ma
                                       vslam_loop_report* reports /* [lanes] */);
 vslam_status vslam_batch_close_loop(vslam_batch* batch, const uint8_t* lane_mask, const vslam_loop_params* params,
                                     vslam_loop_report* reports /* [lanes] */);
+/* The two calls that finish a lane's loop closing, between two steps, in the shape of vslam_batch_close_loop: per masked lane what
+ * vslam_system_fuse_loop, respectively vslam_system_global_ba, does to a session (their rules, reports and defaults), with the
+ * device work of all lanes in ONE batched call.
+ *   vslam_batch_fuse_loop  every masked lane's sets and upload arrays (its map locked from here to its commit), ONE
+ *                          vslam_fuse_search_batch call for all lanes that reach it, the commits.  vslam_system_fused_pairs on
+ *                          vslam_batch_system(lane) gives a lane's committed pairs.
+ *   vslam_batch_global_ba  every masked lane's flattened problem (its map locked from here to its commit; each lane with its own
+ *                          rig), ONE vslam_global_ba_batch call for all lanes that reach it - the lanes' factorisations run side by
+ *                          side - then per lane the commit, the refresh request, every refPose, the camera and the active set.
+ * A lane's outcome does not depend on the other lanes: a busy lane reports busy = 1 and is untouched; a lane with fewer than two
+ * keyframes reports as the session call does (fuse: no old set, nothing fused; global BA: success = 0).  Lanes outside the mask are
+ * not touched: session, matcher state, report entry.  reports [lanes]: written for the masked lanes.
+ * VSLAM_ERR_INVALID, nothing changed in any lane: a NULL mask or reports; an IMU batch; a negative or non-finite parameter
+ * (depth_ratio inside (0, 1)); a masked lane without a tracked frame (also a restarted lane; the message names the lane).  A
+ * refusal of the batched solve for any lane (a free gauge, a point behind its keyframe, a capacity limit) is returned as it is,
+ * its message naming the lane among those that reached the solve, with no lane changed.
+ * Neither is called from vslam_batch_close_loop: the caller decides when. */
+vslam_status vslam_batch_fuse_loop(vslam_batch* batch, const uint8_t* lane_mask, const vslam_fuse_loop_params* params,
+                                   vslam_fuse_loop_report* reports /* [lanes] */);
+vslam_status vslam_batch_global_ba(vslam_batch* batch, const uint8_t* lane_mask, const vslam_system_gba_params* params,
+                                   vslam_system_gba_report* reports /* [lanes] */);
 /* key slabs the batch has allocated in total (bytes), and how many of them sessions hold / the free list holds; any
  * pointer may be NULL */
 vslam_status vslam_batch_memory(vslam_batch* batch, int64_t* key_slab_bytes, int32_t* slabs_in_use, int32_t* slabs_free);

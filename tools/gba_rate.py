@@ -11,7 +11,12 @@ over the repetitions; the half-bandwidth b after the reordering, the trials, the
 HIP-event timing on, the device time per kernel group; microseconds of the factorisation group per block column and trial.
 Then one problem both bundle adjustments can run, 150 free keyframes of the same corridor: vslam_local_ba (two passes, dense
 reduced system) and vslam_global_ba side by side, with the time per LM trial of each.  Numbers only, no bar.
-usage: python tools/gba_rate.py [out.json] [calls] [reps]"""
+With --lanes N: N such corridors of unequal length (150 .. 250 free keyframes, evenly spread) as ONE vslam_global_ba_batch call
+against the same problems as N vslam_global_ba calls one after the other: two warm-up calls, `reps` repetitions, the wall clock of
+whole calls (upload, loop, download), the device time per kernel group of one more call of each kind, and whether every lane's
+bytes equal its single call's.  Writes profiles/gba_batch_rate.json.
+usage: python tools/gba_rate.py [out.json] [calls] [reps]
+       python tools/gba_rate.py --lanes N [out.json] [reps]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("gtsam-vslam_amd", "tests"):
@@ -73,7 +78,47 @@ def timed(fn, calls, reps):
     return dict(median=float(np.median(per)), min=float(min(per)), max=float(max(per)))
 
 
+def batch_main(n_lanes, argv):
+    out_path = argv[0] if argv else os.path.join(ROOT, "profiles", "gba_batch_rate.json")
+    reps = int(argv[1]) if len(argv) > 1 else 3
+    sizes = [int(round(v)) for v in np.linspace(150, 250, n_lanes)] if n_lanes > 1 else [200]
+    probs = [corridor(n, seed=10 + i) for i, n in enumerate(sizes)]
+    lanes = [dict(rig=p["rig"], sigma_factor=gr.SIGMA, inv_sigma_factor=gr.INV_SIGMA, prob=p) for p in probs]
+    single = lambda: [vc.global_ba(p["rig"], gr.SIGMA, gr.INV_SIGMA, p) for p in probs]
+    batch = lambda: vc.global_ba_batch(lanes)
+    a, b = single(), batch()
+    same = all(x[k].tobytes() == y[k].tobytes() for x, y in zip(a, b) for k in ("kf_pose", "lm", "pair_wrong")) and \
+        all(x["report"] == y["report"] for x, y in zip(a, b))
+    ms_single, ms_batch = timed(single, 1, reps), timed(batch, 1, reps)
+    longest = int(np.argmax([r["report"]["iterations"] * r["report"]["n_free"] for r in a]))
+    p = probs[longest]
+    ms_longest = timed(lambda: vc.global_ba(p["rig"], gr.SIGMA, gr.INV_SIGMA, p), 1, reps)
+    vc.global_ba_set_timing(True)
+    batch()
+    g_batch = vc.global_ba_timings()
+    g_single = {}
+    for p in probs:
+        vc.global_ba(p["rig"], gr.SIGMA, gr.INV_SIGMA, p)
+        for k, v in vc.global_ba_timings().items():
+            g_single[k] = g_single.get(k, 0.0) + v
+    vc.global_ba_set_timing(False)
+    res = dict(protocol="2 warm-up calls, %d repetitions, host clock around whole calls (upload, LM loop, download); kernel groups from HIP "
+                        "events of one more call of each kind (the single calls' groups summed over the lanes)" % reps,
+               lanes=n_lanes, free_keyframes=sizes, landmarks=[len(p["lm"]) for p in probs], pairs=[len(p["pair_kf"]) for p in probs],
+               half_bandwidth=[r["report"]["half_bandwidth"] for r in a], lm_trials=[r["report"]["iterations"] for r in a],
+               rounds=max(r["report"]["iterations"] for r in a), lanes_equal_single_calls_bitwise=bool(same),
+               ms_batched_call=ms_batch, ms_single_calls_together=ms_single, ms_longest_lane_alone=dict(ms_longest, lane=longest),
+               single_over_batched=ms_single["median"] / ms_batch["median"], batched_over_longest_lane=ms_batch["median"] / ms_longest["median"],
+               kernel_group_ms_batched=g_batch, kernel_group_ms_single_calls_summed=g_single)
+    print(json.dumps(res), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
+    if "--lanes" in sys.argv:
+        at = sys.argv.index("--lanes")
+        return batch_main(int(sys.argv[at + 1]), sys.argv[1:at] + sys.argv[at + 2:])
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "gba_rate.json")
     calls = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
