@@ -190,8 +190,9 @@ struct vslam_batch {
                             const vslam_reloc_params* prm, double* T_wc_out, vslam_reloc_report* reps, bool imuCall = false,
                             const vslam_imu_bucket* imu = nullptr, vslam_reloc_imu_report* ireps = nullptr);
     // correct: vslam_batch_correct_loop (kfLoop [B], T_wc_corrected [B][16]); else vslam_batch_close_loop (both null)
+    // ireps != null: the _imu forms for an IMU batch (the yaw-only correction of every masked lane about its own gravity)
     vslam_status loop(bool correct, const uint8_t* mask, const int32_t* kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm,
-                      vslam_loop_report* reps);
+                      vslam_loop_report* reps, vslam_loop_imu_report* ireps = nullptr);
     // what fuse_loop and global_ba refuse, in the order of loop(): the arguments and an IMU batch, (the parameters,) then any masked
     // lane's loop_check with the lane in the message; nothing has changed when one fails.  *nOn: masked lanes
     vslam_status followup_check_args(const char* fn, const uint8_t* mask, const void* reps) const;
@@ -976,11 +977,17 @@ vslam_status vslam_batch::relocalize(const uint8_t* const* L, const uint8_t* con
 // detection through the batched relocalisation stage (one launch per stage for all lanes that have candidates), ONE batched pose-graph
 // solve and ONE move-points launch for all lanes that reach the solve.  A lane's outcome does not depend on the other lanes: a busy lane
 // reports busy, a lane that finds nothing reports success = 0, both untouched.  Refusals come first and change nothing in any lane.
+// ireps != null: the _imu calls for an IMU batch - the same stages with every lane's claim projected
+// about its own gravity (loop_build_imu), ONE vslam_pose_graph_optimize_yaw_batch with each lane's axis, loop_hold_unmoved before
+// the move of the points and loop_commit_imu after it.
 vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t* kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm,
-                               vslam_loop_report* reps) {
-    const char* const fn = correct ? "vslam_batch_correct_loop" : "vslam_batch_close_loop";
+                               vslam_loop_report* reps, vslam_loop_imu_report* ireps) {
+    const bool imuCall = ireps != nullptr;
+    const char* const fn = imuCall ? (correct ? "vslam_batch_correct_loop_imu" : "vslam_batch_close_loop_imu")
+                                   : (correct ? "vslam_batch_correct_loop" : "vslam_batch_close_loop");
     if (!mask || !reps || (correct && (!kfLoop || !T_wc_corrected))) { set_error("%s: invalid arguments", fn); return VSLAM_ERR_INVALID; }
-    if (useImu) { set_error("%s: an IMU batch cannot close loops yet (its velocity and gravity frame would have to follow)", fn); return VSLAM_ERR_INVALID; }
+    if (useImu && !imuCall) { set_error("%s: an IMU batch cannot close loops yet (its velocity and gravity frame would have to follow)", fn); return VSLAM_ERR_INVALID; }
+    if (!useImu && imuCall) { set_error("%s: the batch has no IMU (vslam_batch_close_loop / _correct_loop serve it)", fn); return VSLAM_ERR_INVALID; }
     vslam_loop_params P;
     vslam_reloc_params RP{};
     if (!resolve_loop_params(prm, P)) { set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID; }
@@ -991,7 +998,7 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
         if (!mask[b]) continue;
         nOn++;
         snprintf(who, sizeof who, "%s: lane %d", fn, b);
-        VS_CHECK(sys[b]->loop_check(who));
+        VS_CHECK(imuCall ? sys[b]->loop_check_imu(who) : sys[b]->loop_check(who));
         if (correct) VS_CHECK(sys[b]->loop_check_correct(who, kfLoop[b], T_wc_corrected + 16 * (size_t)b));
         else VS_CHECK(sys[b]->loop_check_close(who));
     }
@@ -1010,6 +1017,7 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
         vslam_loop_report& r = reps[b];
         r = vslam_loop_report{};
         r.kf_loop = correct ? kfLoop[b] : -1;
+        if (imuCall) sys[b]->loop_imu_report_init(&ireps[b]);
         if (sys[b]->loop_busy()) { r.busy = 1; continue; }
         if (correct) {
             r.success = 1;
@@ -1085,6 +1093,7 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
             const M4 T_corr = m4_rigid_inv(m4_from(Tcw.data() + 16 * (size_t)b));
             loop_drift(T_corr, sys[b]->camPoseInv, &r);
             if (!P.detect_only) solve.push_back({b, best, T_corr});
+            else if (imuCall) loop_project_yaw(T_corr, sys[b]->camPose, sys[b]->camPoseInv, sys[b]->cfg.gravity, &ireps[b]);
         }
     }
     // ---- correction: every lane's graph, one solve, one move-points launch, the commits ---------------------------------------------
@@ -1092,6 +1101,7 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
         const int ns = (int)solve.size();
         std::vector<vslam_system::LoopGraph> G((size_t)ns);
         std::vector<vslam_pgo_graph> graphs((size_t)ns);
+        std::vector<vslam_pgo_yaw_graph> ygraphs((size_t)(imuCall ? ns : 0));
         std::vector<vslam_pgo_report> pr((size_t)ns);
         std::vector<PgoMoveGraph> mv((size_t)ns);
         {
@@ -1099,15 +1109,23 @@ vslam_status vslam_batch::loop(bool correct, const uint8_t* mask, const int32_t*
             for (int i = 0; i < ns; i++) {
                 vslam_system* s = sys[solve[i].lane];
                 locks.emplace_back(s->mapMutex);
-                VS_CHECK(s->loop_build(solve[i].kf, solve[i].T_corr, P, &reps[solve[i].lane], G[i]));
+                if (imuCall) VS_CHECK(s->loop_build_imu(solve[i].kf, solve[i].T_corr, P, &reps[solve[i].lane], &ireps[solve[i].lane], G[i]));
+                else VS_CHECK(s->loop_build(solve[i].kf, solve[i].T_corr, P, &reps[solve[i].lane], G[i]));
                 graphs[i] = vslam_pgo_graph{G[i].poses.data(), G[i].fixed.data(), G[i].K, G[i].edges.data(), (int32_t)G[i].edges.size(), G[i].fresh.data()};
                 mv[i] = PgoMoveGraph{G[i].xyz.data(), G[i].ref.data(), G[i].nMp, G[i].poses.data(), G[i].fresh.data(), G[i].K, G[i].moved.data()};
+                if (imuCall) { ygraphs[i].graph = graphs[i]; for (int k = 0; k < 3; k++) ygraphs[i].axis[k] = s->cfg.gravity[k]; }
             }
-            VS_CHECK(vslam_pose_graph_optimize_batch(graphs.data(), ns, &P.pgo, device, pr.data()));
+            if (imuCall) {
+                VS_CHECK(vslam_pose_graph_optimize_yaw_batch(ygraphs.data(), ns, &P.pgo, device, pr.data()));
+                for (int i = 0; i < ns; i++) loop_hold_unmoved(G[i]);
+            } else {
+                VS_CHECK(vslam_pose_graph_optimize_batch(graphs.data(), ns, &P.pgo, device, pr.data()));
+            }
             VS_CHECK(pgo_move_points_batch(mv.data(), ns, device));
             for (int i = 0; i < ns; i++) {
                 reps[solve[i].lane].pgo = pr[i];
-                sys[solve[i].lane]->loop_commit(G[i], &reps[solve[i].lane]);
+                if (imuCall) sys[solve[i].lane]->loop_commit_imu(G[i], &reps[solve[i].lane], &ireps[solve[i].lane]);
+                else sys[solve[i].lane]->loop_commit(G[i], &reps[solve[i].lane]);
             }
         }
         for (int i = 0; i < ns; i++) VS_CHECK(sys[solve[i].lane]->loop_activate(&reps[solve[i].lane]));
@@ -1289,6 +1307,20 @@ vslam_status vslam_batch_correct_loop(vslam_batch* b, const uint8_t* lane_mask, 
     if (!b) return VSLAM_ERR_INVALID;
     if (!kf_loop || !T_wc_corrected) { set_error("vslam_batch_correct_loop: invalid arguments"); return VSLAM_ERR_INVALID; }
     return b->loop(true, lane_mask, kf_loop, T_wc_corrected, params, reports);
+}
+
+vslam_status vslam_batch_correct_loop_imu(vslam_batch* b, const uint8_t* lane_mask, const int32_t* kf_loop, const double* T_wc_corrected,
+                                          const vslam_loop_params* params, vslam_loop_report* reports, vslam_loop_imu_report* imu_reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    if (!kf_loop || !T_wc_corrected || !imu_reports) { set_error("vslam_batch_correct_loop_imu: invalid arguments"); return VSLAM_ERR_INVALID; }
+    return b->loop(true, lane_mask, kf_loop, T_wc_corrected, params, reports, imu_reports);
+}
+
+vslam_status vslam_batch_close_loop_imu(vslam_batch* b, const uint8_t* lane_mask, const vslam_loop_params* params, vslam_loop_report* reports,
+                                        vslam_loop_imu_report* imu_reports) {
+    if (!b) return VSLAM_ERR_INVALID;
+    if (!imu_reports) { set_error("vslam_batch_close_loop_imu: invalid arguments"); return VSLAM_ERR_INVALID; }
+    return b->loop(false, lane_mask, nullptr, nullptr, params, reports, imu_reports);
 }
 
 vslam_status vslam_batch_close_loop(vslam_batch* b, const uint8_t* lane_mask, const vslam_loop_params* params, vslam_loop_report* reports) {

@@ -195,17 +195,9 @@ vslam_status vslam_system::loop_vote(const int* pairs, size_t n, const uint8_t* 
     return VSLAM_OK;
 }
 
-vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_report* rep) {
-    if (!rep) return VSLAM_ERR_INVALID;
-    VS_CHECK(loop_check("vslam_system_close_loop"));
-    vslam_loop_params P;
-    vslam_reloc_params RP;
-    if (!resolve_loop_params(prm, P)) { set_error("vslam_system_close_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
-    VS_CHECK(reloc_resolve_params(&P.reloc, RP));
-    VS_CHECK(loop_check_close("vslam_system_close_loop"));
-    *rep = vslam_loop_report{};
-    rep->kf_loop = -1;
-    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+// close_loop's detection, shared with close_loop_imu: candidates, the relocalisation stage on the frame the matcher holds, the vote.
+// rep->success and rep->kf_loop say whether a loop was found; T_corr is the claimed pose then.  Nothing of the session changes.
+vslam_status vslam_system::loop_detect(const char* fn, const vslam_loop_params& P, const vslam_reloc_params& RP, vslam_loop_report* rep, M4& T_corr) {
     const size_t n = (size_t)loop_candidates(P.min_kf_gap);
     rep->n_candidates = (int)n;
     rep->reloc.n_points = (int)n;
@@ -242,15 +234,176 @@ vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_r
         std::vector<uint8_t> flags(std::max(C, 1), 0);
         VS_CHECK(fm->relocalize_debug(nullptr, 0, nullptr, 0, nullptr, 0, flags.data(), C, nullptr));
         int best = -1;
-        VS_CHECK(loop_vote(pairs.data(), n, flags.data(), C, "vslam_system_close_loop", &best));
+        VS_CHECK(loop_vote(pairs.data(), n, flags.data(), C, fn, &best));
         if (best < 0) return VSLAM_OK;
         rep->kf_loop = best;
     }
     rep->success = 1;
-    const M4 T_corr = m4_rigid_inv(m4_from(T_cw));
+    T_corr = m4_rigid_inv(m4_from(T_cw));
     loop_drift(T_corr, camPoseInv, rep);
-    if (P.detect_only) return VSLAM_OK;
+    return VSLAM_OK;
+}
+
+vslam_status vslam_system::close_loop(const vslam_loop_params* prm, vslam_loop_report* rep) {
+    if (!rep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check("vslam_system_close_loop"));
+    vslam_loop_params P;
+    vslam_reloc_params RP;
+    if (!resolve_loop_params(prm, P)) { set_error("vslam_system_close_loop: negative or non-finite parameter"); return VSLAM_ERR_INVALID; }
+    VS_CHECK(reloc_resolve_params(&P.reloc, RP));
+    VS_CHECK(loop_check_close("vslam_system_close_loop"));
+    *rep = vslam_loop_report{};
+    rep->kf_loop = -1;
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    M4 T_corr;
+    VS_CHECK(loop_detect("vslam_system_close_loop", P, RP, rep, T_corr));
+    if (!rep->success || P.detect_only) return VSLAM_OK;
     return loop_apply(rep->kf_loop, T_corr, P, rep);
+}
+
+// ---- loop closing of a stereo + IMU session (vslam_hip.h): the yaw-only correction ------------------
+vslam_status vslam_system::loop_check_imu(const char* fn) const {
+    if (monoMode) { set_error("%s: a mono session cannot close loops (stereo fixes the scale of the correction)", fn); return VSLAM_ERR_INVALID; }
+    if (!cfg.use_imu) { set_error("%s: the session has no IMU (vslam_system_close_loop / _correct_loop serve it)", fn); return VSLAM_ERR_INVALID; }
+    if (relocPending) { set_error("%s: a two-phase relocalisation is pending (the session has a pose but no velocity yet)", fn); return VSLAM_ERR_INVALID; }
+    const double* g = cfg.gravity;
+    const double n2 = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+    if (!std::isfinite(n2) || !(n2 > 0.0)) { set_error("%s: the session's gravity is zero or not finite", fn); return VSLAM_ERR_INVALID; }
+    if (keyFrames.empty()) { set_error("%s: no tracked frame yet", fn); return VSLAM_ERR_INVALID; }
+    return VSLAM_OK;
+}
+
+// the rotation angle of R (row-major 3x3), accurate at small angles too: atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2)
+static double rotation_angle(const double* R) {
+    const double q[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    return std::atan2(0.5 * std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), 0.5 * (R[0] + R[4] + R[8] - 1.0));
+}
+
+// T' = [Exp(theta g) R_cam | t_corr] with theta the twist of D = T_corr * camPose^-1 about g = gravity / |gravity| (closed form)
+M4 vslam_sys::loop_project_yaw(const M4& T_corr, const M4& camPose, const M4& camPoseInv, const double* gravity, vslam_loop_imu_report* irep) {
+    const double nrm = std::sqrt(gravity[0] * gravity[0] + gravity[1] * gravity[1] + gravity[2] * gravity[2]);
+    const double g[3] = {gravity[0] / nrm, gravity[1] / nrm, gravity[2] / nrm};
+    const M4 D = m4_mul(T_corr, camPoseInv);
+    const double R[9] = {D[0], D[1], D[2], D[4], D[5], D[6], D[8], D[9], D[10]};
+    const double q[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    double Rg[3];
+    mat3_vec(R, g, Rg);
+    const double theta = std::atan2(g[0] * q[0] + g[1] * q[1] + g[2] * q[2], (R[0] + R[4] + R[8]) - (g[0] * Rg[0] + g[1] * Rg[1] + g[2] * Rg[2]));
+    const double w[3] = {theta * g[0], theta * g[1], theta * g[2]};
+    double Ex[9];
+    so3_expmap(w, Ex);
+    M4 Tp = m4_identity();
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) Tp[4 * r + c] = Ex[3 * r] * camPose[c] + Ex[3 * r + 1] * camPose[4 + c] + Ex[3 * r + 2] * camPose[8 + c];
+        Tp[4 * r + 3] = T_corr[4 * r + 3];
+    }
+    double E[9];                                           // R'^T R_corr: what the projection drops
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) E[3 * r + c] = Tp[r] * T_corr[c] + Tp[4 + r] * T_corr[4 + c] + Tp[8 + r] * T_corr[8 + c];
+    irep->yaw = theta;
+    irep->tilt_dropped = rotation_angle(E);
+    memcpy(irep->T_wc_projected, Tp.data(), 16 * sizeof(double));
+    return Tp;
+}
+
+// stage 1 (mapMutex held): a finished local BA is propagated (the projection needs the camera pose the graph will see), the claim
+// is projected, then loop_build on the projected pose
+vslam_status vslam_system::loop_build_imu(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep,
+                                          vslam_loop_imu_report* irep, LoopGraph& G) {
+    if (LBADone) {
+        VS_CHECK(change_poses_lca(endLBAIdx));
+        LBADone = false;
+    }
+    const M4 Tp = loop_project_yaw(T_corr, camPose, camPoseInv, cfg.gravity, irep);
+    G.camBefore = camPose;
+    return loop_build(kfLoop, Tp, P, rep, G);
+}
+
+// between the solve and the move of the map points: a map point whose first observing keyframe came back with the same bytes
+// is not touched
+void vslam_sys::loop_hold_unmoved(vslam_system::LoopGraph& G) {
+    G.nMoved = 0;
+    for (int m = 0; m < G.nMp; m++) {
+        const int r = G.ref[m];
+        if (r < 0) continue;
+        if (!memcmp(&G.poses[16 * (size_t)r], &G.fresh[16 * (size_t)r], 16 * sizeof(double))) G.ref[m] = -1;
+        else G.nMoved++;
+    }
+}
+
+// stage 3 (mapMutex held): loop_commit, then the world-frame IMU state follows the camera: dR = R_cam,new R_cam,old^T
+void vslam_system::loop_commit_imu(const LoopGraph& G, vslam_loop_report* rep, vslam_loop_imu_report* irep) {
+    loop_commit(G, rep);
+    double dR[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++)
+            dR[3 * r + c] = camPose[4 * r] * G.camBefore[4 * c] + camPose[4 * r + 1] * G.camBefore[4 * c + 1] + camPose[4 * r + 2] * G.camBefore[4 * c + 2];
+    double v[3], pv[3];
+    mat3_vec(dR, velocity, v);
+    mat3_vec(dR, predVelocity, pv);
+    for (int k = 0; k < 3; k++) { velocity[k] = v[k]; predVelocity[k] = pv[k]; irep->velocity[k] = v[k]; }
+}
+
+vslam_status vslam_system::loop_apply_imu(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, vslam_loop_imu_report* irep) {
+    VS_HIP(hipSetDevice(cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        LoopGraph G;
+        VS_CHECK(loop_build_imu(kfLoop, T_corr, P, rep, irep, G));
+        VS_CHECK(vslam_pose_graph_optimize_yaw(G.poses.data(), G.fixed.data(), G.K, G.edges.data(), (int)G.edges.size(), cfg.gravity, &P.pgo, cfg.device,
+                                               G.fresh.data(), &rep->pgo));
+        loop_hold_unmoved(G);
+        VS_CHECK(vslam_pose_graph_move_points(G.xyz.data(), G.ref.data(), G.poses.data(), G.fresh.data(), G.nMp, G.K, cfg.device, G.moved.data()));
+        loop_commit_imu(G, rep, irep);
+    }
+    return loop_activate(rep);
+}
+
+void vslam_system::loop_imu_report_init(vslam_loop_imu_report* irep) const {
+    *irep = vslam_loop_imu_report{};
+    memcpy(irep->T_wc_projected, camPose.data(), 16 * sizeof(double));
+    for (int k = 0; k < 3; k++) irep->velocity_before[k] = irep->velocity[k] = velocity[k];
+}
+
+vslam_status vslam_system::correct_loop_imu(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep,
+                                            vslam_loop_imu_report* irep) {
+    static const char* const fn = "vslam_system_correct_loop_imu";
+    if (!T_wc_corrected || !rep || !irep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check_imu(fn));
+    vslam_loop_params P;
+    if (!resolve_loop_params(prm, P)) { set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID; }
+    VS_CHECK(loop_check_correct(fn, kfLoop, T_wc_corrected));
+    *rep = vslam_loop_report{};
+    rep->kf_loop = kfLoop;
+    loop_imu_report_init(irep);
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    rep->success = 1;
+    const M4 T_corr = m4_from(T_wc_corrected);
+    loop_drift(T_corr, camPoseInv, rep);
+    return loop_apply_imu(kfLoop, T_corr, P, rep, irep);
+}
+
+vslam_status vslam_system::close_loop_imu(const vslam_loop_params* prm, vslam_loop_report* rep, vslam_loop_imu_report* irep) {
+    static const char* const fn = "vslam_system_close_loop_imu";
+    if (!rep || !irep) return VSLAM_ERR_INVALID;
+    VS_CHECK(loop_check_imu(fn));
+    vslam_loop_params P;
+    vslam_reloc_params RP;
+    if (!resolve_loop_params(prm, P)) { set_error("%s: negative or non-finite parameter", fn); return VSLAM_ERR_INVALID; }
+    VS_CHECK(reloc_resolve_params(&P.reloc, RP));
+    VS_CHECK(loop_check_close(fn));
+    *rep = vslam_loop_report{};
+    rep->kf_loop = -1;
+    loop_imu_report_init(irep);
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    M4 T_corr;
+    VS_CHECK(loop_detect(fn, P, RP, rep, T_corr));
+    if (!rep->success) return VSLAM_OK;
+    if (P.detect_only) {                                   // (the projection of the claim under the camera pose as it is: nothing is propagated)
+        loop_project_yaw(T_corr, camPose, camPoseInv, cfg.gravity, irep);
+        return VSLAM_OK;
+    }
+    return loop_apply_imu(rep->kf_loop, T_corr, P, rep, irep);
 }
 
 // The duplicate map points of a revisited place (vslam_hip.h): B = the non-outlier map points created up to latestKF - min_kf_gap,
@@ -625,6 +778,22 @@ vslam_status vslam_system_correct_loop(vslam_system* s, int32_t kf_loop, const d
 vslam_status vslam_system_close_loop(vslam_system* s, const vslam_loop_params* params, vslam_loop_report* report) {
     if (!s) return VSLAM_ERR_INVALID;
     const vslam_status st = s->close_loop(params, report);
+    if (st == VSLAM_OK) memcpy(report->T_wc, s->camPose.data(), 16 * sizeof(double));
+    return st;
+}
+
+vslam_status vslam_system_correct_loop_imu(vslam_system* s, int32_t kf_loop, const double* T_wc_corrected, const vslam_loop_params* params,
+                                           vslam_loop_report* report, vslam_loop_imu_report* imu_report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    const vslam_status st = s->correct_loop_imu(kf_loop, T_wc_corrected, params, report, imu_report);
+    if (st == VSLAM_OK) memcpy(report->T_wc, s->camPose.data(), 16 * sizeof(double));
+    return st;
+}
+
+vslam_status vslam_system_close_loop_imu(vslam_system* s, const vslam_loop_params* params, vslam_loop_report* report,
+                                         vslam_loop_imu_report* imu_report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    const vslam_status st = s->close_loop_imu(params, report, imu_report);
     if (st == VSLAM_OK) memcpy(report->T_wc, s->camPose.data(), 16 * sizeof(double));
     return st;
 }

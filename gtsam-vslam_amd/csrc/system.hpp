@@ -303,6 +303,7 @@ struct vslam_system {
         std::vector<vslam_pgo_edge> edges;
         std::vector<double> xyz, moved;            // [nMp][3] map points before / after
         std::vector<int> ref;                      // [nMp] first observing keyframe or -1
+        M4 camBefore;                              // (IMU sessions) the camera pose the graph was built under
     };
     vslam_status loop_build(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, LoopGraph& G);
     void loop_commit(const LoopGraph& G, vslam_loop_report* rep);
@@ -316,6 +317,18 @@ struct vslam_system {
     vslam_status loop_check_close(const char* fn) const;
     vslam_status correct_loop(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep);
     vslam_status close_loop(const vslam_loop_params* prm, vslam_loop_report* rep);
+    // close_loop's detection (candidates, relocalisation stage, vote), shared with close_loop_imu: success / kf_loop / drift in rep
+    vslam_status loop_detect(const char* fn, const vslam_loop_params& P, const vslam_reloc_params& RP, vslam_loop_report* rep, M4& T_corr);
+    // stereo + IMU sessions: the claim projected to a rotation about gravity and a translation, the
+    // yaw-only solve, and the world-frame IMU state (velocity, predVelocity) rotated with the camera.  Stages as above: loop_build_imu
+    // and loop_commit_imu with mapMutex held by one holder; between them the solve, loop_hold_unmoved and the move of the points.
+    vslam_status loop_check_imu(const char* fn) const;
+    void loop_imu_report_init(vslam_loop_imu_report* irep) const;
+    vslam_status loop_build_imu(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, vslam_loop_imu_report* irep, LoopGraph& G);
+    void loop_commit_imu(const LoopGraph& G, vslam_loop_report* rep, vslam_loop_imu_report* irep);
+    vslam_status loop_apply_imu(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, vslam_loop_imu_report* irep);
+    vslam_status correct_loop_imu(int kfLoop, const double* T_wc_corrected, const vslam_loop_params* prm, vslam_loop_report* rep, vslam_loop_imu_report* irep);
+    vslam_status close_loop_imu(const vslam_loop_params* prm, vslam_loop_report* rep, vslam_loop_imu_report* irep);
     // the duplicate map points of a revisited place become one: the two sets, vslam_fuse_search under
     // the current camera, the commit of fuse_host.hpp.  fusedPairs: the (absorbed, kept) pairs of the last call (test tap)
     std::vector<int> fusedPairs;
@@ -425,4 +438,8 @@ bool resolve_loop_params(const vslam_loop_params* prm, vslam_loop_params& P);
 bool resolve_fuse_loop_params(const char* fn, const vslam_fuse_loop_params* prm, vslam_fuse_loop_params& P);
 bool resolve_system_gba_params(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P);
 void loop_drift(const M4& T_corr, const M4& camPoseInv, vslam_loop_report* rep);
+// the projection of a claimed pose of an IMU session (fills yaw, tilt_dropped and T_wc_projected); the map points whose reference
+// keyframe the solve returned unchanged are taken out of the move
+M4 loop_project_yaw(const M4& T_corr, const M4& camPose, const M4& camPoseInv, const double* gravity, vslam_loop_imu_report* irep);
+void loop_hold_unmoved(vslam_system::LoopGraph& G);
 }  // namespace vslam_sys

@@ -407,6 +407,50 @@ def pose_graph_optimize_batch(graphs, max_iterations=0, lambda0=0.0, device=0):
     return [None if outs[g] is None else (outs[g], _pgo_report_dict(reps[g])) for g in range(B)]
 
 
+class PgoYawGraph(C.Structure):
+    _fields_ = [("graph", PgoGraph), ("axis", C.c_double * 3)]
+
+
+def pose_graph_optimize_yaw(poses, fixed, edges, axis, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_pose_graph_optimize_yaw: pose_graph_optimize with rotations confined to `axis` (3, any non-zero length) and world
+    translations.  Returns (new poses, report dict)."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 4, 4)
+    fixed = np.ascontiguousarray(fixed, np.uint8)
+    assert len(fixed) == len(poses)
+    m = len(edges)
+    ea = edges if isinstance(edges, np.ndarray) else pgo_edges(edges)
+    ax = np.ascontiguousarray(axis, np.float64).reshape(3)
+    prm = PgoParams(int(max_iterations), float(lambda0))
+    rep = PgoReport()
+    out = np.zeros_like(poses)
+    _chk(lib().vslam_pose_graph_optimize_yaw(_p(poses), _p(fixed), len(poses), _p(ea), m, _p(ax), C.byref(prm), int(device), _p(out), C.byref(rep)))
+    return out, _pgo_report_dict(rep)
+
+
+def pose_graph_optimize_yaw_batch(graphs, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_pose_graph_optimize_yaw_batch: graphs = [(poses, fixed, edges, axis) or None (an idle lane), ...], one parameter set
+    for all.  Returns [(new poses, report dict) or None, ...]."""
+    B = len(graphs)
+    tab = (PgoYawGraph * max(B, 1))()
+    reps = (PgoReport * max(B, 1))()
+    keep, outs = [], [None] * B
+    for g, gr in enumerate(graphs):
+        if gr is None:
+            continue
+        poses = np.ascontiguousarray(gr[0], np.float64).reshape(-1, 4, 4)
+        fixed = np.ascontiguousarray(gr[1], np.uint8)
+        assert len(fixed) == len(poses)
+        ea = gr[2] if isinstance(gr[2], np.ndarray) else pgo_edges(gr[2])
+        ax = np.ascontiguousarray(gr[3], np.float64).reshape(3)
+        outs[g] = np.zeros_like(poses)
+        keep.append((poses, fixed, ea))
+        tab[g].graph = PgoGraph(poses.ctypes.data, fixed.ctypes.data, len(poses), ea.ctypes.data, len(gr[2]), outs[g].ctypes.data)
+        tab[g].axis[:] = [float(v) for v in ax]
+    prm = PgoParams(int(max_iterations), float(lambda0))
+    _chk(lib().vslam_pose_graph_optimize_yaw_batch(tab, B, C.byref(prm), int(device), reps))
+    return [None if outs[g] is None else (outs[g], _pgo_report_dict(reps[g])) for g in range(B)]
+
+
 def pose_graph_move_points(points, ref_index, T_old, T_new, device=0):
     """vslam_pose_graph_move_points: T_new[ref] * T_old[ref]^-1 * X per point (ref < 0: unchanged)"""
     points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
@@ -429,6 +473,13 @@ def pose_graph_timings():
     names = (C.c_char_p * 8)(); ms = (C.c_float * 8)(); n = C.c_int32()
     _chk(lib().vslam_pose_graph_timings(names, ms, 8, C.byref(n)))
     return {names[i].decode(): float(ms[i]) for i in range(n.value)}
+
+
+def pose_graph_solve_count():
+    """solves (single or batched, 6-DoF or yaw-only) that reached the device on this thread since pose_graph_set_timing"""
+    n = C.c_int64()
+    _chk(lib().vslam_pose_graph_solve_count(C.byref(n)))
+    return n.value
 
 
 class FuseParams(C.Structure):
@@ -539,6 +590,16 @@ def _loop_report_dict(rep):
     d["reloc"] = _reloc_report_dict(rep.reloc)
     d["pgo"] = _pgo_report_dict(rep.pgo)
     return d
+
+
+class LoopImuReport(C.Structure):
+    _fields_ = [("yaw", C.c_double), ("tilt_dropped", C.c_double), ("T_wc_projected", C.c_double * 16),
+                ("velocity_before", C.c_double * 3), ("velocity", C.c_double * 3)]
+
+
+def _loop_imu_report_dict(rep):
+    return dict(yaw=rep.yaw, tilt_dropped=rep.tilt_dropped, T_wc_projected=np.array(list(rep.T_wc_projected)).reshape(4, 4),
+                velocity_before=np.array(list(rep.velocity_before)), velocity=np.array(list(rep.velocity)))
 
 
 def relocalize_batch(matchers, points, descs, T_out=None, **params):
@@ -1563,6 +1624,23 @@ class System:
         _chk(self.L.vslam_system_close_loop(self.h_sys, C.byref(prm), C.byref(rep)))
         return _loop_report_dict(rep)
 
+    def correct_loop_imu(self, kf_loop, T_wc_corrected, **params):
+        """vslam_system_correct_loop_imu (a stereo + IMU session): correct_loop with the claim projected to a rotation about gravity
+        and a translation, the yaw-only solve, and the velocity rotated with the camera.  Returns (report dict, IMU report dict)."""
+        T = np.ascontiguousarray(T_wc_corrected, np.float64).reshape(4, 4)
+        rep = LoopReport(); irep = LoopImuReport()
+        prm = self._loop_params(params)
+        _chk(self.L.vslam_system_correct_loop_imu(self.h_sys, int(kf_loop), _p(T), C.byref(prm), C.byref(rep), C.byref(irep)))
+        return _loop_report_dict(rep), _loop_imu_report_dict(irep)
+
+    def close_loop_imu(self, **params):
+        """vslam_system_close_loop_imu: close_loop's detection on the frame of the last track(), then (unless detect_only=1) the
+        correction of correct_loop_imu.  Returns (report dict, IMU report dict)."""
+        rep = LoopReport(); irep = LoopImuReport()
+        prm = self._loop_params(params)
+        _chk(self.L.vslam_system_close_loop_imu(self.h_sys, C.byref(prm), C.byref(rep), C.byref(irep)))
+        return _loop_report_dict(rep), _loop_imu_report_dict(irep)
+
     def fuse_loop(self, **params):
         """vslam_system_fuse_loop: the duplicate map points of the place the camera sees become one.  params: radius, depth_ratio,
         max_hamming, min_kf_gap.  Returns the report dict (busy: nothing was done)."""
@@ -2165,6 +2243,29 @@ class Batch:
         prm = System._loop_params(params)
         _chk(self.L.vslam_batch_correct_loop(self.h_b, _p(mk), _p(kf), _p(T), C.byref(prm), reps))
         return [_loop_report_dict(reps[b]) if mk[b] else None for b in range(self.lanes)]
+
+    def close_loop_imu(self, mask=None, **params):
+        """vslam_batch_close_loop_imu (an IMU batch): per masked lane what System.close_loop_imu does, the detection batched and ONE
+        yaw-only solve for all lanes.  Returns [(report dict, IMU report dict) or None for lanes outside the mask]."""
+        mk = self._loop_mask(mask)
+        reps = (LoopReport * self.lanes)(); ireps = (LoopImuReport * self.lanes)()
+        prm = System._loop_params(params)
+        _chk(self.L.vslam_batch_close_loop_imu(self.h_b, _p(mk), C.byref(prm), reps, ireps))
+        return [(_loop_report_dict(reps[b]), _loop_imu_report_dict(ireps[b])) if mk[b] else None for b in range(self.lanes)]
+
+    def correct_loop_imu(self, kf_loops, poses, mask=None, **params):
+        """vslam_batch_correct_loop_imu: kf_loops [lanes], poses [lanes, 4, 4] (read for the masked lanes; None entries allowed
+        elsewhere).  Returns [(report dict, IMU report dict) or None for lanes outside the mask]."""
+        mk = self._loop_mask(mask)
+        kf = np.array([int(k) if k is not None else 0 for k in kf_loops], np.int32)
+        T = np.zeros((self.lanes, 4, 4))
+        for b in range(self.lanes):
+            if poses[b] is not None:
+                T[b] = np.asarray(poses[b], np.float64).reshape(4, 4)
+        reps = (LoopReport * self.lanes)(); ireps = (LoopImuReport * self.lanes)()
+        prm = System._loop_params(params)
+        _chk(self.L.vslam_batch_correct_loop_imu(self.h_b, _p(mk), _p(kf), _p(T), C.byref(prm), reps, ireps))
+        return [(_loop_report_dict(reps[b]), _loop_imu_report_dict(ireps[b])) if mk[b] else None for b in range(self.lanes)]
 
     def fuse_loop(self, mask=None, **params):
         """vslam_batch_fuse_loop: per masked lane (None: all) what System.fuse_loop does, the searches of all lanes in one batched

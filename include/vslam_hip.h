@@ -502,6 +502,36 @@ typedef struct vslam_pgo_graph {     /* one lane; n == 0: idle lane (its report 
 } vslam_pgo_graph;
 vslam_status vslam_pose_graph_optimize_batch(const vslam_pgo_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
                                              int32_t device, vslam_pgo_report* reports /* [lanes] */);
+/* The YAW-ONLY (4-DoF) solve of the same graphs (csrc/pgo_yaw.hip, csrc/pgo_yaw_dev.hpp; DESIGN.md section 6 item 29, restated
+ * by tests/pgo_yaw_ref.py): what a loop correction of a session with an IMU needs, whose world frame carries gravity.  Graph,
+ * edges, residual, cost, weights, LM schedule, stopping rules, refusals, capacities and report are those of
+ * vslam_pose_graph_optimize.  It differs in four ways:
+ *   axis        g = axis / sqrt(x^2 + y^2 + z^2), in fp64 on the host (the axis needs no normalising by the caller).  A zero or
+ *               non-finite axis: VSLAM_ERR_INVALID, nothing launched.
+ *   parameters  four per free pose, (theta, delta);  retraction T_k <- [Exp(theta g) R_k, t_k + delta]: a rotation about g and a
+ *               translation, both on the world side.  Hence R_new R_old^T g = g for every pose: roll and pitch about g never
+ *               change (the 6-DoF solve tilts g by 1e-3 .. 6e-2 rad on the graphs of the tests).
+ *   Jacobians   J4 = J6 * M_k with M_k = [[R_k^T g, 0], [0, R_k^T]] (6x4) and J6 the 6-DoF Jacobian, multiplied in registers
+ *               (k_pgoy_linearize_b stores 24 doubles a side)
+ *   solve       H block-banded with 4x4 fp64 blocks, g with 4 entries per pose; damping lambda diag(H), pivot rule and accept /
+ *               reject rule are the existing ones.  k_pgoy_assemble_b carries THREE block columns per wave (20 lanes each, each
+ *               walking its own incidence list in ascending order: no atomics); k_pgoy_band_chol_b is the walk of
+ *               k_pgo_band_chol_b with 4x4 blocks.  Two calls on the same input return the same bytes; the host waits once per
+ *               round, for one int.
+ * The final cost is never below the 6-DoF solve's of the same graph started from the same poses when both converge (fewer
+ * degrees of freedom).  The single call is the one-lane case of the batched one; a lane (graph and its own axis) returns, byte
+ * for byte, what the single call returns for it; a lane with graph.n == 0 is idle.  vslam_pose_graph_set_timing /
+ * vslam_pose_graph_timings serve these calls too; their groups are pgoy_linearize, pgoy_assemble, pgoy_band_chol, pgoy_retract,
+ * pgoy_cost. */
+typedef struct vslam_pgo_yaw_graph {     /* one lane of the yaw-only solve */
+    vslam_pgo_graph graph;
+    double axis[3];                      /* the world axis that rotations are confined to (gravity); any non-zero length */
+} vslam_pgo_yaw_graph;
+vslam_status vslam_pose_graph_optimize_yaw(const double* T_wc, const uint8_t* fixed, int32_t n, const vslam_pgo_edge* edges, int32_t m,
+                                           const double axis[3], const vslam_pgo_params* params, int32_t device,
+                                           double* T_wc_out /* [n][16]; may be T_wc */, vslam_pgo_report* report);
+vslam_status vslam_pose_graph_optimize_yaw_batch(const vslam_pgo_yaw_graph* graphs, int32_t lanes, const vslam_pgo_params* params,
+                                                 int32_t device, vslam_pgo_report* reports /* [lanes] */);
 /* k_pgo_move_points_b with one lane: points_out[k] = T_new[r] * T_old[r]^-1 * points_xyz[k] with r = ref_index[k] (rigid inverse:
  * R^T (X - t)); r < 0 leaves the point as it is; r >= n_poses: VSLAM_ERR_INVALID, nothing launched.  points_out may be points_xyz. */
 vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_t* ref_index, const double* T_old, const double* T_new,
@@ -513,6 +543,9 @@ vslam_status vslam_pose_graph_move_points(const double* points_xyz, const int32_
  * k_pgo_reduce_b and k_pgo_decide_b, the initial reduce and decide included). */
 vslam_status vslam_pose_graph_set_timing(int32_t on);
 vslam_status vslam_pose_graph_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
+/* the same hook: how many solves (calls of any of the four optimise entry points, a batched call counting once) have reached the
+ * device on the calling thread since its last vslam_pose_graph_set_timing - what shows that a batched loop call made ONE solve */
+vslam_status vslam_pose_graph_solve_count(int64_t* n_out);
 
 /* ---------------------------------------------------------------------------
  * Global bundle adjustment (no reference counterpart: the reference closes no loops; DESIGN.md section 6 item 27, restated in
@@ -1236,6 +1269,38 @@ typedef struct vslam_loop_report {
 vslam_status vslam_system_correct_loop(vslam_system* sys, int32_t kf_loop, const double* T_wc_corrected,
                                        const vslam_loop_params* params, vslam_loop_report* report);
 vslam_status vslam_system_close_loop(vslam_system* sys, const vslam_loop_params* params, vslam_loop_report* report);
+/* Loop closing for stereo + IMU sessions (use_imu = 1): the two calls above with a YAW-ONLY
+ * correction.  The world frame of such a session carries cfg.gravity, and roll and pitch are observable from the IMU, so a
+ * correction may rotate keyframes only about g = gravity / |gravity| and translate them; the calls above keep refusing IMU
+ * sessions.  Signatures, `busy`, detect_only, detection (candidates, the relocalisation stage with save / restore of the four
+ * stereo arrays, the vote), graph, fixed set, edges, the move of the map points, commit and activation are those of the calls
+ * above, with three differences:
+ *   projection  the claimed pose is projected first.  D = T_wc_corrected * T_wc^-1, q = (R32 - R23, R13 - R31, R21 - R12) of R_D,
+ *               theta = atan2(g . q, tr R_D - g^T R_D g): the rotation about g closest to R_D (it maximises tr(Exp(theta g)^T R_D)).
+ *               T' = [Exp(theta g) R_cam | t_corrected]; the loop edge is built from D' = T' * T_wc^-1.  What the projection
+ *               drops (the rotation between T' and the claim) is reported, never applied.
+ *   solve       vslam_pose_graph_optimize_yaw with axis cfg.gravity.  A map point whose first observing keyframe comes back
+ *               with unchanged bytes is not touched (a claim without yaw and translation changes nothing, bit for bit);
+ *               points_moved counts the map points that did move.
+ *   IMU state   after the commit, with dR = R_cam,new * R_cam,old^T (a rotation about g): velocity <- dR velocity and the
+ *               prediction's velocity likewise.  bias, the last good bias and gravity are untouched (body-frame quantities,
+ *               and g is the axis of dR); nothing else of a session's IMU state lives in the world frame.
+ * vslam_loop_report keeps its meaning: drift and T_wc_corrected are those of the UNPROJECTED claim.
+ * detect_only: the IMU report holds the projection of the found claim under the camera pose AS IT IS (nothing is propagated,
+ * nothing changes).  The applying path first propagates a finished local BA (local_mapping = 2), which may move the camera pose:
+ * a following vslam_system_correct_loop_imu on the same claim can then report a slightly different yaw and T_wc_projected.
+ * VSLAM_ERR_INVALID, nothing changed: a mono session, a session with use_imu = 0 (it has the calls above), a pending two-phase
+ * relocalisation (vslam_system_relocalize_imu has committed a pose but no velocity yet), and everything the calls above refuse. */
+typedef struct vslam_loop_imu_report {
+    double yaw;                       /* theta: the rotation about g that is applied to the camera [rad] */
+    double tilt_dropped;              /* rotation angle between the projected pose T' and the claim [rad] */
+    double T_wc_projected[16];        /* T' */
+    double velocity_before[3], velocity[3];      /* world-frame velocity before / after the call */
+} vslam_loop_imu_report;
+vslam_status vslam_system_correct_loop_imu(vslam_system* sys, int32_t kf_loop, const double* T_wc_corrected,
+                                           const vslam_loop_params* params, vslam_loop_report* report, vslam_loop_imu_report* imu_report);
+vslam_status vslam_system_close_loop_imu(vslam_system* sys, const vslam_loop_params* params, vslam_loop_report* report,
+                                         vslam_loop_imu_report* imu_report);
 /* test taps: activeMapPoints (map-point indices, in order); every sortedKFWeights entry as (keyframe, other, weight) triples,
  * keyframes ascending, entries in list order; per map point its first observing keyframe (-1: none) and creating keyframe */
 vslam_status vslam_system_active_points(vslam_system* sys, int32_t cap, int32_t* n_out, int32_t* index);
@@ -1547,6 +1612,19 @@ vslam_status vslam_batch_correct_loop(vslam_batch* batch, const uint8_t* lane_ma
                                       vslam_loop_report* reports /* [lanes] */);
 vslam_status vslam_batch_close_loop(vslam_batch* batch, const uint8_t* lane_mask, const vslam_loop_params* params,
                                     vslam_loop_report* reports /* [lanes] */);
+/* The same two calls for the lanes of an IMU batch (use_imu = 1): a masked lane gets what vslam_system_close_loop_imu /
+ * vslam_system_correct_loop_imu does to a session (projection about the lane's own gravity, yaw-only solve, velocity rotated with
+ * the camera), in the shape above: the detection batched as above, every lane that reaches the
+ * correction builds its graph on its projected claim, then ONE vslam_pose_graph_optimize_yaw_batch (each lane with its own axis
+ * cfg.gravity) and ONE k_pgo_move_points_b launch for all of them, then the commit per lane.  A lane's outcome is what a session
+ * driven alone gets.  imu_reports [lanes]: written for the masked lanes, like reports.
+ * VSLAM_ERR_INVALID, nothing changed in any lane: a batch without IMU (it has the calls above), a masked lane with a pending
+ * two-phase relocalisation, NULL imu_reports, and everything the calls above refuse (they keep refusing IMU batches). */
+vslam_status vslam_batch_correct_loop_imu(vslam_batch* batch, const uint8_t* lane_mask, const int32_t* kf_loop /* [lanes] */,
+                                          const double* T_wc_corrected /* [lanes][16] */, const vslam_loop_params* params,
+                                          vslam_loop_report* reports /* [lanes] */, vslam_loop_imu_report* imu_reports /* [lanes] */);
+vslam_status vslam_batch_close_loop_imu(vslam_batch* batch, const uint8_t* lane_mask, const vslam_loop_params* params,
+                                        vslam_loop_report* reports /* [lanes] */, vslam_loop_imu_report* imu_reports /* [lanes] */);
 /* The two calls that finish a lane's loop closing, between two steps, in the shape of vslam_batch_close_loop: per masked lane what
  * vslam_system_fuse_loop, respectively vslam_system_global_ba, does to a session (their rules, reports and defaults), with the
  * device work of all lanes in ONE batched call.

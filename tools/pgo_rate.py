@@ -17,7 +17,14 @@ python tools/pgo_rate.py --lanes G [out.json] [calls] [reps] times vslam_pose_gr
 the lanes stop in different rounds.  Same protocol; reported per nominal size: the batched call, the G single calls of the same
 graphs one after another, the single call on the nominal chain alone (the figure profiles/pgo_rate.json holds for the single call),
 the rounds of the batched call (its longest lane's trials) against every lane's trials, and whether every lane's poses equal its
-single call's bytes.  Default output: profiles/pgo_batch_rate.json."""
+single call's bytes.  Default output: profiles/pgo_batch_rate.json.
+
+python tools/pgo_rate.py --yaw [out.json] [calls] [reps] times vslam_pose_graph_optimize_yaw (axis (0, 1, 0)) on the 1 000- and
+4 000-pose chains, and vslam_pose_graph_optimize on the same graphs in the same process as the yardstick.  Same protocol; per size
+and solve: the call's time, the trials, the costs, the device time per kernel group, and the walk's cost per block column
+(the band_chol group over trials x free poses: the walk's dependency chain is what bounds it).  The two
+solves run different numbers of trials on different problems, so the per-column and per-trial figures are the comparable ones.
+Default output: profiles/pgo_yaw_rate.json."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("gtsam-vslam_amd", "tests"):
@@ -95,7 +102,48 @@ def main_lanes(G, argv):
         f.write("\n")
 
 
+YAW_SIZES = (1000, 4000)
+
+
+def main_yaw(argv):
+    out_path = argv[0] if len(argv) > 0 else os.path.join(ROOT, "profiles", "pgo_yaw_rate.json")
+    calls = int(argv[1]) if len(argv) > 1 else 3
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    axis = (0.0, 1.0, 0.0)
+    res = dict(protocol="2 warm-up calls, %d repetitions of %d calls, host clock around calls that end in a device synchronise; kernel "
+                        "groups from HIP events of one more repetition; both solves in one process, the 6-DoF call first" % (reps, calls),
+               axis=axis, sizes={})
+    for n in YAW_SIZES:
+        poses, fixed, edges = out_and_back(n)
+        ea = vc.pgo_edges(edges)
+        solves = (("six_dof", "pgo_band_chol", lambda: vc.pose_graph_optimize(poses, fixed, ea)),
+                  ("yaw", "pgoy_band_chol", lambda: vc.pose_graph_optimize_yaw(poses, fixed, ea, axis)))
+        r = dict(poses=n, edges=len(edges))
+        for name, walk, fn in solves:
+            t = timed(fn, calls, reps)
+            out, rep = fn()
+            vc.pose_graph_set_timing(True)
+            groups = {}
+            for _ in range(calls):
+                fn()
+                for k, v in vc.pose_graph_timings().items():
+                    groups[k] = groups.get(k, 0.0) + v / calls
+            vc.pose_graph_set_timing(False)
+            cols = rep["iterations"] * rep["n_free"]
+            r[name] = dict(ms_per_call=t, kernel_group_ms=groups, half_bandwidth=rep["half_bandwidth"], lm_trials=rep["iterations"],
+                           accepted=rep["accepted"], rejected=rep["rejected"], initial_cost=rep["initial_cost"], final_cost=rep["final_cost"],
+                           ms_per_trial=t["median"] / max(rep["iterations"], 1),
+                           band_chol_us_per_column=1e3 * groups.get(walk, 0.0) / max(cols, 1))
+        res["sizes"][str(n)] = r
+        print(json.dumps(r), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main(argv):
+    if "--yaw" in argv:
+        return main_yaw([a for a in argv if a != "--yaw"])
     if "--lanes" in argv:
         k = argv.index("--lanes")
         return main_lanes(int(argv[k + 1]), argv[:k] + argv[k + 2:])
