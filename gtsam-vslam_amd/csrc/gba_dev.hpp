@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "dmath.hpp"
 #include "pgo_dev.hpp"
+#include "gba_pack_host.hpp"
 
 namespace {
 
@@ -300,6 +301,24 @@ __device__ __forceinline__ void gba_chi2_pair(int p, const GbaDev& D, const PgoC
         w = ((fl & 1) && out[0]) || ((fl & 2) && out[1]);
     }
     wrong[p] = w;
+}
+
+// a lane of a batched call (gba_pack_host.hpp): the lane's sizes and camera, and its part of the concatenated arrays that B points to
+__device__ __forceinline__ GbaDev gba_lane_dev(const GbaLane* T, const GbaDev& B) {
+    GbaDev D;
+    D.K = T->K; D.L = T->L; D.P = T->P; D.M = T->M; D.nf = T->nf; D.b = T->b; D.nBlk = T->nBlk;
+    D.cam = GbaCam{T->fx, T->fy, T->cx, T->cy, T->bl};
+    const size_t kf0 = (size_t)T->kf0, lm0 = (size_t)T->lm0, p0 = (size_t)T->pair0, ln = (size_t)T->lane;
+    D.edges = B.edges + (size_t)T->edge0;
+    D.pos = B.pos + kf0;
+    D.rowStart = B.rowStart + (size_t)T->free0 + ln; D.inc = B.inc + (size_t)T->inc0;
+    D.pairKf = B.pairKf + p0; D.pairLm = B.pairLm + p0; D.pairFlags = B.pairFlags + p0;
+    D.pairUv = B.pairUv + p0 * 4; D.pairIs = B.pairIs + p0 * 2; D.pairThr = B.pairThr + p0 * 2;
+    D.kfLocal = B.kfLocal + kf0; D.lmPresent = B.lmPresent + lm0;
+    D.lmStart = B.lmStart + lm0 + ln; D.lmPairs = B.lmPairs + (size_t)T->lp0;
+    D.blkC = B.blkC + (size_t)T->blk0; D.blkD = B.blkD + (size_t)T->blk0; D.blkStart = B.blkStart + (size_t)T->blk0 + ln;
+    D.list = B.list + (size_t)T->list0 * 2;
+    return D;
 }
 
 }  // namespace

@@ -335,13 +335,19 @@ void vslam_sys::loop_hold_unmoved(vslam_system::LoopGraph& G) {
 void vslam_system::loop_commit_imu(const LoopGraph& G, vslam_loop_report* rep, vslam_loop_imu_report* irep) {
     loop_commit(G, rep);
     double dR[9];
+    imu_follow_camera(G.camBefore, dR);
+    for (int k = 0; k < 3; k++) irep->velocity[k] = velocity[k];
+}
+
+// (mapMutex held) velocity and predVelocity turned by dR = R_cam,new R_cam,old^T; dR [9] out
+void vslam_system::imu_follow_camera(const M4& camBefore, double* dR) {
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++)
-            dR[3 * r + c] = camPose[4 * r] * G.camBefore[4 * c] + camPose[4 * r + 1] * G.camBefore[4 * c + 1] + camPose[4 * r + 2] * G.camBefore[4 * c + 2];
+            dR[3 * r + c] = camPose[4 * r] * camBefore[4 * c] + camPose[4 * r + 1] * camBefore[4 * c + 1] + camPose[4 * r + 2] * camBefore[4 * c + 2];
     double v[3], pv[3];
     mat3_vec(dR, velocity, v);
     mat3_vec(dR, predVelocity, pv);
-    for (int k = 0; k < 3; k++) { velocity[k] = v[k]; predVelocity[k] = pv[k]; irep->velocity[k] = v[k]; }
+    for (int k = 0; k < 3; k++) { velocity[k] = v[k]; predVelocity[k] = pv[k]; }
 }
 
 vslam_status vslam_system::loop_apply_imu(int kfLoop, const M4& T_corr, const vslam_loop_params& P, vslam_loop_report* rep, vslam_loop_imu_report* irep) {
@@ -475,9 +481,17 @@ void vslam_system::fuse_commit(const FuseSets& F, vslam_fuse_loop_report* rep) {
 }
 
 vslam_status vslam_system::fuse_loop(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
-    static const char* const fn = "vslam_system_fuse_loop";
+    return fuse_loop_run("vslam_system_fuse_loop", false, prm, rep);
+}
+
+// stereo + IMU sessions: the same stages (fusion is geometry and bookkeeping; the IMU state is not touched)
+vslam_status vslam_system::fuse_loop_imu(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
+    return fuse_loop_run("vslam_system_fuse_loop_imu", true, prm, rep);
+}
+
+vslam_status vslam_system::fuse_loop_run(const char* fn, bool imu, const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep) {
     if (!rep) return VSLAM_ERR_INVALID;
-    VS_CHECK(loop_check(fn));
+    VS_CHECK(imu ? loop_check_imu(fn) : loop_check(fn));
     vslam_fuse_loop_params P;
     if (!resolve_fuse_loop_params(fn, prm, P)) return VSLAM_ERR_INVALID;
     *rep = vslam_fuse_loop_report{};
@@ -667,6 +681,58 @@ vslam_status vslam_system::global_ba(const vslam_system_gba_params* prm, vslam_s
     return gba_activate(rep);
 }
 
+// ---- vslam_system_global_ba_imu (vslam_hip.h): the stages above around the yaw-only solve -------
+vslam_status vslam_system::gba_check_imu(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const {
+    VS_CHECK(loop_check_imu(fn));
+    return resolve_system_gba_params(fn, prm, P) ? VSLAM_OK : VSLAM_ERR_INVALID;
+}
+
+vslam_status vslam_system::global_ba_imu(const vslam_system_gba_params* prm, vslam_system_gba_report* rep, vslam_gba_imu_report* irep) {
+    static const char* const fn = "vslam_system_global_ba_imu";
+    if (!rep || !irep) return VSLAM_ERR_INVALID;
+    vslam_system_gba_params P;
+    VS_CHECK(gba_check_imu(fn, prm, P));
+    *rep = vslam_system_gba_report{};
+    *irep = vslam_gba_imu_report{};
+    for (int k = 0; k < 3; k++) irep->velocity_before[k] = irep->velocity[k] = velocity[k];
+    memcpy(irep->T_wc, camPose.data(), 16 * sizeof(double));
+    if (loop_busy()) { rep->busy = 1; return VSLAM_OK; }
+    if (keyFrames.size() < 2) return VSLAM_OK;
+    VS_HIP(hipSetDevice(cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(mapMutex);
+        if (LBADone) {                                  // the propagation gba_flatten would make, made here: the camera pose the
+            VS_CHECK(change_poses_lca(endLBAIdx));         // adjustment starts from is taken after it, as loop_build_imu takes camBefore
+            LBADone = false;
+        }
+        const M4 camBefore = camPose;
+        GbaFlat F;
+        VS_CHECK(gba_flatten(P.edge_weight, F));
+        rep->n_keyframes = F.P.n_kf; rep->n_landmarks = F.P.n_lm; rep->n_pairs = F.P.n_pairs; rep->n_edges = (int)F.edges.size();
+        vslam_gba_result R{};
+        R.kf_pose_wc = F.kfOut.data(); R.lm_xyz = F.lmOut.data(); R.pair_wrong = F.wrong.data();
+        VS_CHECK(vslam_global_ba_yaw(&F.P, F.edges.empty() ? nullptr : F.edges.data(), (int)F.edges.size(), cfg.gravity, &P.gba, cfg.device, &R));
+        rep->gba = R.report;
+        VS_CHECK(gba_finish(F, rep));
+        double dR[9], Rg[3];                               // the world-frame IMU state follows the camera, as in loop_commit_imu
+        imu_follow_camera(camBefore, dR);
+        const double nrm = std::sqrt(cfg.gravity[0] * cfg.gravity[0] + cfg.gravity[1] * cfg.gravity[1] + cfg.gravity[2] * cfg.gravity[2]);
+        const double g[3] = {cfg.gravity[0] / nrm, cfg.gravity[1] / nrm, cfg.gravity[2] / nrm};
+        const double q[3] = {dR[7] - dR[5], dR[2] - dR[6], dR[3] - dR[1]};
+        mat3_vec(dR, g, Rg);
+        irep->yaw = std::atan2(g[0] * q[0] + g[1] * q[1] + g[2] * q[2], (dR[0] + dR[4] + dR[8]) - (g[0] * Rg[0] + g[1] * Rg[1] + g[2] * Rg[2]));
+        for (int k = 0; k < 3; k++) irep->velocity[k] = velocity[k];
+        memcpy(irep->T_wc, camPose.data(), 16 * sizeof(double));
+    }
+    return gba_activate(rep);
+}
+
+// the flattened problem a global-BA call would build now (the test tap of vslam_system_global_ba_problem / _problem_imu)
+static vslam_status gba_problem_tap(const char* fn, bool imu, vslam_system* s, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                    uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                    int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                    vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor);
+
 extern "C" {
 
 vslam_status vslam_system_global_ba(vslam_system* s, const vslam_system_gba_params* params, vslam_system_gba_report* report) {
@@ -674,16 +740,44 @@ vslam_status vslam_system_global_ba(vslam_system* s, const vslam_system_gba_para
     return s->global_ba(params, report);
 }
 
+vslam_status vslam_system_global_ba_imu(vslam_system* s, const vslam_system_gba_params* params, vslam_system_gba_report* report,
+                                        vslam_gba_imu_report* imu_report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->global_ba_imu(params, report, imu_report);
+}
+
+vslam_status vslam_system_fuse_loop_imu(vslam_system* s, const vslam_fuse_loop_params* params, vslam_fuse_loop_report* report) {
+    if (!s) return VSLAM_ERR_INVALID;
+    return s->fuse_loop_imu(params, report);
+}
+
 vslam_status vslam_system_global_ba_problem(vslam_system* s, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
                                             uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
                                             int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
                                             vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor) {
-    static const char* const fn = "vslam_system_global_ba_problem";
+    return gba_problem_tap("vslam_system_global_ba_problem", false, s, edge_weight, arrays, sizes, kf_pose_wc, kf_fixed, kf_local, lm_xyz, lm_index, pair_kf,
+                           pair_lm, pair_flags, pair_uv, pair_octave, edges, sigma_factor, inv_sigma_factor);
+}
+
+vslam_status vslam_system_global_ba_problem_imu(vslam_system* s, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                                uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                                int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                                vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor) {
+    return gba_problem_tap("vslam_system_global_ba_problem_imu", true, s, edge_weight, arrays, sizes, kf_pose_wc, kf_fixed, kf_local, lm_xyz, lm_index, pair_kf,
+                           pair_lm, pair_flags, pair_uv, pair_octave, edges, sigma_factor, inv_sigma_factor);
+}
+
+}  // extern "C"
+
+static vslam_status gba_problem_tap(const char* fn, bool imu, vslam_system* s, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                    uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                    int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                    vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor) {
     if (!s || !sizes) return VSLAM_ERR_INVALID;
     vslam_system_gba_params prm{};
     prm.edge_weight = edge_weight;
     vslam_system_gba_params P;
-    VS_CHECK(s->gba_check(fn, &prm, P));
+    VS_CHECK(imu ? s->gba_check_imu(fn, &prm, P) : s->gba_check(fn, &prm, P));
     if (s->loop_busy()) { set_error("%s: a mapping pass is in flight", fn); return VSLAM_ERR_INVALID; }
     VS_HIP(hipSetDevice(s->cfg.device));
     std::lock_guard<std::mutex> lk(s->mapMutex);
@@ -704,8 +798,6 @@ vslam_status vslam_system_global_ba_problem(vslam_system* s, double edge_weight,
     memcpy(sigma_factor, s->sigmaF.data(), (size_t)nLev * 4); memcpy(inv_sigma_factor, s->invSigmaF.data(), (size_t)nLev * 4);
     return VSLAM_OK;
 }
-
-}  // extern "C"
 
 extern "C" {
 

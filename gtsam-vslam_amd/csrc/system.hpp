@@ -365,6 +365,13 @@ struct vslam_system {
     vslam_status gba_finish(GbaFlat& F, vslam_system_gba_report* rep);      // commit, refresh request, every refPose, the camera
     vslam_status gba_activate(vslam_system_gba_report* rep);                // the active set (takes mapMutex itself); success = 1
     vslam_status global_ba(const vslam_system_gba_params* prm, vslam_system_gba_report* rep);
+    // stereo + IMU sessions: the stages of fuse_loop and global_ba behind loop_check_imu, the solve
+    // vslam_global_ba_yaw about cfg.gravity, and the world-frame IMU state turned with the camera (imu_follow_camera, mapMutex held)
+    vslam_status fuse_loop_run(const char* fn, bool imu, const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep);
+    vslam_status fuse_loop_imu(const vslam_fuse_loop_params* prm, vslam_fuse_loop_report* rep);
+    vslam_status gba_check_imu(const char* fn, const vslam_system_gba_params* prm, vslam_system_gba_params& P) const;
+    void imu_follow_camera(const M4& camBefore, double* dR);
+    vslam_status global_ba_imu(const vslam_system_gba_params* prm, vslam_system_gba_report* rep, vslam_gba_imu_report* irep);
     // the cameras' rectifiers for raw frames (borrowed; both set or both null)
     const vslam_rectifier* rectL = nullptr; const vslam_rectifier* rectR = nullptr;
     vslam_status set_rectifiers(const vslam_rectifier* l, const vslam_rectifier* r, const char* fn);

@@ -780,6 +780,10 @@ class SystemGbaReport(C.Structure):
                                           "n_active_after", "reserved")] + [("gba", GbaReport)]
 
 
+class GbaImuReport(C.Structure):
+    _fields_ = [("yaw", C.c_double), ("velocity_before", C.c_double * 3), ("velocity", C.c_double * 3), ("T_wc", C.c_double * 16)]
+
+
 def _gba_report_dict(rep):
     return {f[0]: getattr(rep, f[0]) for f in GbaReport._fields_ if f[0] != "reserved"}
 
@@ -799,6 +803,16 @@ def _fuse_loop_report_dict(rep):
 def global_ba(rig, sigma_factor, inv_sigma_factor, prob, edges=None, max_iterations=0, lambda0=0.0, device=0):
     """vslam_global_ba on a flattened problem dict (the keys local_ba takes; kf_id may be missing: it is not used) with optional
     relative-pose edges as pgo_edges takes them (or its array).  Returns dict(kf_pose, lm, pair_wrong, report)."""
+    return _global_ba(None, rig, sigma_factor, inv_sigma_factor, prob, edges, max_iterations, lambda0, device)
+
+
+def global_ba_yaw(rig, sigma_factor, inv_sigma_factor, prob, axis, edges=None, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_global_ba_yaw: global_ba with keyframes that move only by a rotation about `axis` (3 floats, any non-zero length) and
+    a translation"""
+    return _global_ba(np.ascontiguousarray(axis, np.float64).reshape(3), rig, sigma_factor, inv_sigma_factor, prob, edges, max_iterations, lambda0, device)
+
+
+def _global_ba(axis, rig, sigma_factor, inv_sigma_factor, prob, edges, max_iterations, lambda0, device):
     if "kf_id" not in prob:
         prob = dict(prob, kf_id=np.arange(len(prob["kf_pose"]), dtype=np.int64))
     P, _, keep = ba_problem_structs(rig, sigma_factor, inv_sigma_factor, prob)
@@ -809,7 +823,10 @@ def global_ba(rig, sigma_factor, inv_sigma_factor, prob, edges=None, max_iterati
     R = GbaResult()
     R.kf_pose_wc, R.lm_xyz, R.pair_wrong = _p(kfOut), _p(lmOut), _p(wrong)
     prm = GbaParams(int(max_iterations), float(lambda0))
-    _chk(lib().vslam_global_ba(C.byref(P), None if ea is None else _p(ea), m, C.byref(prm), int(device), C.byref(R)))
+    if axis is None:
+        _chk(lib().vslam_global_ba(C.byref(P), None if ea is None else _p(ea), m, C.byref(prm), int(device), C.byref(R)))
+    else:
+        _chk(lib().vslam_global_ba_yaw(C.byref(P), None if ea is None else _p(ea), m, _p(axis), C.byref(prm), int(device), C.byref(R)))
     del keep
     return dict(kf_pose=kfOut[:n_kf], lm=lmOut[:n_lm], pair_wrong=wrong[:n_pairs], report=_gba_report_dict(R.report))
 
@@ -824,8 +841,21 @@ def global_ba_batch(lanes, max_iterations=0, lambda0=0.0, device=0):
     (K, 4, 4) float64, lm (L, 3) float64, pair_wrong (P) uint8) of the caller's own C-contiguous arrays for the call to write into
     (default: fresh arrays); in_place: the result arrays are the problem's own (its kf_pose and lm must be C-contiguous float64
     arrays, which are then overwritten).  Returns [None or dict(kf_pose, lm, pair_wrong, report), ...]."""
+    return _global_ba_batch(False, lanes, max_iterations, lambda0, device)
+
+
+class GbaYawLane(C.Structure):
+    _fields_ = [("lane", GbaLane), ("axis", C.c_double * 3)]
+
+
+def global_ba_yaw_batch(lanes, max_iterations=0, lambda0=0.0, device=0):
+    """vslam_global_ba_yaw_batch: the lanes of global_ba_batch, each with its own `axis` (3 floats, any non-zero length)"""
+    return _global_ba_batch(True, lanes, max_iterations, lambda0, device)
+
+
+def _global_ba_batch(yaw, lanes, max_iterations, lambda0, device):
     B = len(lanes)
-    tab = (GbaLane * max(B, 1))()
+    tab = ((GbaYawLane if yaw else GbaLane) * max(B, 1))()
     keep, outs = [], [None] * B
     for g, ln in enumerate(lanes):
         if ln is None:
@@ -853,9 +883,10 @@ def global_ba_batch(lanes, max_iterations=0, lambda0=0.0, device=0):
         R.kf_pose_wc, R.lm_xyz, R.pair_wrong = _p(kfOut), _p(lmOut), _p(wrong)
         keep.append((P, R, kp, ea))
         outs[g] = (R, kfOut[:n_kf], lmOut[:n_lm], wrong[:n_pairs])
-        tab[g] = GbaLane(C.pointer(P), None if ea is None else ea.ctypes.data, m, C.pointer(R))
+        entry = GbaLane(C.pointer(P), None if ea is None else ea.ctypes.data, m, C.pointer(R))
+        tab[g] = GbaYawLane(entry, (C.c_double * 3)(*[float(v) for v in ln["axis"]])) if yaw else entry
     prm = GbaParams(int(max_iterations), float(lambda0))
-    _chk(lib().vslam_global_ba_batch(tab, B, C.byref(prm), int(device)))
+    _chk((lib().vslam_global_ba_yaw_batch if yaw else lib().vslam_global_ba_batch)(tab, B, C.byref(prm), int(device)))
     return [None if o is None else dict(kf_pose=o[1], lm=o[2], pair_wrong=o[3], report=_gba_report_dict(o[0].report)) for o in outs]
 
 
@@ -1699,11 +1730,31 @@ class System:
         _chk(self.L.vslam_system_global_ba(self.h_sys, C.byref(prm), C.byref(rep)))
         return _system_gba_report_dict(rep)
 
-    def global_ba_problem(self, edge_weight=0.0):
+    def fuse_loop_imu(self, **params):
+        """vslam_system_fuse_loop_imu (a stereo + IMU session): fuse_loop; the IMU state is not touched"""
+        prm = self._fuse_loop_params(params)
+        rep = FuseLoopReport()
+        _chk(self.L.vslam_system_fuse_loop_imu(self.h_sys, C.byref(prm), C.byref(rep)))
+        return _fuse_loop_report_dict(rep)
+
+    def global_ba_imu(self, edge_weight=0.0, max_iterations=0, lambda0=0.0):
+        """vslam_system_global_ba_imu (a stereo + IMU session): global_ba with keyframes that move only by a rotation about gravity
+        and a translation; the velocity turns with the camera.  Returns (report dict, dict(yaw, velocity_before, velocity, T_wc))."""
+        prm = SystemGbaParams(GbaParams(int(max_iterations), float(lambda0)), float(edge_weight))
+        rep = SystemGbaReport(); irep = GbaImuReport()
+        _chk(self.L.vslam_system_global_ba_imu(self.h_sys, C.byref(prm), C.byref(rep), C.byref(irep)))
+        return _system_gba_report_dict(rep), dict(yaw=irep.yaw, velocity_before=np.array(irep.velocity_before), velocity=np.array(irep.velocity),
+                                                  T_wc=np.array(irep.T_wc).reshape(4, 4))
+
+    def global_ba_problem_imu(self, edge_weight=0.0):
+        """test tap: global_ba_problem on a stereo + IMU session (what global_ba_imu would build now)"""
+        return self.global_ba_problem(edge_weight, call=self.L.vslam_system_global_ba_problem_imu)
+
+    def global_ba_problem(self, edge_weight=0.0, call=None):
         """test tap: (problem dict as global_ba takes it, plus lm_index, sigma_factor and inv_sigma_factor; edges array) that
         Session.global_ba would build now"""
         sz = (C.c_int32 * 5)()
-        call = self.L.vslam_system_global_ba_problem
+        call = call or self.L.vslam_system_global_ba_problem
         _chk(call(self.h_sys, C.c_double(edge_weight), 0, sz, *([None] * 13)))
         K, Lm, NP, M, nLev = (int(v) for v in sz)
         z = lambda shape, dt: np.zeros(shape, dt)

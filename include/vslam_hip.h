@@ -633,10 +633,43 @@ typedef struct vslam_gba_lane {            /* one lane; problem == NULL or probl
     vslam_gba_result* result;              /* as for vslam_global_ba; its arrays may be the problem's */
 } vslam_gba_lane;
 vslam_status vslam_global_ba_batch(const vslam_gba_lane* lanes, int32_t n_lanes, const vslam_gba_params* params, int32_t device);
+/* The global bundle adjustment with YAW-ONLY (4-DoF) keyframes (csrc/gba_yaw.hip, csrc/gba_yaw_dev.hpp; DESIGN.md section 6
+ * item 30, restated by tests/gba_yaw_ref.py, which is the authority): what a stereo + IMU session needs from a global
+ * adjustment, whose world frame carries gravity and whose roll and pitch the IMU observes.  THE RULES are those of
+ * vslam_global_ba above - factors, presence, gauge, LM schedule, damping, flags, refusals and limits - with ONE change:
+ *   axis        g = axis / sqrt(x^2 + y^2 + z^2), in fp64 on the host (the expression of vslam_pose_graph_optimize_yaw; the axis
+ *               needs no normalising by the caller).  A zero or non-finite axis: VSLAM_ERR_INVALID, nothing launched, nothing
+ *               written.  Every lane of the batched call has its own axis.
+ *   parameters  four per free keyframe, (theta, delta);  retraction T <- [Exp(theta g) R, t + delta].  Hence
+ *               R_new R_old^T g = g for every keyframe (to 1e-12): roll and pitch about g never change, where the 6-DoF call
+ *               tilts g by 2e-3 .. 1.5e-1 rad on the problems of the tests.  Landmarks stay additive.  Fixed and isolated
+ *               keyframes and thin landmarks come back bit for bit.
+ *   Jacobians   projection factor: the 6-DoF factor unchanged, then Jp4 [2][4] = Jp6 [2][6] * M_k in registers, with
+ *               M_k = [[R_k^T g, 0], [0, R_k^T]] (6x4); Jl, the residual and the cost term are unchanged.  Edges: the Jacobians of
+ *               vslam_pose_graph_optimize_yaw (24 doubles a side).  The cost does not depend on the parameterisation.
+ *   solve       W and Y are [4][3] per pair; the reduced camera system is block-banded with 4x4 fp64 blocks, gathered THREE
+ *               listed blocks per wave (20 lanes each: 16 elements and, on a diagonal block, 4 gradient components; each block
+ *               walks its own list in ascending order, so an element's sum does not depend on the block's company), factored and
+ *               solved by the 4x4 walk of vslam_pose_graph_optimize_yaw, one workgroup per lane.  Damping is lambda diag(H) on
+ *               the 4x4 pose diagonal and on the landmark diagonal, before the elimination.  The steps are laid out as
+ *               n_free * 4 pose entries followed by n_lm * 3; |delta|_inf runs over both.
+ * No floating-point atomics: the same input gives the same bytes, and a lane's bytes do not depend on the other lanes or on
+ * their order.  vslam_global_ba_yaw is the one-lane case of vslam_global_ba_yaw_batch (one set of kernels); a lane whose problem
+ * is NULL or has n_kf == 0 is idle (nothing read, its axis included, nothing written).  The batched call's refusals and sums
+ * over all lanes are those of vslam_global_ba_batch.  With every keyframe fixed only bodies shared with vslam_global_ba run: the
+ * result equals that call's byte for byte.  Without landmarks the call is vslam_pose_graph_optimize_yaw on the edges.
+ * vslam_global_ba_set_timing / _timings below cover these calls too, with the same group names. */
+typedef struct vslam_gba_yaw_lane {        /* one lane of the yaw-only adjustment */
+    vslam_gba_lane lane;
+    double axis[3];                        /* the world axis that keyframe rotations are confined to (gravity); any non-zero length */
+} vslam_gba_yaw_lane;
+vslam_status vslam_global_ba_yaw(const struct vslam_ba_problem* problem, const vslam_pgo_edge* edges, int32_t n_edges, const double axis[3],
+                                 const vslam_gba_params* params, int32_t device, vslam_gba_result* result);
+vslam_status vslam_global_ba_yaw_batch(const vslam_gba_yaw_lane* lanes, int32_t n_lanes, const vslam_gba_params* params, int32_t device);
 /* measurement hook of tools/gba_rate.py, in the form of the pose-graph one: device time (HIP events) per kernel group of the
- * calling thread's last vslam_global_ba or vslam_global_ba_batch (a batched call's figures are those of all its lanes
- * together) - gba_linearize, gba_landmarks, gba_assemble, gba_band_chol, gba_back, gba_cost, gba_chi2; off by default;
- * thread-local state. */
+ * calling thread's last vslam_global_ba, vslam_global_ba_batch, vslam_global_ba_yaw or vslam_global_ba_yaw_batch (a batched
+ * call's figures are those of all its lanes together) - gba_linearize, gba_landmarks, gba_assemble, gba_band_chol, gba_back,
+ * gba_cost, gba_chi2; off by default; thread-local state. */
 vslam_status vslam_global_ba_set_timing(int32_t on);
 vslam_status vslam_global_ba_timings(const char** names, float* ms, int32_t cap, int32_t* n_out);
 
@@ -1406,6 +1439,37 @@ vslam_status vslam_system_global_ba_problem(vslam_system* sys, double edge_weigh
                                             uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
                                             int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
                                             vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor);
+/* Duplicate fusion and the global adjustment for stereo + IMU sessions (use_imu = 1): what follows
+ * a vslam_system_close_loop_imu / _correct_loop_imu whose report has corrected = 1.  vslam_system_fuse_loop,
+ * vslam_system_global_ba and vslam_system_global_ba_problem keep refusing IMU sessions; the three calls below are refused
+ * (VSLAM_ERR_INVALID, nothing changed) for a mono session, a session with use_imu = 0 (it has the calls above) and while a
+ * two-phase relocalisation is pending, with the messages of the IMU loop calls, and for everything the calls above refuse.
+ *   vslam_system_fuse_loop_imu      the stages, parameters, report and `busy` of vslam_system_fuse_loop, unchanged: fusion is
+ *                                   geometry and bookkeeping.  Nothing of the IMU state is touched (velocity, bias, last good
+ *                                   bias and the pending flag come back with the same bytes).
+ *   vslam_system_global_ba_imu      steps 1 - 4 of vslam_system_global_ba, then vslam_global_ba_yaw with axis cfg.gravity in
+ *                                   place of step 5, then steps 6 and 7: every keyframe moves only by a rotation about
+ *                                   g = gravity / |gravity| and a translation, so R_new R_old^T g = g for each of them and for
+ *                                   the camera, which is re-anchored on the latest keyframe.  The world-frame IMU state follows
+ *                                   the camera as after a loop correction: with dR = R_cam,new * R_cam,old^T (R_cam,old the
+ *                                   camera after step 1, as the loop calls take it) velocity <- dR velocity and the prediction's
+ *                                   velocity likewise, before the active set is rebuilt.  bias, the last good bias, gravity and
+ *                                   the pending flag are untouched.  `busy` and a session with fewer than two keyframes
+ *                                   (success = 0, nothing changed, both velocities of the IMU report the session's) are those
+ *                                   of vslam_system_global_ba.
+ *   vslam_system_global_ba_problem_imu   the test tap of vslam_system_global_ba_problem on an IMU session. */
+typedef struct vslam_gba_imu_report {
+    double yaw;                       /* the camera's yaw: the twist of dR about g [rad] */
+    double velocity_before[3], velocity[3];      /* world-frame velocity before / after the call */
+    double T_wc[16];                  /* the camera pose after the call (the unchanged one when nothing was committed) */
+} vslam_gba_imu_report;
+vslam_status vslam_system_fuse_loop_imu(vslam_system* sys, const vslam_fuse_loop_params* params, vslam_fuse_loop_report* report);
+vslam_status vslam_system_global_ba_imu(vslam_system* sys, const vslam_system_gba_params* params, vslam_system_gba_report* report,
+                                        vslam_gba_imu_report* imu_report);
+vslam_status vslam_system_global_ba_problem_imu(vslam_system* sys, double edge_weight, int32_t arrays, int32_t* sizes, double* kf_pose_wc,
+                                                uint8_t* kf_fixed, uint8_t* kf_local, double* lm_xyz, int32_t* lm_index, int32_t* pair_kf,
+                                                int32_t* pair_lm, uint8_t* pair_flags, float* pair_uv, int32_t* pair_octave,
+                                                vslam_pgo_edge* edges, float* sigma_factor, float* inv_sigma_factor);
 /* test tap: the IMU state of a session; any pointer may be NULL */
 vslam_status vslam_system_imu_state(vslam_system* sys, double* velocity3, double* bias6, double* bias_good6, int32_t* pending);
 /* test taps for the velocity rule alone, on a bare matcher: the bucket of imu is pre-integrated (k_imu_preintegrate_b) with

@@ -15,8 +15,11 @@ With --lanes N: N such corridors of unequal length (150 .. 250 free keyframes, e
 against the same problems as N vslam_global_ba calls one after the other: two warm-up calls, `reps` repetitions, the wall clock of
 whole calls (upload, loop, download), the device time per kernel group of one more call of each kind, and whether every lane's
 bytes equal its single call's.  Writes profiles/gba_batch_rate.json.
+With --yaw: vslam_global_ba_yaw / _batch beside the 6-DoF calls in the same process, on the 2 000-keyframe corridor (single) and
+on the sixteen corridors of --lanes 16 (batched), with the per-group timings of both.  Writes profiles/gba_yaw_rate.json.
 usage: python tools/gba_rate.py [out.json] [calls] [reps]
-       python tools/gba_rate.py --lanes N [out.json] [reps]"""
+       python tools/gba_rate.py --lanes N [out.json] [reps]
+       python tools/gba_rate.py --yaw [out.json] [reps]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("gtsam-vslam_amd", "tests"):
@@ -115,7 +118,62 @@ def batch_main(n_lanes, argv):
         json.dump(res, f, indent=1)
 
 
+YAW_AXIS = (0.3, 0.9, -0.2)
+
+
+def yaw_main(argv):
+    """vslam_global_ba_yaw beside vslam_global_ba in one process: the 2 000-keyframe corridor as single calls, the sixteen corridors
+    of --lanes 16 as batched calls; wall clock of whole calls and the device time per kernel group of one more call of each kind"""
+    out_path = argv[0] if argv else os.path.join(ROOT, "profiles", "gba_yaw_rate.json")
+    reps = int(argv[1]) if len(argv) > 1 else 3
+    groups_of = lambda fn: (vc.global_ba_set_timing(True), fn(), vc.global_ba_timings(), vc.global_ba_set_timing(False))[2]
+    report = lambda r: {k: r["report"][k] for k in ("iterations", "accepted", "rejected", "n_free", "half_bandwidth", "initial_cost", "final_cost")}
+
+    def tilt(out, prob):
+        g = np.array(YAW_AXIS) / np.linalg.norm(YAW_AXIS)
+        return float(max(np.abs(n[:3, :3] @ o[:3, :3].T @ g - g).max() for n, o in zip(out["kf_pose"], prob["kf_pose"])))
+
+    res = dict(protocol="2 warm-up calls, %d repetitions, host clock around whole calls (upload, LM loop, download), both calls alternating "
+                        "in one process; kernel groups from HIP events of one more call of each kind; axis (%g, %g, %g)" % ((reps,) + YAW_AXIS))
+    prob = corridor(2000)
+    six = lambda: vc.global_ba(prob["rig"], gr.SIGMA, gr.INV_SIGMA, prob)
+    yaw = lambda: vc.global_ba_yaw(prob["rig"], gr.SIGMA, gr.INV_SIGMA, prob, YAW_AXIS)
+    a, b = six(), yaw()
+    row = dict(keyframes=2001, landmarks=len(prob["lm"]), pairs=len(prob["pair_kf"]), six_dof=report(a), yaw=report(b),
+               gravity_error_six_dof=tilt(a, prob), gravity_error_yaw=tilt(b, prob))
+    row["ms_per_call_six_dof"], row["ms_per_call_yaw"] = timed(six, 1, reps), timed(yaw, 1, reps)
+    row["ms_per_trial_six_dof"] = row["ms_per_call_six_dof"]["median"] / max(a["report"]["iterations"], 1)
+    row["ms_per_trial_yaw"] = row["ms_per_call_yaw"]["median"] / max(b["report"]["iterations"], 1)
+    row["kernel_group_ms_six_dof"], row["kernel_group_ms_yaw"] = groups_of(six), groups_of(yaw)
+    for name, r in (("six_dof", a), ("yaw", b)):
+        row["us_band_chol_per_column_and_trial_" + name] = 1e3 * row["kernel_group_ms_" + name].get("gba_band_chol", 0.0) / (r["report"]["n_free"] * max(r["report"]["iterations"], 1))
+    print("single", json.dumps(row), flush=True)
+    res["single_2000_keyframes"] = row
+    sizes = [int(round(v)) for v in np.linspace(150, 250, 16)]
+    probs = [corridor(n, seed=10 + i) for i, n in enumerate(sizes)]
+    lanes = [dict(rig=p["rig"], sigma_factor=gr.SIGMA, inv_sigma_factor=gr.INV_SIGMA, prob=p) for p in probs]
+    yaw_lanes = [dict(ln, axis=YAW_AXIS) for ln in lanes]
+    six_b = lambda: vc.global_ba_batch(lanes)
+    yaw_b = lambda: vc.global_ba_yaw_batch(yaw_lanes)
+    a, b = six_b(), yaw_b()
+    alone = [vc.global_ba_yaw(p["rig"], gr.SIGMA, gr.INV_SIGMA, p, YAW_AXIS) for p in probs]
+    same = all(x[k].tobytes() == y[k].tobytes() for x, y in zip(alone, b) for k in ("kf_pose", "lm", "pair_wrong")) and \
+        all(x["report"] == y["report"] for x, y in zip(alone, b))
+    row = dict(lanes=16, free_keyframes=sizes, lm_trials_six_dof=[r["report"]["iterations"] for r in a], lm_trials_yaw=[r["report"]["iterations"] for r in b],
+               half_bandwidth=[r["report"]["half_bandwidth"] for r in b], yaw_lanes_equal_single_calls_bitwise=bool(same))
+    row["ms_batched_call_six_dof"], row["ms_batched_call_yaw"] = timed(six_b, 1, reps), timed(yaw_b, 1, reps)
+    row["ms_per_round_six_dof"] = row["ms_batched_call_six_dof"]["median"] / max(row["lm_trials_six_dof"])
+    row["ms_per_round_yaw"] = row["ms_batched_call_yaw"]["median"] / max(row["lm_trials_yaw"])
+    row["kernel_group_ms_six_dof"], row["kernel_group_ms_yaw"] = groups_of(six_b), groups_of(yaw_b)
+    print("batched", json.dumps(row), flush=True)
+    res["batched_16_corridors"] = row
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
+    if "--yaw" in sys.argv:
+        return yaw_main([a for a in sys.argv[1:] if a != "--yaw"])
     if "--lanes" in sys.argv:
         at = sys.argv.index("--lanes")
         return batch_main(int(sys.argv[at + 1]), sys.argv[1:at] + sys.argv[at + 2:])
